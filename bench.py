@@ -7,9 +7,13 @@
 One "step" = forward + MSE+0.25*latent loss + backward + EMA codebook update + Adam on one batch of
 synthetic 256x256 images already resident in HBM (BASELINE.json configs[1]: default two-level
 VQVAE, batch 32 per GPU; weak scaling: every rank keeps 32 images, one packed RCCL all-reduce per
-step).  Rank 0 prints ONE JSON line.  The line also carries
+step).  Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up,
+--warmup steps, --steps timed steps (nothing else inside them), the optional --dump-outputs, the line.
+--dump-outputs DIR writes what the last timed step handed its caller (see dump_outputs).
+--full adds what the headline does not need, each outside the timed steps:
+  parity       -- recon-MSE of the first two images through the HIP path and the CPU oracle (before warm-up)
   roofline     -- the dominant kernel (fp32-MFMA 3x3 conv, csrc/vq2_wino.hip / vq2_conv.hip): algorithmic
-                  FLOPs of its launches / their HIP-event time, measured live in the timed region
+                  FLOPs of its launches / their HIP-event time, over a profiled pass of --steps further steps
   cpu_baseline -- the CPU oracle (PyTorch-CPU restatement of the reference graph, kind "port") timed on
                   this box's host cores on a bounded sample (N=1, rank 0 only)
 """
@@ -46,13 +50,22 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the loss terms and the trained state of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure parity vs the CPU oracle, the CPU baseline and the HIP-event roofline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without parity and CPU baseline")
+    ap.add_argument("--no-prof", action="store_true", help="--full without the HIP-event profiled pass")
     ap.add_argument("--prof-all", action="store_true",
-                    help="bracket EVERY GEMM launch (per-shape table; perturbs the step by ~6%%); default: only "
+                    help="--full: bracket EVERY GEMM launch (per-shape table; perturbs a step by ~6%%); default: only "
                          "the dominant kernel")
-    ap.add_argument("--kernel-table", default="", help="write the per-kernel table (JSON) here")
-    return ap.parse_args()
+    ap.add_argument("--kernel-table", default="", help="--full: write the per-kernel table (JSON) here")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.prof_all or args.kernel_table) and not (args.full and not args.no_prof):
+        ap.error("--prof-all and --kernel-table need --full (and no --no-prof)")
+    return args
 
 
 def prof_report(lib):
@@ -95,6 +108,44 @@ def cpu_baseline(size, n_embed, budget_s=7.0):
             "sample": f"oracle train steps of batch {b} at {size}x{size}, 1 warm-up + {best['steps']} timed "
                       f"({best['seconds']} s) at {best['threads']} threads; torch {torch.__version__} CPU kernels",
             "runs": runs}
+
+
+DUMP_ELEMENTS = 1 << 23   # float32 elements (32 MB) written by --dump-outputs at most
+
+
+def dump_outputs(path, out, model):
+    """What the last timed step handed its caller: the loss terms it returned (loss.npy, recon.npy, latent.npy) and
+    the trained state it left in the model (state.<state_dict key>.npy, flattened), all float32.  A state larger than
+    DUMP_ELEMENTS (VQVAE_Deep: 27 M) is written as a seeded sample of the same share of every tensor, at positions
+    that depend only on the state's layout, so two builds are compared element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k in ("loss", "recon", "latent"):
+        np.save(os.path.join(path, k + ".npy"), out[k].detach().float().cpu().numpy())
+    sd = model.state_dict()
+    share = min(1.0, DUMP_ELEMENTS / sum(v.numel() for v in sd.values()))
+    gen = torch.Generator().manual_seed(1234)
+    for k, v in sd.items():
+        v = v.detach().float().cpu().reshape(-1)
+        if share < 1.0:
+            v = v[torch.randperm(v.numel(), generator=gen)[:max(1, int(v.numel() * share))].sort().values]
+        np.save(os.path.join(path, f"state.{k}.npy"), v.numpy())
+
+
+def profiled_pass(lib, trainer, img, steps, level, barrier):
+    """--full: `steps` more train steps with the library's HIP-event brackets on (level 2: the dominant kernel's
+    launches on every 4th step, each pair of events costs ~10 us of stream time; level 1: every GEMM-shaped launch on
+    every step).  Kept out of the timed steps, so the headline figure carries no events."""
+    every = 1 if level == 1 else 4
+    sampled = 0
+    for i in range(steps):
+        on = i % every == 0
+        lib.vq2_prof_enable(level if on else 0)
+        sampled += 1 if on else 0
+        trainer.step(img)
+    barrier()
+    lib.vq2_prof_enable(0)
+    return prof_report(lib), sampled
 
 
 class DeepStep:
@@ -167,10 +218,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # "recon-MSE parity" half of the BASELINE metric, recorded with the number: the first two images through the HIP
-    # path and through the CPU oracle (eval forward: same weights, same codebooks), outside the timed region
+    # --full: "recon-MSE parity" half of the BASELINE metric, recorded with the number: the first two images through the
+    # HIP path and through the CPU oracle (eval forward: same weights, same codebooks), outside the timed region
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not deep:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not deep:
         import torch.nn.functional as F
         st0 = O.make_state(cfg, 1234)
         model.eval()
@@ -188,22 +239,12 @@ def main():
     for _ in range(args.warmup):
         out = trainer.step(img)
     barrier()
-    # live roofline: the dominant kernel's launches are bracketed by HIP events on every 4th timed step (each pair of
-    # events costs ~10 us of stream time: sampling keeps the measurement inside the timed region at a quarter of the cost)
-    level = 0 if args.no_prof else (1 if (args.prof_all or args.kernel_table) else 2)
-    every = 1 if level == 1 else 4
-    sampled = 0
     t0 = time.perf_counter()
-    for i in range(args.steps):
-        on = level and i % every == 0
-        lib.vq2_prof_enable(level if on else 0)
-        sampled += 1 if on else 0
+    for _ in range(args.steps):
         out = trainer.step(img)
     t_host = time.perf_counter() - t0   # host time to ENQUEUE the steps (launch-bound if close to dt)
     barrier()
     dt = time.perf_counter() - t0
-    lib.vq2_prof_enable(0)
-    kernels = prof_report(lib) if not args.no_prof else {}
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -211,6 +252,13 @@ def main():
     loss = float(out["loss"])
     if not (loss == loss):
         raise SystemExit("loss is NaN")
+    early_buckets = trainer.early_buckets if trainer.dp else 0   # of the warm-up and timed steps
+    if args.dump_outputs and rank == 0:   # every rank holds the same state after the all-reduced step
+        dump_outputs(args.dump_outputs, out, model)
+    kernels, sampled, level = {}, 0, 0
+    if args.full and not args.no_prof:
+        level = 1 if (args.prof_all or args.kernel_table) else 2
+        kernels, sampled = profiled_pass(lib, trainer, img, args.steps, level, barrier)
 
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -266,11 +314,11 @@ def main():
             line["collectives"] = {"backend": dist.get_backend(), "data_path": trainer.comm.name,
                                    "world": trainer.comm.world(), "buckets_per_step": len(trainer.bucket_bytes) or 1,
                                    "bucket_bytes": trainer.bucket_bytes or {"all": 4 * trainer.arena.flat_g.numel()},
-                                   "early_buckets": trainer.early_buckets,
+                                   "early_buckets": early_buckets,
                                    "steps": args.steps + args.warmup}
         if parity is not None:
             line["parity"] = parity
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(size, n_embed)
         if kernels:
             line["kernel_ms_per_step"] = {k: round(v["ms"] / max(sampled, 1), 4) for k, v in fam.items()}

@@ -13,11 +13,11 @@ cd /tmp && export TMPDIR=/tmp
 for w in ${WORKLOADS:-c2 c4 c5}; do
   B="python3 $ROOT/bench.py --workload $w --no-cpu-baseline"
   if [ $w = c2 ]; then   # the headline line carries the CPU baseline too
-    python3 $ROOT/bench.py --workload $w --steps 30 --warmup 10 > $OUT/${R}_${w}_bench.json 2> /dev/null
+    python3 $ROOT/bench.py --workload $w --full --steps 30 --warmup 10 > $OUT/${R}_${w}_bench.json 2> /dev/null
   else
-    $B --steps 30 --warmup 10 > $OUT/${R}_${w}_bench.json 2> /dev/null
+    $B --full --steps 30 --warmup 10 > $OUT/${R}_${w}_bench.json 2> /dev/null
   fi
-  $B --steps 8 --warmup 3 --kernel-table $OUT/${R}_${w}_kernel_table_hip_events.json > /dev/null 2>&1
+  $B --full --steps 8 --warmup 3 --kernel-table $OUT/${R}_${w}_kernel_table_hip_events.json > /dev/null 2>&1
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$w -o $R -- $B --steps 10 --warmup 3 --no-prof > /dev/null 2>&1
   cp $OUT/prof_$w/${R}_kernel_stats.csv $OUT/${R}_${w}_rocprofv3_kernel_stats.csv
   P="$B --steps 4 --warmup 2 --no-prof"
@@ -35,5 +35,5 @@ for w in ${WORKLOADS:-c2 c4 c5}; do
 done
 # next-row f4: the default VQVAE_Deep through the drop-in module (bench line + per-shape table)
 python3 $ROOT/bench.py --workload deep --steps 20 --warmup 5 --no-prof > $OUT/${R}_deep_bench.json 2> /dev/null
-python3 $ROOT/bench.py --workload deep --steps 8 --warmup 3 --kernel-table $OUT/${R}_deep_kernel_table_hip_events.json > /dev/null 2>&1
+python3 $ROOT/bench.py --workload deep --full --steps 8 --warmup 3 --kernel-table $OUT/${R}_deep_kernel_table_hip_events.json > /dev/null 2>&1
 echo "deep done: $(grep -o '"value": [0-9.]*' $OUT/${R}_deep_bench.json | head -1)"
