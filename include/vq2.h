@@ -302,7 +302,7 @@ int vq2_comm_destroy(void);
 int vq2_debug_mfma_peak(float *scratch, int32_t blocks, int32_t iters, vq2_stream_t stream);
 /* same through v_mfma_f32_16x16x4_f32: iters x 64 MFMAs per wave, 2*16*16*4 FLOP each */
 int vq2_debug_mfma_peak16(float *scratch, int32_t blocks, int32_t iters, vq2_stream_t stream);
-/* diagnostic only: per-phase cycle stamps of the 128x128x32 conv tile into buf[16] (NULL = off) */
+/* diagnostic only: lifetime clocks of four workgroups of the dominant 3x3 conv kernels into buf[16] (NULL = off) */
 int vq2_debug_set_rb_stamps(unsigned long long *buf); /* same for the fused ResBlock backward kernel: buf[64] */
 int vq2_debug_set_stamps(unsigned long long *buf);
 

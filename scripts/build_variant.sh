@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a second libvq2 from the working tree with extra compiler flags, for A/B runs in ONE gpurun call:
-#   bash scripts/build_variant.sh old "-DVQ2_RB_WRITE_AFTER=0"   ->  vq-vae-2-pytorch_amd/libvq2_old.so
-#   VQ2_LIB=$PWD/vq-vae-2-pytorch_amd/libvq2_old.so python scripts/rb_occupancy.py
+#   bash scripts/build_variant.sh o2 "-O2"   ->  vq-vae-2-pytorch_amd/libvq2_o2.so
+#   VQ2_LIB=$PWD/vq-vae-2-pytorch_amd/libvq2_o2.so python scripts/rb_occupancy.py
 set -euo pipefail
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 TAG=$1; shift

@@ -1,9 +1,8 @@
-"""In-kernel clock of the dominant conv instantiation (the F(2,3) Winograd kernel, or with VQ2_WINO=0 the direct four-per-CU
-128x128x16 tile; 3x3 128->128 at 64x64, batch 32):
+"""In-kernel clock of the dominant conv instantiation (the F(2,3) Winograd kernel, or with VQ2_FORMS=direct the direct
+four-per-CU 128x128x16 tile; 3x3 128->128 at 64x64, batch 32):
 lifetime of four workgroups in shader cycles (s_memtime) and in 10 ns ticks (s_memrealtime), after two seconds of
-back-to-back launches (MI355X_MICROARCH.md, DVFS give-back item 6).   VQ2_CLOCKPROBE=1 python scripts/clock_probe.py"""
+back-to-back launches (MI355X_MICROARCH.md, DVFS give-back item 6).   python scripts/clock_probe.py"""
 import ctypes as C, os, sys, time, torch
-os.environ["VQ2_CLOCKPROBE"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vqvae2_amd
 from vqvae2_amd import ops
@@ -31,7 +30,7 @@ for slot, r in enumerate(buf.cpu().view(4, 4).tolist()):
     cyc, ticks, mfmas = r[0], r[1], r[2]
     if not ticks: continue
     clk = cyc / ticks * 0.1
-    res = 4 if os.environ.get("VQ2_WINO") == "0" else 2     # resident waves per SIMD (workgroups per CU)
+    res = 4 if os.environ.get("VQ2_FORMS") == "direct" else 2     # resident waves per SIMD (workgroups per CU)
     print(f"workgroup {8 + 256 * slot}: {cyc} cycles in {ticks * 10} ns -> {clk:.2f} GHz; {mfmas} MFMAs per wave x 64 cycles = "
           f"{mfmas * 64} pipe cycles; with {res} waves per SIMD resident the pipe needs {res * mfmas * 64} cycles per round of tiles -> "
           f"utilisation {res * mfmas * 64 / cyc:.2f}; fp32 MFMA peak at this clock {256 * 4 * 64 * clk / 1e3:.0f} TFLOP/s")

@@ -554,8 +554,8 @@ def test_general_kernels_with_every_fast_path_switched_off():
     """The general kernels that the specialised ones replaced -- conv_gemm_kernel (no buffer-descriptor addressing),
     wgrad_kernel, the four-phase GEMM form of the sub-pixel layers, the two-launch ResBlock -- still back every shape the
     fast paths decline (k > 5, tensors beyond 2^29 elements).  Run the ragged-shape and fused-flag cases through them in
-    a child process (the library reads its switches once per process)."""
-    env = dict(os.environ, VQ2_FAST="0", VQ2_WFAST="0", VQ2_SUBPIX="0", VQ2_C4="0", VQ2_RB_FUSED="0", VQ2_WSWAP="0")
+    a child process (the library reads VQ2_FORMS once per process)."""
+    env = dict(os.environ, VQ2_FORMS="general")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-p", "no:cacheprovider",
                         "-k", "ragged_conv_shapes or channel_slices"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "2 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
@@ -564,9 +564,8 @@ def test_general_kernels_with_every_fast_path_switched_off():
 def test_direct_forms_with_every_winograd_path_switched_off():
     """The direct implicit-GEMM / sub-pixel / fused-ResBlock kernels that the Winograd-domain forms replaced on rows of whole
     64-pixel segments still back every other shape (and every tensor beyond 1 GiB).  Run the model-level parity cases
-    through them in a child process (the library reads its switches once per process)."""
-    env = dict(os.environ, VQ2_WINO="0", VQ2_WINO_K4="0", VQ2_WINO_SP="0", VQ2_WWINO="0", VQ2_WWINO_K4="0", VQ2_WWINO_SW="0",
-               VQ2_RB_WINO="0")
+    through them in a child process (the library reads VQ2_FORMS once per process)."""
+    env = dict(os.environ, VQ2_FORMS="direct")
     parity = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_parity.py")
     r = subprocess.run([sys.executable, "-m", "pytest", parity, "-q", "-x", "-p", "no:cacheprovider",
                         "-k", "full256 or 128px or tiny_vqvae_dropin"], env=env, capture_output=True, text=True, timeout=900)

@@ -104,6 +104,59 @@ def test_weight_gradient_plans_and_slab_layouts_without_gpu(amd):
         assert 1 <= job.S <= 256
 
 
+_FORMS_CHILD = r"""
+import ctypes, importlib.util, json, sys
+spec = importlib.util.spec_from_file_location("vq2_lib", sys.argv[1])   # the binding alone: ops.py checks VQ2_FORMS too
+L = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(L)
+L.lib.vq2_conv_wgrad_workspace_bytes.restype = ctypes.c_size_t
+out = {}
+for cout in (128, 32):
+    d = L.ConvDesc()
+    d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad = 32, 64, 64, 128, cout, 3, 3, 1, 1
+    d.ldx, d.ldy, d.Cir, d.Cor = 128, cout, 128, cout
+    job = L.WgradJob()
+    dummy = ctypes.c_void_p(16)
+    rc = L.lib.vq2_wgrad_job_init(ctypes.byref(d), dummy, dummy, dummy, ctypes.byref(job))
+    out[cout] = dict(rc=rc, err=L.lib.vq2_last_error().decode(), swapped=job.swapped, S=job.S, n_units_w=job.n_units_w,
+                     ws=L.lib.vq2_conv_wgrad_workspace_bytes(ctypes.byref(d)))
+print(json.dumps(out))
+"""
+
+
+def test_forms_switch_plans_in_a_child_process(amd):
+    """VQ2_FORMS turns whole families of forms off (csrc/vq2_common.h).  The library reads it once per process, so each
+    value gets a child: "direct" plans the direct weight-gradient layout where the Winograd one is the default, "general"
+    also stops exchanging the roles of x and dy, and any other value is refused by the library and by the package."""
+    import json
+    import subprocess
+    import sys
+
+    def run(value):
+        env = dict(os.environ, VQ2_FORMS=value)
+        r = subprocess.run([sys.executable, "-c", _FORMS_CHILD, amd._lib.__file__], env=env, capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return {int(k): v for k, v in json.loads(r.stdout.strip().splitlines()[-1]).items()}
+
+    full, wide = 128 * 9 * 128 // 32, 128 * 3 * 128 // 32   # reduction units of the direct and the F(2,3) layouts
+    p = run("all")
+    assert p[128]["rc"] == 0 and (p[128]["swapped"] >> 1) & 3 == 1 and p[128]["n_units_w"] == wide
+    assert p[32]["swapped"] == 1 | (3 << 1)
+    p = run("direct")
+    assert p[128]["rc"] == 0 and p[128]["swapped"] == 0 and p[128]["n_units_w"] == full
+    assert p[128]["ws"] == (p[128]["S"] * 128 * 9 * 128 + p[128]["S"] * 128) * 4      # K axis 9 * I
+    assert p[32]["rc"] == 0 and p[32]["swapped"] == 1                               # exchanged roles, direct form
+    p = run("general")
+    assert p[128]["swapped"] == 0 and p[128]["n_units_w"] == full
+    assert p[32]["rc"] == 0 and p[32]["swapped"] == 0
+    p = run("winograd")
+    assert p[128]["rc"] != 0 and "VQ2_FORMS" in p[128]["err"] and p[128]["ws"] == 0
+    r = subprocess.run([sys.executable, "-c", "import vqvae2_amd"], cwd=ROOT, env=dict(os.environ, VQ2_FORMS="winograd"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "VQ2_FORMS" in r.stderr, r.stderr[-2000:]
+
+
 def test_invalid_arguments_are_rejected_without_gpu(amd):
     lib = amd._lib.lib
     d = amd._lib.ConvDesc()

@@ -28,6 +28,16 @@ struct ProfScope {
     ~ProfScope() { if (id >= 0) prof_end(id, s); }
 };
 
+// Every dispatch decision is a function of the layer's shape and strides, except for one switch that turns whole
+// families of forms off (tests reach the paths the faster forms shadow with it).  VQ2_FORMS, read once per process:
+//   unset or "all"  every form
+//   "direct"        no minimal-filtering form: no Winograd conv, Winograd weight gradient or Winograd-domain ResBlock
+//   "general"       nor any specialised fast kernel: the general implicit-GEMM kernels only
+// Any other value is refused: check_forms() fails with a message that names the variable.
+enum { FORMS_GENERAL = 0, FORMS_DIRECT = 1, FORMS_ALL = 2 };
+int forms();
+int check_forms();
+
 static inline hipStream_t to_stream(vq2_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -20,15 +20,13 @@
 // ConvTranspose2d(k4,s2,p1) and the data-gradient of a stride-2 4x4 conv are the same
 // sub-pixel decomposition: 4 output phases, each a 2x2 stride-1 conv; blockIdx.z = phase.
 #include "vq2_conv.h"
-#include <type_traits>
-#include <stdlib.h>
 
 namespace vq2 {
 
 
 // BK = depth of one staged chunk; LDS rows are padded to BK+4 floats (144 B / 80 B), which makes the
 // ds_read_b128 fragment reads conflict-free (16-byte slot index = row*9 resp. row*5 mod 16).
-template <int WAVES_M, int WAVES_N, int MT, int NT, int BK, bool STAMP = false>
+template <int WAVES_M, int WAVES_N, int MT, int NT, int BK>
 __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void conv_gemm_kernel(const ConvGemmParams P) {
     constexpr int LDK = BK + 4;
     constexpr int BM = WAVES_M * MT * 32;
@@ -175,33 +173,15 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
     load_chunk(ra0, rb0);
     store_chunk(0, ra0, rb0);
     __syncthreads();
-    {
-        unsigned long long t_load = 0, t_mfma = 0, t_store = 0, t_bar = 0;
-        for (int c = 0; c < nchunks; ++c) {
-            const int buf = c & 1;
-            unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-            if constexpr (STAMP) s0 = __builtin_amdgcn_s_memtime();
-            if (c + 1 < nchunks) {
-                advance_k();
-                load_chunk(ra0, rb0);  // global loads in flight while the matrix pipe works on chunk c
-            }
-            if constexpr (STAMP) { __builtin_amdgcn_sched_barrier(0); s1 = __builtin_amdgcn_s_memtime(); }
-            compute(buf);
-            if constexpr (STAMP) { __builtin_amdgcn_sched_barrier(0); s2 = __builtin_amdgcn_s_memtime(); }
-            if (c + 1 < nchunks) store_chunk(buf ^ 1, ra0, rb0);
-            if constexpr (STAMP) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); s3 = __builtin_amdgcn_s_memtime(); }
-            __syncthreads();
-            if constexpr (STAMP) {
-                const unsigned long long s4 = __builtin_amdgcn_s_memtime();
-                t_load += s1 - s0; t_mfma += s2 - s1; t_store += s3 - s2; t_bar += s4 - s3;
-            }
+    for (int c = 0; c < nchunks; ++c) {
+        const int buf = c & 1;
+        if (c + 1 < nchunks) {
+            advance_k();
+            load_chunk(ra0, rb0);  // global loads in flight while the matrix pipe works on chunk c
         }
-        if constexpr (STAMP) {
-            if (P.stamps && blockIdx.x == 64 && lane == 0) {
-                P.stamps[wave * 4 + 0] = t_load; P.stamps[wave * 4 + 1] = t_mfma;
-                P.stamps[wave * 4 + 2] = t_store; P.stamps[wave * 4 + 3] = t_bar;
-            }
-        }
+        compute(buf);
+        if (c + 1 < nchunks) store_chunk(buf ^ 1, ra0, rb0);
+        __syncthreads();
     }
 
     // ---- epilogue: lane holds column (lane&31) of 16 rows per 32x32 tile.
@@ -264,9 +244,9 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
 
 
 // ====================================================================== low-VALU variant of the kernel
-// Cycle stamps (scripts/stamp_conv.py) showed that with two waves per SIMD the partner's fp32 MFMAs
-// starve a wave's vector ALU: the ~200 address/bounds instructions per chunk of the kernel above stretch
-// from ~1.0k to ~4.8k cycles, and the LDS-store/barrier phases end up unhidden.  This variant does the
+// Cycle stamps (of a phase-stamp build of the kernel above, since removed) showed that with two waves per SIMD
+// the partner's fp32 MFMAs starve a wave's vector ALU: the ~200 address/bounds instructions per chunk of the
+// kernel above stretch from ~1.0k to ~4.8k cycles, and the LDS-store/barrier phases end up unhidden.  This variant does the
 // same math with ~1/5 of the VALU work:
 //   * operands are fetched with raw BUFFER loads: 32-bit byte offsets, out-of-range lanes get a poisoned
 //     offset and the hardware range check returns zeros (no exec-mask branches, no 64-bit address math)
@@ -274,13 +254,12 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
 //   * per chunk: (tap, ci) advance without loops, tap offset from a small LDS table
 //   * epilogue: 32-bit offsets, one add per element; sub-pixel phases share one division per tile row
 // Limits (checked by the launcher): KH*KW <= 32, every tensor < 2 GiB.
-static int tune(const char *name, int dflt);
 
 // OCC4: four workgroups per CU (BK = 16, <= 128 VGPRs, exactly 40 KiB of LDS: the tap table is replaced by a
 // per-thread (kh, kw) counter) -- all 1,024 tiles of a 64x64-resolution layer are then resident at once: ONE
 // round, so one exposed prologue and one epilogue burst per launch instead of two.
 // UNI (Ci % BK == 0, K % BK == 0: every layer but the 3-channel ones): see the scalar k tracking below.
-// CLOCK (diagnostic instantiation only, scripts/stamp_conv.py): four workgroups leave their lifetime in shader cycles
+// CLOCK (diagnostic instantiation only, scripts/clock_probe.py): four workgroups leave their lifetime in shader cycles
 // (s_memtime) and in 10 ns ticks (s_memrealtime) -- the in-kernel clock the chip holds under this kernel's load.
 template <int WAVES_M, int WAVES_N, int MT, int NT, int BK, bool PIPE, bool RELU_IN, bool OCC4 = false, bool UNI = OCC4, bool TAPIN = false,
           bool CLOCK = false>
@@ -619,8 +598,7 @@ static int launch_conv_gemm_fast(const ConvGemmParams &P, hipStream_t s) {
     const long gib = 1L << 30;
     const bool small = (long)P.N * P.H * P.W * P.ldx * 4 < gib && (long)P.Co * P.K * P.phases * 4 < gib;
     const bool uni = small && (OCC4 || (P.Ci % BK == 0 && P.K % BK == 0));
-    static const int tapin = tune("VQ2_TAPIN", 1);
-    const bool tap_inner = uni && tapin && P.KH * P.KW > 1 && P.Ci > 32 && P.Ci % 32 == 0;
+    const bool tap_inner = uni && P.KH * P.KW > 1 && P.Ci > 32 && P.Ci % 32 == 0;
     auto kern = P.relu_in ? (uni ? (tap_inner ? conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, true, true>
                                               : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, true, false>)
                                  : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, OCC4>)
@@ -628,9 +606,8 @@ static int launch_conv_gemm_fast(const ConvGemmParams &P, hipStream_t s) {
                                               : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, false>)
                                  : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, OCC4>);
     ConvGemmParams Q = P;
-    if constexpr (OCC4) {   // in-kernel clock probe of the dominant instantiation (vq2_debug_set_stamps + VQ2_CLOCKPROBE=1)
-        static const int probe = tune("VQ2_CLOCKPROBE", 0);
-        if (probe && g_stamps && tap_inner && !P.relu_in) {
+    if constexpr (OCC4) {   // in-kernel clock probe of the dominant instantiation (vq2_debug_set_stamps)
+        if (g_stamps && tap_inner && !P.relu_in) {
             kern = conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, true, true>;
             Q.stamps = g_stamps;
         }
@@ -646,12 +623,11 @@ static int launch_conv_gemm_fast(const ConvGemmParams &P, hipStream_t s) {
     return check_launch("conv_gemm_fast_kernel");
 }
 
-template <int WAVES_M, int WAVES_N, int MT, int NT, int BK, bool STAMP = false>
+template <int WAVES_M, int WAVES_N, int MT, int NT, int BK>
 static int launch_conv_gemm(const ConvGemmParams &P, hipStream_t s) {
     constexpr int BM = WAVES_M * MT * 32, BN = WAVES_N * NT * 32;
-    static const int lds_pad = getenv("VQ2_LDS_PAD") ? atoi(getenv("VQ2_LDS_PAD")) : 0;  // experiments: force 1 WG/CU
-    const size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + lds_pad;
-    auto kern = conv_gemm_kernel<WAVES_M, WAVES_N, MT, NT, BK, STAMP>;
+    const size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
+    auto kern = conv_gemm_kernel<WAVES_M, WAVES_N, MT, NT, BK>;
     allow_big_lds(kern, lds);
     dim3 grid(((P.M + BM - 1) / BM) * ((P.Co + BN - 1) / BN) * P.phases);
     const char *name = "conv_gemm";
@@ -880,9 +856,9 @@ static int launch_subpixel(const ConvGemmParams &P, hipStream_t s) {
 // epilogue (2.2-2.8 TB/s of algorithmic bytes on the generic tile).  They are HBM-bound (AI ~ 20): this kernel keeps
 // the whole 64 x 64 weight panel in registers, stages the 18 x 34-pixel input patch of an 8 x 16 output tile in LDS
 // (one 16-byte pixel = one tap of the depth: a fragment read IS the im2col), walks four tiles per workgroup with the
-// next tile's patch in flight behind the current tile's MFMAs, and swaps the operand roles (weights = MFMA rows,
-// pixels = columns) so that a lane ends up with 4 CONSECUTIVE output channels of one pixel: bias, mask and store are
-// 16-byte accesses (8 stores per lane instead of 32).
+// next tile's patch in flight behind the current tile's MFMAs.  The masked form (the data gradient) swaps the operand
+// roles (weights = MFMA rows, pixels = columns) so that a lane ends up with 4 CONSECUTIVE output channels of one pixel:
+// bias, mask and store are 16-byte accesses (8 stores per lane instead of 32).
 namespace c4 {
 constexpr int TH = 8, TW = 16;                    // output pixels per tile
 constexpr int PH = 2 * TH + 2, PW = 2 * TW + 2;   // input patch
@@ -891,7 +867,7 @@ constexpr int P_LD = (NP + 255) / 256;            // 3 patch loads per thread
 constexpr int COOB = 0x7F000000;
 }  // namespace c4
 
-template <bool HAS_MASK, bool SWAP, bool C4>
+template <bool HAS_MASK, bool C4>
 __global__ __launch_bounds__(256, 3) void conv_k4s2_c4_kernel(const ConvGemmParams P) {
     using namespace c4;
     __shared__ float4 patch[NP];
@@ -960,7 +936,7 @@ __global__ __launch_bounds__(256, 3) void conv_k4s2_c4_kernel(const ConvGemmPara
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         u32x4 mk[2][4];
-        if (HAS_MASK && SWAP) {    // the mask of this lane's 16 outputs, requested BEHIND the MFMAs instead of after them
+        if (HAS_MASK) {    // the mask of this lane's 16 outputs, requested BEHIND the MFMAs instead of after them
             const int oy = y0 + ty, ox = x0 + tx;
             const bool pv = oy < P.Ho && ox < P.Wo;
             const int pix = (n * P.Ho + oy) * P.Wo + ox;
@@ -979,7 +955,7 @@ __global__ __launch_bounds__(256, 3) void conv_k4s2_c4_kernel(const ConvGemmPara
             for (int j = 0; j < 2; ++j) {
                 // the 4th channel is zero padding on both operands when the layer has 3 real channels: its product
                 // adds an exact 0 and is skipped (a quarter of the matrix work)
-                if (SWAP) {
+                if (HAS_MASK) {
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[j][k8].x, a.x, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[j][k8].y, a.y, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[j][k8].z, a.z, acc[j], 0, 0, 0);
@@ -993,7 +969,7 @@ __global__ __launch_bounds__(256, 3) void conv_k4s2_c4_kernel(const ConvGemmPara
             }
         }
         const int relu_floor_bits = P.relu_out ? 0 : (int)0x80000000;
-        if (SWAP) {
+        if (HAS_MASK) {
             // epilogue: lane = pixel (ty, tx); registers 4g..4g+3 of block j = channels 32*j + 8*g + 4*h + (0..3)
             const int oy = y0 + ty, ox = x0 + tx;
             const bool pv = oy < P.Ho && ox < P.Wo;
@@ -1172,9 +1148,8 @@ __global__ __launch_bounds__(512, 2) void conv1x1_k64_kernel(const ConvGemmParam
 }
 
 static bool conv_k64_ok(const ConvGemmParams &P) {
-    static const int on = getenv("VQ2_K64") ? atoi(getenv("VQ2_K64")) : 1;
     const long gib = 1L << 30;
-    return on && P.phases == 1 && P.KH == 1 && P.KW == 1 && P.stride == 1 && P.pad_h == 0 && P.pad_w == 0 && P.Ci == 64 &&
+    return P.phases == 1 && P.KH == 1 && P.KW == 1 && P.stride == 1 && P.pad_h == 0 && P.pad_w == 0 && P.Ci == 64 &&
            P.K == 64 && P.Co % 32 == 0 && P.Co >= 64 && P.Co <= 192 && P.M >= 16384 && P.ldx % 4 == 0 &&
            (long)P.M * P.ldx * 4 < gib && (long)P.M * P.ldy * 4 < gib && (long)P.M * (P.ldm > P.ldr ? P.ldm : P.ldr) * 4 < gib;
 }
@@ -1220,74 +1195,44 @@ static int launch_conv_c4(const ConvGemmParams &P, hipStream_t s) {
     // measured (scripts/microbench.py c4s2_3_64 / t_64_3; generic tile: 75 / 88 us): the plain layer streams best with
     // coalesced 4-byte stores and 4 tiles per workgroup (45 us, 3.7 TB/s of algorithmic bytes); the masked one with the
     // 16-byte form whose mask loads sit behind the MFMAs and 8 tiles per workgroup (72 us, 4.2 TB/s)
-    static const int swap_m = tune("VQ2_C4_SWAP_MASK", 1), swap_p = tune("VQ2_C4_SWAP", 0);
-    static const int tpw_m = tune("VQ2_C4_TPW_MASK", 8), tpw_p = tune("VQ2_C4_TPW", 4);
-    const bool swap = P.mask ? swap_m : swap_p;
-    const int tpw = P.mask ? tpw_m : tpw_p;
     const bool c4 = !(P.ci_real > 0 && P.ci_real <= 3);
-    auto pick = [&](auto m, auto sw) {
-        constexpr bool M = decltype(m)::value, S = decltype(sw)::value;
-        return c4 ? conv_k4s2_c4_kernel<M, S, true> : conv_k4s2_c4_kernel<M, S, false>;
-    };
-    auto kern = P.mask ? (swap ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{}))
-                       : (swap ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{}));
+    auto kern = P.mask ? (c4 ? conv_k4s2_c4_kernel<true, true> : conv_k4s2_c4_kernel<true, false>)
+                       : (c4 ? conv_k4s2_c4_kernel<false, true> : conv_k4s2_c4_kernel<false, false>);
     ConvGemmParams Q = P;
-    Q.c4_tpw = tpw < 1 ? 1 : tpw;
+    Q.c4_tpw = P.mask ? 8 : 4;
     hipLaunchKernelGGL(kern, dim3((tiles + Q.c4_tpw - 1) / Q.c4_tpw), dim3(256), 0, s, Q);
     return check_launch("conv_k4s2_c4_kernel");
-}
-
-static int tune(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
-// vq2_debug_set_stamps without VQ2_CLOCKPROBE: the phase-stamp build of the older 128x128x32 kernel takes every launch
-static bool legacy_stamps() {
-    static const int probe = tune("VQ2_CLOCKPROBE", 0);
-    return g_stamps != nullptr && !probe;
 }
 
 static int run_conv_gemm(const ConvGemmParams &P, hipStream_t s) {
     // Tile by output-channel count (GEMM N).  Chunk depth per tile measured on MI355X: the 128x128 tile is
     // register-bound at 2 waves/SIMD and prefers BK=32; the narrower tiles run 4+ waves/SIMD with BK=16.
-    static const int bk128 = tune("VQ2_BK128", 32), bk64 = tune("VQ2_BK64", 16), bk32 = tune("VQ2_BK32", 16);
-    static const int small_m = tune("VQ2_SMALL_M", 1);
     // few row tiles (the 32x32-resolution layers): halve the tile height so every CU still holds >= 2
     // workgroups and the matrix pipe of a SIMD always has a second wave to switch to
     const long wgs128 = (long)((P.M + 127) / 128) * ((P.Co + 127) / 128) * P.phases;
-    static const int fast = tune("VQ2_FAST", 1);
     const long lim = (1L << 29);  // elements: every tensor below 2 GiB so that 32-bit byte offsets suffice
-    const bool fast_ok = fast && P.KH * P.KW <= 32 && (long)P.N * P.H * P.W * P.ldx < lim &&
+    const bool fast_ok = forms() > FORMS_GENERAL && P.KH * P.KW <= 32 && (long)P.N * P.H * P.W * P.ldx < lim &&
                          (long)P.N * P.Hy * P.Wy * P.ldy < lim && (long)P.N * P.Hy * P.Wy * (P.ldm > P.ldr ? P.ldm : P.ldr) < lim &&
                          (long)P.Co * P.K * P.phases < lim;
-    static const int c4k = tune("VQ2_C4", 1);
-    if (c4k && fast_ok && !legacy_stamps() && conv_c4_ok(P)) return launch_conv_c4(P, s);
-    if (fast_ok && !legacy_stamps() && conv_k64_ok(P)) return launch_conv_k64(P, s);
-    if (fast_ok && !legacy_stamps() && wino3_ok(P)) {   // vq2_wino.hip
+    if (fast_ok && conv_c4_ok(P)) return launch_conv_c4(P, s);
+    if (fast_ok && conv_k64_ok(P)) return launch_conv_k64(P, s);
+    if (fast_ok && wino3_ok(P)) {   // vq2_wino.hip
         ConvGemmParams Q = P;
-        Q.stamps = g_stamps;        // (non-null only under vq2_debug_set_stamps + VQ2_CLOCKPROBE=1: the clock-probe instantiation)
+        Q.stamps = g_stamps;        // (non-null only under vq2_debug_set_stamps: the clock-probe instantiation)
         return launch_wino3(Q, s);
     }
-    static const int subpix = tune("VQ2_SUBPIX", 1);
     const long big = 0x7F000000L / 4;   // the patch kernel's out-of-range sentinel must stay above every tensor
     // (a launch of <= 256 workgroups with a short depth is better off with the 64-row GEMM tiles: measured)
     const long sp_wgs = (long)P.N * ((P.W + sp::TW - 1) / sp::TW) * ((P.H + sp::TH - 1) / sp::TH) * (P.Co / 64);
-    if (fast_ok && !legacy_stamps() && subpix && P.phases == 4 && P.Co % 64 == 0 && P.Ci % 16 == 0 && P.K == 4 * P.Ci &&
+    if (fast_ok && P.phases == 4 && P.Co % 64 == 0 && P.Ci % 16 == 0 && P.K == 4 * P.Ci &&
         (sp_wgs >= 512 || P.K >= 512) &&
         (long)P.N * P.H * P.W * P.ldx < big && (long)P.N * P.Hy * P.Wy * P.ldy < big &&
         (long)P.N * P.Hy * P.Wy * (P.ldm > P.ldr ? P.ldm : P.ldr) < big)
         return launch_subpixel(P, s);
-    if (fast_ok && !legacy_stamps()) {
-        static const int t32 = tune("VQ2_T32", 1), tk = tune("VQ2_TSHORTK", 0), t64 = tune("VQ2_T64", 0),
-                         tsm = tune("VQ2_TSM", 1);
-        if (small_m && wgs128 < 400 && P.Co > 32) {
-            if (P.Co > 64) {
-                if (tsm == 1) return launch_conv_gemm_fast<2, 2, 1, 2, 32>(P, s);
-                return launch_conv_gemm_fast<2, 2, 1, 2, 16>(P, s);
-            }
-            if (tsm == 1) return launch_conv_gemm_fast<2, 2, 1, 1, 32>(P, s);
-            return launch_conv_gemm_fast<2, 2, 1, 1, 16>(P, s);
+    if (fast_ok) {
+        if (wgs128 < 400 && P.Co > 32) {
+            if (P.Co > 64) return launch_conv_gemm_fast<2, 2, 1, 2, 32>(P, s);
+            return launch_conv_gemm_fast<2, 2, 1, 1, 32>(P, s);
         }
         if (P.Co > 64) {
             // K <= 64 (the 1x1 convs out of 32/64 channels): one or two chunks, HBM/epilogue-bound ->
@@ -1296,48 +1241,24 @@ static int run_conv_gemm(const ConvGemmParams &P, hipStream_t s) {
                 // N = 192 (data gradient of quantize_conv_b, vqvae.py:189): a 192-wide tile covers the row in ONE pass --
                 // with 128-wide tiles the second column tile is half empty (a quarter of the MFMAs wasted) and the dy
                 // rows are read twice
-                static const int t192 = tune("VQ2_T192", 1);
-                if (P.Co > 128 && P.Co <= 192 && t192 == 1) return launch_conv_gemm_fast<2, 2, 1, 3, 16>(P, s);
-                if (P.Co > 128 && P.Co <= 192 && t192 == 2) return launch_conv_gemm_fast<2, 2, 2, 3, 16>(P, s);
-                if (P.Co > 128 && P.Co <= 192 && t192 == 3) return launch_conv_gemm_fast<4, 1, 1, 6, 16>(P, s);
+                if (P.Co > 128 && P.Co <= 192) return launch_conv_gemm_fast<2, 2, 1, 3, 16>(P, s);
                 return launch_conv_gemm_fast<2, 2, 1, 2, 16>(P, s);
             }
-            if (tk == 1 && P.K <= 512) return launch_conv_gemm_fast<2, 2, 1, 2, 16>(P, s);   // 64 x 128 for short K
-            if (tk == 2 && P.K <= 512) return launch_conv_gemm_fast<2, 2, 1, 2, 32>(P, s);
-            static const int t128 = tune("VQ2_T128", 0);
-            if (t128 == 1) return launch_conv_gemm_fast<2, 2, 2, 2, 16>(P, s);   // 3 workgroups per CU
             // 513..1024 tiles (every 64x64-resolution layer at batch 32): four workgroups per CU hold ALL tiles at
             // once -- one round instead of two in lock-step (measured +1..3 % per launch, 7.30 -> 7.23 ms/step)
             const bool below_gib = (long)P.N * P.H * P.W * P.ldx * 4 < (1L << 30) && (long)P.Co * P.K * P.phases * 4 < (1L << 30);
-            if (P.Ci % 16 == 0 && below_gib && (t128 == 2 || (t128 == 0 && wgs128 > 512 && wgs128 <= 1024)))
-                return launch_conv_gemm_fast<2, 2, 2, 2, 16, true>(P, s);
+            if (P.Ci % 16 == 0 && below_gib && wgs128 > 512 && wgs128 <= 1024) return launch_conv_gemm_fast<2, 2, 2, 2, 16, true>(P, s);
             return launch_conv_gemm_fast<2, 2, 2, 2, 32>(P, s);
         }
-        if (P.Co > 32) {
-            if (t64 == 1) return launch_conv_gemm_fast<2, 2, 2, 1, 32>(P, s);
-            return launch_conv_gemm_fast<2, 2, 2, 1, 16>(P, s);
-        }
-        if (t32 == 1) return launch_conv_gemm_fast<4, 1, 1, 1, 32>(P, s);
-        if (t32 == 2) return launch_conv_gemm_fast<4, 1, 2, 1, 16>(P, s);
-        if (t32 == 3) return launch_conv_gemm_fast<4, 1, 2, 1, 32>(P, s);
-        return launch_conv_gemm_fast<4, 1, 1, 1, 16>(P, s);
+        if (P.Co > 32) return launch_conv_gemm_fast<2, 2, 2, 1, 16>(P, s);
+        return launch_conv_gemm_fast<4, 1, 1, 1, 32>(P, s);
     }
-    if (small_m && wgs128 < 400 && P.Co > 32) {
+    if (wgs128 < 400 && P.Co > 32) {
         if (P.Co > 64) return launch_conv_gemm<2, 2, 1, 2, 16>(P, s);      // 64 x 128
         return launch_conv_gemm<2, 2, 1, 1, 16>(P, s);                     // 64 x 64
     }
-    if (P.Co > 64) {
-        if (bk128 == 16) return launch_conv_gemm<2, 2, 2, 2, 16>(P, s);
-        if (legacy_stamps()) { ConvGemmParams Q = P; Q.stamps = g_stamps; return launch_conv_gemm<2, 2, 2, 2, 32, true>(Q, s); }
-        return launch_conv_gemm<2, 2, 2, 2, 32>(P, s);                     // 128 x 128
-    }
-    if (P.Co > 32) {
-        static const int tall64 = tune("VQ2_TALL64", 0);
-        if (tall64) return launch_conv_gemm<4, 1, 2, 2, 16>(P, s);         // 256 x 64: each wave 64 x 64
-        if (bk64 == 32) return launch_conv_gemm<2, 2, 2, 1, 32>(P, s);
-        return launch_conv_gemm<2, 2, 2, 1, 16>(P, s);                     // 128 x 64
-    }
-    if (bk32 == 32) return launch_conv_gemm<4, 1, 1, 1, 32>(P, s);
+    if (P.Co > 64) return launch_conv_gemm<2, 2, 2, 2, 32>(P, s);          // 128 x 128
+    if (P.Co > 32) return launch_conv_gemm<2, 2, 2, 1, 16>(P, s);          // 128 x 64
     return launch_conv_gemm<4, 1, 1, 1, 16>(P, s);                         // 128 x 32
 }
 
@@ -1493,6 +1414,7 @@ static bool use_convT_small(const vq2_conv_desc *d) {
 
 static int check_desc(const vq2_conv_desc *d) {
     VQ2_REQUIRE(d != nullptr, "conv desc is null");
+    if (int e = check_forms()) return e;
     VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0, "conv desc: non-positive dims");
     VQ2_REQUIRE(d->Ci % 4 == 0 && d->Co % 4 == 0, "conv desc: Ci=%d, Co=%d must be multiples of 4", d->Ci, d->Co);
     VQ2_REQUIRE(d->ldx >= d->Ci && d->ldx % 4 == 0, "conv desc: ldx=%d must be >= Ci and a multiple of 4", d->ldx);
@@ -1710,8 +1632,8 @@ extern "C" int vq2_conv_dgrad_ex(const vq2_conv_desc *d, int flags, const float 
     return run_conv_gemm(P, to_stream(stream));
 }
 
-// diagnostic only: when set, the 128x128x32 conv tile runs its STAMP build and workgroup 64 writes, per
-// wave, the summed s_memtime cycles of {load issue, MFMA phase, LDS store, barrier} to buf[16]
+// diagnostic only (scripts/clock_probe.py): when set, the 3x3 Winograd kernel and the direct four-per-CU tile run their
+// CLOCK instantiations, and four workgroups write their lifetime in cycles and in 10 ns ticks to buf[16]
 extern "C" int vq2_debug_set_stamps(unsigned long long *buf) {
     g_stamps = buf;
     return VQ2_OK;

@@ -2,6 +2,7 @@
 #include "vq2_common.h"
 #include <atomic>
 #include <mutex>
+#include <stdlib.h>
 #include <string.h>
 #include <utility>
 #include <vector>
@@ -16,6 +17,24 @@ int set_error(int code, const char *fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
+}
+
+static const char *forms_value() { return getenv("VQ2_FORMS"); }
+
+int forms() {
+    static const int level = [] {
+        const char *v = forms_value();
+        if (!v || !strcmp(v, "all")) return (int)FORMS_ALL;
+        if (!strcmp(v, "direct")) return (int)FORMS_DIRECT;
+        if (!strcmp(v, "general")) return (int)FORMS_GENERAL;
+        return -1;
+    }();
+    return level;
+}
+
+int check_forms() {
+    if (forms() >= 0) return VQ2_OK;
+    return set_error(VQ2_ERR_INVALID, "VQ2_FORMS=\"%s\": expected all, direct or general", forms_value());
 }
 
 int check_launch(const char *what) {

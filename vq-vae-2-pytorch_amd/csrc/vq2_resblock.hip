@@ -17,22 +17,12 @@
 // variant that split the depth between two wave groups was measured equal at 32x32 and dropped).
 #include "vq2_common.h"
 #include "vq2_rbwino.h"
-#include <stdlib.h>
 
 namespace vq2 {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef VQ2_RB_WRITE_AFTER
-#define VQ2_RB_WRITE_AFTER 1   // staging order of the slice pipelines (A/B builds: scripts/build_variant.sh)
-#endif
-
 namespace rb {
-constexpr bool WRITE_AFTER = VQ2_RB_WRITE_AFTER != 0;
-#ifndef VQ2_RB_INTERLEAVE
-#define VQ2_RB_INTERLEAVE 1
-#endif
-constexpr bool INTERLEAVE = VQ2_RB_INTERLEAVE != 0;   // staging instructions woven into the MFMA stream (forward kernel)
 constexpr unsigned RSRC_FLAGS = 0x00020000;
 constexpr int OOB = 0x7F000000;   // >= num_records of every descriptor (tensors are checked to be smaller), and
                                   // OOB + any in-tensor slice offset does not wrap
@@ -67,27 +57,11 @@ struct ResFwdParams {
     int N, H, W, ldx, ldr, ldy;
     int tiles_x, tiles_y;
     int relu_out;
-    int dephase, first_round;   // see dephase_start
     unsigned long long *stamps; // diagnostic (vq2_debug_set_rb_stamps): s_memtime at the phase boundaries of 2 workgroups
 };
 
 __device__ __forceinline__ float4 u4_as_f4(u32x4 v) {
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
-// De-phased start.  Two workgroups share a CU (one wave of each per SIMD).  Launched together they run in lock-step:
-// both fetch their first slices together, share the matrix pipe through their MFMA phases and burst their epilogue
-// stores together, so memory phases never sit beside matrix phases.  The workgroup that arrives in the SECOND wave slot
-// of its SIMD (HW_REG_HW_ID[3:0] != 0) during the launch's first resident round waits `cycles` before it starts; from
-// then on the two stay out of phase (a freed slot is refilled when ITS workgroup ends).  While the second one waits,
-// the first has the matrix pipe to itself, so the wait is not lost time.  Speed only: results cannot depend on it.
-__device__ __forceinline__ void dephase_start(int cycles, int first_round_blocks) {
-    if (cycles <= 0 || (int)blockIdx.x >= first_round_blocks) return;
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    if ((hw & 15u) == 0u) return;
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)cycles) __builtin_amdgcn_s_sleep(8);
 }
 
 __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams P) {
@@ -113,7 +87,6 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
         }
     };
     stamp(0);
-    dephase_start(P.dephase, P.first_round);
     const int tiles = P.tiles_x * P.tiles_y;
     const int vid = xcd_remap(blockIdx.x, gridDim.x);
     const int n = vid / tiles;
@@ -178,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
     // hit the 16-byte LDS slots exactly like 32 consecutive rows do -- conflict-free ds_read_b128 for every tap.
     const int a_frag = ((2 * wq + (l31 >> 4)) * PW + (l31 < 16 ? l31 : ((l31 + 14) & 15))) * LDK + fk;
     const int b_frag = l31 * LDK + fk;
-    // Staging INSIDE the MFMA stream (round 3).  Fine stamps of a slice iteration (VQ2_RB_FINE build): 4,651 cycles of
+    // Staging INSIDE the MFMA stream (round 3).  Fine stamps of a slice iteration (a diagnostic build, since removed): 4,651 cycles of
     // MFMAs (72 x 64: the chain itself is perfect), but 909 cycles to ISSUE the eight buffer loads of the slice after next
     // and 525 for the eight LDS stores of the next one, all in front of the first MFMA -- a quarter of the iteration with an
     // idle matrix pipe when the wave is alone on its SIMD.  A vector-memory or LDS-store instruction issued right behind an
@@ -193,32 +166,6 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
         if (j < A_LD) r.a[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, a_off[j], s * CS * 4, 0);
         else r.b[j - A_LD] = __builtin_amdgcn_raw_buffer_load_b128(rw1, b_off[j - A_LD], s * CS * 4, 0);
     };
-    auto compute = [&](int buf) {
-        const float *a0 = As + buf * A_FLOATS + a_frag;
-        const float *b0 = Bs + buf * B_FLOATS + b_frag;
-        // fragment pairs double-buffered by hand: pair p+1 is requested before the four MFMAs of pair p (left to itself
-        // the compiler reuses one register set and waits for every pair in front of its MFMAs)
-        constexpr int NP = 9 * (CS / 8);
-        float4 fa[2], fb[2];
-        fa[0] = *reinterpret_cast<const float4 *>(a0);
-        fb[0] = *reinterpret_cast<const float4 *>(b0);
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const int cur = p & 1, nxt = cur ^ 1;
-            if (p + 1 < NP) {
-                const int tap = (p + 1) / (CS / 8), k8 = (p + 1) % (CS / 8);
-                fa[nxt] = *reinterpret_cast<const float4 *>(a0 + ((tap / 3) * PW + (tap % 3)) * LDK + 8 * k8);
-                fb[nxt] = *reinterpret_cast<const float4 *>(b0 + tap * 32 * LDK + 8 * k8);
-            }
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].x, fb[cur].x, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].y, fb[cur].y, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].z, fb[cur].z, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].w, fb[cur].w, acc1, 0, 0, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // next pair's two LDS reads first ...
-            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);   // ... then this pair's MFMAs
-        }
-    };
-
     // pixel of GEMM row l31 of this wave, and per accumulator register (row = rowq + (r&3) + 8*(r>>2)) the byte
     // offsets of that pixel in x / y at this lane's channel: column block j adds the immediate j*128
     int pix_lane;
@@ -245,8 +192,8 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
     // requested at once, then the 72 MFMAs of slice s -- the barrier follows them directly (no load wait and no LDS
     // stores between the last MFMA of one slice and the first of the next).  Slices 0 and 1 are requested back to back
     // into two register sets, so the peeled first iteration does not wait for a request it has just made.
-    // compute(buf) with the staging of slice s+1 (store) and s+2 (load) woven in; do_store / do_load are uniform
-    auto stage2_load = [&](int i) {      // one of the 16 + 64 loads of stage2_prefetch
+    // the MFMAs of slice s with the staging of slice s+1 (store) and s+2 (load) woven in; do_store / do_load are uniform
+    auto stage2_load = [&](int i) {      // one of the loads stage 2 needs: the 1x1 panel, the skip path x, the biases
         constexpr int NW2 = NJ * (CM / 8);
         if (i < NW2) {
             const int j = i / (CM / 8), k8 = i % (CM / 8);
@@ -309,82 +256,18 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
     store_slice(0, R0);
     __syncthreads();
     stamp(1);
-    auto stage2_prefetch = [&]() {   // what stage 2 needs, fetched behind the last slice's 72 MFMAs
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int k8 = 0; k8 < CM / 8; ++k8)
-                w2f[j][k8] = u4_as_f4(__builtin_amdgcn_raw_buffer_load_b128(
-                    rw2, ((j * 32 + l31) * CM + fk + 8 * k8) * 4, 0, 0));
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                acc2[j][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xoff[r] + j * 128, 0, 0));
-        b1v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb1, l31 * 4, 0, 0));
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) b2v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb2, (j * 32 + l31) * 4, 0, 0));
-    };
-    if (WRITE_AFTER && INTERLEAVE) {
-        // slice 0: the registers R1 hold slice 1 (requested up front), R0 is free for slice 2
-        store_slice(1, R1);
+    // slice 0: the registers R1 hold slice 1 (requested up front), R0 is free for slice 2
+    store_slice(1, R1);
+    __builtin_amdgcn_sched_barrier(0);
+    compute_staged(0, 0, R0, false, true, false);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    for (int s = 1; s < NS; ++s) {
+        const int buf = s & 1;
         __builtin_amdgcn_sched_barrier(0);
-        compute_staged(0, 0, R0, false, true, false);
+        compute_staged(buf, s, R0, s + 1 < NS, s + 2 < NS, s + 1 == NS);
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
-        for (int s = 1; s < NS; ++s) {
-            const int buf = s & 1;
-            __builtin_amdgcn_sched_barrier(0);
-            compute_staged(buf, s, R0, s + 1 < NS, s + 2 < NS, s + 1 == NS);
-            __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();
-        }
-    } else if (WRITE_AFTER) {
-        store_slice(1, R1);
-        issue_loads(2, R0);
-        __builtin_amdgcn_sched_barrier(0);   // the fetches must be in flight BEFORE the 72 MFMAs, not sunk behind them
-        compute(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-#ifdef VQ2_RB_FINE   // diagnostic variant build (scripts/build_variant.sh fine -DVQ2_RB_FINE): where a slice iteration goes
-        unsigned long long f_store = 0, f_issue = 0, f_mfma = 0, f_bar = 0;
-#define VQ2_FT(acc, stmt) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t0_ = __builtin_amdgcn_s_memtime(); \
-                            stmt; __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     \
-                            acc += __builtin_amdgcn_s_memtime() - t0_; }
-#else
-#define VQ2_FT(acc, stmt) { stmt; }
-#endif
-        for (int s = 1; s < NS; ++s) {
-            const int buf = s & 1;
-            VQ2_FT(f_store, if (s + 1 < NS) store_slice(buf ^ 1, R0))
-            VQ2_FT(f_issue, if (s + 2 < NS) issue_loads(s + 2, R0); else if (s + 1 == NS) stage2_prefetch())
-            __builtin_amdgcn_sched_barrier(0);
-            VQ2_FT(f_mfma, compute(buf))
-            __builtin_amdgcn_sched_barrier(0);
-            VQ2_FT(f_bar, __syncthreads())
-        }
-#undef VQ2_FT
-#ifdef VQ2_RB_FINE
-        if (stamp_slot >= 0 && lane == 0) {
-            unsigned long long *fs = P.stamps + 64 + (stamp_slot * 4 + wq) * 4;   // behind the 64 coarse stamp words
-            fs[0] = f_store; fs[1] = f_issue; fs[2] = f_mfma; fs[3] = f_bar;
-        }
-#endif
-    } else {   // write-before-barrier order: slice s+1 is requested in front of the MFMAs of slice s and stored behind them
-        __builtin_amdgcn_sched_barrier(0);
-        compute(0);
-        __builtin_amdgcn_sched_barrier(0);
-        store_slice(1, R1);
-        __syncthreads();
-        for (int s = 1; s < NS; ++s) {
-            const int buf = s & 1;
-            if (s + 1 < NS) issue_loads(s + 1, R0); else stage2_prefetch();
-            __builtin_amdgcn_sched_barrier(0);
-            compute(buf);
-            __builtin_amdgcn_sched_barrier(0);
-            if (s + 1 < NS) store_slice(buf ^ 1, R0);
-            __syncthreads();
-        }
     }
     stamp(2);
     // every wave is past its last fragment read: the staging buffers may be overwritten
@@ -488,7 +371,6 @@ struct ResBwdParams {
     float *b2_slab;    // [grid][128 co]        partial 1x1 bias gradients (with w2_slab)
     int N, H, W, ldg, ldr, ldx, lddh, lddx;
     int tiles_x, tiles_y;
-    int dephase, first_round;     // see dephase_start
     unsigned long long *stamps;   // diagnostic (vq2_debug_set_stamps): s_memtime at the phase boundaries of 2 workgroups
 };
 
@@ -512,7 +394,6 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
         }
     };
     stamp(0);
-    dephase_start(P.dephase, P.first_round);
     const int tiles = P.tiles_x * P.tiles_y;
     const int vid = xcd_remap(blockIdx.x, gridDim.x);
     const int n = vid / tiles;
@@ -622,12 +503,8 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
 #pragma unroll
     for (int s = 0; s < NSA; ++s) {
         const int buf = s & 1;
-        if (WRITE_AFTER) {
-            if (s + 1 < NSA) store_a(s + 1, s == 0 ? RA1 : RA0);   // (slices 0 and 1 were requested back to back)
-            if (s + 2 < NSA) issue_a(s + 2, RA0); else if (s + 2 == NSA) issue_b(0);
-        } else {
-            if (s > 0 && s + 1 < NSA) issue_a(s + 1, RA0); else if (s + 1 == NSA) issue_b(0);
-        }
+        if (s + 1 < NSA) store_a(s + 1, s == 0 ? RA1 : RA0);   // (slices 0 and 1 were requested back to back)
+        if (s + 2 < NSA) issue_a(s + 2, RA0); else if (s + 2 == NSA) issue_b(0);
         __builtin_amdgcn_sched_barrier(0);
         {
             const float *b = Wa + buf * WA_FLOATS + l31 * LDA + fk;
@@ -667,7 +544,6 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
             if (lane < 32) wr[16 * 64 + lane] = bs;
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (!WRITE_AFTER && s + 1 < NSA) store_a(s + 1, s == 0 ? RA1 : RA0);
         __syncthreads();
         if (fuse_w2) {   // wave wq sums accumulator rows 4*wq..4*wq+3 of the four partial blocks; wave 0 the bias partials
             float *slab = P.w2_slab + ((size_t)blockIdx.x * CC + s * 32) * CM;
@@ -688,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
     // (requested two slices ago) goes to LDS first and tap 1's is requested before the dh write, so that neither is
     // waited for at a barrier.
     store_b(0);
-    if (WRITE_AFTER) issue_b(1);
+    issue_b(1);
     {
         const __amdgpu_buffer_rsrc_t rdh = __builtin_amdgcn_make_buffer_rsrc(P.dh, 0, npix * P.lddh * 4, RSRC_FLAGS);
 #pragma unroll
@@ -750,84 +626,49 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
         const int buf = tap & 1;
-        if (!(WRITE_AFTER && INTERLEAVE)) {
-            if (WRITE_AFTER) {
-                if (tap + 1 < 9) store_b(buf ^ 1);
-                if (tap + 2 < 9) issue_b(tap + 2);
-            } else if (tap + 1 < 9) {
-                issue_b(tap + 1);
-            }
-            if (tap < 4) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q)
-                    mtmp[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, poff[q], tap * 128, 0));
-            }
-            if (tap >= 5) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q)
-                    gres[tap - 5][q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                        rg, SAME_LD ? poff[q] : (pixr[SAME_LD ? 0 : q] >= 0 ? pixr[SAME_LD ? 0 : q] * P.ldg * 4 + l31 * 4 : OOB),
-                        (tap - 5) * 128, 0));
-            }
-        }
         __builtin_amdgcn_sched_barrier(0);
         {
             const float *a = Dh + a_frag + ((tap / 3) * PW + (tap % 3)) * LDA;
             const float *b = Wb + buf * WB_FLOATS + l31 * LDA + fk;
-            if (WRITE_AFTER && INTERLEAVE) {
-                // 16 groups of four MFMAs (k8 outer, column block inner); the fragments of group g+1 are requested before
-                // the MFMAs of group g, and behind every group sit (between scheduling fences, see the forward kernel):
-                //   groups 0-3    one LDS store of the NEXT tap's panel (registers requested during the previous tap)
-                //   groups 4-7    one load of the panel after next
-                //   groups 0-7    two mask loads (taps 0-3: they have eight groups to land before the fold below)
-                //   groups 0-15   one skip-gradient load (taps 5-8: consumed in the epilogue only)
-                float4 fa[2], fb[2];
-                fa[0] = *reinterpret_cast<const float4 *>(a);
-                fb[0] = *reinterpret_cast<const float4 *>(b);
+            // 16 groups of four MFMAs (k8 outer, column block inner); the fragments of group g+1 are requested before
+            // the MFMAs of group g, and behind every group sit (between scheduling fences, see the forward kernel):
+            //   groups 0-3    one LDS store of the NEXT tap's panel (registers requested during the previous tap)
+            //   groups 4-7    one load of the panel after next
+            //   groups 0-7    two mask loads (taps 0-3: they have eight groups to land before the fold below)
+            //   groups 0-15   one skip-gradient load (taps 5-8: consumed in the epilogue only)
+            float4 fa[2], fb[2];
+            fa[0] = *reinterpret_cast<const float4 *>(a);
+            fb[0] = *reinterpret_cast<const float4 *>(b);
 #pragma unroll
-                for (int g = 0; g < 16; ++g) {
-                    const int k8 = g >> 2, j = g & 3, cur = g & 1, nxt = cur ^ 1, ca = k8 & 1;
-                    if (g + 1 < 16) {
-                        const int k8n = (g + 1) >> 2, jn = (g + 1) & 3;
-                        fb[nxt] = *reinterpret_cast<const float4 *>(b + jn * 32 * LDA + 8 * k8n);
-                        if (jn == 0) fa[k8n & 1] = *reinterpret_cast<const float4 *>(a + 8 * k8n);
-                    }
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ca].x, fb[cur].x, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ca].y, fb[cur].y, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ca].z, fb[cur].z, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ca].w, fb[cur].w, acc[j], 0, 0, 0);
-                    if (g + 1 < 16) {     // next group's LDS reads first, then this group's MFMAs
-                        if (((g + 1) & 3) == 0) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                        else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (g < 4 && tap + 1 < 9) store_b_one(buf ^ 1, g);
-                    if (g >= 4 && g < 8 && tap + 2 < 9) issue_b_one(tap + 2, g - 4);
-                    if (tap < 4 && g < 8) {
-#pragma unroll
-                        for (int q = 2 * g; q < 2 * g + 2; ++q)
-                            mtmp[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, poff[q], tap * 128, 0));
-                    }
-                    if (tap >= 5)
-                        gres[tap - 5][g] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                            rg, SAME_LD ? poff[g] : (pixr[SAME_LD ? 0 : g] >= 0 ? pixr[SAME_LD ? 0 : g] * P.ldg * 4 + l31 * 4 : OOB),
-                            (tap - 5) * 128, 0));
-                    __builtin_amdgcn_sched_barrier(0);
+            for (int g = 0; g < 16; ++g) {
+                const int k8 = g >> 2, j = g & 3, cur = g & 1, nxt = cur ^ 1, ca = k8 & 1;
+                if (g + 1 < 16) {
+                    const int k8n = (g + 1) >> 2, jn = (g + 1) & 3;
+                    fb[nxt] = *reinterpret_cast<const float4 *>(b + jn * 32 * LDA + 8 * k8n);
+                    if (jn == 0) fa[k8n & 1] = *reinterpret_cast<const float4 *>(a + 8 * k8n);
                 }
-            } else {
-#pragma unroll
-                for (int k8 = 0; k8 < CM / 8; ++k8) {
-                    const float4 fa = *reinterpret_cast<const float4 *>(a + 8 * k8);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float4 fb = *reinterpret_cast<const float4 *>(b + j * 32 * LDA + 8 * k8);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, fb.x, acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, fb.y, acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, fb.z, acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.w, fb.w, acc[j], 0, 0, 0);
-                    }
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ca].x, fb[cur].x, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ca].y, fb[cur].y, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ca].z, fb[cur].z, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ca].w, fb[cur].w, acc[j], 0, 0, 0);
+                if (g + 1 < 16) {     // next group's LDS reads first, then this group's MFMAs
+                    if (((g + 1) & 3) == 0) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                    else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 }
+                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (g < 4 && tap + 1 < 9) store_b_one(buf ^ 1, g);
+                if (g >= 4 && g < 8 && tap + 2 < 9) issue_b_one(tap + 2, g - 4);
+                if (tap < 4 && g < 8) {
+#pragma unroll
+                    for (int q = 2 * g; q < 2 * g + 2; ++q)
+                        mtmp[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, poff[q], tap * 128, 0));
+                }
+                if (tap >= 5)
+                    gres[tap - 5][g] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                        rg, SAME_LD ? poff[g] : (pixr[SAME_LD ? 0 : g] >= 0 ? pixr[SAME_LD ? 0 : g] * P.ldg * 4 + l31 * 4 : OOB),
+                        (tap - 5) * 128, 0));
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -835,7 +676,6 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
 #pragma unroll
             for (int q = 0; q < 16; ++q) mbits[tap >> 1] |= (mtmp[q] > 0.f ? 1u : 0u) << ((tap & 1) * 16 + q);
         }
-        if (!WRITE_AFTER && tap + 1 < 9) store_b(buf ^ 1);
         __syncthreads();
     }
     stamp(4);
@@ -857,24 +697,8 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
 
 }  // namespace vq2
 
-// De-phased start (dephase_start above): only when the launch has more workgroups than one per CU (otherwise nobody
-// shares a SIMD) -- cycles from VQ2_RB_DEPHASE_FWD / VQ2_RB_DEPHASE_BWD (0 = off).
-static void rb_dephase(int grid, int bwd, int *cycles, int *first_round) {
-    static const int c_fwd = getenv("VQ2_RB_DEPHASE_FWD") ? atoi(getenv("VQ2_RB_DEPHASE_FWD")) : 0;
-    static const int c_bwd = getenv("VQ2_RB_DEPHASE_BWD") ? atoi(getenv("VQ2_RB_DEPHASE_BWD")) : 0;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    *cycles = grid > cus ? (bwd ? c_bwd : c_fwd) : 0;
-    *first_round = 2 * cus;
-}
-
 static unsigned long long *g_rb_stamps = nullptr, *g_rb_stamps_fwd = nullptr;
-// buf[64]: backward kernel; buf + 64 (another 64 words): forward kernel (+ 32 more in the VQ2_RB_FINE diagnostic build)
+// buf[64]: backward kernel; buf + 64 (another 64 words): forward kernel
 extern "C" int vq2_debug_set_rb_stamps(unsigned long long *buf) { g_rb_stamps = buf; g_rb_stamps_fwd = buf ? buf + 64 : nullptr; return VQ2_OK; }
 
 extern "C" int vq2_resblock_supported(int32_t C, int32_t Cm) { return (C == vq2::rb::CC && Cm == vq2::rb::CM) ? 1 : 0; }
@@ -884,6 +708,7 @@ extern "C" int vq2_resblock_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int3
                                 float *r, int32_t ldr, float *y, int32_t ldy, vq2_stream_t stream) {
     using namespace vq2;
     VQ2_REQUIRE(N > 0 && H > 0 && W > 0, "resblock_fwd: empty tensor");
+    if (int e = check_forms()) return e;
     if (!vq2_resblock_supported(C, Cm))
         return set_error(VQ2_ERR_UNSUPPORTED, "resblock_fwd: fused kernel is built for channel=%d, n_res_channel=%d (got %d, %d)",
                          rb::CC, rb::CM, C, Cm);
@@ -914,7 +739,6 @@ extern "C" int vq2_resblock_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int3
     P.tiles_x = (W + rb::TW - 1) / rb::TW; P.tiles_y = (H + rb::TH - 1) / rb::TH;
     P.relu_out = (flags & VQ2_RELU_OUT) != 0;
     const int grid = N * P.tiles_x * P.tiles_y;
-    rb_dephase(grid, 0, &P.dephase, &P.first_round);
     P.stamps = g_rb_stamps_fwd;
     hipStream_t s = to_stream(stream);
     const char *name = "resblock_fwd";
@@ -978,7 +802,6 @@ extern "C" int vq2_resblock_bwd_data(int32_t N, int32_t H, int32_t W, int32_t C,
     P.w2_slab = static_cast<float *>(w2_ws);
     P.b2_slab = w2_ws ? P.w2_slab + (size_t)grid * C * Cm : nullptr;
     const size_t lds = w2_ws ? rbb::LDS_BYTES_W2 : rbb::LDS_BYTES;
-    rb_dephase(grid, 1, &P.dephase, &P.first_round);
     if (ldg == ldx && lddx == ldx) {
         allow_big_lds(resblock_bwd_data_kernel<true>, lds);
         hipLaunchKernelGGL(resblock_bwd_data_kernel<true>, dim3(grid), dim3(256), lds, s, P);

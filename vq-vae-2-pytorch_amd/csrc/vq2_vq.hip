@@ -13,7 +13,6 @@
 // dist is evaluated exactly as the reference writes it (vqvae.py:44-48):
 //     (||x||^2 - 2*(x.e)) + ||e||^2      in fp32, in that order.
 #include "vq2_common.h"
-#include <stdlib.h>
 
 namespace vq2 {
 
@@ -582,17 +581,11 @@ extern "C" int vq2_vq_prepare(const float *embed, float *embedT, float *enorm, i
 }
 
 // big = 512-vector workgroups (16 waves, whole 512-code tiles); S = number of K-splits; kper = codes per split
-static int vq_tune(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 static void vq_plan(int64_t M, int32_t D, int32_t K, bool &big, int &S, int &kper) {
     big = M >= 512 * 256;   // 512-vector workgroups still cover every CU
     S = 1;
     kper = K;
     if (D > 64) { big = false; return; }   // embed_dim 128 / 256 (VQVAE_Deep): one 8-wave shape, see vq2_vq_fwd
-    static const int split_small = vq_tune("VQ2_VQ_SPLIT_SMALL", 1);
     if (!big && K >= 1024) {
         const int64_t want = (512 * 256 + M - 1) / M;           // splits that bring the launch to one 16-wave workgroup per CU
         const int64_t most = K / 512;                            // at least one full 512-code tile per split
@@ -600,7 +593,7 @@ static void vq_plan(int64_t M, int32_t D, int32_t K, bool &big, int &S, int &kpe
         big = S > 1;
         if (big) kper = ((K + S - 1) / S + 511) / 512 * 512;
     }
-    if (!big && S == 1 && split_small && K >= 256 && (M + 127) / 128 < 1024) {
+    if (!big && S == 1 && K >= 256 && (M + 127) / 128 < 1024) {
         // few vectors and a small codebook (the top level of the default model: M = 32,768, K = 512): 128-vector
         // workgroups searching ONE 128-code tile each -- four times the workgroups, no staging loop (45 -> 38 us; the
         // same split of the full-size launch was measured 40 % SLOWER than its 512-vector workgroups and is not taken)

@@ -13,7 +13,6 @@
 // from NHWC memory: v_mfma_f32_32x32x2_f32 wants A[i][k] / B[k][j] with lanes along i / j,
 // and consecutive lanes read consecutive channels -> conflict-free ds_read_b32, no transposes.
 #include "vq2_common.h"
-#include <stdlib.h>
 
 namespace vq2 {
 
@@ -813,8 +812,10 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     // of the WIDE tensor x re-reads it KH*KW times through L2.  The same sum with the roles exchanged,
     //   dw[co][ci][kh][kw] = sum_q relu(x)[q][ci] * dy[q - (kh-p, kw-p)][co],
     // gathers the NARROW tensor dy instead (flipped taps, pad' = K-1-p) and streams x once.
-    static const int wswap = getenv("VQ2_WSWAP") ? atoi(getenv("VQ2_WSWAP")) : 1;
-    if (wswap && !d->transposed && d->stride == 1 && 2 * d->pad == d->KH - 1 && d->KH > 1 && d->Co <= 32 && d->Ci >= 64) {
+    // (Exchanged roles and the Winograd modes below are fast-kernel forms: VQ2_FORMS=general plans neither, =direct no
+    // Winograd mode.)
+    const bool fast = forms() > FORMS_GENERAL, wino = forms() == FORMS_ALL;
+    if (fast && !d->transposed && d->stride == 1 && 2 * d->pad == d->KH - 1 && d->KH > 1 && d->Co <= 32 && d->Ci >= 64) {
         p.swapped = 1;
         p.O = d->Ci; p.I = d->Co;
         p.M = d->N * d->H * d->W;
@@ -828,10 +829,7 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     }
     p.K = d->KH * d->KW * p.I;
     p.wino = 0;
-    static const int wwino3 = getenv("VQ2_WWINO_SW") ? atoi(getenv("VQ2_WWINO_SW")) : 1;
-    static const int wwino = getenv("VQ2_WWINO") ? atoi(getenv("VQ2_WWINO")) : 1;
-    static const int wfast = getenv("VQ2_WFAST") ? atoi(getenv("VQ2_WFAST")) : 1;
-    if (wwino && wfast && !p.swapped && !d->transposed && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 &&
+    if (wino && !p.swapped && !d->transposed && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 &&
         p.O % 128 == 0 && p.I % 128 == 0 && (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0)) &&
         (long)d->N * d->H * d->W * d->ldx < (1L << 29) &&
         (long)d->N * d->H * d->W * d->ldy < (1L << 29)) {
@@ -839,10 +837,9 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
         p.K = 12 * p.I;
         p.M = p.M / 2;
     }
-    static const int wwino4 = getenv("VQ2_WWINO_K4") ? atoi(getenv("VQ2_WWINO_K4")) : 1;
     {   // 4x4 stride-2 conv / conv-transpose: F(2,2) by column parity over output column pairs
         const int wo = d->transposed ? d->W : d->W / 2;       // width of the G operand's grid
-        if (wwino4 && wfast && !p.swapped && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad == 1 && d->H % 2 == 0 &&
+        if (wino && !p.swapped && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad == 1 && d->H % 2 == 0 &&
             d->W % 2 == 0 && p.O % 128 == 0 && (p.I == 64 || p.I % 128 == 0) &&
             (wo % 64 == 0 || (wo == 32 && (d->transposed ? d->H : d->H / 2) % 2 == 0)) &&
             (long)d->N * d->H * d->W * d->ldx < (1L << 29) &&
@@ -856,16 +853,15 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     // 128 x 96 = one kernel row of a 3x3 conv with 32 gathered channels (the ResBlock weight gradient with
     // exchanged roles, K = 288): 48 MFMAs per wave and chunk instead of 16 for the same staging
     static const int cand[6][2] = {{128, 128}, {64, 128}, {32, 256}, {128, 96}, {128, 32}, {64, 64}};
-    static const int t96 = getenv("VQ2_W96") ? atoi(getenv("VQ2_W96")) : 1;
     long best = -1;
     for (int c = 0; c < (p.wino ? 1 : 6); ++c) {
-        if (cand[c][1] == 96 && (!t96 || p.M < 65536)) continue;   // measured: +6 % at 131072 rows, -9 % at 32768
+        if (cand[c][1] == 96 && p.M < 65536) continue;   // measured: +6 % at 131072 rows, -9 % at 32768
         const long po = (p.O + cand[c][0] - 1) / cand[c][0] * cand[c][0];
         const long pk = (p.K + cand[c][1] - 1) / cand[c][1] * cand[c][1];
         const long work = po * pk;
         if (best < 0 || work < best) { best = work; p.bmo = cand[c][0]; p.bnk = cand[c][1]; }
     }
-    if (wwino3 && wfast && p.swapped && d->KH == 3 && d->pad == 1 && p.I == 32 && p.O % 128 == 0 &&
+    if (wino && p.swapped && d->KH == 3 && d->pad == 1 && p.I == 32 && p.O % 128 == 0 &&
         (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0)) &&
         (long)d->N * d->H * d->W * d->ldx < (1L << 29) && (long)d->N * d->H * d->W * d->ldy < (1L << 29)) {
         p.wino = 3;                 // exchanged roles + F(2,3): four 128 x 96 tiles (v) of three kernel rows each
@@ -908,9 +904,8 @@ template <int WAVES_M, int WAVES_N, int MT, int NT>
 static int launch_wgrad(const WgradParams &P, int S, hipStream_t s) {
     constexpr int BMO = WAVES_M * MT * 32, BNK = WAVES_N * NT * 32;
     const size_t lds = (size_t)2 * WG_BKR * (BMO + BNK) * sizeof(float);
-    static const int fast = getenv("VQ2_WFAST") ? atoi(getenv("VQ2_WFAST")) : 1;
     const long lim = 1L << 29;
-    const bool fast_ok = fast && P.Wo % WG_BKR == 0 && P.rows_per_split % WG_BKR == 0 &&
+    const bool fast_ok = forms() > FORMS_GENERAL && P.Wo % WG_BKR == 0 && P.rows_per_split % WG_BKR == 0 &&
                          (long)P.N * P.H * P.W * P.ldx < lim && (long)P.M * P.ldg < lim;
     auto kern = wgrad_kernel<WAVES_M, WAVES_N, MT, NT>;
     if (fast_ok) {   // ReLU flags are compile-time in the fast kernel: every vector instruction competes with the MFMAs
@@ -1001,7 +996,7 @@ static int colsum_impl(const float *dy, int64_t rows, int C, int ld, float *db, 
 using namespace vq2;
 
 extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) {
-    if (!d || d->N <= 0 || d->Ci <= 0 || d->Co <= 0) return 0;
+    if (!d || check_forms() || d->N <= 0 || d->Ci <= 0 || d->Co <= 0) return 0;
     const WgradPlan p = plan_wgrad(d);
     return ((size_t)p.S * p.O * p.K + bias_ws_floats(d, p)) * sizeof(float);
 }
@@ -1010,6 +1005,7 @@ extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) {
 static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
                       size_t ws_bytes, vq2_stream_t stream, bool reduce) {
     VQ2_REQUIRE(d && x && dy && ws && (dw || !reduce), "conv_wgrad: null pointer");
+    if (int e = check_forms()) return e;
     VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0 && d->Ci % 4 == 0 && d->Co % 4 == 0,
                 "conv_wgrad: bad dims");
     VQ2_REQUIRE(d->ldx >= d->Ci && d->ldy >= d->Co && d->ldx % 4 == 0 && d->ldy % 4 == 0, "conv_wgrad: bad strides");
@@ -1102,6 +1098,7 @@ extern "C" int vq2_conv_wgrad_partial(const vq2_conv_desc *d, int flags, const f
 
 extern "C" int vq2_wgrad_job_init(const vq2_conv_desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
     VQ2_REQUIRE(d && ws && dw && job, "wgrad_job_init: null pointer");
+    if (int e = check_forms()) return e;
     const WgradPlan p = plan_wgrad(d);
     const int cir = d->Cir ? d->Cir : d->Ci, cor = d->Cor ? d->Cor : d->Co;
     const float *w = static_cast<const float *>(ws);

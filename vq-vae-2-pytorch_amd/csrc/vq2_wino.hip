@@ -20,10 +20,6 @@
 // (include/vq2.h: same ABI): the three taps of a kernel row are transformed while they are staged.
 #include "vq2_conv.h"
 
-#ifndef VQ2_WINO_EXP
-#define VQ2_WINO_EXP 0   // timing experiments (wrong results): 1 no loads in the loop, 2 no loads + no LDS stores, 3 no input
-#endif                   // transform, 4 no weight transform, 5 no barrier in the loop, 6 no output stores
-
 namespace vq2 {
 namespace wino {
 
@@ -101,14 +97,13 @@ __device__ __forceinline__ void store_pairs(const ConvGemmParams &P, int co0, in
                 if (has_res) v += rs[q];
                 if (mask_last) v = (mk[q] > 0.f) ? v : 0.f;
                 v = relu_floor(v, relu_bits);
-                if (VQ2_WINO_EXP != 6 || v == 123.456f)
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, pix[q] * ldy4 + co4, 0, 0);
             }
         }
     }
 }
 
-// CLOCK (diagnostic instantiation, scripts/clock_probe.py with VQ2_CLOCKPROBE=1): workgroups 8, 264, ... leave their lifetime in
+// CLOCK (diagnostic instantiation, scripts/clock_probe.py): workgroups 8, 264, ... leave their lifetime in
 // shader cycles (s_memtime), in 10 ns ticks (s_memrealtime) and their MFMA count per wave.
 template <int TPW, int NT, int BNT, bool RELU_IN, bool CLOCK = false>
 __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void wino3_kernel(const ConvGemmParams P) {
@@ -166,8 +161,8 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void wino3_kernel(const ConvG
         const float4 g0 = as_f4(rb[0]), g1 = as_f4(rb[1]), g2 = as_f4(rb[2]);
         const float4 t = add4(g0, g2);
         *reinterpret_cast<float4 *>(b + 0 * BNT * LDK + b_dst) = g0;
-        *reinterpret_cast<float4 *>(b + 1 * BNT * LDK + b_dst) = VQ2_WINO_EXP == 4 ? g1 : add4(t, g1);
-        *reinterpret_cast<float4 *>(b + 2 * BNT * LDK + b_dst) = VQ2_WINO_EXP == 4 ? g1 : sub4(t, g1);
+        *reinterpret_cast<float4 *>(b + 1 * BNT * LDK + b_dst) = add4(t, g1);
+        *reinterpret_cast<float4 *>(b + 2 * BNT * LDK + b_dst) = sub4(t, g1);
         *reinterpret_cast<float4 *>(b + 3 * BNT * LDK + b_dst) = g2;
     };
     auto store_a = [&](float *a, int j) {
@@ -201,12 +196,10 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void wino3_kernel(const ConvG
 #pragma unroll
             for (int j = 0; j < NT; ++j) fb[v][j] = *reinterpret_cast<const float4 *>(b + (v * BNT + j * 32) * LDK + lane_b);
         float4 fv[4];
-        if (VQ2_WINO_EXP == 3) { fv[0] = d0; fv[1] = d1; fv[2] = d2; fv[3] = d3; } else {
         fv[0] = sub4(d0, d2);
         fv[1] = add4(d1, d2);
         fv[2] = sub4(d2, d1);
         fv[3] = sub4(d1, d3);
-        }
 #define VQ2_WINO_STEP(C)                                                                                          \
     _Pragma("unroll") for (int v = 0; v < 4; ++v) _Pragma("unroll") for (int j = 0; j < NT; ++j)                  \
         acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fv[v].C, fb[v][j].C, acc[v][j], 0, 0, 0);
@@ -235,27 +228,23 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void wino3_kernel(const ConvG
         for (int kh = 0; kh < 3; ++kh) {
             const int nkh = (kh + 1) % 3;
             const int ncb = (kh == 2) ? cbn : cbi;
-            if (VQ2_WINO_EXP != 1 && VQ2_WINO_EXP != 2) {
-                if (role_b && VQ2_WINO_EXP != 8) load_b(nkh, ncb * BK);
-                // the next block's patch: issued BEHIND the weight loads of kernel row 0 and stored a chunk later, so that an
-                // activation line that has to come from HBM has two chunks of time and never holds up the weight tile
-                // (loads return in order: waiting for a younger load waits for every older one)
-                if (kh == 0 && VQ2_WINO_EXP != 7) {
+            if (role_b) load_b(nkh, ncb * BK);
+            // the next block's patch: issued BEHIND the weight loads of kernel row 0 and stored a chunk later, so that an
+            // activation line that has to come from HBM has two chunks of time and never holds up the weight tile
+            // (loads return in order: waiting for a younger load waits for every older one)
+            if (kh == 0) {
 #pragma unroll
-                    for (int j = 0; j < A_LD; ++j) ra[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, a_off[j] + cbn * BK * 4, 0, 0);
-                }
+                for (int j = 0; j < A_LD; ++j) ra[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, a_off[j] + cbn * BK * 4, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);   // (the scheduler otherwise sinks the loads to just before their stores)
             compute(a_cur, Bs + (c & 1) * B_FLOATS_T, kh);
             __builtin_amdgcn_sched_barrier(0);
-            if (VQ2_WINO_EXP != 2) {
-                if (role_b) store_b(Bs + ((c + 1) & 1) * B_FLOATS_T);
-                if (kh == 1) {
+            if (role_b) store_b(Bs + ((c + 1) & 1) * B_FLOATS_T);
+            if (kh == 1) {
 #pragma unroll
-                    for (int j = 0; j < A_LD; ++j) store_a(a_nxt, j);
-                }
+                for (int j = 0; j < A_LD; ++j) store_a(a_nxt, j);
             }
-            if (VQ2_WINO_EXP != 5) __syncthreads();
+            __syncthreads();
             ++c;
         }
     }
@@ -669,26 +658,20 @@ static int launch(const ConvGemmParams &P, hipStream_t s) {
     return check_launch("wino3_kernel");
 }
 
-static int tune(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 }  // namespace wino
 
 // Shapes the Winograd kernels take: 3x3, stride 1, pad 1, output the size of the input, whole 64-channel output tiles,
 // 8-channel input blocks (at least 32 channels), rows of whole 64-pixel segments (or 32-pixel ones with H % 4 == 0), tensors
 // below 1 GiB (32-bit offsets with an additive out-of-range penalty); likewise the 4x4 stride-2 and sub-pixel forms.
 bool wino3_ok(const ConvGemmParams &P) {
-    static const int on = wino::tune("VQ2_WINO", 1), on4 = wino::tune("VQ2_WINO_K4", 1);
+    if (forms() < FORMS_ALL) return false;
     const long gib = 1L << 30;
-    static const int onsp = wino::tune("VQ2_WINO_SP", 1);
     if (P.phases == 4)   // sub-pixel conv-transpose: F(2,2) per output phase
-        return onsp && P.KH == 2 && P.KW == 2 && P.K == 4 * P.Ci && P.Hy == 2 * P.H && P.Wy == 2 * P.W &&
+        return P.KH == 2 && P.KW == 2 && P.K == 4 * P.Ci && P.Hy == 2 * P.H && P.Wy == 2 * P.W &&
                ((P.W % 64 == 0 && P.H % 4 == 0) || (P.W % 32 == 0 && P.H % 8 == 0)) && P.Ci % wino::BK == 0 && P.Ci >= 32 && P.Co % 64 == 0 && P.ldx % 4 == 0 &&
                (long)P.N * P.H * P.W * P.ldx * 4 < gib && (long)P.N * P.Hy * P.Wy * P.ldy * 4 < gib &&
                (long)P.N * P.Hy * P.Wy * (P.ldm > P.ldr ? P.ldm : P.ldr) * 4 < gib && (long)4 * P.Co * P.K * 4 < gib;
-    if (on4 && P.KH == 4 && P.KW == 4 && P.stride == 2 && P.pad_h == 1 && P.pad_w == 1 && P.phases == 1)   // F(2,2) by parity
+    if (P.KH == 4 && P.KW == 4 && P.stride == 2 && P.pad_h == 1 && P.pad_w == 1 && P.phases == 1)   // F(2,2) by parity
         return 2 * P.Ho == P.H && 2 * P.Wo == P.W && P.Hy == P.Ho && P.Wy == P.Wo &&
                ((P.Wo % 64 == 0 && P.Ho % 2 == 0) || (P.Wo % 32 == 0 && P.Ho % 4 == 0)) &&
                P.Ci % wino::BK == 0 && P.Ci >= 32 && P.Co % 64 == 0 && P.ldx % 4 == 0 &&
@@ -698,12 +681,9 @@ bool wino3_ok(const ConvGemmParams &P) {
                (long)P.N * P.H * P.W * P.ldx * 4 < gib && (long)P.N * P.Ho * P.Wo * P.ldy * 4 < gib &&
                (long)P.N * P.Ho * P.Wo * (P.ldm > P.ldr ? P.ldm : P.ldr) * 4 < gib && (long)P.Co * P.K * 4 < gib;
     const bool rows64 = P.W % 64 == 0 && P.H % 2 == 0, rows32 = P.W % 32 == 0 && P.H % 4 == 0;
-    static const int minci = wino::tune("VQ2_WINO_MINCI", 32);   // (3x3 32 -> 128 at 64x64: 89.6 -> 74.5 us)
-    // (diagnostic only -- a non-zero value makes the choice, and with it the rounding, depend on the batch size)
-    static const int minwg = wino::tune("VQ2_WINO_MINWG", 0);    // fewest 64-pair x 64-channel tiles worth a Winograd launch
-    if ((long)P.N * P.H * P.W / 128 * (P.Co / 64) < minwg) return false;
-    return on && P.KH == 3 && P.KW == 3 && P.stride == 1 && P.pad_h == 1 && P.pad_w == 1 && P.phases == 1 &&
-           P.Ho == P.H && P.Wo == P.W && P.Hy == P.H && P.Wy == P.W && P.Ci % wino::BK == 0 && P.Ci >= minci &&
+    // (from 32 input channels: 3x3 32 -> 128 at 64x64, 89.6 -> 74.5 us)
+    return P.KH == 3 && P.KW == 3 && P.stride == 1 && P.pad_h == 1 && P.pad_w == 1 && P.phases == 1 &&
+           P.Ho == P.H && P.Wo == P.W && P.Hy == P.H && P.Wy == P.W && P.Ci % wino::BK == 0 && P.Ci >= 32 &&
            P.Co % 64 == 0 && (rows64 || rows32) && P.ldx % 4 == 0 &&
            (long)P.N * P.H * P.W * P.ldx * 4 < gib && (long)P.N * P.H * P.W * P.ldy * 4 < gib &&
            (long)P.N * P.H * P.W * (P.ldm > P.ldr ? P.ldm : P.ldr) * 4 < gib && (long)P.Co * P.K * 4 < gib;
@@ -714,8 +694,7 @@ int launch_wino3(const ConvGemmParams &P, hipStream_t s) {
     // 128-channel tiles where they still give every CU two workgroups; 64-channel tiles otherwise (64-channel outputs, the
     // 32x32 level)
     const long wgs128 = (long)P.N * P.Ho * P.Wo / 128 * (P.Co / 128);
-    static const int force = wino::tune("VQ2_WINO_TILE", 0);     // 1: 128-channel tiles whenever possible, 2: 64-channel tiles
-    const bool wide = P.Co % 128 == 0 && (force == 1 || (force != 2 && wgs128 >= 400));
+    const bool wide = P.Co % 128 == 0 && wgs128 >= 400;
     if (P.KH == 4) {
         if (P.Wo % 64 == 0 && P.Ho % 2 == 0)
             return wide ? wino::launch_k4s2<32, 2, 128>(P, s) : wino::launch_k4s2<32, 1, 64>(P, s);

@@ -549,8 +549,14 @@ def conv_op(x, weight, bias, spec, relu_in=False, relu_out=False, residual=None,
     return ConvFn.apply(x, weight, bias, residual, spec, flags, out, grad_stash, mask_input, premasked)
 
 
+# VQ2_FORMS (read once per process, like the library: csrc/vq2_common.h): "all" (default) or "direct" keep the fused
+# kernels; "general" runs only the general kernels, and with them the ResBlock as separate conv launches
+_FORMS = os.environ.get("VQ2_FORMS", "all")
+if _FORMS not in ("all", "direct", "general"):
+    raise ValueError(f"VQ2_FORMS={_FORMS!r}: expected all, direct or general")
+
 # one-launch ResBlock forward (csrc/vq2_resblock.hip) where the channel counts allow it
-RESBLOCK_FUSED = [os.environ.get("VQ2_RB_FUSED", "1") != "0"]
+RESBLOCK_FUSED = [_FORMS != "general"]
 
 
 class ResBlockFn(Function):
