@@ -41,10 +41,11 @@ typedef void *vq2_stream_t;
 
 /* ABI revision of THIS header.  It moves whenever an entry point changes its argument list or the meaning of an
  * argument / workspace (revision 2: vq2_vq_fwd lost its counts/sumsT arguments and vq2_vq_fwd_workspace_floats
- * went from (M) to (M, D, K); revision 3: round-3 additions, see INTEGRATION.md "ABI history").  vq2_version()
+ * went from (M) to (M, D, K); revision 3: round-3 additions; revision 4: the two diagnostic probe exports removed;
+ * see INTEGRATION.md "ABI history").  vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 3
+#define VQ2_API_VERSION 4
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -302,9 +303,6 @@ int vq2_comm_destroy(void);
 int vq2_debug_mfma_peak(float *scratch, int32_t blocks, int32_t iters, vq2_stream_t stream);
 /* same through v_mfma_f32_16x16x4_f32: iters x 64 MFMAs per wave, 2*16*16*4 FLOP each */
 int vq2_debug_mfma_peak16(float *scratch, int32_t blocks, int32_t iters, vq2_stream_t stream);
-/* diagnostic only: lifetime clocks of four workgroups of the dominant 3x3 conv kernels into buf[16] (NULL = off) */
-int vq2_debug_set_rb_stamps(unsigned long long *buf); /* same for the fused ResBlock backward kernel: buf[64] */
-int vq2_debug_set_stamps(unsigned long long *buf);
 
 #ifdef __cplusplus
 }

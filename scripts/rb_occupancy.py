@@ -19,7 +19,7 @@ for n, hw in ((32, 32), (64, 32), (128, 32), (8, 64), (16, 64), (32, 64), (64, 6
         y.backward(g)
     import time
     t0 = time.time()
-    while time.time() - t0 < 1.0:       # the clock needs ~1 s of load to settle (scripts/clock_probe.py)
+    while time.time() - t0 < 1.0:       # the clock needs ~1 s of load to settle ("What the peak is")
         for _ in range(20):
             run()
         torch.cuda.synchronize()

@@ -54,10 +54,9 @@ def _run(world, rank, imgs, steps, warm=False):
     return {k: v.detach().cpu().numpy() for k, v in m.state_dict().items()}, float(out["loss"])
 
 
-def _worker(rank, world, port, out, wgrad_stream, warm=False):
+def _worker(rank, world, port, out, warm=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
-    os.environ["VQ2_WGRAD_STREAM"] = wgrad_stream
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     full = O.make_images(4, 32, 1234)
@@ -67,10 +66,9 @@ def _worker(rank, world, port, out, wgrad_stream, warm=False):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("wgrad_stream", ["0", "1"])
-def test_two_rank_trainer_equals_single_rank_on_full_batch(tmp_path, wgrad_stream):
+def test_two_rank_trainer_equals_single_rank_on_full_batch(tmp_path):
     out = str(tmp_path / "dp_gpu")
-    mp.spawn(_worker, args=(2, _free_port(), out, wgrad_stream), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, _free_port(), out), nprocs=2, join=True)
     r0, r1 = np.load(out + ".rank0.npz"), np.load(out + ".rank1.npz")
     ref, _ = _run(1, 0, O.make_images(4, 32, 1234), 2)
     for k, v in ref.items():
@@ -84,7 +82,7 @@ def test_initial_broadcast_drops_the_prepared_codebook_cache(tmp_path):
     trainer's initial broadcast they must search rank 0's (replicas bit-identical, and equal to one rank that started
     from rank 0's state and saw the whole batch)."""
     out = str(tmp_path / "dp_warm")
-    mp.spawn(_worker, args=(2, _free_port(), out, "1", True), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, _free_port(), out, True), nprocs=2, join=True)
     r0, r1 = np.load(out + ".rank0.npz"), np.load(out + ".rank1.npz")
     for k in r0.files:
         assert np.array_equal(r0[k], r1[k]), f"{k}: replicas diverged (stale prepared codebook on rank 1?)"

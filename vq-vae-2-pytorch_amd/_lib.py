@@ -91,8 +91,6 @@ def _load():
         "vq2_comm_destroy": (C.c_int, []),
         "vq2_debug_mfma_peak": (C.c_int, [P, I32, I32, P]),
         "vq2_debug_mfma_peak16": (C.c_int, [P, I32, I32, P]),
-        "vq2_debug_set_rb_stamps": (C.c_int, [P]),
-        "vq2_debug_set_stamps": (C.c_int, [P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

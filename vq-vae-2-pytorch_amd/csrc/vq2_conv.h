@@ -24,7 +24,6 @@ struct ConvGemmParams {
     int c4_tpw;           // conv_k4s2_c4_kernel: tiles per workgroup
     int ci_real;          // real input channels (<= Ci; the rest are zero padding), 0 = Ci
     double flops, bytes;  // algorithmic work of this launch (for the profiler only)
-    unsigned long long *stamps;  // diagnostic build only (STAMP): per-phase cycle totals of workgroup 0
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
 
 
 // ====================================================================== low-VALU variant of the kernel
-// Cycle stamps (of a phase-stamp build of the kernel above, since removed) showed that with two waves per SIMD
+// Cycle counts (of a phase-timing build of the kernel above, since removed) showed that with two waves per SIMD
 // the partner's fp32 MFMAs starve a wave's vector ALU: the ~200 address/bounds instructions per chunk of the
 // kernel above stretch from ~1.0k to ~4.8k cycles, and the LDS-store/barrier phases end up unhidden.  This variant does the
 // same math with ~1/5 of the VALU work:
@@ -259,13 +259,8 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
 // per-thread (kh, kw) counter) -- all 1,024 tiles of a 64x64-resolution layer are then resident at once: ONE
 // round, so one exposed prologue and one epilogue burst per launch instead of two.
 // UNI (Ci % BK == 0, K % BK == 0: every layer but the 3-channel ones): see the scalar k tracking below.
-// CLOCK (diagnostic instantiation only, scripts/clock_probe.py): four workgroups leave their lifetime in shader cycles
-// (s_memtime) and in 10 ns ticks (s_memrealtime) -- the in-kernel clock the chip holds under this kernel's load.
-template <int WAVES_M, int WAVES_N, int MT, int NT, int BK, bool PIPE, bool RELU_IN, bool OCC4 = false, bool UNI = OCC4, bool TAPIN = false,
-          bool CLOCK = false>
+template <int WAVES_M, int WAVES_N, int MT, int NT, int BK, bool PIPE, bool RELU_IN, bool OCC4 = false, bool UNI = OCC4, bool TAPIN = false>
 __global__ __launch_bounds__(256, OCC4 ? 4 : ((MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1)) void conv_gemm_fast_kernel(const ConvGemmParams P) {
-    unsigned long long clk_t0 = 0, clk_r0 = 0;
-    if constexpr (CLOCK) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
     constexpr int LDK = BK + 4;
     constexpr int BM = WAVES_M * MT * 32;
     constexpr int BN = WAVES_N * NT * 32;
@@ -577,17 +572,7 @@ __global__ __launch_bounds__(256, OCC4 ? 4 : ((MT * NT == 4) ? (BK == 16 ? 3 : 2
             }
         }
     }
-    if constexpr (CLOCK) {
-        if (P.stamps && tid == 0 && (blockIdx.x & 255) == 8 && blockIdx.x < 1024) {
-            const int slot = blockIdx.x >> 8;
-            P.stamps[slot * 4 + 0] = __builtin_amdgcn_s_memtime() - clk_t0;
-            P.stamps[slot * 4 + 1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
-            P.stamps[slot * 4 + 2] = (unsigned long long)nchunks * (BK / 2) * MT * NT;   // MFMAs of one wave
-        }
-    }
 }
-
-static unsigned long long *g_stamps = nullptr;  // set by vq2_debug_set_stamps: diagnostic cycle stamps
 
 template <int WAVES_M, int WAVES_N, int MT, int NT, int BK, bool OCC4 = false>
 static int launch_conv_gemm_fast(const ConvGemmParams &P, hipStream_t s) {
@@ -605,13 +590,6 @@ static int launch_conv_gemm_fast(const ConvGemmParams &P, hipStream_t s) {
                           : (uni ? (tap_inner ? conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, true>
                                               : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, false>)
                                  : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, OCC4>);
-    ConvGemmParams Q = P;
-    if constexpr (OCC4) {   // in-kernel clock probe of the dominant instantiation (vq2_debug_set_stamps)
-        if (g_stamps && tap_inner && !P.relu_in) {
-            kern = conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, true, true>;
-            Q.stamps = g_stamps;
-        }
-    }
     allow_big_lds(kern, lds);
     dim3 grid(nwg);
     const char *name = "conv_gemm";
@@ -619,7 +597,7 @@ static int launch_conv_gemm_fast(const ConvGemmParams &P, hipStream_t s) {
         name = prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d", BM, BN, BK, P.M, P.Co, P.K, P.KH, P.stride,
                           P.phases);
     ProfScope prof(name, P.flops, P.bytes, s, BM == 128 && BN == 128);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, Q);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, P);
     return check_launch("conv_gemm_fast_kernel");
 }
 
@@ -1216,11 +1194,7 @@ static int run_conv_gemm(const ConvGemmParams &P, hipStream_t s) {
                          (long)P.Co * P.K * P.phases < lim;
     if (fast_ok && conv_c4_ok(P)) return launch_conv_c4(P, s);
     if (fast_ok && conv_k64_ok(P)) return launch_conv_k64(P, s);
-    if (fast_ok && wino3_ok(P)) {   // vq2_wino.hip
-        ConvGemmParams Q = P;
-        Q.stamps = g_stamps;        // (non-null only under vq2_debug_set_stamps: the clock-probe instantiation)
-        return launch_wino3(Q, s);
-    }
+    if (fast_ok && wino3_ok(P)) return launch_wino3(P, s);   // vq2_wino.hip
     const long big = 0x7F000000L / 4;   // the patch kernel's out-of-range sentinel must stay above every tensor
     // (a launch of <= 256 workgroups with a short depth is better off with the 64-row GEMM tiles: measured)
     const long sp_wgs = (long)P.N * ((P.W + sp::TW - 1) / sp::TW) * ((P.H + sp::TH - 1) / sp::TH) * (P.Co / 64);
@@ -1630,11 +1604,4 @@ extern "C" int vq2_conv_dgrad_ex(const vq2_conv_desc *d, int flags, const float 
                          cir * cor * d->KH * d->KW);
     }
     return run_conv_gemm(P, to_stream(stream));
-}
-
-// diagnostic only (scripts/clock_probe.py): when set, the 3x3 Winograd kernel and the direct four-per-CU tile run their
-// CLOCK instantiations, and four workgroups write their lifetime in cycles and in 10 ns ticks to buf[16]
-extern "C" int vq2_debug_set_stamps(unsigned long long *buf) {
-    g_stamps = buf;
-    return VQ2_OK;
 }

@@ -57,7 +57,6 @@ struct ResFwdParams {
     int N, H, W, ldx, ldr, ldy;
     int tiles_x, tiles_y;
     int relu_out;
-    unsigned long long *stamps; // diagnostic (vq2_debug_set_rb_stamps): s_memtime at the phase boundaries of 2 workgroups
 };
 
 __device__ __forceinline__ float4 u4_as_f4(u32x4 v) {
@@ -79,14 +78,6 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wq = wave;
     const int l31 = lane & 31, fk = 4 * (lane >> 5);
-    const int stamp_slot = (P.stamps && (blockIdx.x == 8 || blockIdx.x == 520)) ? (blockIdx.x == 8 ? 0 : 1) : -1;
-    auto stamp = [&](int i) {
-        if (stamp_slot >= 0 && lane == 0) {
-            P.stamps[(stamp_slot * 4 + wq) * 8 + i] = __builtin_amdgcn_s_memtime();
-            if (i == 0 || i == 5) P.stamps[(stamp_slot * 4 + wq) * 8 + (i == 0 ? 6 : 7)] = __builtin_amdgcn_s_memrealtime();
-        }
-    };
-    stamp(0);
     const int tiles = P.tiles_x * P.tiles_y;
     const int vid = xcd_remap(blockIdx.x, gridDim.x);
     const int n = vid / tiles;
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
     // hit the 16-byte LDS slots exactly like 32 consecutive rows do -- conflict-free ds_read_b128 for every tap.
     const int a_frag = ((2 * wq + (l31 >> 4)) * PW + (l31 < 16 ? l31 : ((l31 + 14) & 15))) * LDK + fk;
     const int b_frag = l31 * LDK + fk;
-    // Staging INSIDE the MFMA stream (round 3).  Fine stamps of a slice iteration (a diagnostic build, since removed): 4,651 cycles of
+    // Staging INSIDE the MFMA stream (round 3).  Fine s_memtime timings of a slice iteration (a diagnostic build, since removed): 4,651 cycles of
     // MFMAs (72 x 64: the chain itself is perfect), but 909 cycles to ISSUE the eight buffer loads of the slice after next
     // and 525 for the eight LDS stores of the next one, all in front of the first MFMA -- a quarter of the iteration with an
     // idle matrix pipe when the wave is alone on its SIMD.  A vector-memory or LDS-store instruction issued right behind an
@@ -255,7 +246,6 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
     issue_loads(1, R1);
     store_slice(0, R0);
     __syncthreads();
-    stamp(1);
     // slice 0: the registers R1 hold slice 1 (requested up front), R0 is free for slice 2
     store_slice(1, R1);
     __builtin_amdgcn_sched_barrier(0);
@@ -269,7 +259,6 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
     }
-    stamp(2);
     // every wave is past its last fragment read: the staging buffers may be overwritten
     // r = relu(acc1 + b1): to LDS for stage 2 now; its 16 stores to HBM (the backward pass needs r) are issued behind the
     // MFMAs of stage 2's first column block, and the 16 stores of every finished column block behind the MFMAs of the
@@ -291,7 +280,6 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
         }
     }
     // a wave reads back only the 32 rows it wrote itself (LDS operations of one wave complete in order): no barrier
-    stamp(3);
     // ---- stage 2: 1x1 conv on the r tile, on top of x + b2
     const int relu_floor_bits = P.relu_out ? 0 : (int)0x80000000;
     {
@@ -326,15 +314,12 @@ __global__ __launch_bounds__(256, 2) void resblock_fwd_kernel(const ResFwdParams
             }
         }
     }
-    stamp(4);
     // ---- epilogue: optional trailing ReLU (vqvae.py:122,144) and store of the last column block
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float v = relu_floor(acc2[NJ - 1][r], relu_floor_bits);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, yoff[r] + (NJ - 1) * 128, 0, 0);
     }
-    if (stamp_slot >= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(5);
 }
 
 
@@ -371,7 +356,6 @@ struct ResBwdParams {
     float *b2_slab;    // [grid][128 co]        partial 1x1 bias gradients (with w2_slab)
     int N, H, W, ldg, ldr, ldx, lddh, lddx;
     int tiles_x, tiles_y;
-    unsigned long long *stamps;   // diagnostic (vq2_debug_set_stamps): s_memtime at the phase boundaries of 2 workgroups
 };
 
 template <bool SAME_LD>
@@ -385,15 +369,6 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
 
     const int tid = threadIdx.x, lane = tid & 63, wq = tid >> 6;
     const int l31 = lane & 31, fk = 4 * (lane >> 5), rowq = 4 * (lane >> 5);
-    const int stamp_slot = (P.stamps && (blockIdx.x == 8 || blockIdx.x == 520)) ? (blockIdx.x == 8 ? 0 : 1) : -1;
-    auto stamp = [&](int i) {
-        if (stamp_slot >= 0 && lane == 0) {
-            P.stamps[(stamp_slot * 4 + wq) * 8 + i] = __builtin_amdgcn_s_memtime();
-            // slots 6 / 7: the 100 MHz real-time counter at the first / last stamp (in-kernel clock = cycles / time)
-            if (i == 0 || i == 5) P.stamps[(stamp_slot * 4 + wq) * 8 + (i == 0 ? 6 : 7)] = __builtin_amdgcn_s_memrealtime();
-        }
-    };
-    stamp(0);
     const int tiles = P.tiles_x * P.tiles_y;
     const int vid = xcd_remap(blockIdx.x, gridDim.x);
     const int n = vid / tiles;
@@ -456,7 +431,7 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
         for (int q = 0; q < 16; ++q) {
             // (the load is UNCONDITIONAL with a poisoned offset for the waves that have no second block: written as
             //  `cond ? load : 0` hipcc branches around every load and waits vmcnt(0) behind each -- 16 dependent memory
-            //  round trips in front of the first MFMA, the whole "prologue" of round 2's stamps)
+            //  round trips in front of the first MFMA, the whole "prologue" of round 2's phase timings)
             const int pix = __shfl(pixA[bi], rowq + (q & 3) + 8 * (q >> 2), 64);
             rmask[bi][q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
                 rr, (bi < nblk && pix >= 0) ? pix * P.ldr * 4 + l31 * 4 : OOB, 0, 0));
@@ -497,7 +472,6 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
 
     store_a(0, RA0);
     __syncthreads();
-    stamp(1);
     // same pipeline as the forward kernel: slice s+1 goes from registers to LDS at the START of iteration s, the next
     // request follows at once, the barrier directly follows the MFMAs
 #pragma unroll
@@ -559,7 +533,6 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
             __syncthreads();   // the scratch is rewritten by the next slice
         }
     }
-    stamp(2);
     // every wave is past its last phase-A fragment read: Dh and Wb may overwrite the slice buffers.  Tap 0's panel
     // (requested two slices ago) goes to LDS first and tap 1's is requested before the dh write, so that neither is
     // waited for at a barrier.
@@ -586,7 +559,6 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
         }
     }
     __syncthreads();
-    stamp(3);
 
     // ---------------------------------------------------------------- phase B: 3x3 data gradient from the dh patch
     f32x16 acc[4];
@@ -678,7 +650,6 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
         }
         __syncthreads();
     }
-    stamp(4);
     // ---------------------------------------------------------------- epilogue: outer ReLU mask, skip gradient
     const __amdgpu_buffer_rsrc_t rdx = __builtin_amdgcn_make_buffer_rsrc(P.dx, 0, npix * P.lddx * 4, RSRC_FLAGS);
 #pragma unroll
@@ -691,15 +662,9 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_data_kernel(const ResBwdP
                 __float_as_uint(v), rdx,
                 SAME_LD ? poff[q] : (pixr[SAME_LD ? 0 : q] >= 0 ? pixr[SAME_LD ? 0 : q] * P.lddx * 4 + l31 * 4 : OOB), j * 128, 0);
         }
-    if (stamp_slot >= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(5);
 }
 
 }  // namespace vq2
-
-static unsigned long long *g_rb_stamps = nullptr, *g_rb_stamps_fwd = nullptr;
-// buf[64]: backward kernel; buf + 64 (another 64 words): forward kernel
-extern "C" int vq2_debug_set_rb_stamps(unsigned long long *buf) { g_rb_stamps = buf; g_rb_stamps_fwd = buf ? buf + 64 : nullptr; return VQ2_OK; }
 
 extern "C" int vq2_resblock_supported(int32_t C, int32_t Cm) { return (C == vq2::rb::CC && Cm == vq2::rb::CM) ? 1 : 0; }
 
@@ -725,7 +690,7 @@ extern "C" int vq2_resblock_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int3
         RbwFwdParams Q{};
         Q.x = x; Q.w1 = w1p; Q.b1 = b1; Q.w2 = w2p; Q.b2 = b2; Q.r = r; Q.y = y;
         Q.N = N; Q.H = H; Q.W = W; Q.ldx = ldx; Q.ldr = ldr; Q.ldy = ldy; Q.relu_out = (flags & VQ2_RELU_OUT) != 0;
-        if (ldr >= Cm && rbw_fwd_ok(Q) && !g_rb_stamps_fwd) {
+        if (ldr >= Cm && rbw_fwd_ok(Q)) {
             hipStream_t s = to_stream(stream);
             const char *name = "resblock_fwd_wino";
             if (prof_enabled()) name = prof_label("resblock_fwd_wino|M=%d,C=%d,Cm=%d", N * H * W, C, Cm);
@@ -739,7 +704,6 @@ extern "C" int vq2_resblock_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int3
     P.tiles_x = (W + rb::TW - 1) / rb::TW; P.tiles_y = (H + rb::TH - 1) / rb::TH;
     P.relu_out = (flags & VQ2_RELU_OUT) != 0;
     const int grid = N * P.tiles_x * P.tiles_y;
-    P.stamps = g_rb_stamps_fwd;
     hipStream_t s = to_stream(stream);
     const char *name = "resblock_fwd";
     if (prof_enabled()) name = prof_label("resblock_fwd|M=%d,C=%d,Cm=%d", N * H * W, C, Cm);
@@ -794,7 +758,6 @@ extern "C" int vq2_resblock_bwd_data(int32_t N, int32_t H, int32_t W, int32_t C,
     P.N = N; P.H = H; P.W = W; P.ldg = ldg; P.ldr = ldr; P.ldx = ldx; P.lddh = lddh; P.lddx = lddx;
     P.tiles_x = (W + rb::TW - 1) / rb::TW; P.tiles_y = (H + rb::TH - 1) / rb::TH;
     const int grid = N * P.tiles_x * P.tiles_y;
-    P.stamps = g_rb_stamps;
     hipStream_t s = to_stream(stream);
     const char *name = "resblock_bwd_data";
     if (prof_enabled()) name = prof_label("resblock_bwd_data|M=%d,C=%d,Cm=%d", N * H * W, C, Cm);

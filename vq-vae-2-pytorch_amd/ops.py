@@ -247,7 +247,7 @@ class WgradBatch:
         self.tables = {}
         self.dirty = True
 
-    def launch(self, spec, x, dy, relu_in, weight, bias, want_db, side=None):
+    def launch(self, spec, x, dy, relu_in, weight, bias, want_db, side):
         n, h, w, _ = x.shape
         key = (id(weight), n, h, w, ld_of(x), ld_of(dy), relu_in)
         d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
@@ -262,9 +262,9 @@ class WgradBatch:
             ent = {"ws": ws, "nbytes": nbytes, "job": job, "dw": dw, "db": db, "used": False}
             self.entries[key] = ent
             self.dirty = True
-        if side is not None and n * h * w > WGRAD_STREAM_MAX_PIXELS:
-            side = None        # a launch that fills the chip by itself gains nothing from a second stream
-        if side is not None:   # off the backward critical path: overlaps the next layers' data gradients
+        # off the backward critical path: overlaps the next layers' data gradients.  A launch that fills the chip by
+        # itself gains nothing from a second stream.
+        if n * h * w <= WGRAD_STREAM_MAX_PIXELS:
             side.wait_event(torch.cuda.current_stream().record_event())
             with torch.cuda.stream(side):
                 check(lib.vq2_conv_wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
@@ -327,13 +327,13 @@ class WgradBatch:
 
 class StepContext:
     """What one Stage1Trainer's backward pass shares between its layers: the deferred split-K reduction
-    (WgradBatch) and the optional side stream for weight gradients.  Hung on the trainer's own parameters as
+    (WgradBatch) and the side stream for weight gradients.  Hung on the trainer's own parameters as
     `_vq2_ctx`; `active` only while that trainer's backward runs (a stand-alone .backward() on the same model
     takes the immediate per-layer path).  Weight gradients are off the backward critical path (only the optimizer
     consumes them), so on a side stream they overlap the next layers' data-gradient launches; only legal when
     they land in arena slots that nobody reads before the trainer joins the streams."""
 
-    def __init__(self, wgrad_stream=None):
+    def __init__(self, wgrad_stream):
         self.batch = WgradBatch()
         self.stream = wgrad_stream
         self.active = False
@@ -347,7 +347,7 @@ def _step_ctx(weight):
 # Only launches too small to fill the chip go to the side stream (measured on MI355X, batch 32: the 32x32-resolution
 # layers, <= 32,768 pixels: 7.19 -> 7.13 ms per step; every weight gradient there: 7.34 -- two chip-filling kernels
 # of different streams do not share CUs usefully)
-WGRAD_STREAM_MAX_PIXELS = int(os.environ.get("VQ2_WGRAD_STREAM_MAXPIX", "40000"))
+WGRAD_STREAM_MAX_PIXELS = 40000
 
 
 def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=True):
@@ -363,8 +363,8 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
         return (dw if want_dw else None), db
     dw = _grad_slot(weight)
     db = _grad_slot(bias) if (bias is not None and want_db) else None
-    side = sc.stream if sc is not None else None
-    if side is not None and getattr(weight, "_vq2_grad", None) is not None and dw.data_ptr() == weight._vq2_grad.data_ptr():
+    if sc is not None and getattr(weight, "_vq2_grad", None) is not None and dw.data_ptr() == weight._vq2_grad.data_ptr():
+        side = sc.stream
         side.wait_event(torch.cuda.current_stream().record_event())
         with torch.cuda.stream(side):
             ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)

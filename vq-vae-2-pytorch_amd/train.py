@@ -57,13 +57,12 @@ class Stage1Trainer:
             hp.wait_stream(torch.cuda.current_stream())
             torch.cuda.set_stream(hp)
         # this trainer's backward-pass state hangs on ITS parameters (no process-global state)
-        wgrad_stream = torch.cuda.Stream() if os.environ.get("VQ2_WGRAD_STREAM", "1") != "0" else None
+        wgrad_stream = torch.cuda.Stream()
         self.ctx = ops.StepContext(wgrad_stream)
         for p in self.arena.params:
             p._vq2_ctx = self.ctx
-        if os.environ.get("VQ2_STATS_STREAM", "1") != "0":
-            for q in self.quantizers:      # the EMA statistics are consumed after backward: off the main stream
-                q.stats_stream = wgrad_stream
+        for q in self.quantizers:      # the EMA statistics are consumed after backward: off the main stream
+            q.stats_stream = wgrad_stream
         # every weight panel (forward and data-gradient layouts) re-packed by one launch per step
         layers = []
         for name, mod in model.named_modules():
@@ -94,12 +93,9 @@ class Stage1Trainer:
         self._sent = []             # [lo, hi) slices of flat_g already handed to the communicator in this step
         self._hooks_seen = {}
         self.buckets = []           # (name, lo, hi, params of the slice)
-        self._send_early = False
-        self.early_flush = os.environ.get("VQ2_EARLY_FLUSH", "1") != "0" and self.ctx.stream is not None
-        overlap = self.dp and os.environ.get("VQ2_DP_OVERLAP", "1") != "0"
         split = getattr(model, "quantize_conv_b", None)
         enc_t = getattr(model, "enc_t", None)
-        if split is not None and enc_b is not None and enc_t is not None and (self.early_flush or overlap):
+        if split is not None and enc_b is not None and enc_t is not None:
             a = self.arena
             off = lambda p: a.n_extra + a.offset[id(p)]
             lo_tail = off(split.weight)
@@ -110,10 +106,9 @@ class Stage1Trainer:
                             ("middle", 0, lo_tail, inside(0, lo_tail)),
                             ("head", lo_head, total, inside(lo_head, total))]
             self.bucket_bytes = {name: 4 * (hi - lo) for name, lo, hi, _ in self.buckets}
-            self._send_early = overlap
             for prm in (split.weight, split.bias):
                 prm.register_post_accumulate_grad_hook(lambda _p: self._group_done("tail", 2))
-            if overlap:     # (single GPU: one early slab reduction is enough, a second one only adds a launch)
+            if self.dp:     # (single GPU: one early slab reduction is enough, a second one only adds a launch)
                 first = enc_t.blocks[0]
                 for prm in (first.weight, first.bias):
                     prm.register_post_accumulate_grad_hook(lambda _p: self._group_done("middle", 2))
@@ -145,15 +140,11 @@ class Stage1Trainer:
         if not all(p.grad is not None and p.grad.data_ptr() == p._vq2_grad.data_ptr() for p in params):
             return      # autograd ordered the graph differently: keep the slice for the collective after backward
         side = self.ctx.stream
-        if side is not None:
-            side.wait_event(torch.cuda.current_stream().record_event())
-            with torch.cuda.stream(side):
-                self.ctx.batch.flush()
-                ev = side.record_event()
-        else:
+        side.wait_event(torch.cuda.current_stream().record_event())
+        with torch.cuda.stream(side):
             self.ctx.batch.flush()
-            ev = torch.cuda.current_stream().record_event()
-        if not self._send_early:
+            ev = side.record_event()
+        if not self.dp:
             return
         with torch.cuda.stream(self.comm_stream):
             self.comm_stream.wait_event(ev)
@@ -195,8 +186,7 @@ class Stage1Trainer:
             torch.autograd.backward(roots, seeds)
         finally:
             self.ctx.active = False
-        if self.ctx.stream is not None:
-            torch.cuda.current_stream().wait_stream(self.ctx.stream)   # all slabs written
+        torch.cuda.current_stream().wait_stream(self.ctx.stream)   # all slabs written
         self.ctx.batch.flush()   # one launch reduces the split-K slabs of every layer into the arena
         if self.dp:
             if not self.arena.grads_ready():
