@@ -33,24 +33,28 @@ def amd():
 
 
 RAGGED = [
-    # kind, cin, cout, k, stride, pad, N, H, W
-    ("conv", 8, 12, 3, 1, 1, 1, 5, 7), ("conv", 20, 36, 3, 1, 1, 3, 9, 4), ("conv", 4, 8, 1, 1, 0, 2, 1, 1),
-    ("conv", 12, 8, 5, 1, 2, 1, 6, 6), ("conv", 16, 40, 7, 1, 3, 1, 8, 5), ("conv", 3, 8, 4, 2, 1, 2, 10, 6),
-    ("conv", 36, 132, 4, 2, 1, 1, 12, 8), ("conv", 5, 7, 3, 1, 1, 2, 4, 4), ("conv", 160, 136, 3, 1, 1, 1, 13, 11),
-    ("convT", 8, 12, 4, 2, 1, 1, 3, 5), ("convT", 20, 3, 4, 2, 1, 2, 5, 3), ("convT", 16, 2, 4, 2, 1, 1, 4, 70),
-    ("convT", 132, 68, 4, 2, 1, 1, 6, 7), ("convT", 5, 6, 4, 2, 1, 1, 2, 2),
-    # shapes that take the LDS-patch sub-pixel kernel (output channels % 64 == 0, reduction channels % 16 == 0):
-    # ragged tiles, two 64-channel groups, and the data gradient of a stride-2 conv
-    ("convT", 32, 64, 4, 2, 1, 2, 5, 19), ("convT", 16, 128, 4, 2, 1, 1, 9, 33), ("conv", 64, 48, 4, 2, 1, 2, 10, 14),
-    ("conv", 128, 32, 4, 2, 1, 1, 18, 34),
+    # kind, cin, cout, k, stride, pad, N, H, W, what runs the forward / data gradient ("gemm": conv_gemm_fast_kernel tiles;
+    # "general": conv_gemm_kernel for both, more than 32 taps; "gemm4": the 64-row conv_gemm tiles in four phases;
+    # "small": convT_small forward).  No row of these shapes is a multiple of 32 pixels: every weight gradient is wgrad_kernel.
+    ("conv", 8, 12, 3, 1, 1, 1, 5, 7, "gemm"), ("conv", 20, 36, 3, 1, 1, 3, 9, 4, "gemm"), ("conv", 4, 8, 1, 1, 0, 2, 1, 1, "gemm"),
+    ("conv", 12, 8, 5, 1, 2, 1, 6, 6, "gemm"), ("conv", 16, 40, 7, 1, 3, 1, 8, 5, "general"), ("conv", 3, 8, 4, 2, 1, 2, 10, 6, "gemm"),
+    ("conv", 36, 132, 4, 2, 1, 1, 12, 8, "gemm"), ("conv", 5, 7, 3, 1, 1, 2, 4, 4, "gemm"), ("conv", 160, 136, 3, 1, 1, 1, 13, 11, "gemm"),
+    ("convT", 8, 12, 4, 2, 1, 1, 3, 5, "gemm"), ("convT", 20, 3, 4, 2, 1, 2, 5, 3, "gemm"), ("convT", 16, 2, 4, 2, 1, 1, 4, 70, "small"),
+    ("convT", 132, 68, 4, 2, 1, 1, 6, 7, "gemm"), ("convT", 5, 6, 4, 2, 1, 1, 2, 2, "gemm"),
+    # sub-pixel shapes (output channels % 64 == 0, reduction channels % 16 == 0) with ragged tiles, two 64-channel groups, and
+    # the data gradient of a stride-2 conv.  With K < 512 and a handful of tiles they run the 64-row conv_gemm tiles in four
+    # phases, no longer subpixel_conv_kernel (its gate: >= 512 workgroups or K >= 512 -- both sides of both clauses are cases
+    # of tests/test_gpu_dispatch.py)
+    ("convT", 32, 64, 4, 2, 1, 2, 5, 19, "gemm4"), ("convT", 16, 128, 4, 2, 1, 1, 9, 33, "gemm4"),
+    ("conv", 64, 48, 4, 2, 1, 2, 10, 14, "gemm4"), ("conv", 128, 32, 4, 2, 1, 1, 18, 34, "gemm4"),
     # the <= 3-channel reconstruction kernel (32-channel slices): ragged 8x32 tiles
-    ("convT", 32, 3, 4, 2, 1, 2, 9, 35), ("convT", 64, 2, 4, 2, 1, 1, 17, 5),
+    ("convT", 32, 3, 4, 2, 1, 2, 9, 35, "small"), ("convT", 64, 2, 4, 2, 1, 1, 17, 5, "small"),
 ]
 
 
 def test_ragged_conv_shapes_fwd_and_grads(amd):
     dev = torch.device("cuda:0")
-    for idx, (kind, cin, cout, k, s, p, n, h, w) in enumerate(RAGGED):
+    for idx, (kind, cin, cout, k, s, p, n, h, w, runs) in enumerate(RAGGED):
         tag = f"rag{idx}"
         x = t(rng.normal(3, tag + ".x", (n, cin, h, w)))
         if kind == "conv":
@@ -70,9 +74,28 @@ def test_ragged_conv_shapes_fwd_and_grads(amd):
         gy = t(rng.normal(3, tag + ".gy", tuple(yr.shape)))
         yr.backward(gy)
         xg = x.to(dev).requires_grad_(True)
-        y = m(xg)
+
+        def step():
+            y = m(xg)
+            y.backward(gy.to(dev))
+            return y
+        y, seen = _launched(amd, step)
         assert tuple(y.shape) == tuple(yr.shape), tag
-        y.backward(gy.to(dev))
+        convs = [lab for lab in seen if lab.startswith(("conv", "subpixel", "wgrad"))]
+        # fwd, dgrad, wgrad (the report has one line per label: a square layer's forward and data gradient may share theirs)
+        assert sum(lab.startswith("wgrad<") for lab in convs) == 1 and len(convs) in (2, 3), (tag, seen)
+        assert all(lab.endswith(",gen") for lab in convs if lab.startswith("wgrad<")), (tag, convs)
+        if os.environ.get("VQ2_FORMS", "all") == "general" or runs == "general":   # conv_gemm_kernel (and the one kernel of <= 3 channels)
+            assert all(lab.endswith(",gen") or lab.startswith("convT_small|") for lab in convs), (tag, convs)
+            assert runs != "general" or not any(lab.startswith("convT_small|") for lab in convs), (tag, convs)
+        elif runs == "gemm4":
+            assert sum(lab.startswith("conv_gemm<64x") and ",ph4," in lab and not lab.endswith(",gen") for lab in convs) == 1, (tag, convs)
+            assert not any(lab.startswith("subpixel_conv") for lab in convs), (tag, convs)
+        elif runs == "small":
+            assert any(lab.startswith("convT_small|") for lab in convs), (tag, convs)
+        else:
+            assert any(lab.startswith("conv_gemm<") and not lab.endswith(",gen") for lab in convs), (tag, convs)
+            assert not any(lab.startswith(("convT_small|", "subpixel_conv", "conv_wino")) for lab in convs), (tag, convs)
         close(y, yr, what=tag + ".y")
         close(xg.grad, xr.grad, what=tag + ".gx")
         close(m.weight.grad, wr.grad, rtol=5e-4, atol=1e-4, what=tag + ".gw")

@@ -171,6 +171,105 @@ def test_invalid_arguments_are_rejected_without_gpu(amd):
     assert lib.vq2_adam_step(None, None, None, None, 0, 1e-3, .9, .999, 1e-8, 1, 1.0, None) == 1
     with pytest.raises(RuntimeError):
         amd._lib.check(1, "x")
+    # tensors from 2^31 elements are refused by check_desc before any pointer is looked at (int32 indexing) ...
+    d = amd._lib.ConvDesc()
+    d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad, d.ldx, d.ldy = 2048, 64, 64, 128, 128, 3, 3, 1, 1, 256, 128
+    assert 2048 * 64 * 64 * 256 == 1 << 31
+    assert lib.vq2_conv_fwd(ctypes.byref(d), 0, None, None, None, None, 0, None, None) == 1
+    assert b"exceeds 2^31 elements" in lib.vq2_last_error()
+    d.ldx, d.ldy = 128, 256                                    # ... on the output side as well
+    assert lib.vq2_conv_dgrad(ctypes.byref(d), None, None, None, 0, None, 0, None, 128, None) == 1
+    assert b"exceeds 2^31 elements" in lib.vq2_last_error()
+    d.N = 2047                                                 # one image fewer passes check_desc: the next check speaks
+    assert lib.vq2_conv_fwd(ctypes.byref(d), 0, None, None, None, None, 0, None, None) == 1
+    assert b"null pointer" in lib.vq2_last_error()
+    # ... and a conv-transpose to <= 4 channels from 0x7F000000 bytes (its kernel's out-of-range offset) is unsupported:
+    # 508 images of 128x128x64 are 0x7F000000 bytes exactly, 507 pass (tests/test_gpu_dispatch.py runs those)
+    t = amd._lib.ConvDesc()
+    t.N, t.H, t.W, t.Ci, t.Co, t.KH, t.KW, t.stride, t.pad, t.ldx, t.ldy = 508, 128, 128, 64, 4, 4, 4, 2, 1, 64, 4
+    t.transposed, t.Cir, t.Cor = 1, 64, 3
+    assert 508 * 128 * 128 * 64 * 4 == 0x7F000000
+    # (the refusals below come before any launch, but they need non-null, 16-byte aligned pointers: a real host allocation,
+    #  so that a regression of a refusal cannot hand a kernel an address nobody owns)
+    backing = ctypes.create_string_buffer(4096 + 16)
+    dummy = ctypes.c_void_p((ctypes.addressof(backing) + 15) & ~15)
+    rc = lib.vq2_conv_fwd(ctypes.byref(t), 0, dummy, dummy, None, None, 0, dummy, None)
+    assert rc == 2 and b"limited to tensors below 2130706432 bytes" in lib.vq2_last_error()
+    with pytest.raises(RuntimeError, match="split the batch"):
+        amd._lib.check(rc, "conv_fwd")
+    # the same layer with a residual, ReLU-out or more than 65535 images: its weight panel exists in that kernel's layout only
+    t.N = 2
+    assert lib.vq2_conv_fwd(ctypes.byref(t), 2, dummy, dummy, None, None, 0, dummy, None) == 2
+    assert b"neither a residual nor ReLU-out" in lib.vq2_last_error()
+    assert lib.vq2_conv_fwd(ctypes.byref(t), 0, dummy, dummy, None, dummy, 4, dummy, None) == 2
+    t.N, t.H, t.W = 65536, 1, 1
+    assert lib.vq2_conv_fwd(ctypes.byref(t), 0, dummy, dummy, None, None, 0, dummy, None) == 2
+    assert b"65535 images" in lib.vq2_last_error()
+
+
+def _label_families_in_source():
+    """Every kernel label the library can print, tile included, read from csrc/*.hip: the prof_label format strings, and for
+    the templated launchers the template arguments at their call sites."""
+    src = {f: open(os.path.join(ROOT, "vq-vae-2-pytorch_amd", "csrc", f)).read()
+           for f in os.listdir(os.path.join(ROOT, "vq-vae-2-pytorch_amd", "csrc")) if f.endswith((".hip", ".cpp"))}
+    fams = set(m.split("|")[0] for text in src.values() for m in re.findall(r'prof_label\("([^"]+)"', text))
+    conv, wino, wgrad = src["vq2_conv.hip"], src["vq2_wino.hip"], src["vq2_wgrad.hip"]
+    tiles = {"fast": set(), "gen": set(), "wgrad": set(), "wino": set()}
+    for a, b, c, d_, bk in re.findall(r"return launch_conv_gemm_fast<(\d), (\d), (\d), (\d), (\d+)", conv):
+        tiles["fast"].add("conv_gemm<%dx%dx%s>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32, bk))
+    for a, b, c, d_, bk in re.findall(r"return launch_conv_gemm<(\d), (\d), (\d), (\d), (\d+)", conv):
+        tiles["gen"].add("conv_gemm<%dx%dx%s>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32, bk))
+    for a, b, c, d_ in re.findall(r"launch_wgrad<(\d), (\d), (\d), (\d)>\(P", wgrad):
+        tiles["wgrad"].add("wgrad<%dx%d>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32))
+    cand = re.search(r"cand\[6\]\[2\] = \{(.*?)\};", wgrad).group(1)
+    assert tiles["wgrad"] == set("wgrad<%sx%s>" % t for t in re.findall(r"\{(\d+), (\d+)\}", cand))   # launchers == candidates
+    for tpw, nt in re.findall(r"wino::launch<(\d+), (\d), \d+>", wino):
+        tiles["wino"].add("conv_wino3<%dx%d,nt%s>" % (64 // int(tpw), 2 * int(tpw), nt))
+    for tpw, nt in re.findall(r"wino::launch_k4s2<(\d+), (\d), \d+>", wino):
+        tiles["wino"].add("conv_wino_k4s2<%dx%d,nt%s>" % (64 // int(tpw), 2 * int(tpw), nt))
+    for tpw in re.findall(r"wino::launch_subpixel2<(\d+)>", wino):
+        tiles["wino"].add("conv_wino_subpixel<%dx%d>" % (128 // int(tpw), 2 * int(tpw)))
+    return fams, tiles
+
+
+def test_every_kernel_label_in_the_source_has_a_dispatch_case():
+    """Census without a GPU: a kernel family or a tile added to csrc/ without a case in tests/test_gpu_dispatch.py fails here.
+    (The GPU side of the census asserts that the table really produces EXPECTED_LABELS.)"""
+    import test_gpu_dispatch as D
+    fams, tiles = _label_families_in_source()
+    assert len(tiles["fast"]) == 8 and len(tiles["gen"]) == 5 and len(tiles["wgrad"]) == 6 and len(tiles["wino"]) == 10, tiles
+    exp = D.EXPECTED_LABELS
+    fam_of = lambda labels: set(l.split("|")[0] for l in labels)
+    # every family name (the text before '<' or '|') is covered by the table or is a non-conv family with tests of its own
+    covered = set(f.split("<")[0] for f in fam_of(exp["all"] | exp["general"] | D.BIG_LABELS)) | D.OTHER_FAMILIES
+    assert set(f.split("<")[0] for f in fams) <= covered, sorted(set(f.split("<")[0] for f in fams) - covered)
+    fast = set(l.split("|")[0] for l in exp["all"] if l.startswith("conv_gemm") and not l.endswith("|gen"))
+    assert tiles["fast"] == fast, (sorted(tiles["fast"] - fast), sorted(fast - tiles["fast"]))
+    gen = set(l.split("|")[0] for l in exp["general"] if l.startswith("conv_gemm"))
+    assert tiles["gen"] == gen, (sorted(tiles["gen"] - gen), sorted(gen - tiles["gen"]))
+    assert tiles["wino"] == set(l.split("|")[0] for l in exp["all"] if l.startswith("conv_wino"))
+    for forms, variant in (("all", "fast"), ("general", "gen")):     # every weight-gradient tile on both kernels
+        have = set(l.split("|")[0].replace("sw", "") for l in exp[forms] if l.startswith("wgrad") and l.endswith(variant))
+        assert tiles["wgrad"] == have, (forms, sorted(tiles["wgrad"] - have))
+    assert {"subpixel_conv|", "conv_k4s2_c4|", "conv1x1_k64|", "convT_small|", "wgrad<128x96>sw|fast", "wgrad<128x32>sw|fast"} <= exp["all"]
+    # the literal sets are what the table says, for every value of VQ2_FORMS; every case sits in exactly one place
+    for forms, col in (("all", 11), ("direct", 12), ("general", 13)):
+        assert set(c[col] for c in D.CASES) == exp[forms], forms
+    assert len(set(D.case_id(c) for c in D.CASES)) == len(D.CASES)
+
+
+def test_dispatch_table_tolerances_bite_on_the_cpu():
+    """One small case of every label family of the dispatch table: the comparison with fp64 fails when one product is
+    dropped from a plain fp32 computation, and passes without (tests/test_gpu_dispatch.py::_bites; checked for the whole
+    table when it was written)."""
+    import test_gpu_dispatch as D
+    done = set()
+    for c in sorted(D.CASES, key=lambda c: c[7] * c[8] * c[9] * c[2] * c[3] * c[4] ** 2):
+        fam = c[11].split("|")[0].split("<")[0] + c[0]
+        if fam not in done:
+            done.add(fam)
+            D._bites(c)
+    assert len(done) >= 12
 
 
 def test_state_dict_layout_matches_reference(amd):

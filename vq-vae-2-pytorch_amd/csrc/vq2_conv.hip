@@ -594,8 +594,10 @@ static int launch_conv_gemm_fast(const ConvGemmParams &P, hipStream_t s) {
     dim3 grid(nwg);
     const char *name = "conv_gemm";
     if (prof_enabled())
-        name = prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d", BM, BN, BK, P.M, P.Co, P.K, P.KH, P.stride,
-                          P.phases);
+        // (the last field names the instantiation: tap = uniform chunks with the taps innermost, uni = uniform chunks,
+        //  var = chunks that may straddle taps; conv_gemm_kernel says gen)
+        name = prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d,%s", BM, BN, BK, P.M, P.Co, P.K, P.KH, P.stride,
+                          P.phases, tap_inner ? "tap" : uni ? "uni" : "var");
     ProfScope prof(name, P.flops, P.bytes, s, BM == 128 && BN == 128);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, P);
     return check_launch("conv_gemm_fast_kernel");
@@ -610,7 +612,7 @@ static int launch_conv_gemm(const ConvGemmParams &P, hipStream_t s) {
     dim3 grid(((P.M + BM - 1) / BM) * ((P.Co + BN - 1) / BN) * P.phases);
     const char *name = "conv_gemm";
     if (prof_enabled())
-        name = prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d", BM, BN, BK, P.M, P.Co, P.K, P.KH, P.stride,
+        name = prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d,gen", BM, BN, BK, P.M, P.Co, P.K, P.KH, P.stride,
                           P.phases);
     ProfScope prof(name, P.flops, P.bytes, s, BM == 128 && BN == 128 && BK == 32);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, P);
@@ -1382,8 +1384,10 @@ __global__ __launch_bounds__(256, 2) void convT_small_mfma_kernel(const float *_
         }
 }
 
+// (a function of the layer alone: the weight panel is packed for this kernel from a descriptor whose batch size is not
+//  the forward launch's, so nothing about the launch may enter here)
 static bool use_convT_small(const vq2_conv_desc *d) {
-    return d->transposed && d->Co == 4 && d->Cor >= 1 && d->Cor <= 3 && d->Ci % 16 == 0 && d->N <= 65535;
+    return d->transposed && d->Co == 4 && d->Cor >= 1 && d->Cor <= 3 && d->Ci % 16 == 0;
 }
 
 static int check_desc(const vq2_conv_desc *d) {
@@ -1512,8 +1516,12 @@ extern "C" int vq2_conv_fwd(const vq2_conv_desc *d, int flags, const float *x, c
     VQ2_REQUIRE(x && wp && y, "conv_fwd: null pointer");
     VQ2_REQUIRE(aligned16(x) && aligned16(wp) && aligned16(y), "conv_fwd: pointers must be 16-byte aligned");
     VQ2_REQUIRE(!residual || (ldres >= d->Co), "conv_fwd: ldres < Co");
-    if (use_convT_small(d) && !residual && !(flags & VQ2_RELU_OUT)) {
-        // (the weight panel of this layer is packed for THIS kernel: there is no other path to fall through to)
+    if (use_convT_small(d)) {
+        // (the weight panel of this layer is packed for THIS kernel: there is no other path to fall through to, and the
+        //  general kernels would read the panel in their own layout -- a launch this kernel cannot take is refused)
+        if (residual || (flags & VQ2_RELU_OUT) || d->N > 65535)
+            return set_error(VQ2_ERR_UNSUPPORTED, "conv_fwd: a conv-transpose to <= 3 channels takes neither a residual nor "
+                             "ReLU-out, and at most 65535 images per launch (split the batch)");
         if (!((double)d->N * 4 * d->H * d->W * d->ldy * 4 < (double)ctm::COOB && (double)d->N * d->H * d->W * d->ldx * 4 < (double)ctm::COOB))
             return set_error(VQ2_ERR_UNSUPPORTED, "conv_fwd: a conv-transpose to <= 4 channels is limited to tensors below %d bytes "
                              "(split the batch)", ctm::COOB);

@@ -900,13 +900,18 @@ static size_t bias_ws_floats(const vq2_conv_desc *d, const WgradPlan &p) {
     return taps ? (size_t)p.S * nslots * p.I : (size_t)p.S * p.O;
 }
 
+// wgrad_fast_kernel in its direct forms: rows of whole 32-pixel chunks, tensors that 32-bit byte offsets reach
+static bool wgrad_fast_ok(const WgradParams &P) {
+    const long lim = 1L << 29;
+    return forms() > FORMS_GENERAL && P.Wo % WG_BKR == 0 && P.rows_per_split % WG_BKR == 0 &&
+           (long)P.N * P.H * P.W * P.ldx < lim && (long)P.M * P.ldg < lim;
+}
+
 template <int WAVES_M, int WAVES_N, int MT, int NT>
 static int launch_wgrad(const WgradParams &P, int S, hipStream_t s) {
     constexpr int BMO = WAVES_M * MT * 32, BNK = WAVES_N * NT * 32;
     const size_t lds = (size_t)2 * WG_BKR * (BMO + BNK) * sizeof(float);
-    const long lim = 1L << 29;
-    const bool fast_ok = forms() > FORMS_GENERAL && P.Wo % WG_BKR == 0 && P.rows_per_split % WG_BKR == 0 &&
-                         (long)P.N * P.H * P.W * P.ldx < lim && (long)P.M * P.ldg < lim;
+    const bool fast_ok = wgrad_fast_ok(P);
     auto kern = wgrad_kernel<WAVES_M, WAVES_N, MT, NT>;
     if (fast_ok) {   // ReLU flags are compile-time in the fast kernel: every vector instruction competes with the MFMAs
         if (P.relu_x) kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, true, false>;
@@ -1051,7 +1056,8 @@ static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const f
     const double pix_out_ = d->transposed ? 4.0 * pix_in_ : (double)P.M * (p.wino ? 2.0 : 1.0);
     const double macs_ = d->transposed ? pix_in_ * 16.0 * cir_ * cor_ : pix_out_ * d->KH * d->KW * cir_ * cor_;
     const char *pname = "wgrad";
-    if (prof_enabled()) pname = prof_label("wgrad<%dx%d>%s|O=%d,K=%d,M=%d,S=%d,k%d", p.bmo, p.bnk, p.wino == 3 ? "swwino" : p.swapped ? "sw" : (p.wino == 1 ? "wino" : p.wino == 2 ? "wino4" : ""), p.O, p.K, p.M, p.S, d->KH);
+    if (prof_enabled()) pname = prof_label("wgrad<%dx%d>%s|O=%d,K=%d,M=%d,S=%d,k%d,%s", p.bmo, p.bnk, p.wino == 3 ? "swwino" : p.swapped ? "sw" : (p.wino == 1 ? "wino" : p.wino == 2 ? "wino4" : ""), p.O, p.K, p.M, p.S, d->KH,
+                                            p.wino || wgrad_fast_ok(P) ? "fast" : "gen");   // wgrad_fast_kernel or wgrad_kernel
     ProfScope prof(pname, 2.0 * macs_, 4.0 * (pix_in_ * cir_ + pix_out_ * cor_ + cir_ * cor_ * d->KH * d->KW), s);
     if (p.wino == 3) {
         auto kern = P.relu_g ? wgrad_fast_kernel<4, 1, 1, 3, false, true, 3> : wgrad_fast_kernel<4, 1, 1, 3, false, false, 3>;
