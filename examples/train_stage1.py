@@ -4,14 +4,18 @@ Mirrors /root/reference/train_vqvae.py:209-237 (flags), :144-206 (main: model, o
 CycleScheduler, --resume, checkpoint every 10 epochs as checkpoint/vqvae_{epoch:03d}.pt in the
 reference's state_dict format) and :27-141 (per-step: recon MSE + 0.25 * latent, running mse
 aggregated over ranks).  The re-ID parts of the fork are out of scope.  Data: a directory of .npy
-image batches ([N,3,H,W] float32, already normalised) or, without --path, synthetic N(0,1) images
-(there is no torchvision / dataset access in this environment).
+image batches -- uint8 [N,H,W,3] pixels as an image decoder leaves them (pinned-memory prefetch on a copy
+stream, ToTensor + Normalize + CenterCrop(--size) on the GPU inside the step; --norm picks the statistics:
+half = 0.5 / 0.5 as extract_code.py:52, imagenet = those of train_vqvae.py:154), or [N,3,H,W] float32,
+already normalised -- or, without --path, synthetic images: N(0,1) floats, with --dtype uint8 random pixels
+through the 8-bit path (there is no torchvision / dataset access in this environment).
 
 Every rank runs the SAME number of steps: the batches found under --path are dealt round-robin and the
 remainder that would give some ranks one step more is dropped (what DistributedSampler's equal shards do for
 the reference), and the CycleScheduler's n_iter is that per-rank count x epochs (train_vqvae.py:189-195).
 
     python examples/train_stage1.py --size 256 --batch_size 32 --epoch 1 --iters 50
+    python examples/train_stage1.py --size 256 --batch_size 32 --epoch 1 --path /data/ffhq_u8 --norm half
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_stage1.py ...
 """
 import argparse
@@ -48,6 +52,27 @@ def load_batch(item, args, gen, device):
     return torch.from_numpy(np.ascontiguousarray(np.load(f, mmap_mode="r")[i:i + args.batch_size])).float().to(device)
 
 
+NORMS = {"half": ((0.5, 0.5, 0.5), (0.5, 0.5, 0.5)),                       # extract_code.py:52
+         "imagenet": ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))}       # train_vqvae.py:154
+
+
+def data_is_uint8(args, plan):
+    if not args.path:
+        return args.dtype == "uint8"
+    return np.load(plan[0][0], mmap_mode="r").dtype == np.uint8
+
+
+def host_u8_batches(args, plan, epochs, gen):
+    """Host side of the 8-bit path: every batch of every remaining epoch, in the order the loop consumes them."""
+    for _ in range(epochs):
+        for item in plan:
+            if item is None:
+                yield torch.randint(0, 256, (args.batch_size, args.size, args.size, 3), dtype=torch.uint8, generator=gen)
+            else:
+                f, i = item
+                yield np.load(f, mmap_mode="r")[i:i + args.batch_size]      # copied once, into pinned memory
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n_gpu", type=int, default=1)            # kept for CLI parity; world size comes from the launcher
@@ -61,6 +86,8 @@ def main():
     ap.add_argument("--path", type=str, default="")
     ap.add_argument("--iters", type=int, default=100, help="synthetic batches per epoch when --path is not given")
     ap.add_argument("--out", default="checkpoint")
+    ap.add_argument("--norm", choices=sorted(NORMS), default="half", help="statistics for uint8 data")
+    ap.add_argument("--dtype", choices=("float32", "uint8"), default="float32", help="what the synthetic run draws")
     args = ap.parse_args()
 
     rank, local_rank, world = dist.bringup("nccl")             # launch.py:52-92 (RCCL group + device binding)
@@ -69,7 +96,10 @@ def main():
     # every rank may build its model from its own RNG state: the trainer broadcasts rank 0's (DDP, train_vqvae.py:166-171)
     model = vqvae2_amd.VQVAE().to(device)
     plan = plan_batches(args, rank, world)
-    trainer = vqvae2_amd.Stage1Trainer(model, lr=args.lr, sched=args.sched, n_iter=len(plan) * args.epoch)
+    u8 = data_is_uint8(args, plan)
+    normalizer = vqvae2_amd.ImageNormalizer(*NORMS[args.norm], layout="hwc", crop=(args.size, args.size)) if u8 else None
+    trainer = vqvae2_amd.Stage1Trainer(model, lr=args.lr, sched=args.sched, n_iter=len(plan) * args.epoch,
+                                       normalizer=normalizer)
     first_epoch = 0
     if args.resume:                                            # train_vqvae.py:173-182
         sd = torch.load(args.resume, map_location=device, weights_only=True)
@@ -79,10 +109,11 @@ def main():
             print(f"==> loaded checkpoint {args.resume} (epoch {first_epoch})")
 
     gen = torch.Generator(device="cpu").manual_seed(1234 + rank)
+    feed = vqvae2_amd.HostBatchPrefetcher(host_u8_batches(args, plan, args.epoch - first_epoch, gen), device) if u8 else None
     for epoch in range(first_epoch, args.epoch):
         mse_sum = torch.zeros(2, device=device)                # (sum of recon * batch, count)
         for i, item in enumerate(plan):
-            img = load_batch(item, args, gen, device)
+            img = next(feed) if u8 else load_batch(item, args, gen, device)
             out = trainer.step(img)
             mse_sum[0] += out["recon"] * img.shape[0]
             mse_sum[1] += img.shape[0]
@@ -101,6 +132,8 @@ def main():
             full = trainer.state_dict()
             full["epoch"] = epoch + 1
             torch.save(full, os.path.join(args.out, f"trainer_{tag}.pt"))                   # exact-resume extras
+    if feed is not None:
+        feed.close()
     dist.synchronize()
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

@@ -42,10 +42,11 @@ typedef void *vq2_stream_t;
 /* ABI revision of THIS header.  It moves whenever an entry point changes its argument list or the meaning of an
  * argument / workspace (revision 2: vq2_vq_fwd lost its counts/sumsT arguments and vq2_vq_fwd_workspace_floats
  * went from (M) to (M, D, K); revision 3: round-3 additions; revision 4: the two diagnostic probe exports removed;
+ * revision 5: vq2_u8_to_nhwc4 added;
  * see INTEGRATION.md "ABI history").  vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 4
+#define VQ2_API_VERSION 5
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -195,6 +196,21 @@ int vq2_nchw_to_nhwc(const float *src, float *dst, int32_t N, int32_t C, int32_t
                      vq2_stream_t stream);
 int vq2_nhwc_to_nchw(const float *src, float *dst, int32_t N, int32_t C, int32_t H, int32_t W, int32_t ld,
                      vq2_stream_t stream);
+
+/* 8-bit images in: ToTensor + Normalize (+ the centre crop, which is only an offset) + layout change of the reference's
+ * loader (train_vqvae.py:149-155, extract_code.py:47-53), fused into the conversion to the internal 4-float pixel:
+ *     dst[n][y][x][c] = lut[c][ src(n, y0 + y, x0 + x, c) ]  for c < C,   0 for C <= c < 4
+ * The normalisation is a table of 256 floats per channel that the HOST builds with the reference's own fp32
+ * operations, lut[c][v] = (float(v) / 255 - mean[c]) / std[c] as ToTensor and Normalize execute them, so the result is
+ * bit-identical to that loader for any mean / std.  1 <= C <= 4; the crop window [y0, y0 + H) x [x0, x0 + W) lies inside
+ * the Hs x Ws source; dst is 16-byte aligned.  Row segments that start and end on 4-byte boundaries of src (HWC: x0 * C,
+ * Ws * C and W * C multiples of 4; CHW: x0, Ws and W) are read as dwords, anything else byte by byte -- same result.
+ * No synchronisation; the caller owns all memory. */
+#define VQ2_U8_HWC 0   /* src [N][Hs][Ws][C]  (what image decoders produce)                                  */
+#define VQ2_U8_CHW 1   /* src [N][C][Hs][Ws]  (torchvision PILToTensor / the reference's arrays transposed) */
+int vq2_u8_to_nhwc4(const uint8_t *src, int layout, int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t y0,
+                    int32_t x0, int32_t H, int32_t W, const float *lut /* device, [C][256] */,
+                    float *dst /* [N][H][W][4] */, vq2_stream_t stream);
 /* g = dy * (y > 0) over [pixels, C] with pixel strides: backward of a fused VQ2_RELU_OUT
  * (vqvae.py:122,144); with dy == y it is the forward ReLU itself */
 int vq2_relu_bwd(const float *dy, int32_t lddy, const float *y, int32_t ldy, float *g, int32_t ldg, int64_t pixels,

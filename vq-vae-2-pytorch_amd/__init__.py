@@ -11,3 +11,4 @@ from . import ops  # noqa: F401
 from . import codes  # noqa: F401
 from .optim import FusedAdam, CycleScheduler  # noqa: F401
 from .train import Stage1Trainer, stage1_loss  # noqa: F401
+from .data import ImageNormalizer, HostBatchPrefetcher  # noqa: F401

@@ -175,15 +175,107 @@ __global__ void scale_kernel(const float *__restrict__ src, const float *__restr
         dst[i] = src[i] * s;
 }
 
+// ------------------------------------------------------------------ 8-bit image -> normalised NHWC4
+// ToTensor + Normalize (+ crop) + layout change of the reference's loader (train_vqvae.py:149-155,
+// extract_code.py:47-53) in one pass: dst[n][y][x][c] = lut[c][src byte], pad lanes 0.  The table (built on the host
+// with the reference's own fp32 operations, so the result does not depend on how a division is lowered here) sits in
+// LDS.  A workgroup converts tiles of U8_TILE consecutive output pixels; thread t stores pixels t, t + 256, ... of the
+// tile as one float4 each (consecutive lanes, consecutive 16-byte pixels).  DWORD: the tile's source bytes come in as
+// aligned dwords, consecutive lanes consecutive dwords, through an LDS staging area -- HWC as the C * U8_TILE / 4
+// dwords of the cropped byte stream (a lane's dword k: 4 pixels = 12 bytes in three loads at C = 3), CHW as one dword
+// of 4 pixels per channel plane; the launcher checks that no dword straddles a row.  Otherwise single byte loads.
+constexpr int U8_TILE = 1024;
+
+struct U8Params {
+    const uint8_t *src; const float *lut; float4 *dst;
+    int64_t total;            // N * H * W output pixels
+    int64_t ntiles;
+    int C, H, W, Hs, Ws, y0, x0;
+};
+
+// source element offset of channel 0 of output pixel (row grow = n * H + y, column x)
+template <int LAYOUT>
+__device__ __forceinline__ int64_t u8_src_offset(const U8Params &P, int64_t grow, int x) {
+    const int64_t n = grow / P.H;
+    const int y = (int)(grow - n * P.H) + P.y0;
+    if (LAYOUT == VQ2_U8_HWC) return ((n * P.Hs + y) * P.Ws + P.x0 + x) * P.C;
+    return (n * P.C * P.Hs + y) * P.Ws + P.x0 + x;
+}
+
+template <int LAYOUT, bool DWORD>
+__global__ __launch_bounds__(256) void u8_to_nhwc4_kernel(const U8Params P) {
+    __shared__ float lut[4 * 256];
+    __shared__ uint32_t stage[DWORD ? U8_TILE : 1];   // U8_TILE pixels x <= 4 bytes
+    const int t = threadIdx.x, C = P.C;
+    for (int i = t; i < C * 256; i += 256) lut[i] = P.lut[i];
+    __syncthreads();
+    const int64_t plane = (int64_t)P.Hs * P.Ws;
+    for (int64_t tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x) {
+        const int64_t tile0 = tile * U8_TILE;
+        if (DWORD) {
+            if (LAYOUT == VQ2_U8_HWC) {
+                // byte stream of the cropped image: rows of W * C bytes (a multiple of 4, as is every row's start)
+                const uint32_t rowb = (uint32_t)P.W * C;
+                const int64_t s0 = tile0 * C, row0 = s0 / rowb;
+                const uint32_t off0 = (uint32_t)(s0 - row0 * rowb);
+                for (int k = 0; k < C; ++k) {
+                    const uint32_t d = t + 256 * k;
+                    if (s0 + 4 * (int64_t)d < P.total * C) {
+                        const uint32_t u = off0 + 4 * d, r = u / rowb;
+                        const int64_t o = u8_src_offset<LAYOUT>(P, row0 + r, 0) + (u - r * rowb);
+                        stage[d] = *reinterpret_cast<const uint32_t *>(P.src + o);
+                    }
+                }
+            } else if (tile0 + 4 * t < P.total) {
+                // 4 consecutive pixels of one row (W, x0 and Ws are multiples of 4): one dword per channel plane
+                const int64_t row0 = tile0 / P.W;
+                const uint32_t u = (uint32_t)(tile0 - row0 * P.W) + 4 * t, r = u / (uint32_t)P.W;
+                const int64_t o = u8_src_offset<LAYOUT>(P, row0 + r, (int)(u - r * (uint32_t)P.W));
+                for (int c = 0; c < C; ++c)
+                    stage[c * (U8_TILE / 4) + t] = *reinterpret_cast<const uint32_t *>(P.src + o + c * plane);
+            }
+            __syncthreads();
+        }
+        const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
+#pragma unroll
+        for (int j = 0; j < U8_TILE / 256; ++j) {
+            const int q = j * 256 + t;
+            const int64_t g = tile0 + q;
+            if (g >= P.total) break;
+            uint32_t b[4] = {0, 0, 0, 0};
+            if (DWORD) {
+                for (int c = 0; c < C; ++c) b[c] = LAYOUT == VQ2_U8_HWC ? sb[q * C + c] : sb[c * U8_TILE + q];
+            } else {
+                const int64_t grow = g / P.W;
+                const int64_t o = u8_src_offset<LAYOUT>(P, grow, (int)(g - grow * P.W));
+                for (int c = 0; c < C; ++c) b[c] = P.src[o + (LAYOUT == VQ2_U8_HWC ? c : c * plane)];
+            }
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            v.x = lut[b[0]];
+            if (C > 1) v.y = lut[256 + b[1]];
+            if (C > 2) v.z = lut[512 + b[2]];
+            if (C > 3) v.w = lut[768 + b[3]];
+            P.dst[g] = v;
+        }
+        if (DWORD) __syncthreads();   // the staging area is refilled by the next tile
+    }
+}
+
 }  // namespace vq2
 
 using namespace vq2;
+
+// (format strings by name: tests/test_host_cpu.py's census of conv label families reads the literal ones)
+static const char NCHW4_LABEL[] = "nchw_to_nhwc4|N=%d,H=%d,W=%d,C=%d";
+static const char U8_LABEL[] = "u8_to_nhwc4|N=%d,H=%d,W=%d,C=%d,%s,%s";
 
 extern "C" int vq2_nchw_to_nhwc(const float *src, float *dst, int32_t N, int32_t C, int32_t H, int32_t W, int32_t ld,
                                 vq2_stream_t stream) {
     VQ2_REQUIRE(src && dst && N > 0 && C > 0 && H > 0 && W > 0 && ld >= C, "nchw_to_nhwc: bad arguments");
     if (ld == 4 && aligned16(dst)) {
         const int64_t HW4 = (int64_t)H * W, total = HW4 * N;
+        ProfScope prof(prof_level() ? prof_label(NCHW4_LABEL, N, H, W, C) : "", 0.0, (double)total * (4 * C + 16),
+                       to_stream(stream));
         hipLaunchKernelGGL(nchw_to_nhwc4_kernel, dim3(grid_for(total)), dim3(256), 0, to_stream(stream), src,
                            reinterpret_cast<float4 *>(dst), C, HW4, total);
         return check_launch("nchw_to_nhwc4_kernel");
@@ -193,6 +285,37 @@ extern "C" int vq2_nchw_to_nhwc(const float *src, float *dst, int32_t N, int32_t
     dim3 grid((HW + 31) / 32, (ld + 31) / 32, N);
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, to_stream(stream), src, dst, C, HW, ld);
     return check_launch("nchw_to_nhwc_kernel");
+}
+
+extern "C" int vq2_u8_to_nhwc4(const uint8_t *src, int layout, int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t y0,
+                               int32_t x0, int32_t H, int32_t W, const float *lut, float *dst, vq2_stream_t stream) {
+    VQ2_REQUIRE(src && lut && dst, "u8_to_nhwc4: null pointer");
+    VQ2_REQUIRE(layout == VQ2_U8_HWC || layout == VQ2_U8_CHW, "u8_to_nhwc4: layout %d is neither VQ2_U8_HWC nor VQ2_U8_CHW", layout);
+    VQ2_REQUIRE(C >= 1 && C <= 4, "u8_to_nhwc4: %d channels (1..4 fit the 4-float pixel)", C);
+    VQ2_REQUIRE(N > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "u8_to_nhwc4: non-positive dimension");
+    VQ2_REQUIRE(y0 >= 0 && x0 >= 0 && (int64_t)y0 + H <= Hs && (int64_t)x0 + W <= Ws,
+                "u8_to_nhwc4: crop %dx%d at (%d, %d) leaves the %dx%d source", H, W, y0, x0, Hs, Ws);
+    VQ2_REQUIRE(aligned16(dst), "u8_to_nhwc4: dst must be 16-byte aligned");
+    VQ2_REQUIRE((int64_t)Ws * C < (1 << 30), "u8_to_nhwc4: source rows of 2^30 bytes and more are not supported");
+    U8Params P;
+    P.src = src; P.lut = lut; P.dst = reinterpret_cast<float4 *>(dst);
+    P.total = (int64_t)N * H * W;
+    P.ntiles = (P.total + U8_TILE - 1) / U8_TILE;
+    P.C = C; P.H = H; P.W = W; P.Hs = Hs; P.Ws = Ws; P.y0 = y0; P.x0 = x0;
+    // dword loads need every row segment to start and end on a 4-byte boundary of the source
+    const bool hwc = layout == VQ2_U8_HWC;
+    const int unit = hwc ? C : 1;   // bytes per pixel within one row segment
+    const bool dword = (reinterpret_cast<uintptr_t>(src) & 3u) == 0 && ((int64_t)W * unit) % 4 == 0 &&
+                       ((int64_t)x0 * unit) % 4 == 0 && ((int64_t)Ws * unit) % 4 == 0;
+    hipStream_t s = to_stream(stream);
+    ProfScope prof(prof_level() ? prof_label(U8_LABEL, N, H, W, C, hwc ? "hwc" : "chw", dword ? "dword" : "byte") : "",
+                   0.0, (double)P.total * (C + 16), s);
+    const dim3 grid((unsigned)(P.ntiles < 2048 ? P.ntiles : 2048)), block(256);
+    if (hwc && dword) hipLaunchKernelGGL((u8_to_nhwc4_kernel<VQ2_U8_HWC, true>), grid, block, 0, s, P);
+    else if (hwc) hipLaunchKernelGGL((u8_to_nhwc4_kernel<VQ2_U8_HWC, false>), grid, block, 0, s, P);
+    else if (dword) hipLaunchKernelGGL((u8_to_nhwc4_kernel<VQ2_U8_CHW, true>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((u8_to_nhwc4_kernel<VQ2_U8_CHW, false>), grid, block, 0, s, P);
+    return check_launch("u8_to_nhwc4_kernel");
 }
 
 extern "C" int vq2_nhwc_to_nchw(const float *src, float *dst, int32_t N, int32_t C, int32_t H, int32_t W, int32_t ld,

@@ -451,6 +451,32 @@ def to_nhwc(x):
     return NchwToNhwc.apply(x)
 
 
+U8_LAYOUTS = {"hwc": 0, "chw": 1}   # VQ2_U8_HWC / VQ2_U8_CHW of include/vq2.h
+
+
+def u8_to_nhwc4(img, lut, layout, box=None):
+    """uint8 image batch ([N,Hs,Ws,C] for "hwc", [N,C,Hs,Ws] for "chw") -> the internal NHWC tensor [N,H,W,4] of
+    lut[c][byte] (pad lanes 0): ToTensor + Normalize + crop + layout change in one launch (vq2_u8_to_nhwc4).
+    lut: device float32 [C,256]; box = (y0, x0, H, W), default the whole image."""
+    if not (isinstance(img, torch.Tensor) and img.is_cuda and img.dtype == torch.uint8):
+        raise RuntimeError(f"vqvae2_amd: 8-bit image batch must be a uint8 tensor on the MI355X (got "
+                           f"{getattr(img, 'dtype', type(img))} on {getattr(img, 'device', '?')}); "
+                           "this package has no CPU path")
+    if layout not in U8_LAYOUTS:
+        raise ValueError(f"layout must be 'hwc' or 'chw', not {layout!r}")
+    if img.dim() != 4 or not img.is_contiguous():
+        raise RuntimeError("expected a contiguous 4-D uint8 batch")
+    n, hs, ws, c = img.shape if layout == "hwc" else (img.shape[0], img.shape[2], img.shape[3], img.shape[1])
+    _require_cuda(lut, "normalisation table")
+    if tuple(lut.shape) != (c, 256) or not lut.is_contiguous() or lut.device != img.device:
+        raise RuntimeError(f"normalisation table of shape {tuple(lut.shape)} for a batch of {c} channels")
+    y0, x0, h, w = (0, 0, hs, ws) if box is None else box
+    out = torch.empty((n, h, w, 4), device=img.device, dtype=torch.float32)
+    check(lib.vq2_u8_to_nhwc4(_p(img), U8_LAYOUTS[layout], n, c, hs, ws, y0, x0, h, w, _p(lut), _p(out), _stream()),
+          "u8_to_nhwc4")
+    return out
+
+
 def from_nhwc(y, c):
     """Internal NHWC -> NCHW-shaped result (zero-copy channels-last view when C % 4 == 0)."""
     if y.shape[3] == c:

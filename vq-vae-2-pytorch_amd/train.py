@@ -26,10 +26,14 @@ class Stage1Trainer:
     Data parallelism (one process per GPU): like DDP's constructor (train_vqvae.py:166-171) the trainer first
     broadcasts rank 0's parameters and buffers, so replicas built from different RNG states start identical; every
     step then SUM-all-reduces the flat gradient buffer (Adam divides by the world size) in two buckets.
-    VQ2_DP_FORCE=1 takes this path whenever a process group exists, also at world size 1."""
+    VQ2_DP_FORCE=1 takes this path whenever a process group exists, also at world size 1.
 
-    def __init__(self, model, lr=3e-4, sched=None, n_iter=None, betas=(0.9, 0.999), eps=1e-8):
+    normalizer: a data.ImageNormalizer; step() then also takes uint8 image batches on the device (the loader's
+    ToTensor + Normalize + CenterCrop run as one kernel inside the step, train_vqvae.py:149-155)."""
+
+    def __init__(self, model, lr=3e-4, sched=None, n_iter=None, betas=(0.9, 0.999), eps=1e-8, normalizer=None):
         self.model = model
+        self.normalizer = normalizer
         live = model.live_parameters() if hasattr(model, "live_parameters") else list(model.parameters())
         self.quantizers = [m for m in model.modules() if type(m).__name__ == "Quantize"]
         extra = sum(q.n_embed * (q.dim + 1) for q in self.quantizers)
@@ -165,18 +169,33 @@ class Stage1Trainer:
 
     # ------------------------------------------------------------------ the step
     def step(self, img, return_dec=False):
-        """One training step on this rank's batch (img: NCHW); returns device scalars (no host sync)."""
+        """One training step on this rank's batch (img: float32 NCHW, or a uint8 batch in the normalizer's layout);
+        returns device scalars (no host sync)."""
         model = self.model
+        u8 = getattr(img, "dtype", None) == torch.uint8
+        if u8 and self.normalizer is None:
+            raise TypeError("Stage1Trainer.step: a uint8 batch needs Stage1Trainer(..., normalizer=ImageNormalizer(...))")
         model.train()
         self.arena.zero_grad()   # the EMA statistics slots are fully rewritten by vq2_vq_stats: nothing to zero
-        if hasattr(model, "forward_nhwc"):
+        if u8 and hasattr(model, "forward_nhwc"):
+            # the same step from 8-bit pixels: x comes normalised out of the conversion launch; the MSE denominator and
+            # the channel count are those of the logical (cropped) NCHW image
+            x = self.normalizer(img)
+            n, channels, h, w = self.normalizer.out_shape(img)
+            dec, diff = model.forward_nhwc(x)
+            loss, recon, latent, d_dec, d_diff = ops.stage1_loss_and_seeds(dec, diff, x, LATENT_LOSS_WEIGHT, n * channels * h * w)
+            roots, seeds = (dec, diff), (d_dec, d_diff)
+        elif hasattr(model, "forward_nhwc"):
             # loss evaluated in the kernels' own NHWC4 layout: no layout conversion of the
             # reconstruction or of its gradient (the zero pad lane contributes nothing)
             x = ops.to_nhwc(img)
+            channels = img.shape[1]
             dec, diff = model.forward_nhwc(x)
             loss, recon, latent, d_dec, d_diff = ops.stage1_loss_and_seeds(dec, diff, x, LATENT_LOSS_WEIGHT, img.numel())
             roots, seeds = (dec, diff), (d_dec, d_diff)
         else:
+            if u8:
+                img = self.normalizer.nchw(img)
             dec, diff = model(img)
             loss, recon, latent = stage1_loss(dec, diff, img)
             roots, seeds = (loss,), (None,)
@@ -208,7 +227,7 @@ class Stage1Trainer:
         out = {"loss": loss.detach(), "recon": recon, "latent": latent}
         if return_dec:
             d = dec.detach()
-            out["dec"] = ops.from_nhwc(d, img.shape[1]) if hasattr(model, "forward_nhwc") else d
+            out["dec"] = ops.from_nhwc(d, channels) if hasattr(model, "forward_nhwc") else d
         return out
 
     # ------------------------------------------------------------------ checkpoint / resume
