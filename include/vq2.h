@@ -221,6 +221,8 @@ int vq2_slice_copy(const float *src, int32_t lds, float *dst, int32_t ldd, int64
 
 /* ------------------------------------------------------------------ Quantize (vqvae.py:28-78)
  * x[M,D] rows (NHWC latents), embed[D,K] (reference layout).
+ * D % 4 == 0 in 4..256 (any such D, not only powers of two), 1 <= K; vq2_vq_stats also needs K <= 16384.  embed need only
+ * be 16-byte aligned as a whole: when K % 4 != 0 its rows are not, and vq2_vq_fwd stages them with dword loads.
  * vq2_vq_prepare: embedT[K,D] and enorm[K] = sum_d embed[d,k]^2      (vqvae.py:47)
  * vq2_vq_fwd:  idx[M] (int64) = first argmin_k ||x||^2 - 2 x.e_k + ||e_k||^2 (vqvae.py:44-49)
  *              out[M,D] = x + (e_idx - x)                            (vqvae.py:52,73)
@@ -253,7 +255,8 @@ int vq2_vq_ema_update(float *embed, float *cluster_size, float *embed_avg, const
                       int32_t D, int32_t K, double decay, double eps, float *scratch /* >= 1 float */,
                       vq2_stream_t stream);
 /* the same update, also leaving embedT / enorm of the UPDATED codebook (what vq2_vq_prepare would compute before
- * the next forward, bit for bit): one launch less per quantizer and step.  D must divide 256. */
+ * the next forward, bit for bit): one launch less per quantizer and step.  D <= 256 (a block of 256 threads owns floor(256 / D)
+ * whole codes; enorm is summed in vq2_vq_prepare's order for every D). */
 int vq2_vq_ema_update_prepare(float *embed, float *cluster_size, float *embed_avg, const float *counts,
                               const float *sumsT, int32_t D, int32_t K, double decay, double eps, float *scratch,
                               float *embedT, float *enorm, vq2_stream_t stream);

@@ -18,7 +18,7 @@ namespace vq2 {
 
 constexpr int VQ_ROWS = 128;    // latent vectors per loss partial (32 per wave)
 
-// DP = D rounded up to {16,32,64}; NW = waves per workgroup (32 vectors each); VQ_CT = codes staged per LDS tile.
+// DP = D rounded up to {16,32,64,128,256}; NW = waves per workgroup (32 vectors each); VQ_CT = codes staged per LDS tile.
 // <DP,4,128>: 128 vectors per workgroup, 32 KB tiles, ~5 workgroups per CU -- small launches.
 // <DP,16,512>: 512 vectors per workgroup and the reference's whole 512-code codebook (128 KB) staged ONCE, no
 // barrier in the main loop, 16 waves per CU; a quarter of the workgroups also means a quarter of the same-address
@@ -58,7 +58,17 @@ __device__ __forceinline__ void vq_finish(const float (&xf)[DP / 2], int besti, 
 // M = 32,768, K = 8,192) would put ONE wave on each SIMD, with nothing to overlap its argmin / staging phases.
 // Split s searches codes [s*kper, (s+1)*kper) and leaves (best distance, best index) in pbest / pidx [S][M];
 // vq_merge_kernel takes the first minimum over the splits in ascending code order -- the same index as one pass.
-template <int DP, int NW, int VQ_CT>
+//
+// RK (ragged K, K % 4 != 0): the codebook rows embed + d*K are only 4-byte aligned, so the tile is staged with dword
+// buffer loads and a range test per element instead of one per float4.  A compile-time variant: the RK = false
+// instantiations keep the instruction stream they had before the flag existed.
+// Word 3 of the gfx9 raw-buffer descriptor: DATA_FORMAT = 32 bit, everything else 0 (raw, unswizzled); the range check is
+// byte offset >= num_records.  VQ_OOB is positive as the signed 32-bit voffset the builtin takes and above every
+// num_records vq2_vq_fwd accepts (D*K*4 < VQ_OOB is required there), so such a load returns 0 and touches no memory.
+constexpr int VQ_OOB = 0x7FFFFFF0;
+constexpr unsigned VQ_RSRC_FLAGS = 0x00020000;
+
+template <int DP, int NW, int VQ_CT, bool RK>
 __global__ __launch_bounds__(64 * NW) void vq_fwd_kernel(const float *__restrict__ x, int ldx,
                                                      const float *__restrict__ embed,   // [D][K]
                                                      const float *__restrict__ embedT,  // [K][D]
@@ -101,11 +111,30 @@ __global__ __launch_bounds__(64 * NW) void vq_fwd_kernel(const float *__restrict
     for (int ct0 = kbeg; ct0 < kend; ct0 += VQ_CT) {
         __syncthreads();
         // stage E[:, ct0:ct0+VQ_CT] (zero-padded) and its norms
-        for (int t = tid; t < DP * (VQ_CT / 4); t += NT) {
-            const int d = t / (VQ_CT / 4), c4 = (t % (VQ_CT / 4)) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (d < D && ct0 + c4 < kend) v = *reinterpret_cast<const float4 *>(embed + (size_t)d * K + ct0 + c4);
-            *reinterpret_cast<float4 *>(Es + d * VQ_CT + c4) = v;
+        if constexpr (RK) {
+            const __amdgpu_buffer_rsrc_t re =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(embed), 0, D * K * 4, VQ_RSRC_FLAGS);
+            constexpr int U = 8;   // loads in flight per thread (a rolled loop would wait for each one)
+            static_assert((DP * VQ_CT) % (NT * U) == 0, "tile is a whole number of 8-load rounds");
+#pragma unroll 1
+            for (int t0 = tid; t0 < DP * VQ_CT; t0 += NT * U) {
+                float v[U];
+#pragma unroll
+                for (int j = 0; j < U; ++j) {
+                    const int t = t0 + j * NT, d = t / VQ_CT, c = t % VQ_CT;
+                    const int off = (d < D && ct0 + c < kend) ? (d * K + ct0 + c) * 4 : VQ_OOB;
+                    v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(re, off, 0, 0));
+                }
+#pragma unroll
+                for (int j = 0; j < U; ++j) Es[t0 + j * NT] = v[j];
+            }
+        } else {
+            for (int t = tid; t < DP * (VQ_CT / 4); t += NT) {
+                const int d = t / (VQ_CT / 4), c4 = (t % (VQ_CT / 4)) * 4;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (d < D && ct0 + c4 < kend) v = *reinterpret_cast<const float4 *>(embed + (size_t)d * K + ct0 + c4);
+                *reinterpret_cast<float4 *>(Es + d * VQ_CT + c4) = v;
+            }
         }
         // codes past K get norm +inf: their distance never wins, no per-element range test below
         for (int t = tid; t < VQ_CT; t += NT) En[t] = (ct0 + t < kend) ? enorm[ct0 + t] : __builtin_inff();
@@ -377,6 +406,7 @@ __global__ __launch_bounds__(256) void vq_stats_chunk_kernel(const float *__rest
 // be a latency chain of n dependent L2 round trips (n = 2,048 when every vector of a 32 x 64 x 64 batch picks the same
 // code), so the fold is a fixed two-stage tree instead: CL = 256 / (D/4) interleaved chains (thread (c, q) adds the
 // float4 q of chunks g0 + c, g0 + c + CL, ... in order, 16 loads in flight), then the CL chain sums in order of c.
+// Threads past the last whole chain (c >= CL, when D/4 does not divide 256) take no part.
 __global__ __launch_bounds__(256) void vq_stats_fix_kernel(int K, int D, const int *__restrict__ codeoff,
                                                            const float *__restrict__ carry, float *__restrict__ sumsT) {
     __shared__ float4 red[256];
@@ -384,6 +414,7 @@ __global__ __launch_bounds__(256) void vq_stats_fix_kernel(int K, int D, const i
     const int s = codeoff[k], e = codeoff[k + 1];
     const int Q = D >> 2, CL = 256 / Q;
     const int q = threadIdx.x % Q, c = threadIdx.x / Q;
+    const bool act = c < CL;   // Q does not divide 256 (D = 48: 21 chains, 252 threads): the rest of the block is idle
     float4 *dst = reinterpret_cast<float4 *>(sumsT + (size_t)k * D);
     if (e == s) {
         if (c == 0) dst[q] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -393,7 +424,7 @@ __global__ __launch_bounds__(256) void vq_stats_fix_kernel(int K, int D, const i
     if (g0 == g1) return;   // the chunk kernel wrote the complete sum
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     constexpr int U = 16;
-    for (int gb = g0 + c; gb <= g1; gb += CL * U) {
+    for (int gb = act ? g0 + c : g1 + 1; gb <= g1; gb += CL * U) {
         float4 v[U];
 #pragma unroll
         for (int j = 0; j < U; ++j) {
@@ -410,7 +441,7 @@ __global__ __launch_bounds__(256) void vq_stats_fix_kernel(int K, int D, const i
             acc.w += v[j].w;
         }
     }
-    red[threadIdx.x] = acc;
+    if (act) red[threadIdx.x] = acc;
     __syncthreads();
     if (c == 0) {
         float4 t = red[q];
@@ -500,10 +531,11 @@ __global__ __launch_bounds__(1024) void vq_ema_counts_kernel(float *__restrict__
 
 // vqvae.py:64, 67-70: embed_avg EMA and the normalised codebook; thread index runs over [k][d] so the
 // transposed statistics are read coalesced
-// PREP (embedT / enorm outputs, 256 % D == 0): the launch also leaves what the NEXT forward's vq2_vq_prepare would
+// PREP (embedT / enorm outputs, D <= 256): the launch also leaves what the NEXT forward's vq2_vq_prepare would
 // compute -- the transposed codebook and ||e_k||^2 summed in vq_prepare_kernel's own order (four chains over
 // d = g, g+4, ..., then (p0+p1)+(p2+p3)), so distances and indices are bit-identical to preparing separately.  A block's
-// 256 threads own 256/D complete codes (256 and the grid stride are multiples of D).
+// first `per` = floor(256/D) * D threads own floor(256/D) complete codes (`per` and the grid stride are multiples of D; the
+// other 256 - per threads, none when D divides 256, only meet the barriers).
 template <bool PREP>
 __global__ __launch_bounds__(256) void vq_ema_embed_kernel(float *__restrict__ embed, const float *__restrict__ cluster_size,
                                                            float *__restrict__ embed_avg, const float *__restrict__ sumsT,
@@ -515,10 +547,11 @@ __global__ __launch_bounds__(256) void vq_ema_embed_kernel(float *__restrict__ e
     const float n = n_in[0];
     const float denom = n + keps;
     const int total = D * K;
-    const int rounds = (total + gridDim.x * 256 - 1) / (gridDim.x * 256);
+    const int per = PREP ? (256 / D) * D : 256;   // threads of a block that own an element
+    const int rounds = (total + gridDim.x * per - 1) / (gridDim.x * per);
     for (int r = 0; r < rounds; ++r) {
-        const int t = (r * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-        const bool tv = t < total;
+        const int t = (r * gridDim.x + blockIdx.x) * per + threadIdx.x;
+        const bool tv = (!PREP || (int)threadIdx.x < per) && t < total;
         const int k = tv ? t / D : 0, d = tv ? t - k * D : 0;
         float e = 0.f;
         if (tv) {
@@ -617,13 +650,16 @@ extern "C" int vq2_vq_fwd(const float *x, int32_t ldx, const float *embed, const
                           int64_t M, int32_t D, int32_t K, int64_t *idx, float *out, int32_t ldo, float *ws,
                           vq2_stream_t stream) {
     VQ2_REQUIRE(x && embed && embedT && enorm && idx && ws, "vq_fwd: null pointer");
-    VQ2_REQUIRE(M > 0 && K > 0 && K % 4 == 0 && D >= 4 && D <= 256 && (D & (D - 1)) == 0,
-                "vq_fwd: need D a power of two in 4..256 and K %% 4 == 0 (D=%d K=%d)", D, K);
+    VQ2_REQUIRE(M > 0 && K > 0 && D >= 4 && D <= 256 && D % 4 == 0,
+                "vq_fwd: need D %% 4 == 0 in 4..256 and K >= 1 (D=%d K=%d)", D, K);
+    VQ2_REQUIRE((int64_t)D * K * 4 < VQ_OOB, "vq_fwd: codebook too large (D=%d K=%d)", D, K);
     VQ2_REQUIRE(ldx >= D && ldx % 4 == 0 && (!out || (ldo >= D && ldo % 4 == 0)), "vq_fwd: bad pixel strides");
+    // (embed: the dword staging of the ragged variant would not need it; kept so that one contract holds for every K)
     VQ2_REQUIRE(aligned16(x) && aligned16(embed) && aligned16(embedT) && (!out || aligned16(out)),
                 "vq_fwd: pointers must be 16-byte aligned");
     hipStream_t s = to_stream(stream);
-    ProfScope prof(prof_label("vq_fwd|M=%lld,D=%d,K=%d", (long long)M, D, K), 2.0 * (double)M * D * K,
+    const bool ragged = K % 4 != 0;   // codebook rows not 16-byte aligned: the dword-staging kernels
+    ProfScope prof(prof_label("vq_fwd|M=%lld,D=%d,K=%d%s", (long long)M, D, K, ragged ? ",ragged" : ""), 2.0 * (double)M * D * K,
                    4.0 * ((double)M * D * 2 + (double)D * K), s);
     bool big; int S, kper;
     vq_plan(M, D, K, big, S, kper);
@@ -631,19 +667,26 @@ extern "C" int vq2_vq_fwd(const float *x, int32_t ldx, const float *embed, const
     const size_t nparts = (size_t)((M + VQ_ROWS - 1) / VQ_ROWS);
     float *pbest = S > 1 ? ws + (nparts + 3) / 4 * 4 : nullptr;
     int *pidx = S > 1 ? reinterpret_cast<int *>(pbest + (size_t)S * M) : nullptr;
-#define VQ2_LAUNCH_VQ(DP, NW, CT)                                                                                    \
+#define VQ2_LAUNCH_VQ_(DP, NW, CT, RK)                                                                                   \
     do {                                                                                                             \
         const size_t lds = ((size_t)DP * CT + CT + NW) * sizeof(float);                                              \
         const unsigned grid = (unsigned)((M + 32 * NW - 1) / (32 * NW));                                             \
-        allow_big_lds(vq_fwd_kernel<DP, NW, CT>, lds);                                                               \
-        hipLaunchKernelGGL((vq_fwd_kernel<DP, NW, CT>), dim3(grid, S), dim3(64 * NW), lds, s, x, ldx, embed, embedT, enorm, \
-                           M, D, K, idx, out, ldo, loss_partial, kper, pbest, pidx);                                 \
+        allow_big_lds(vq_fwd_kernel<DP, NW, CT, RK>, lds);                                                           \
+        hipLaunchKernelGGL((vq_fwd_kernel<DP, NW, CT, RK>), dim3(grid, S), dim3(64 * NW), lds, s, x, ldx, embed, embedT,     \
+                           enorm, M, D, K, idx, out, ldo, loss_partial, kper, pbest, pidx);                          \
         if (int e = check_launch("vq_fwd_kernel")) return e;                                                         \
         if (S > 1)                                                                                                   \
             hipLaunchKernelGGL((vq_merge_kernel<(DP <= 64 ? DP : 64)>), dim3((unsigned)((M + 127) / 128)), dim3(256), 0, s,  \
                                x, ldx, embedT, M, D, S, pbest, pidx, idx, out, ldo, loss_partial);                   \
     } while (0)
-    // D = 128 / 256: this lane's half of the vector is 64 / 128 B-fragment registers, so 8 waves per workgroup
+#define VQ2_LAUNCH_VQ(DP, NW, CT)                                                                                    \
+    do {                                                                                                             \
+        if (ragged) VQ2_LAUNCH_VQ_(DP, NW, CT, true);                                                                \
+        else VQ2_LAUNCH_VQ_(DP, NW, CT, false);                                                                      \
+    } while (0)
+    // D that is not a power of two runs on the next larger DP: the kernel zero-fills the columns d >= D, which add
+    // exact zeros to every dot product.
+    // D in 65..256: this lane's half of the vector is 64 / 128 B-fragment registers, so 8 waves per workgroup
     // (two per SIMD, <= 256 VGPRs) and code tiles of 256 / 128 (128 KB of LDS)
     if (D > 128) VQ2_LAUNCH_VQ(256, 8, 128);
     else if (D > 64) VQ2_LAUNCH_VQ(128, 8, 256);
@@ -651,6 +694,7 @@ extern "C" int vq2_vq_fwd(const float *x, int32_t ldx, const float *embed, const
     else if (D <= 32) { if (big) VQ2_LAUNCH_VQ(32, 16, 512); else VQ2_LAUNCH_VQ(32, 4, 128); }
     else { if (big) VQ2_LAUNCH_VQ(64, 16, 512); else VQ2_LAUNCH_VQ(64, 4, 128); }
 #undef VQ2_LAUNCH_VQ
+#undef VQ2_LAUNCH_VQ_
     return check_launch("vq_fwd_kernel");
 }
 
@@ -685,8 +729,8 @@ extern "C" size_t vq2_vq_stats_workspace_bytes(int64_t M, int32_t D, int32_t K) 
 extern "C" int vq2_vq_stats(const float *x, int32_t ldx, const int64_t *idx, int64_t M, int32_t D, int32_t K,
                             float *counts, float *sumsT, void *ws, size_t ws_bytes, vq2_stream_t stream) {
     VQ2_REQUIRE(x && idx && counts && sumsT && ws, "vq_stats: null pointer");
-    VQ2_REQUIRE(M > 0 && M < (1ll << 24) && D >= 4 && D <= 256 && (D & (D - 1)) == 0 && K > 0 && K <= 16384 && ldx >= D,
-                "vq_stats: need 0 < M < 2^24, D a power of two in 4..256, K <= 16384 (M=%lld D=%d K=%d)", (long long)M, D, K);
+    VQ2_REQUIRE(M > 0 && M < (1ll << 24) && D >= 4 && D <= 256 && D % 4 == 0 && K > 0 && K <= 16384 && ldx >= D,
+                "vq_stats: need 0 < M < 2^24, D %% 4 == 0 in 4..256, K <= 16384 (M=%lld D=%d K=%d)", (long long)M, D, K);
     VQ2_REQUIRE(aligned16(sumsT), "vq_stats: sumsT must be 16-byte aligned");
     const StatsLayout L = stats_layout(M, D, K);
     if (ws_bytes < L.total) return set_error(VQ2_ERR_WORKSPACE, "vq_stats: workspace %zu < %zu bytes", ws_bytes, L.total);
@@ -749,7 +793,8 @@ static int ema_update_impl(float *embed, float *cluster_size, float *embed_avg, 
     hipLaunchKernelGGL(vq_ema_counts_kernel, dim3(1), dim3(1024), 0, s, cluster_size, counts, K, (float)decay, alpha,
                        scratch);
     if (int e = check_launch("vq_ema_counts_kernel")) return e;
-    const int blocks = (D * K + 255) / 256;
+    const int per = embedT ? (256 / D) * D : 256;   // see vq_ema_embed_kernel
+    const int blocks = (D * K + per - 1) / per;
     const dim3 grid(blocks > 1024 ? 1024 : blocks);
     if (embedT)
         hipLaunchKernelGGL(vq_ema_embed_kernel<true>, grid, dim3(256), 0, s, embed, cluster_size, embed_avg, sumsT, D, K,
@@ -774,7 +819,7 @@ extern "C" int vq2_vq_ema_update_prepare(float *embed, float *cluster_size, floa
                                          float *scratch, float *embedT, float *enorm, vq2_stream_t stream) {
     VQ2_REQUIRE(embed && cluster_size && embed_avg && counts && sumsT && scratch && embedT && enorm && D > 0 && K > 0,
                 "vq_ema_update_prepare: bad arguments");
-    VQ2_REQUIRE(D <= 256 && 256 % D == 0, "vq_ema_update_prepare: D must divide 256 (D=%d)", D);
+    VQ2_REQUIRE(D <= 256, "vq_ema_update_prepare: need D <= 256 (D=%d)", D);
     return ema_update_impl(embed, cluster_size, embed_avg, counts, sumsT, D, K, decay, eps, scratch, embedT, enorm,
                            to_stream(stream));
 }

@@ -771,10 +771,34 @@ def vq_prepare(embed):
     return embed_t, enorm
 
 
+# The EMA statistics of one quantizer (vqvae.py:55-56) travel as ONE flat fp32 buffer
+#     [counts (K) | zero pad to a multiple of 4 floats | sumsT (K*D)]
+# so that sumsT starts on a 16-byte boundary for every K (no pad, i.e. today's [counts | sumsT], when K % 4 == 0).
+# The pad is written once, when the buffer is allocated: the statistics kernels never touch it and it rides through
+# the all-reduce as zeros.  Everything that slices such a buffer goes through these three functions.
+def vq_stats_numel(k, d):
+    return (k + 3) // 4 * 4 + k * d
+
+
+def vq_stats_views(stats, k, d):
+    """(counts [K], sumsT [K*D]) views of a statistics buffer."""
+    if stats.numel() != vq_stats_numel(k, d) or not stats.is_contiguous():
+        raise RuntimeError(f"vq statistics buffer must be contiguous with {vq_stats_numel(k, d)} floats (K={k}, D={d})")
+    off = (k + 3) // 4 * 4
+    return stats[:k], stats[off:]
+
+
+def vq_stats_alloc(k, d, device):
+    stats = torch.empty(vq_stats_numel(k, d), device=device, dtype=torch.float32)
+    if k % 4:
+        stats[k:(k + 3) // 4 * 4].zero_()
+    return stats
+
+
 class QuantizeFn(Function):
     """vqvae.py:42-75 minus the EMA update (done by the module after the all-reduce).
     Returns (ste_out [N,H,W,D], diff 0-dim, idx int64 [N,H,W], stats) where stats is the flat
-    fp32 buffer [counts (K) | sumsT (K*D)] of vqvae.py:55-56 (None in eval mode)."""
+    fp32 statistics buffer of vqvae.py:55-56 in the layout of vq_stats_views (None in eval mode)."""
 
     @staticmethod
     def forward(ctx, x, embed, want_stats, stats_buf, out_buf, prep=None, stats_stream=None):
@@ -801,23 +825,22 @@ class QuantizeFn(Function):
         stats = None
         if want_stats:
             if stats_buf is not None:
-                if stats_buf.numel() != k + k * d or not stats_buf.is_contiguous():
-                    raise RuntimeError("QuantizeFn: stats buffer must be contiguous with K + K*D floats")
                 stats = stats_buf.view_as(stats_buf)
             else:
-                stats = torch.empty(k + k * d, device=x.device, dtype=torch.float32)
-            # every element of stats is written (deterministic sort + ordered sums, no atomics, no zeroing)
+                stats = vq_stats_alloc(k, d, x.device)
+            counts, sums_t = vq_stats_views(stats, k, d)
+            # every count and sum is written (deterministic sort + ordered sums, no atomics, no zeroing)
             nbytes = lib.vq2_vq_stats_workspace_bytes(m, d, k)
             ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.int32)
             if stats_stream is not None and stats_buf is not None:
                 stats_stream.wait_event(torch.cuda.current_stream().record_event())
                 with torch.cuda.stream(stats_stream):
-                    check(lib.vq2_vq_stats(_p(x), ld_of(x), _p(idx), m, d, k, _p(stats[:k]), _p(stats[k:]), _p(ws), nbytes,
+                    check(lib.vq2_vq_stats(_p(x), ld_of(x), _p(idx), m, d, k, _p(counts), _p(sums_t), _p(ws), nbytes,
                                            _stream()), "vq_stats")
                 for tns in (x, idx, ws):
                     tns.record_stream(stats_stream)
             else:
-                check(lib.vq2_vq_stats(_p(x), ld_of(x), _p(idx), m, d, k, _p(stats[:k]), _p(stats[k:]), _p(ws), nbytes,
+                check(lib.vq2_vq_stats(_p(x), ld_of(x), _p(idx), m, d, k, _p(counts), _p(sums_t), _p(ws), nbytes,
                                        _stream()), "vq_stats")
         diff = torch.empty((), device=x.device, dtype=torch.float32)
         check(lib.vq2_vq_loss(_p(part), m, d, _p(diff), _stream()), "vq_loss")
@@ -848,9 +871,9 @@ class QuantizeFn(Function):
 def vq_ema_update(embed, cluster_size, embed_avg, stats, decay, eps, prep_out=None):
     """prep_out: (embedT [K,D], enorm [K]) buffers that receive the prepared form of the UPDATED codebook (same launch)."""
     d, k = embed.shape
-    counts, sums_t = stats[:k], stats[k:]
+    counts, sums_t = vq_stats_views(stats, k, d)
     scratch = torch.empty(4, device=embed.device, dtype=torch.float32)
-    if prep_out is not None and 256 % d == 0:
+    if prep_out is not None:
         check(lib.vq2_vq_ema_update_prepare(_p(embed), _p(cluster_size), _p(embed_avg), _p(counts), _p(sums_t), d, k,
                                             float(decay), float(eps), _p(scratch), _p(prep_out[0]), _p(prep_out[1]),
                                             _stream()), "vq_ema_update_prepare")

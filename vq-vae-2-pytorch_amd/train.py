@@ -36,7 +36,7 @@ class Stage1Trainer:
         self.normalizer = normalizer
         live = model.live_parameters() if hasattr(model, "live_parameters") else list(model.parameters())
         self.quantizers = [m for m in model.modules() if type(m).__name__ == "Quantize"]
-        extra = sum(q.n_embed * (q.dim + 1) for q in self.quantizers)
+        extra = sum(ops.vq_stats_numel(q.n_embed, q.dim) for q in self.quantizers)
         # enc_b back-propagates LAST: its parameters go to the end of the arena, so that the gradient buffer reads
         # [EMA statistics | enc_t quantize_conv_t dec_t | quantize_conv_b upsample_t dec | enc_b] and each of the three
         # data-parallel buckets (below) is one contiguous slice
@@ -44,7 +44,7 @@ class Stage1Trainer:
         self.arena = ParamArena(live, extra=extra, last=list(enc_b.parameters()) if enc_b is not None else ())
         off = 0
         for q in self.quantizers:  # EMA statistics ride in the head of the gradient buffer
-            n = q.n_embed * (q.dim + 1)
+            n = ops.vq_stats_numel(q.n_embed, q.dim)   # a multiple of 4: every quantizer's slice stays 16-byte aligned
             q.deferred_stats = self.arena.extra[off:off + n]
             off += n
         self.optimizer = FusedAdam(live, lr=lr, betas=betas, eps=eps, arena=self.arena)
@@ -176,7 +176,9 @@ class Stage1Trainer:
         if u8 and self.normalizer is None:
             raise TypeError("Stage1Trainer.step: a uint8 batch needs Stage1Trainer(..., normalizer=ImageNormalizer(...))")
         model.train()
-        self.arena.zero_grad()   # the EMA statistics slots are fully rewritten by vq2_vq_stats: nothing to zero
+        # the EMA statistics slots are fully rewritten by vq2_vq_stats, and their pad floats (ops.vq_stats_views) were
+        # zeroed with the arena and are never written: nothing to zero
+        self.arena.zero_grad()
         if u8 and hasattr(model, "forward_nhwc"):
             # the same step from 8-bit pixels: x comes normalised out of the conversion launch; the MSE denominator and
             # the channel count are those of the logical (cropped) NCHW image
