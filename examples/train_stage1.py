@@ -16,6 +16,12 @@ the reference), and the CycleScheduler's n_iter is that per-rank count x epochs 
 
     python examples/train_stage1.py --size 256 --batch_size 32 --epoch 1 --iters 50
     python examples/train_stage1.py --size 256 --batch_size 32 --epoch 1 --path /data/ffhq_u8 --norm half
+    python examples/train_stage1.py ... --val_path /data/ffhq_val_u8 --eval_every 500 --sample_every 100
+
+--val_path DIR (same file format as --path) with --eval_every N: every N steps the held-out set goes through
+Stage1Trainer.evaluate -- its batches dealt over the ranks, totals summed -- and rank 0 prints mse, latent, perplexity
+and used codes of both levels.  --sample_every N: rank 0 writes the reference's sample grid (train_vqvae.py:120-139:
+the first min(batch, 25) inputs over their reconstructions, nrow = len(sample)) to sample/{epoch+1:05d}_{i:05d}.png.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_stage1.py ...
 """
 import argparse
@@ -73,6 +79,31 @@ def host_u8_batches(args, plan, epochs, gen):
                 yield np.load(f, mmap_mode="r")[i:i + args.batch_size]      # copied once, into pinned memory
 
 
+def plan_val_batches(args, rank, world):
+    """Every image under --val_path in batches of at most --batch_size (a file's ragged tail is a short batch, as in
+    examples/eval_stage1.py), dealt round-robin; ranks may get one batch more or less (the totals are summed)."""
+    every = []
+    for f in sorted(glob.glob(os.path.join(args.val_path, "*.npy"))):
+        rows = np.load(f, mmap_mode="r").shape[0]
+        every += [(f, i) for i in range(0, rows, args.batch_size)]
+    if not every:
+        raise SystemExit(f"no images under {args.val_path}")
+    return every[rank::world]
+
+
+def val_batches(args, plan, device):
+    for f, i in plan:
+        a = np.ascontiguousarray(np.load(f, mmap_mode="r")[i:i + args.batch_size])
+        t = torch.from_numpy(a)
+        yield (t if a.dtype == np.uint8 else t.float()).to(device)
+
+
+def print_validation(epoch, i, r):
+    print(f"epoch: {epoch + 1}; it {i}; val images: {r['images']}; val mse: {r['mse']:.5f}; val latent: {r['latent']:.3f}; "
+          f"perplexity t/b: {r['perplexity_t']:.1f}/{r['perplexity_b']:.1f}; "
+          f"used codes t/b: {r['used_t']}/{r['used_b']} of {r['n_embed']}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n_gpu", type=int, default=1)            # kept for CLI parity; world size comes from the launcher
@@ -88,7 +119,12 @@ def main():
     ap.add_argument("--out", default="checkpoint")
     ap.add_argument("--norm", choices=sorted(NORMS), default="half", help="statistics for uint8 data")
     ap.add_argument("--dtype", choices=("float32", "uint8"), default="float32", help="what the synthetic run draws")
+    ap.add_argument("--val_path", type=str, default="", help="held-out batches, same file format as --path")
+    ap.add_argument("--eval_every", type=int, default=0, help="steps between evaluations of --val_path (0 = never)")
+    ap.add_argument("--sample_every", type=int, default=0, help="steps between sample grids under sample/ (0 = never)")
     args = ap.parse_args()
+    if args.eval_every and not args.val_path:
+        raise SystemExit("--eval_every needs --val_path")
 
     rank, local_rank, world = dist.bringup("nccl")             # launch.py:52-92 (RCCL group + device binding)
     device = torch.device("cuda", local_rank)
@@ -97,7 +133,10 @@ def main():
     model = vqvae2_amd.VQVAE().to(device)
     plan = plan_batches(args, rank, world)
     u8 = data_is_uint8(args, plan)
-    normalizer = vqvae2_amd.ImageNormalizer(*NORMS[args.norm], layout="hwc", crop=(args.size, args.size)) if u8 else None
+    # (float batches are already normalised: the normaliser then only says which statistics the sample grid inverts)
+    normalizer = vqvae2_amd.ImageNormalizer(*NORMS[args.norm], layout="hwc", crop=(args.size, args.size)) \
+        if (u8 or args.sample_every or args.eval_every) else None
+    val_plan = plan_val_batches(args, rank, world) if args.eval_every else None
     trainer = vqvae2_amd.Stage1Trainer(model, lr=args.lr, sched=args.sched, n_iter=len(plan) * args.epoch,
                                        normalizer=normalizer)
     first_epoch = 0
@@ -117,6 +156,14 @@ def main():
             out = trainer.step(img)
             mse_sum[0] += out["recon"] * img.shape[0]
             mse_sum[1] += img.shape[0]
+            if args.eval_every and (i + 1) % args.eval_every == 0:       # every rank: result() sums over the group
+                r = trainer.evaluate(val_batches(args, val_plan, device))
+                if dist.is_primary():
+                    print_validation(epoch, i, r)
+            if args.sample_every and i % args.sample_every == 0 and dist.is_primary():   # train_vqvae.py:120-139
+                grid = trainer.sample_grid(img[:min(img.shape[0], 25)].contiguous())
+                os.makedirs("sample", exist_ok=True)
+                vqvae2_amd.save_u8_image(grid, f"sample/{str(epoch + 1).zfill(5)}_{str(i).zfill(5)}.png", "hwc")
             if i % 25 == 0:
                 agg = mse_sum.clone()
                 dist.all_reduce(agg)                           # replaces the pickled all_gather of train_vqvae.py:93-100

@@ -42,11 +42,12 @@ typedef void *vq2_stream_t;
 /* ABI revision of THIS header.  It moves whenever an entry point changes its argument list or the meaning of an
  * argument / workspace (revision 2: vq2_vq_fwd lost its counts/sumsT arguments and vq2_vq_fwd_workspace_floats
  * went from (M) to (M, D, K); revision 3: round-3 additions; revision 4: the two diagnostic probe exports removed;
- * revision 5: vq2_u8_to_nhwc4 added;
+ * revision 5: vq2_u8_to_nhwc4 added; revision 6: the evaluation entry points added (vq2_nhwc_to_u8, vq2_sse_per_image,
+ * vq2_index_hist, vq2_eval_accumulate);
  * see INTEGRATION.md "ABI history").  vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 5
+#define VQ2_API_VERSION 6
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -211,6 +212,26 @@ int vq2_nhwc_to_nchw(const float *src, float *dst, int32_t N, int32_t C, int32_t
 int vq2_u8_to_nhwc4(const uint8_t *src, int layout, int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t y0,
                     int32_t x0, int32_t H, int32_t W, const float *lut /* device, [C][256] */,
                     float *dst /* [N][H][W][4] */, vq2_stream_t stream);
+/* 8-bit images out: the reference's invTrans (train_vqvae.py:22-25: Normalize(0, 1/std) then Normalize(-mean, 1)) fused
+ * with the quantisation inside torchvision's save_image (train_vqvae.py:133-139: mul(255).add_(0.5).clamp_(0, 255) to
+ * uint8) and with make_grid's placement.  The inverse of vq2_u8_to_nhwc4.
+ *   src: fp32 NHWC [N,H,W,.] with pixel stride ld >= C, 1 <= C <= 4.
+ *   dst: a canvas of Hc x Wc pixels, VQ2_U8_HWC [Hc][pitch bytes] with pixels of C bytes, or VQ2_U8_CHW [C][Hc][pitch bytes];
+ *        pitch >= the bytes of one canvas row.  Image k goes to the cell with origin
+ *        (row (k / cols) * (H + pad) + pad, column (k % cols) * (W + pad) + pad); every cell must lie inside the canvas.
+ *        Only image pixels are written: padding bytes keep what the caller put there.
+ *        image_pitch = 0: one canvas, as above.  image_pitch > 0, the batch form: the canvas is that of ONE image and
+ *        image k's canvas starts k * image_pitch bytes after dst -- Hc = H, Wc = W, pad = 0 and image_pitch = the bytes
+ *        of an image give the plain batches [N][H][W][C] (HWC) and [N][C][H][W] (CHW).
+ *   arithmetic, per element, in fp32 with every operation rounded on its own:
+ *        u = x / inv_s[c] + m[c]      inv_s[c] = (float)(1.0 / std[c]), m[c] = (float)mean[c]: HOST arrays of C floats
+ *        v = u * 255 + 0.5;  byte = (uint8_t)min(max(v, 0), 255);  NaN gives 0
+ *   Row segments that start and end on 4-byte boundaries of the canvas (HWC: W * C and pad * C multiples of 4; CHW: W and
+ *   pad; dst and pitch multiples of 4) are written as aligned dwords through LDS, anything else byte by byte -- same
+ *   result.  No synchronisation; the caller owns all memory. */
+int vq2_nhwc_to_u8(const float *src, int32_t ld, int32_t N, int32_t C, int32_t H, int32_t W,
+                   const float *inv_s /* host, [C] */, const float *mean /* host, [C] */, uint8_t *dst, int layout,
+                   int32_t Hc, int32_t Wc, int64_t pitch, int32_t cols, int32_t pad, int64_t image_pitch, vq2_stream_t stream);
 /* g = dy * (y > 0) over [pixels, C] with pixel strides: backward of a fused VQ2_RELU_OUT
  * (vqvae.py:122,144); with dy == y it is the forward ReLU itself */
 int vq2_relu_bwd(const float *dy, int32_t lddy, const float *y, int32_t ldy, float *g, int32_t ldg, int64_t pixels,
@@ -298,6 +319,27 @@ int vq2_adam_step(float *p, const float *g, float *m, float *v, int64_t n, doubl
 int vq2_axpby(const float *a, const float *b, float alpha, float *dst, int64_t n, vq2_stream_t stream);
 /* dst = src * scalar[0] * alpha, scalar read on the device (upstream gradient of a loss) */
 int vq2_scale(const float *src, const float *scalar, float alpha, float *dst, int64_t n, vq2_stream_t stream);
+
+/* ------------------------------------------------------------------ held-out evaluation
+ * What the reference's loop keeps beside the loss (train_vqvae.py:93-100: the running mse_sum / mse_n), plus the
+ * code usage of both quantizers (vqvae.py:49-50: the one-hot of embed_ind, summed), without a host synchronisation.
+ * vq2_sse_per_image: sse[n] = sum over the H * W * ld floats of image n of (a - b)^2, a and b dense NHWC with the
+ *              same pixel stride ld (ld % 4 == 0; lanes beyond the real channels must be equal on both sides: the zero
+ *              pad lane of NHWC4).  Fixed reduction tree that depends on (H, W, ld) only: image i of a launch of 9
+ *              is bit for bit image i of a launch of 5.  ws >= vq2_sse_workspace_bytes.
+ * vq2_index_hist: counts[idx[i]] += 1 for i < M (counts int64 [K], ACCUMULATED: the caller zeroes it once).  Integer
+ *              atomics only, so the result is order-independent.  1 <= K <= 16384, M < 2^31.  An index outside [0, K)
+ *              is not counted and sets flag[0] (device int32, never cleared here) to 1: the host reads it with the
+ *              counts and reports a VQ2_ERR_INVALID-class failure.
+ * vq2_eval_accumulate: one workgroup; acc (device, 4 doubles) = (sse_total, elements, latent_total, images):
+ *              acc[0] += sse[0], += sse[1], ... in image order;  acc[1] += N * elems_per_image;
+ *              acc[2] += diff[0] * N (diff: the latent loss of the batch, vqvae.py:240);  acc[3] += N. */
+size_t vq2_sse_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t ld);
+int vq2_sse_per_image(const float *a, const float *b, int32_t N, int32_t H, int32_t W, int32_t ld, float *sse, void *ws,
+                      size_t ws_bytes, vq2_stream_t stream);
+int vq2_index_hist(const int64_t *idx, int64_t M, int32_t K, int64_t *counts, int32_t *flag, vq2_stream_t stream);
+int vq2_eval_accumulate(const float *sse, int32_t N, int64_t elems_per_image, const float *diff, double *acc,
+                        vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ data-parallel exchange (RCCL over xGMI)
  * One communicator per process (= per GPU), owned by the library -- its only persistent state.  Replaces what

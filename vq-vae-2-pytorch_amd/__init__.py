@@ -11,4 +11,5 @@ from . import ops  # noqa: F401
 from . import codes  # noqa: F401
 from .optim import FusedAdam, CycleScheduler  # noqa: F401
 from .train import Stage1Trainer, stage1_loss  # noqa: F401
-from .data import ImageNormalizer, HostBatchPrefetcher  # noqa: F401
+from .data import ImageNormalizer, ImageDenormalizer, HostBatchPrefetcher, grid_layout, save_u8_image  # noqa: F401
+from .evaluate import Evaluator, perplexity_from_counts  # noqa: F401

@@ -57,6 +57,12 @@ def _load():
         "vq2_nchw_to_nhwc": (C.c_int, [P, P, I32, I32, I32, I32, I32, P]),
         "vq2_nhwc_to_nchw": (C.c_int, [P, P, I32, I32, I32, I32, I32, P]),
         "vq2_u8_to_nhwc4": (C.c_int, [P, C.c_int, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P]),
+        "vq2_nhwc_to_u8": (C.c_int, [P, I32, I32, I32, I32, I32, C.POINTER(F), C.POINTER(F), P, C.c_int, I32, I32, I64, I32,
+                                     I32, I64, P]),
+        "vq2_sse_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+        "vq2_sse_per_image": (C.c_int, [P, P, I32, I32, I32, I32, P, P, SZ, P]),
+        "vq2_index_hist": (C.c_int, [P, I64, I32, P, P, P]),
+        "vq2_eval_accumulate": (C.c_int, [P, I32, I64, P, P, P]),
         "vq2_relu_bwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
         "vq2_resblock_supported": (C.c_int, [I32, I32]),
         "vq2_resblock_bwd_data": (C.c_int, [I32, I32, I32, I32, I32, P, I32, P, I32, P, I32, P, P, P, I32, P, I32, P, P]),

@@ -1,0 +1,299 @@
+// Held-out evaluation and 8-bit export: none of these kernels is launched by the train step.
+//   nhwc_to_u8       normalised fp32 NHWC -> 8-bit pixels in a canvas (inverse of u8_to_nhwc4_kernel, vq2_elem.hip)
+//   sse_per_image    one sum of squared differences per image, fixed reduction tree
+//   index_hist       code-usage histogram of a quantizer's indices (integer atomics only)
+//   eval_accumulate  folds a batch into a device accumulator of doubles, so that an evaluation loop never syncs
+#include "vq2_common.h"
+
+namespace vq2 {
+
+// ------------------------------------------------------------------ normalised NHWC -> 8-bit canvas
+// invTrans (train_vqvae.py:22-25) + the quantisation inside torchvision's save_image, per element and in fp32 with
+// every operation rounded on its own (the library is built with -ffp-contract=off):
+//     u = x / inv_s[c] + m[c];   v = u * 255 + 0.5;   byte = trunc(clamp(v, 0, 255));   NaN -> 0
+// A workgroup converts tiles of TOU8_TILE consecutive pixels of the (n, y, x) pixel stream; thread t loads pixels
+// t, t + 256, ... (one 16-byte load each when the pixel stride is 4).  DWORD: the bytes are staged in LDS in
+// destination order and leave as aligned dwords, consecutive lanes consecutive dwords -- HWC as the C * TOU8_TILE / 4
+// dwords of the tile's byte stream (rows of W * C bytes), CHW as one dword of 4 pixels per channel plane; the launcher
+// checks that every row segment of every grid cell starts and ends on a 4-byte boundary.  Otherwise single byte stores.
+constexpr int TOU8_TILE = 1024;
+
+struct ToU8Params {
+    const float *src; uint8_t *dst;
+    int64_t total;            // N * H * W pixels
+    int64_t ntiles;
+    int64_t pitch, plane;     // bytes per canvas row; bytes per canvas channel plane (CHW)
+    int64_t istride;          // batch form: bytes from one image to the next (every image in cell 0 of its own canvas), else 0
+    int C, ld, H, W, cols, pad, vec;
+    float inv_s[4], m[4];
+};
+
+// canvas byte offset of channel 0 of the pixel (row grow = n * H + y, column x): image n sits in grid cell
+// (n / cols, n % cols) whose origin is (cell_row * (H + pad) + pad, cell_col * (W + pad) + pad), torchvision's make_grid.
+// Rows, cells and canvas coordinates fit 32 bits (the launcher checks N * H < 2^31 and the cells against the int32
+// canvas), so the divisions are 32-bit ones; only the final byte offset is 64-bit.
+template <int LAYOUT>
+__device__ __forceinline__ int64_t u8_dst_offset(const ToU8Params &P, uint32_t grow, uint32_t x) {
+    const uint32_t n = grow / (uint32_t)P.H, y = grow - n * (uint32_t)P.H;
+    const uint32_t k = P.istride ? 0u : n;
+    const uint32_t cr = k / (uint32_t)P.cols, cc = k - cr * (uint32_t)P.cols;
+    const uint32_t Y = cr * (uint32_t)(P.H + P.pad) + P.pad + y, X = cc * (uint32_t)(P.W + P.pad) + P.pad + x;
+    return (int64_t)n * P.istride + (int64_t)Y * P.pitch + (LAYOUT == VQ2_U8_HWC ? (int64_t)X * P.C : (int64_t)X);
+}
+
+// a = q * b + r for a tile's first element (the same for every lane): one 32-bit division unless a needs 64 bits
+__device__ __forceinline__ void tile_row(int64_t a, uint32_t b, uint32_t &q, uint32_t &r) {
+    if ((a >> 32) == 0) {
+        q = (uint32_t)a / b;
+        r = (uint32_t)a - q * b;
+    } else {
+        const int64_t q64 = a / b;
+        q = (uint32_t)q64;
+        r = (uint32_t)(a - q64 * b);
+    }
+}
+
+__device__ __forceinline__ uint32_t to_byte(float x, float inv_s, float m) {
+    const float u = x / inv_s + m;
+    float v = u * 255.f + 0.5f;
+    v = fminf(fmaxf(v, 0.f), 255.f);   // fmaxf returns the operand that is a number: NaN -> 0
+    return (uint32_t)v;
+}
+
+template <int LAYOUT, bool DWORD>
+__global__ __launch_bounds__(256) void nhwc_to_u8_kernel(const ToU8Params P) {
+    __shared__ uint32_t stage[DWORD ? TOU8_TILE : 1];   // TOU8_TILE pixels x <= 4 bytes
+    uint8_t *sb = reinterpret_cast<uint8_t *>(stage);
+    const int t = threadIdx.x, C = P.C;
+    for (int64_t tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x) {
+        const int64_t tile0 = tile * TOU8_TILE;
+        // all of the thread's 16-byte loads of the tile are issued before the first one is waited for
+        float4 pix[TOU8_TILE / 256];
+#pragma unroll
+        for (int j = 0; j < TOU8_TILE / 256; ++j) {
+            const int64_t g = tile0 + j * 256 + t;
+            pix[j] = (P.vec && g < P.total) ? reinterpret_cast<const float4 *>(P.src)[g] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        // image row and column of the tile's first pixel; a lane's own row is 32-bit arithmetic from there
+        uint32_t prow0 = 0, pcol0 = 0;
+        if (!DWORD || LAYOUT == VQ2_U8_CHW) tile_row(tile0, (uint32_t)P.W, prow0, pcol0);
+#pragma unroll
+        for (int j = 0; j < TOU8_TILE / 256; ++j) {
+            const int q = j * 256 + t;
+            const int64_t g = tile0 + q;
+            if (g < P.total) {
+                float x[4] = {0.f, 0.f, 0.f, 0.f};
+                if (P.vec) {
+                    x[0] = pix[j].x; x[1] = pix[j].y; x[2] = pix[j].z; x[3] = pix[j].w;
+                } else {
+                    for (int c = 0; c < C; ++c) x[c] = P.src[g * P.ld + c];
+                }
+                uint32_t b[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) b[c] = to_byte(x[c], P.inv_s[c], P.m[c]);
+                if (DWORD) {
+                    for (int c = 0; c < C; ++c) sb[LAYOUT == VQ2_U8_HWC ? q * C + c : c * TOU8_TILE + q] = (uint8_t)b[c];
+                } else {
+                    const uint32_t u = pcol0 + q, r = u / (uint32_t)P.W;
+                    const int64_t o = u8_dst_offset<LAYOUT>(P, prow0 + r, u - r * (uint32_t)P.W);
+                    for (int c = 0; c < C; ++c) P.dst[o + (LAYOUT == VQ2_U8_HWC ? c : c * P.plane)] = (uint8_t)b[c];
+                }
+            }
+        }
+        if (DWORD) {
+            __syncthreads();
+            if (LAYOUT == VQ2_U8_HWC) {
+                // byte stream of the tile: rows of W * C bytes (a multiple of 4, as is every row's start in the canvas)
+                const uint32_t rowb = (uint32_t)P.W * C;
+                const int64_t s0 = tile0 * C;
+                uint32_t row0, off0;
+                tile_row(s0, rowb, row0, off0);
+                for (int k = 0; k < C; ++k) {
+                    const uint32_t d = t + 256 * k;
+                    if (s0 + 4 * (int64_t)d < P.total * C) {
+                        const uint32_t u = off0 + 4 * d, r = u / rowb;
+                        const int64_t o = u8_dst_offset<LAYOUT>(P, row0 + r, 0) + (u - r * rowb);
+                        *reinterpret_cast<uint32_t *>(P.dst + o) = stage[d];
+                    }
+                }
+            } else if (tile0 + 4 * t < P.total) {
+                // 4 consecutive pixels of one row (W and pad are multiples of 4): one dword per channel plane
+                const uint32_t u = pcol0 + 4 * t, r = u / (uint32_t)P.W;
+                const int64_t o = u8_dst_offset<LAYOUT>(P, prow0 + r, u - r * (uint32_t)P.W);
+                for (int c = 0; c < C; ++c)
+                    *reinterpret_cast<uint32_t *>(P.dst + o + c * P.plane) = stage[c * (TOU8_TILE / 4) + t];
+            }
+            __syncthreads();   // the staging area is refilled by the next tile
+        }
+    }
+}
+
+// ------------------------------------------------------------------ per-image sum of squared differences
+// Image n is per4 float4s; split s of S sums the float4s [s * chunk, (s + 1) * chunk): thread t takes t, t + 256, ...
+// in order, then the butterfly of wave_sum, then the four waves.  S and chunk depend on per4 alone, so the tree of an
+// image does not know how many images the launch holds.
+constexpr int SSE_SPLIT4 = 2048, SSE_MAX_SPLITS = 64;
+
+static inline int sse_splits(int64_t per4) {
+    const int64_t s = (per4 + SSE_SPLIT4 - 1) / SSE_SPLIT4;
+    return (int)(s < 1 ? 1 : (s > SSE_MAX_SPLITS ? SSE_MAX_SPLITS : s));
+}
+
+__global__ __launch_bounds__(256) void sse_partial_kernel(const float4 *__restrict__ a, const float4 *__restrict__ b,
+                                                          int64_t per4, int64_t chunk, float *__restrict__ part) {
+    __shared__ float wsum[4];
+    const int64_t n = blockIdx.y, lo = blockIdx.x * chunk;
+    const int64_t hi = lo + chunk < per4 ? lo + chunk : per4;
+    const float4 *pa = a + n * per4, *pb = b + n * per4;
+    float s = 0.f;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        const float4 x = pa[i], y = pb[i];
+        const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
+        s += d0 * d0; s += d1 * d1; s += d2 * d2; s += d3 * d3;
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[n * gridDim.x + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+__global__ __launch_bounds__(64) void sse_final_kernel(const float *__restrict__ part, int S, float *__restrict__ sse) {
+    const int n = blockIdx.x, t = threadIdx.x;
+    const float v = wave_sum(t < S ? part[(int64_t)n * S + t] : 0.f);
+    if (t == 0) sse[n] = v;
+}
+
+// ------------------------------------------------------------------ code-usage histogram
+// int32 histogram of the workgroup's share in LDS, flushed with 64-bit integer atomics (integer addition commutes:
+// the result does not depend on the order).  An index outside [0, K) is counted nowhere and raises the flag.
+__global__ __launch_bounds__(256) void index_hist_kernel(const int64_t *__restrict__ idx, int64_t M, int K,
+                                                         unsigned long long *__restrict__ counts, int *__restrict__ flag) {
+    extern __shared__ int hist[];
+    for (int k = threadIdx.x; k < K; k += 256) hist[k] = 0;
+    __syncthreads();
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
+        const int64_t v = idx[i];
+        if ((uint64_t)v < (uint64_t)K) atomicAdd(&hist[(int)v], 1);
+        else bad = true;
+    }
+    if (bad) atomicOr(flag, 1);
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const int h = hist[k];
+        if (h) atomicAdd(&counts[k], (unsigned long long)h);
+    }
+}
+
+// ------------------------------------------------------------------ batch -> running totals (one workgroup)
+// acc[0] += sse[0], then sse[1], ... one image after the other in double: the total of a set of images does not depend
+// on how the set was cut into batches.  acc[1] += N * elems, acc[2] += diff * N, acc[3] += N.
+__global__ __launch_bounds__(256) void eval_accumulate_kernel(const float *__restrict__ sse, int N, double elems,
+                                                              const float *__restrict__ diff, double *__restrict__ acc) {
+    __shared__ float buf[256];
+    double s = threadIdx.x == 0 ? acc[0] : 0.0;
+    for (int base = 0; base < N; base += 256) {
+        if (base + (int)threadIdx.x < N) buf[threadIdx.x] = sse[base + threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = N - base < 256 ? N - base : 256;
+            for (int i = 0; i < m; ++i) s += (double)buf[i];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        acc[0] = s;
+        acc[1] += (double)N * elems;
+        acc[2] += (double)diff[0] * (double)N;
+        acc[3] += (double)N;
+    }
+}
+
+}  // namespace vq2
+
+using namespace vq2;
+
+extern "C" int vq2_nhwc_to_u8(const float *src, int32_t ld, int32_t N, int32_t C, int32_t H, int32_t W,
+                              const float *inv_s, const float *mean, uint8_t *dst, int layout, int32_t Hc, int32_t Wc,
+                              int64_t pitch, int32_t cols, int32_t pad, int64_t image_pitch, vq2_stream_t stream) {
+    VQ2_REQUIRE(src && dst && inv_s && mean, "nhwc_to_u8: null pointer");
+    VQ2_REQUIRE(layout == VQ2_U8_HWC || layout == VQ2_U8_CHW, "nhwc_to_u8: layout %d is neither VQ2_U8_HWC nor VQ2_U8_CHW", layout);
+    VQ2_REQUIRE(C >= 1 && C <= 4, "nhwc_to_u8: %d channels (1..4)", C);
+    VQ2_REQUIRE(N > 0 && H > 0 && W > 0 && Hc > 0 && Wc > 0 && ld >= C, "nhwc_to_u8: non-positive dimension or ld < C");
+    VQ2_REQUIRE(cols >= 1 && pad >= 0, "nhwc_to_u8: the grid needs cols >= 1 and pad >= 0");
+    const bool hwc = layout == VQ2_U8_HWC;
+    // every image cell, its padding included, lies inside the canvas
+    const int64_t placed = image_pitch ? 1 : N;   // batch form: one image per canvas
+    const int64_t cell_rows = (placed + cols - 1) / cols, cell_cols = placed < cols ? placed : cols;
+    VQ2_REQUIRE(cell_rows * ((int64_t)H + pad) + pad <= Hc && cell_cols * ((int64_t)W + pad) + pad <= Wc,
+                "nhwc_to_u8: %d images of %dx%d in %d columns with padding %d do not fit the %dx%d canvas", N, H, W, cols,
+                pad, Hc, Wc);
+    VQ2_REQUIRE(pitch >= (int64_t)Wc * (hwc ? C : 1), "nhwc_to_u8: pitch %lld is shorter than a canvas row", (long long)pitch);
+    VQ2_REQUIRE(image_pitch == 0 || image_pitch >= pitch * Hc * (hwc ? 1 : C),
+                "nhwc_to_u8: image_pitch %lld is shorter than one image's canvas", (long long)image_pitch);
+    VQ2_REQUIRE((int64_t)W * C < (1 << 30), "nhwc_to_u8: rows of 2^30 bytes and more are not supported");
+    VQ2_REQUIRE((int64_t)N * H < ((int64_t)1 << 31), "nhwc_to_u8: 2^31 image rows and more are not supported");
+    for (int c = 0; c < C; ++c) VQ2_REQUIRE(inv_s[c] != 0.f, "nhwc_to_u8: inv_s[%d] is zero", c);
+    ToU8Params P;
+    P.src = src; P.dst = dst;
+    P.total = (int64_t)N * H * W;
+    P.ntiles = (P.total + TOU8_TILE - 1) / TOU8_TILE;
+    P.pitch = pitch; P.plane = pitch * Hc; P.istride = image_pitch;
+    P.C = C; P.ld = ld; P.H = H; P.W = W; P.cols = cols; P.pad = pad;
+    P.vec = ld == 4 && aligned16(src);
+    for (int c = 0; c < 4; ++c) { P.inv_s[c] = c < C ? inv_s[c] : 1.f; P.m[c] = c < C ? mean[c] : 0.f; }
+    // dword stores need every row segment of every cell to start and end on a 4-byte boundary of the canvas
+    const int unit = hwc ? C : 1;   // bytes per pixel within one row segment
+    const bool dword = (reinterpret_cast<uintptr_t>(dst) & 3u) == 0 && pitch % 4 == 0 && image_pitch % 4 == 0 && ((int64_t)W * unit) % 4 == 0 &&
+                       ((int64_t)pad * unit) % 4 == 0;
+    hipStream_t s = to_stream(stream);
+    const dim3 grid((unsigned)(P.ntiles < 2048 ? P.ntiles : 2048)), block(256);
+    if (hwc && dword) hipLaunchKernelGGL((nhwc_to_u8_kernel<VQ2_U8_HWC, true>), grid, block, 0, s, P);
+    else if (hwc) hipLaunchKernelGGL((nhwc_to_u8_kernel<VQ2_U8_HWC, false>), grid, block, 0, s, P);
+    else if (dword) hipLaunchKernelGGL((nhwc_to_u8_kernel<VQ2_U8_CHW, true>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((nhwc_to_u8_kernel<VQ2_U8_CHW, false>), grid, block, 0, s, P);
+    return check_launch("nhwc_to_u8_kernel");
+}
+
+extern "C" size_t vq2_sse_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t ld) {
+    if (N <= 0 || H <= 0 || W <= 0 || ld <= 0 || ld % 4) return 0;
+    return (size_t)N * sse_splits((int64_t)H * W * (ld / 4)) * sizeof(float);
+}
+
+extern "C" int vq2_sse_per_image(const float *a, const float *b, int32_t N, int32_t H, int32_t W, int32_t ld, float *sse,
+                                 void *ws, size_t ws_bytes, vq2_stream_t stream) {
+    VQ2_REQUIRE(a && b && sse && ws, "sse_per_image: null pointer");
+    VQ2_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && ld > 0 && ld % 4 == 0,
+                "sse_per_image: need 1..65535 images and a pixel stride that is a multiple of 4");
+    VQ2_REQUIRE(aligned16(a) && aligned16(b), "sse_per_image: pointers must be 16-byte aligned");
+    const int64_t per4 = (int64_t)H * W * (ld / 4);
+    const int S = sse_splits(per4);
+    if (ws_bytes < (size_t)N * S * sizeof(float)) return set_error(VQ2_ERR_WORKSPACE, "sse_per_image: workspace too small");
+    hipStream_t s = to_stream(stream);
+    hipLaunchKernelGGL(sse_partial_kernel, dim3(S, N), dim3(256), 0, s, reinterpret_cast<const float4 *>(a),
+                       reinterpret_cast<const float4 *>(b), per4, (per4 + S - 1) / S, static_cast<float *>(ws));
+    if (int e = check_launch("sse_partial_kernel")) return e;
+    hipLaunchKernelGGL(sse_final_kernel, dim3(N), dim3(64), 0, s, static_cast<const float *>(ws), S, sse);
+    return check_launch("sse_final_kernel");
+}
+
+extern "C" int vq2_index_hist(const int64_t *idx, int64_t M, int32_t K, int64_t *counts, int32_t *flag,
+                              vq2_stream_t stream) {
+    VQ2_REQUIRE(idx && counts && flag, "index_hist: null pointer");
+    VQ2_REQUIRE(M > 0 && M < ((int64_t)1 << 31) && K >= 1 && K <= 16384, "index_hist: need 1 <= M < 2^31 and 1 <= K <= 16384");
+    const size_t lds = (size_t)K * sizeof(int);
+    allow_big_lds(index_hist_kernel, lds);
+    int64_t blocks = (M + 4095) / 4096;
+    blocks = blocks > 256 ? 256 : blocks;
+    hipLaunchKernelGGL(index_hist_kernel, dim3((unsigned)blocks), dim3(256), lds, to_stream(stream), idx, M, K,
+                       reinterpret_cast<unsigned long long *>(counts), flag);
+    return check_launch("index_hist_kernel");
+}
+
+extern "C" int vq2_eval_accumulate(const float *sse, int32_t N, int64_t elems_per_image, const float *diff, double *acc,
+                                   vq2_stream_t stream) {
+    VQ2_REQUIRE(sse && diff && acc && N > 0 && elems_per_image > 0, "eval_accumulate: bad arguments");
+    hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(256), 0, to_stream(stream), sse, N, (double)elems_per_image,
+                       diff, acc);
+    return check_launch("eval_accumulate_kernel");
+}

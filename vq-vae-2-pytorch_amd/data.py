@@ -3,6 +3,7 @@
 `img.to(device)` once per step -- with the arithmetic on the GPU and the transfer off the step's critical path.
 
 ImageNormalizer      uint8 batch on the device -> normalised fp32 in the kernels' NHWC4 layout, one launch
+ImageDenormalizer    the way back (train_vqvae.py:22-25, 133-139): normalised fp32 -> uint8 batch or sample grid, one launch
 HostBatchPrefetcher  host uint8 batches -> device uint8 batches through pinned memory on a copy stream
 """
 import collections
@@ -45,6 +46,7 @@ class ImageNormalizer:
             if len(crop) != 2 or min(crop) < 1:
                 raise ValueError("crop must be (H, W) with positive sizes")
         self.layout, self.crop, self.channels = layout, crop, len(mean)
+        self.mean, self.std = mean, std
         v = torch.arange(256, dtype=torch.uint8).float().div(255)                              # ToTensor
         m, s = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
         self.table = v.unsqueeze(0).repeat(len(mean), 1).sub_(m[:, None]).div_(s[:, None])    # Normalize; [C,256]
@@ -91,6 +93,123 @@ class ImageNormalizer:
 
     def nchw(self, img):
         return ops.from_nhwc(self(img), self.channels)
+
+    def inverse(self):
+        """The ImageDenormalizer of the same statistics and layout (cropping has no inverse: it yields the cropped size)."""
+        return ImageDenormalizer(self.mean, self.std, self.layout)
+
+
+def grid_layout(n, h, w, nrow=8, padding=2):
+    """Geometry of torchvision's make_grid for n images of h x w: (canvas height, canvas width, [(y, x) origin of every
+    image]).  Image k sits in cell (k // cols, k % cols) with cols = min(nrow, n); cells are (h + padding) x
+    (w + padding) and the canvas has one more `padding` at its bottom and right.  A single image is returned as it is,
+    without any border (make_grid's early return).  Pure host arithmetic."""
+    n, h, w, nrow, padding = int(n), int(h), int(w), int(nrow), int(padding)
+    if n < 1 or h < 1 or w < 1 or nrow < 1 or padding < 0:
+        raise ValueError("grid_layout: n, h, w and nrow must be positive and padding non-negative")
+    if n == 1:
+        return h, w, [(0, 0)]
+    cols = min(nrow, n)
+    rows = (n + cols - 1) // cols
+    origins = [((k // cols) * (h + padding) + padding, (k % cols) * (w + padding) + padding) for k in range(n)]
+    return rows * (h + padding) + padding, cols * (w + padding) + padding, origins
+
+
+def save_u8_image(canvas, path, layout="hwc"):
+    """Write a uint8 canvas ([H,W,C] for "hwc", [C,H,W] for "chw"; C = 1, 3 or 4; device or host) as a PNG at `path`
+    with PIL where it is importable; otherwise the same array goes to `path` with the extension .npy and a message says
+    so.  Returns the path written.  (One device-to-host copy; encoding stays on the host.)"""
+    a = canvas.detach().cpu().numpy() if isinstance(canvas, torch.Tensor) else np.asarray(canvas)
+    if a.dtype != np.uint8 or a.ndim != 3:
+        raise ValueError("save_u8_image: a 3-D uint8 canvas expected")
+    if layout == "chw":
+        a = a.transpose(1, 2, 0)
+    elif layout != "hwc":
+        raise ValueError(f"layout must be 'hwc' or 'chw', not {layout!r}")
+    a = np.ascontiguousarray(a)
+    try:
+        from PIL import Image
+    except ImportError:
+        alt = path.rsplit(".", 1)[0] + ".npy"
+        np.save(alt, a)
+        print(f"PIL is not importable: wrote the canvas as {alt} instead of {path}")
+        return alt
+    Image.fromarray(a[:, :, 0] if a.shape[2] == 1 else a).save(path)
+    return path
+
+
+class ImageDenormalizer:
+    """Normalised fp32 images -> 8-bit pixels on the GPU (vq2_nhwc_to_u8): the reference's `invTrans`
+    (train_vqvae.py:22-25: Normalize(0, 1 / std) then Normalize(-mean, 1)) followed by what torchvision's save_image does
+    to a float image (`mul(255).add_(0.5).clamp_(0, 255).to(uint8)`, train_vqvae.py:133-139), in that order and in fp32:
+
+        byte = trunc(clamp((x / inv_s[c] + m[c]) * 255 + 0.5, 0, 255)),  inv_s[c] = fp32(1 / std[c]),  m[c] = fp32(mean[c])
+
+    (the `sub(0)` and `div(1)` of the two stages change nothing, and t - (-m) is t + m).  NaN gives 0.  For the
+    statistics the examples ship this maps every value of ImageNormalizer's table back to its byte.
+
+    layout  of the RESULT: "hwc" [N,H,W,C] (what image encoders take) or "chw" [N,C,H,W]
+    denorm(x)           x: an internal NHWC tensor [N,H,W,ceil4(C)] (pass nhwc=True where the shape could be read
+                        either way) or an NCHW-shaped module output [N,C,H,W]  ->  uint8 batch
+    denorm.grid(batches, nrow, padding=2, pad_value=0)   make_grid + the same conversion: ONE uint8 canvas
+                        ([Hc,Wc,C] or [C,Hc,Wc]) holding the images of all batches in order.  No CPU path."""
+
+    def __init__(self, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), layout="hwc"):
+        if layout not in ops.U8_LAYOUTS:
+            raise ValueError(f"layout must be 'hwc' or 'chw', not {layout!r}")
+        mean, std = tuple(float(m) for m in mean), tuple(float(s) for s in std)
+        if len(mean) != len(std) or not 1 <= len(mean) <= 4:
+            raise ValueError("mean and std need one entry per channel, 1 to 4 channels")
+        if any(s == 0.0 for s in std):
+            raise ValueError("std must be non-zero")
+        self.layout, self.channels, self.mean, self.std = layout, len(mean), mean, std
+        # what Normalize makes of its arguments: torch.as_tensor(python double, dtype=float32)
+        self.inv_s = tuple(float(np.float32(1.0 / s)) for s in std)
+        self.m = tuple(float(np.float32(m)) for m in mean)
+
+    def _nhwc(self, x, nhwc=None):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+            raise RuntimeError(f"ImageDenormalizer: expected a 4-D float32 tensor on the MI355X (got "
+                               f"{getattr(x, 'dtype', type(x))} on {getattr(x, 'device', '?')}); no CPU path")
+        c = self.channels
+        as_nhwc, as_nchw = x.shape[3] == ops.ceil4(c), x.shape[1] == c
+        if nhwc is None:
+            if as_nhwc and as_nchw:
+                raise RuntimeError(f"ImageDenormalizer: a tensor of shape {tuple(x.shape)} reads as NHWC and as NCHW; "
+                                   "pass nhwc=True or nhwc=False")
+            nhwc = as_nhwc
+        if nhwc:
+            if not as_nhwc:
+                raise RuntimeError(f"ImageDenormalizer: NHWC input of shape {tuple(x.shape)} for {c} channels")
+            return ops.as_nhwc(x.detach())
+        if not as_nchw:
+            raise RuntimeError(f"ImageDenormalizer: input of shape {tuple(x.shape)} is neither [N,H,W,{ops.ceil4(c)}] "
+                               f"nor [N,{c},H,W]")
+        return ops.to_nhwc(x.detach())
+
+    def __call__(self, x, nhwc=None):
+        return ops.nhwc_to_u8(self._nhwc(x, nhwc), self.channels, self.inv_s, self.m, self.layout)
+
+    def grid(self, batches, nrow=8, padding=2, pad_value=0, nhwc=None):
+        if isinstance(batches, torch.Tensor):
+            batches = [batches]
+        xs = [self._nhwc(b, nhwc) for b in batches]
+        if not xs or any(x.shape[1:3] != xs[0].shape[1:3] or x.device != xs[0].device for x in xs):
+            raise RuntimeError("ImageDenormalizer.grid: one or more batches of images of one size on one GPU expected")
+        n, (h, w), c = sum(x.shape[0] for x in xs), xs[0].shape[1:3], self.channels
+        hc, wc, _ = grid_layout(n, h, w, nrow, padding)
+        cols, pad = (1, 0) if n == 1 else (min(int(nrow), n), int(padding))
+        shape = (hc, wc, c) if self.layout == "hwc" else (c, hc, wc)
+        canvas = torch.full(shape, int(pad_value), device=xs[0].device, dtype=torch.uint8)
+        if len(xs) > 1:     # cells are numbered through all batches: one launch needs them in one tensor
+            cp, k = xs[0].shape[3], 0
+            joined = torch.empty((n, h, w, cp), device=xs[0].device, dtype=torch.float32)
+            for x in xs:
+                ops.check(ops.lib.vq2_slice_copy(ops._p(x), ops.ld_of(x), ops._p(joined[k:]), cp, x.shape[0] * h * w, cp, 0,
+                                                 ops._stream()), "slice_copy")
+                k += x.shape[0]
+            xs = [joined]
+        return ops.nhwc_to_u8(xs[0], c, self.inv_s, self.m, self.layout, canvas=canvas, cols=cols, pad=pad)
 
 
 class HostBatchPrefetcher:

@@ -1,0 +1,122 @@
+"""Held-out evaluation of a stage-1 model: what the reference's loop reports beside the loss -- the running
+`mse_sum / mse_n` of train_vqvae.py:93-100 and the sample grid of :120-139 -- plus the health of both EMA codebooks
+(codes in use, perplexity), gathered on the GPU without a host synchronisation per batch.
+
+Evaluator               accumulates reconstruction error, latent loss and both code histograms over batches
+perplexity_from_counts  exp(entropy) of a code histogram, fp64 on the host
+"""
+import contextlib
+import math
+
+import torch
+from torch import distributed as dist
+
+from . import ops
+
+
+def perplexity_from_counts(counts):
+    """exp(-sum p ln p) with p = counts / sum(counts), in fp64, codes that never occur skipped (0 ln 0 = 0): K for K
+    codes used equally often, 1 when a single code takes every vector.  An empty histogram gives nan."""
+    c = torch.as_tensor(counts).detach().to("cpu", torch.float64).reshape(-1)
+    total = float(c.sum())
+    if total <= 0:
+        return float("nan")
+    p = c[c > 0] / total
+    return float(math.exp(-float((p * p.log()).sum())))
+
+
+@contextlib.contextmanager
+def eval_mode(model):
+    """model.eval() for the block, then every module's OWN train / eval flag back: a model whose modules do not all
+    share one mode (a frozen Quantize kept in eval mode so that its EMA codebook stands still) leaves as it came."""
+    flags = [(mod, mod.training) for mod in model.modules()]
+    model.eval()
+    try:
+        yield
+    finally:
+        for mod, flag in flags:
+            mod.training = flag
+
+
+class Evaluator:
+    """model: a VQVAE (anything with forward_nhwc(x, return_ids=True)); normalizer: a data.ImageNormalizer, needed for
+    uint8 batches and for return_u8.
+
+    update(img)   one batch, float32 NCHW or uint8 in the normaliser's layout: eval-mode forward under no_grad, then five
+                  small launches on the NHWC tensors the forward already has (per-image squared error: partial sums and
+                  their final sum; the two code histograms; one that folds the batch into the device accumulator).
+                  Nothing is read back.
+                  update(img, return_u8=True) returns the reconstruction as uint8 in the input's layout ([N,C,H,W] for
+                  a float batch).  Every module's train / eval flag is restored.
+    result()      ONE device-to-host copy -> {"mse", "latent", "images", "perplexity_t", "perplexity_b", "used_t",
+                  "used_b", "n_embed", "counts_t", "counts_b"}; mse is the mean over every element of every image seen
+                  (train_vqvae.py:83 averaged as :93-100 does), latent the image-weighted mean of the batches' latent
+                  losses.  With a process group the totals and the histograms are summed over the ranks first, on
+                  float64 / int64 tensors.  Raises RuntimeError if a quantizer ever produced an index outside its codebook.
+    reset()       clears the accumulators."""
+
+    def __init__(self, model, normalizer=None):
+        if not hasattr(model, "forward_nhwc"):
+            raise TypeError(f"Evaluator: {type(model).__name__} has no forward_nhwc (VQVAE_Deep's decoder needs a style "
+                            "input that a held-out pass does not have); evaluate a VQVAE")
+        self.model, self.normalizer = model, normalizer
+        self.denormalizer = normalizer.inverse() if normalizer is not None else None
+        self.k_t, self.k_b = model.quantize_t.n_embed, model.quantize_b.n_embed
+        self._state = None
+
+    def _buffers(self, device):
+        """One int64 buffer [accumulator (4 doubles, as bits) | counts_t | counts_b | flag], so that result() is one copy."""
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros(4 + self.k_t + self.k_b + 1, device=device, dtype=torch.int64)
+        s = self._state
+        return (s[:4].view(torch.float64), s[4:4 + self.k_t], s[4 + self.k_t:4 + self.k_t + self.k_b],
+                s[4 + self.k_t + self.k_b:].view(torch.int32)[:1])
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()
+
+    @torch.no_grad()
+    def update(self, img, return_u8=False):
+        model = self.model
+        u8 = getattr(img, "dtype", None) == torch.uint8
+        if (u8 or return_u8) and self.normalizer is None:
+            raise TypeError("Evaluator.update: uint8 batches and return_u8 need Evaluator(model, normalizer=ImageNormalizer(...))")
+        if u8:
+            x = self.normalizer(img)
+            n, channels, h, w = self.normalizer.out_shape(img)
+        else:
+            x = ops.to_nhwc(img)
+            n, channels, h, w = img.shape
+        with eval_mode(model):
+            dec, diff, id_t, id_b = model.forward_nhwc(x, return_ids=True)
+        acc, counts_t, counts_b, flag = self._buffers(x.device)
+        ops.eval_accumulate(ops.sse_per_image(dec, ops.packed(x)), channels * h * w, diff, acc)
+        ops.index_hist(id_t, counts_t, flag)
+        ops.index_hist(id_b, counts_b, flag)
+        if return_u8:
+            d = self.denormalizer
+            return ops.nhwc_to_u8(dec, channels, d.inv_s, d.m, d.layout if u8 else "chw")
+        return None
+
+    def result(self):
+        state = self._state
+        if state is None:       # no batch yet: empty totals (a rank whose share of the data is empty still joins the sums)
+            dev = next(self.model.parameters()).device
+            state = self._state = torch.zeros(4 + self.k_t + self.k_b + 1, device=dev, dtype=torch.int64)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            state = state.clone()
+            dist.all_reduce(state[:4].view(torch.float64))       # the four totals, float64
+            dist.all_reduce(state[4:])                           # both histograms (and the flag), int64
+        host = state.cpu()
+        acc = host[:4].view(torch.float64)
+        counts_t, counts_b = host[4:4 + self.k_t].clone(), host[4 + self.k_t:4 + self.k_t + self.k_b].clone()
+        if int(host[-1]) != 0:
+            raise RuntimeError("Evaluator: a quantizer produced a code index outside [0, n_embed) (vq2_index_hist flag)")
+        images = int(acc[3])
+        return {"mse": float(acc[0] / acc[1]) if images else float("nan"),
+                "latent": float(acc[2] / acc[3]) if images else float("nan"),
+                "images": images,
+                "perplexity_t": perplexity_from_counts(counts_t), "perplexity_b": perplexity_from_counts(counts_b),
+                "used_t": int((counts_t > 0).sum()), "used_b": int((counts_b > 0).sum()),
+                "n_embed": self.k_t if self.k_t == self.k_b else (self.k_t, self.k_b), "counts_t": counts_t, "counts_b": counts_b}

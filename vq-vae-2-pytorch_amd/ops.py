@@ -477,6 +477,74 @@ def u8_to_nhwc4(img, lut, layout, box=None):
     return out
 
 
+def nhwc_to_u8(x, c, inv_s, mean, layout, canvas=None, cols=1, pad=0):
+    """Internal NHWC tensor [N,H,W,>=c] -> 8-bit pixels (vq2_nhwc_to_u8): byte = trunc(clamp((x / inv_s[ch] + mean[ch])
+    * 255 + 0.5, 0, 255)), every operation in fp32.  inv_s / mean: sequences of c Python floats already rounded to fp32.
+    canvas None: a fresh batch, [N,H,W,c] for "hwc" or [N,c,H,W] for "chw".  canvas given (uint8, contiguous,
+    [Hc,Wc,c] or [c,Hc,Wc]): image k is written at make_grid's origin of cell (k // cols, k % cols) with `pad` pixels
+    around every cell; the other bytes of the canvas are left alone."""
+    _require_cuda(x, "activation")
+    if layout not in U8_LAYOUTS:
+        raise ValueError(f"layout must be 'hwc' or 'chw', not {layout!r}")
+    if not is_nhwc_dense(x):
+        raise RuntimeError("nhwc_to_u8: expected a dense NHWC tensor")
+    n, h, w, cp = x.shape
+    if not 1 <= c <= min(cp, 4) or len(inv_s) != c or len(mean) != c:
+        raise RuntimeError(f"nhwc_to_u8: {c} channels with {len(inv_s)} / {len(mean)} statistics from a tensor of {cp} lanes")
+    hwc = layout == "hwc"
+    if canvas is None:
+        out = torch.empty((n, h, w, c) if hwc else (n, c, h, w), device=x.device, dtype=torch.uint8)
+        hc, wc, cols, pad, image_pitch = h, w, 1, 0, h * w * c
+    else:
+        out = canvas
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == x.device and out.dim() == 3
+                and out.is_contiguous() and out.shape[2 if hwc else 0] == c):
+            raise RuntimeError(f"nhwc_to_u8: the canvas must be a contiguous uint8 tensor on {x.device} with {c} channels "
+                               f"in layout '{layout}'")
+        hc, wc = (out.shape[0], out.shape[1]) if hwc else (out.shape[1], out.shape[2])
+        image_pitch = 0
+    fa = (C.c_float * c)(*inv_s)
+    fm = (C.c_float * c)(*mean)
+    check(lib.vq2_nhwc_to_u8(_p(x), ld_of(x), n, c, h, w, fa, fm, _p(out), U8_LAYOUTS[layout], hc, wc,
+                             wc * (c if hwc else 1), int(cols), int(pad), image_pitch, _stream()), "nhwc_to_u8")
+    return out
+
+
+def sse_per_image(a, b):
+    """One fp32 sum of squared differences per image of two dense NHWC tensors of the same shape and pixel stride
+    (vq2_sse_per_image; lanes beyond the real channels must agree, as the zero pad lane of NHWC4 does)."""
+    _require_cuda(a, "reconstruction")
+    _require_cuda(b, "target")
+    if a.shape != b.shape or not (is_nhwc_dense(a) and is_nhwc_dense(b)) or ld_of(a) != ld_of(b) or ld_of(a) != a.shape[3]:
+        raise RuntimeError("sse_per_image: two packed NHWC tensors of one shape expected")
+    n, h, w, ld = a.shape
+    out = torch.empty(n, device=a.device, dtype=torch.float32)
+    nbytes = lib.vq2_sse_workspace_bytes(n, h, w, ld)
+    ws = torch.empty(max(nbytes // 4, 1), device=a.device, dtype=torch.float32)
+    check(lib.vq2_sse_per_image(_p(a), _p(b), n, h, w, ld, _p(out), _p(ws), nbytes, _stream()), "sse_per_image")
+    return out
+
+
+def index_hist(idx, counts, flag):
+    """counts[idx] += 1 (vq2_index_hist): idx int64 of any shape, counts int64 [K] accumulated across calls, flag int32
+    [1] set to 1 by an index outside [0, K) (which is counted nowhere)."""
+    if not (idx.is_cuda and idx.dtype == torch.int64 and counts.dtype == torch.int64 and flag.dtype == torch.int32
+            and counts.is_contiguous() and counts.device == idx.device and flag.device == idx.device):
+        raise RuntimeError("index_hist: int64 indices and counts and an int32 flag on one GPU expected; no CPU path")
+    ic = idx if idx.is_contiguous() else idx.contiguous()
+    check(lib.vq2_index_hist(_p(ic), ic.numel(), counts.numel(), _p(counts), _p(flag), _stream()), "index_hist")
+
+
+def eval_accumulate(sse, elems_per_image, diff, acc):
+    """acc (float64 [4]: sse total, elements, latent total, images) += this batch, on the device (vq2_eval_accumulate)."""
+    if not (acc.dtype == torch.float64 and acc.numel() == 4 and acc.is_contiguous() and acc.is_cuda):
+        raise RuntimeError("eval_accumulate: the accumulator is a float64 [4] tensor on the GPU")
+    d = diff.detach().reshape(-1)
+    if d.numel() != 1 or d.dtype != torch.float32:
+        raise RuntimeError("eval_accumulate: the latent loss is one float32 value")
+    check(lib.vq2_eval_accumulate(_p(sse), sse.numel(), int(elems_per_image), _p(d), _p(acc), _stream()), "eval_accumulate")
+
+
 def from_nhwc(y, c):
     """Internal NHWC -> NCHW-shaped result (zero-copy channels-last view when C % 4 == 0)."""
     if y.shape[3] == c:

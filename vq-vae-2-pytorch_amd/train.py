@@ -232,6 +232,39 @@ class Stage1Trainer:
             out["dec"] = ops.from_nhwc(d, channels) if hasattr(model, "forward_nhwc") else d
         return out
 
+    # ------------------------------------------------------------------ held-out evaluation
+    def evaluate(self, batches, sample=None):
+        """Evaluator.result() over an iterable of batches (float32 NCHW, or uint8 with the trainer's normalizer), between
+        two steps: eval-mode forwards under no_grad that write no EMA statistics slot, no codebook buffer and no
+        parameter, so the steps that follow are bit for bit those of a run that never evaluated; every module's
+        train / eval flag is restored.  Data parallel: every rank calls it (result() sums over the group).  sample: a
+        batch (same forms) whose grid (sample_grid) is returned under "sample"."""
+        from .evaluate import Evaluator
+        ev = Evaluator(self.model, self.normalizer)
+        for img in batches:
+            ev.update(img)
+        out = ev.result()
+        if sample is not None:
+            out["sample"] = self.sample_grid(sample)
+        return out
+
+    def sample_grid(self, sample):
+        """The reference's sample image (train_vqvae.py:133-139) as one uint8 canvas on the device: the inputs on the top
+        row, their eval-mode reconstructions below (nrow = len(sample)), in the normalizer's layout.  No collective:
+        one rank may call it alone.  Leaves trainer and model as evaluate() does."""
+        if self.normalizer is None:
+            raise TypeError("Stage1Trainer.sample_grid needs Stage1Trainer(..., normalizer=ImageNormalizer(...)): its "
+                            "statistics are the ones the grid inverts")
+        from .evaluate import eval_mode
+        model = self.model
+        if not hasattr(model, "forward_nhwc"):
+            raise TypeError(f"Stage1Trainer.sample_grid: {type(model).__name__} has no forward_nhwc")
+        with torch.no_grad():
+            x = self.normalizer(sample) if sample.dtype == torch.uint8 else ops.to_nhwc(sample)
+            with eval_mode(model):
+                dec, _ = model.forward_nhwc(x)
+            return self.normalizer.inverse().grid([x, dec], nrow=x.shape[0], nhwc=True)
+
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self):
         """"model" is exactly what the reference saves (train_vqvae.py:205-206: model.state_dict(), loadable by

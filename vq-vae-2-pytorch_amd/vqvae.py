@@ -351,13 +351,15 @@ class VQVAE(nn.Module):
         quant = ops.CatViewFn.apply(up, quant_b, cat)
         return self.dec.nhwc(quant)
 
-    def forward_nhwc(self, x):
-        """NHWC in ([N,H,W,ceil4(in_channel)], zero padded) -> (NHWC reconstruction, diff [1])."""
+    def forward_nhwc(self, x, return_ids=False):
+        """NHWC in ([N,H,W,ceil4(in_channel)], zero padded) -> (NHWC reconstruction, diff [1]); with return_ids also the
+        code indices of both levels (id_t, id_b), which the same forward computes anyway (Evaluator's histograms)."""
         n, h, w, _ = x.shape
         e = self._e
         cat = torch.empty((n, h // 4, w // 4, 2 * e), device=x.device, dtype=torch.float32)
-        quant_t, quant_b, diff, _, _ = self._encode_nhwc(x, quant_b_out=cat[..., e:])
-        return self._decode_from(quant_t, cat, quant_b), diff
+        quant_t, quant_b, diff, id_t, id_b = self._encode_nhwc(x, quant_b_out=cat[..., e:])
+        dec = self._decode_from(quant_t, cat, quant_b)
+        return (dec, diff, id_t, id_b) if return_ids else (dec, diff)
 
     def forward(self, input):
         dec, diff = self.forward_nhwc(ops.to_nhwc(input))
