@@ -1,6 +1,6 @@
-"""Every conv dispatch branch against fp64, at its shape boundaries (csrc/vq2_conv.hip run_conv_gemm, launch_conv_gemm_fast,
-conv_c4_ok, conv_k64_ok, the sub-pixel gate, use_convT_small; vq2_wino.hip wino3_ok / launch_wino3; vq2_wgrad.hip plan_wgrad /
-launch_wgrad).  Kernel selection is a function of the layer's shape and strides alone, so the only way to reach a kernel is a
+"""Every conv dispatch branch against fp64, at its shape boundaries (csrc/vq2_conv.hip plan_conv with its conv_k4s2_c4,
+conv1x1_k64, Winograd (plan_wino) and sub-pixel gates and its fast-GEMM instantiation flags, use_convT_small; vq2_wgrad.hip
+plan_wgrad / launch_wgrad).  Kernel selection is a function of the layer's shape and strides alone, so the only way to reach a kernel is a
 shape on the right side of every threshold: CASES is that list, written down as data, with the profiler label (tile and
 instantiation included) each case must produce under VQ2_FORMS = all / direct / general.
 
@@ -29,7 +29,7 @@ comparison of the plain fp32 result with the fp64 reference fails in every case 
 tests/test_host_cpu.py runs it for one case of every label family).
 
 Batch invariance (SWITCH_PAIRS): the rows of image 0 computed at batch N equal BITWISE the rows computed at batch N' on the
-other side of each launch-size switch -- 400 / 512 / 1024 tiles in run_conv_gemm, `wide` in launch_wino3 (both row widths,
+other side of each launch-size switch -- 400 / 512 / 1024 tiles in plan_conv, `wide` in plan_wino (both row widths,
 3x3 and k4s2), M >= 16384 of conv1x1_k64.  No exception was found.
 
 Tensors of 1 GiB and more come last (peak device memory of the module: 5.0 GiB)."""
@@ -53,7 +53,7 @@ CASES = [
     # op, transposed, cin, cout, k, stride, pad, N, H, W, flags, label under VQ2_FORMS = all, direct, general
     # flags -- fwd: i ReLU-in, b bias, r residual, o ReLU-out; dgrad: m mask, r residual, a VQ2_MASK_AFTER_RESIDUAL;
     #          wgrad: i ReLU-in, b bias (every wgrad case also runs without ReLU-in)
-    # ---- run_conv_gemm: wgs128 = ceil(M / 128) * ceil(Co / 128) * phases at 400 / 512 / 1024 (8x16 images: wgs128 == N)
+    # ---- plan_conv: wgs128 = ceil(M / 128) * ceil(Co / 128) * phases at 400 / 512 / 1024 (8x16 images: wgs128 == N)
     ('fwd', F, 64, 128, 3, 1, 1, 399, 8, 16, 'ibro',         'conv_gemm<64x128x32>|tap', 'conv_gemm<64x128x32>|tap', 'conv_gemm<64x128x16>|gen'),
     ('fwd', F, 64, 128, 3, 1, 1, 400, 8, 16, 'ibro',         'conv_gemm<128x128x32>|tap', 'conv_gemm<128x128x32>|tap', 'conv_gemm<128x128x32>|gen'),
     ('fwd', F, 64, 128, 3, 1, 1, 400, 8, 16, '',             'conv_gemm<128x128x32>|tap', 'conv_gemm<128x128x32>|tap', 'conv_gemm<128x128x32>|gen'),
@@ -195,21 +195,21 @@ CASES = [
 ]
 
 # the sections of CASES, in order (read the table against the dispatch functions with these):
-#   run_conv_gemm tiles by Co (32 | 36, 64 | 68), K <= 64 (Co 128 | 132 | 192 | 196, K 64 | 68), Ci % 16 in the 512..1024 window;
-#   launch_conv_gemm_fast: Ci % BK (48 on BK 32: var, on BK 16: uni; 40: var), Ci > 32 and Ci % 32 (32 uni, 96 tap), taps > 1;
-#   KH * KW <= 32 (25 fast | 36, 49 general);  conv_c4_ok (Ci 4 | 8, Co 64 | 68, residual, 3 or 4 real channels, mask);
-#   conv_k64_ok (M 16383 | 16384, Ci 64 | 68, Co % 32, Co 32 | 64, 192 | 224);  sub-pixel gate (sp_wgs 511 | 512 at K = 64,
+#   plan_conv tiles by Co (32 | 36, 64 | 68), K <= 64 (Co 128 | 132 | 192 | 196, K 64 | 68), Ci % 16 in the 512..1024 window;
+#   plan_conv's uni / tap_inner: Ci % BK (48 on BK 32: var, on BK 16: uni; 40: var), Ci > 32 and Ci % 32 (32 uni, 96 tap), taps > 1;
+#   KH * KW <= 32 (25 fast | 36, 49 general);  the conv_k4s2_c4 gate (Ci 4 | 8, Co 64 | 68, residual, 3 or 4 real channels, mask);
+#   the conv1x1_k64 gate (M 16383 | 16384, Ci 64 | 68, Co % 32, Co 32 | 64, 192 | 224);  sub-pixel gate (sp_wgs 511 | 512 at K = 64,
 #   K 448 | 512, Co % 64, Ci % 16);  use_convT_small (Cor 3 | 4, Co 4 | 8, Ci % 16; refusals: test_conv_transpose_small_refusals);
-#   wino3_ok / launch_wino3 (rows64 | rows32 | neither, Ci 24 | 32 | 36, Co % 64, Co % 128 for k4s2 on 32-pixel rows, wide 399 | 400).
+#   plan_wino (rows64 | rows32 | neither, Ci 24 | 32 | 36, Co % 64, Co % 128 for k4s2 on 32-pixel rows, wide 399 | 400).
 # Branches that cannot be reached through the ABI, by the code (no case can exist):
 #   - launch_wgrad, `rows_per_split % 32 == 0`: plan_wgrad rounds rows_per_split up to a multiple of 32;
-#   - launch_conv_gemm_fast, `K % BK == 0` once `Ci % BK == 0` holds: K = KH * KW * Ci;
+#   - plan_conv's `uni`, `K % BK == 0` once `Ci % BK == 0` holds: K = KH * KW * Ci;
 #   - the non-uniform instantiation of the four-per-CU 128x128x16 tile: its gate (Ci % 16 == 0, below 1 GiB) implies `small`,
-#     and OCC4 makes `uni` true then;
-#   - conv_c4_ok, `H % 2`, `W % 2`, `KH == 4`, `pad == 1` given stride 2, and conv_k64_ok, `stride == 1` given KH == 1:
+#     and `occ4` makes `uni` true then;
+#   - the conv_k4s2_c4 gate, `H % 2`, `W % 2`, `KH == 4`, `pad == 1` given stride 2, and the conv1x1_k64 gate, `stride == 1` given KH == 1:
 #     check_desc admits stride 2 only as k4 p1 on even sizes (phases == 1 with a 4x4 stride-2 kernel is that layer or the
 #     data gradient of a conv-transpose, which is k4 s2 p1 by check_desc as well).
-# Reachable only with a tensor of 1 GiB: `below_gib == false` inside the 513..1024-tile window (an operand that is a channel slice
+# Reachable only with a tensor of 1 GiB: `small == false` inside the 513..1024-tile window (an operand that is a channel slice
 # of a buffer 2048 floats wide) -- the first case of test_tensors_of_one_gib_and_more.
 # Not every (tile, instantiation) product is enumerated: each tile has a case, and each of tap / uni / var has cases on BK = 16
 # and on BK = 32 tiles; e.g. conv_gemm<64x128x16>|var (K <= 64, Co = 128, Ci = 12) has none.  EXPECTED_LABELS lists exactly
@@ -526,7 +526,7 @@ def _sweep(op, tr, cin, cout, k, s, p, h, w, fl, pairs):
 _TILES = ((399, 400), (512, 513), (1024, 1025))
 _ONE = ((399, 400),)
 SWITCH_PAIRS = (
-    _sweep("fwd", F, 64, 128, 3, 1, 1, 8, 16, "ibro", _TILES) +      # run_conv_gemm: 400, 512, 1024 tiles
+    _sweep("fwd", F, 64, 128, 3, 1, 1, 8, 16, "ibro", _TILES) +      # plan_conv: 400, 512, 1024 tiles
     _sweep("dgrad", F, 128, 64, 3, 1, 1, 8, 16, "mr", _TILES) +
     _sweep("fwd", F, 32, 128, 3, 1, 1, 2, 64, "ibro", _ONE) + _sweep("fwd", F, 32, 128, 3, 1, 1, 4, 32, "", _ONE) +   # wide, 3x3
     _sweep("dgrad", F, 128, 64, 3, 1, 1, 2, 64, "mra", _ONE) + _sweep("dgrad", F, 128, 64, 3, 1, 1, 4, 32, "mr", _ONE) +

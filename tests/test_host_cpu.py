@@ -209,25 +209,26 @@ def test_invalid_arguments_are_rejected_without_gpu(amd):
 
 def _label_families_in_source():
     """Every kernel label the library can print, tile included, read from csrc/*.hip: the prof_label format strings, and for
-    the templated launchers the template arguments at their call sites."""
+    the templated launchers the template arguments in the tile tables (FAST_TILES / GEN_TILES of vq2_conv.hip, the three tables
+    of vq2_wino.hip) and at the call sites of launch_wgrad."""
     src = {f: open(os.path.join(ROOT, "vq-vae-2-pytorch_amd", "csrc", f)).read()
            for f in os.listdir(os.path.join(ROOT, "vq-vae-2-pytorch_amd", "csrc")) if f.endswith((".hip", ".cpp"))}
     fams = set(m.split("|")[0] for text in src.values() for m in re.findall(r'prof_label\("([^"]+)"', text))
     conv, wino, wgrad = src["vq2_conv.hip"], src["vq2_wino.hip"], src["vq2_wgrad.hip"]
     tiles = {"fast": set(), "gen": set(), "wgrad": set(), "wino": set()}
-    for a, b, c, d_, bk in re.findall(r"return launch_conv_gemm_fast<(\d), (\d), (\d), (\d), (\d+)", conv):
+    for a, b, c, d_, bk in re.findall(r"\bfast_tile<(\d), (\d), (\d), (\d), (\d+)", conv):
         tiles["fast"].add("conv_gemm<%dx%dx%s>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32, bk))
-    for a, b, c, d_, bk in re.findall(r"return launch_conv_gemm<(\d), (\d), (\d), (\d), (\d+)", conv):
+    for a, b, c, d_, bk in re.findall(r"\bgen_tile<(\d), (\d), (\d), (\d), (\d+)", conv):
         tiles["gen"].add("conv_gemm<%dx%dx%s>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32, bk))
     for a, b, c, d_ in re.findall(r"launch_wgrad<(\d), (\d), (\d), (\d)>\(P", wgrad):
         tiles["wgrad"].add("wgrad<%dx%d>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32))
     cand = re.search(r"cand\[6\]\[2\] = \{(.*?)\};", wgrad).group(1)
     assert tiles["wgrad"] == set("wgrad<%sx%s>" % t for t in re.findall(r"\{(\d+), (\d+)\}", cand))   # launchers == candidates
-    for tpw, nt in re.findall(r"wino::launch<(\d+), (\d), \d+>", wino):
+    for tpw, nt in re.findall(r"\bwino3_tile<(\d+), (\d), \d+>", wino):
         tiles["wino"].add("conv_wino3<%dx%d,nt%s>" % (64 // int(tpw), 2 * int(tpw), nt))
-    for tpw, nt in re.findall(r"wino::launch_k4s2<(\d+), (\d), \d+>", wino):
+    for tpw, nt in re.findall(r"\bk4s2_tile<(\d+), (\d), \d+>", wino):
         tiles["wino"].add("conv_wino_k4s2<%dx%d,nt%s>" % (64 // int(tpw), 2 * int(tpw), nt))
-    for tpw in re.findall(r"wino::launch_subpixel2<(\d+)>", wino):
+    for tpw in re.findall(r"\bsubpixel2_tile<(\d+)>", wino):
         tiles["wino"].add("conv_wino_subpixel<%dx%d>" % (128 // int(tpw), 2 * int(tpw)))
     return fams, tiles
 

@@ -1,4 +1,5 @@
-// Launch parameters shared by the conv kernels of libvq2 (vq2_conv.hip, vq2_wino.hip).
+// Launch parameters, kernel plan and host helpers shared by the conv kernels of libvq2 (vq2_conv.hip, vq2_wino.hip,
+// vq2_wgrad.hip).
 #pragma once
 #include "vq2_common.h"
 
@@ -30,12 +31,92 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int OOB = 0x7FFFFFF0;  // >= num_records of every descriptor: loads return 0, stores are dropped
 constexpr unsigned RSRC_FLAGS = 0x00020000;
 
+// How many ELEMENTS a tensor may have for a kernel's 32-bit byte offsets, one constant per out-of-range sentinel (the other
+// three, sp::REACH / c4::REACH / ctm::REACH, sit next to their sentinels in vq2_conv.hip):
+//   FAST_REACH     kernels that send lanes out of range with OOB: every tensor below 2 GiB
+//   PENALTY_REACH  kernels that send lanes out of range by ADDING 2^31 to a valid offset (conv_gemm_fast_kernel's uniform
+//                  chunks, the Winograd kernels): as an unsigned buffer offset anything >= 2^31 - (tensor bytes) is out of
+//                  range, so every tensor stays below 1 GiB
+constexpr long FAST_REACH = (1L << 31) / 4;
+constexpr long PENALTY_REACH = (1L << 30) / 4;
+
 __device__ __forceinline__ float4 as_f4(u32x4 v) {
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 
-// vq2_wino.hip: 3x3 stride-1 pad-1 convolutions as F(2,3) Winograd along the image rows
-bool wino3_ok(const ConvGemmParams &P);
-int launch_wino3(const ConvGemmParams &P, hipStream_t s);
+// ---------------------------------------------------------------------------------------------- descriptor helpers
+static inline int real_ci(const vq2_conv_desc *d) { return d->Cir ? d->Cir : d->Ci; }
+static inline int real_co(const vq2_conv_desc *d) { return d->Cor ? d->Cor : d->Co; }
+
+struct ConvHW { int h, w; };
+static inline ConvHW out_hw(const vq2_conv_desc *d) {
+    if (d->transposed) return {2 * d->H, 2 * d->W};
+    return {(d->H + 2 * d->pad - d->KH) / d->stride + 1, (d->W + 2 * d->pad - d->KW) / d->stride + 1};
+}
+
+// Algorithmic work of a layer, the same for its forward, data-gradient and weight-gradient launches (for the profiler only):
+// real channels, every tap once; the input-sized and the output-sized tensor cross memory once each, plus `more_in` /
+// `more_out` further tensors of those sizes (residual, mask), plus the weights.
+struct ConvWork { double flops, bytes; };
+static inline ConvWork conv_work(const vq2_conv_desc *d, int more_in, int more_out) {
+    const double cir = real_ci(d), cor = real_co(d);
+    const ConvHW o = out_hw(d);
+    const double pix_in = (double)d->N * d->H * d->W, pix_out = (double)d->N * o.h * o.w;
+    const double macs = d->transposed ? pix_in * 16.0 * cir * cor : pix_out * d->KH * d->KW * cir * cor;
+    return {2.0 * macs, 4.0 * (pix_in * cir * (1.0 + more_in) + pix_out * cor * (1.0 + more_out) + cir * cor * d->KH * d->KW)};
+}
+
+// ---------------------------------------------------------------------------------------------- extents of a launch
+// Element counts of the tensors of a forward / data-gradient launch, computed once; every "does this tensor fit the 32-bit
+// offsets of that kernel" test compares them with the kernel's reach.
+struct ConvExtents {
+    long x, y, mask, res, w;   // mask / res: output pixels times ldm / ldr, whether or not the pointer is set
+    long aux() const { return mask > res ? mask : res; }
+    bool acts_fit(long reach) const { return x < reach && y < reach && aux() < reach; }
+    bool all_fit(long reach) const { return acts_fit(reach) && w < reach; }
+};
+static inline ConvExtents conv_extents(const ConvGemmParams &P) {
+    const long ypix = (long)P.N * P.Hy * P.Wy;
+    return {(long)P.N * P.H * P.W * P.ldx, ypix * P.ldy, ypix * P.ldm, ypix * P.ldr, (long)P.Co * P.K * P.phases};
+}
+
+// ---------------------------------------------------------------------------------------------- the plan of a launch
+// plan_conv() (vq2_conv.hip) chooses the kernel of a forward / data-gradient launch from the shape and strides alone;
+// launch_conv() launches what the plan says.
+enum ConvFamily {
+    CONV_GEMM_GEN, CONV_GEMM_FAST, CONV_K4S2_C4, CONV_1X1_K64, CONV_SUBPIXEL, CONV_WINO3, CONV_WINO_K4S2, CONV_WINO_SUBPIXEL,
+    CONV_FAMILIES
+};
+
+struct ConvPlan {
+    int family;        // ConvFamily
+    int tile;          // index into the family's tile table (conv_tiles)
+    // instantiation flags (each read by its own family only)
+    bool occ4;         // fast GEMM: four workgroups per CU (a property of the 128x128x16 tile)
+    bool uni;          // fast GEMM: every chunk lies in one tap (scalar k tracking)
+    bool tap_inner;    // fast GEMM: uniform chunks with the taps innermost
+    bool rows64;       // Winograd: rows of whole 64-pixel segments (else 32-pixel segments)
+    bool wide;         // Winograd: 128-channel tiles (else 64)
+    bool c4;           // conv_k4s2_c4: the fourth input channel is real
+    int tpw;           // conv_k4s2_c4: tiles per workgroup
+    int nb;            // conv1x1_k64: Co / 32 column blocks
+};
+
+// A tile of a family: what the label prints of it and the launcher of its instantiations.
+//   GEMM families: dim = BM x BN x BK;   Winograd families: dim = image rows x pixels per row, NT;   conv1x1_k64: dim[0] = NB
+struct ConvTile {
+    int dim[3];
+    int (*launch)(const ConvPlan &, const ConvGemmParams &, const char *name, hipStream_t);
+};
+struct ConvTiles { const ConvTile *tile; int n; };
+ConvTiles conv_tiles(int family);                 // vq2_conv.hip; the Winograd families from wino_tiles
+ConvTiles wino_tiles(int family);                 // vq2_wino.hip
+
+namespace wino {
+constexpr int BK = 8;   // input channels per staged block of the Winograd kernels (vq2_wino.hip)
+}
+
+ConvPlan plan_conv(const ConvGemmParams &P);
+int launch_conv(const ConvPlan &plan, const ConvGemmParams &P, hipStream_t s);
 
 }  // namespace vq2

@@ -575,45 +575,33 @@ __global__ __launch_bounds__(256, OCC4 ? 4 : ((MT * NT == 4) ? (BK == 16 ? 3 : 2
 }
 
 template <int WAVES_M, int WAVES_N, int MT, int NT, int BK, bool OCC4 = false>
-static int launch_conv_gemm_fast(const ConvGemmParams &P, hipStream_t s) {
+static int launch_conv_gemm_fast(const ConvPlan &pl, const ConvGemmParams &P, const char *name, hipStream_t s) {
     constexpr int BM = WAVES_M * MT * 32, BN = WAVES_N * NT * 32;
     const size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (OCC4 ? 0 : 64 * sizeof(int));
     const unsigned nwg = ((P.M + BM - 1) / BM) * ((P.Co + BN - 1) / BN) * P.phases;
-    // uniform k tracking whenever a chunk never straddles two taps (every layer except the 3-channel ones)
-    const long gib = 1L << 30;
-    const bool small = (long)P.N * P.H * P.W * P.ldx * 4 < gib && (long)P.Co * P.K * P.phases * 4 < gib;
-    const bool uni = small && (OCC4 || (P.Ci % BK == 0 && P.K % BK == 0));
-    const bool tap_inner = uni && P.KH * P.KW > 1 && P.Ci > 32 && P.Ci % 32 == 0;
-    auto kern = P.relu_in ? (uni ? (tap_inner ? conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, true, true>
-                                              : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, true, false>)
-                                 : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, OCC4>)
-                          : (uni ? (tap_inner ? conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, true>
-                                              : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, false>)
-                                 : conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, OCC4>);
+    void (*kern)(const ConvGemmParams);
+    switch ((P.relu_in ? 4 : 0) | (pl.tap_inner ? 2 : pl.uni ? 1 : 0)) {   // ReLU-in x (tap, uni, var)
+        case 4 | 2: kern = conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, true, true>; break;
+        case 4 | 1: kern = conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, true, false>; break;
+        case 4:     kern = conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, true, OCC4, OCC4>; break;
+        case 2:     kern = conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, true>; break;
+        case 1:     kern = conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, true, false>; break;
+        default:    kern = conv_gemm_fast_kernel<WAVES_M, WAVES_N, MT, NT, BK, true, false, OCC4, OCC4>; break;
+    }
     allow_big_lds(kern, lds);
     dim3 grid(nwg);
-    const char *name = "conv_gemm";
-    if (prof_enabled())
-        // (the last field names the instantiation: tap = uniform chunks with the taps innermost, uni = uniform chunks,
-        //  var = chunks that may straddle taps; conv_gemm_kernel says gen)
-        name = prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d,%s", BM, BN, BK, P.M, P.Co, P.K, P.KH, P.stride,
-                          P.phases, tap_inner ? "tap" : uni ? "uni" : "var");
     ProfScope prof(name, P.flops, P.bytes, s, BM == 128 && BN == 128);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, P);
     return check_launch("conv_gemm_fast_kernel");
 }
 
 template <int WAVES_M, int WAVES_N, int MT, int NT, int BK>
-static int launch_conv_gemm(const ConvGemmParams &P, hipStream_t s) {
+static int launch_conv_gemm(const ConvPlan &, const ConvGemmParams &P, const char *name, hipStream_t s) {
     constexpr int BM = WAVES_M * MT * 32, BN = WAVES_N * NT * 32;
     const size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
     auto kern = conv_gemm_kernel<WAVES_M, WAVES_N, MT, NT, BK>;
     allow_big_lds(kern, lds);
     dim3 grid(((P.M + BM - 1) / BM) * ((P.Co + BN - 1) / BN) * P.phases);
-    const char *name = "conv_gemm";
-    if (prof_enabled())
-        name = prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d,gen", BM, BN, BK, P.M, P.Co, P.K, P.KH, P.stride,
-                          P.phases);
     ProfScope prof(name, P.flops, P.bytes, s, BM == 128 && BN == 128 && BK == 32);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, P);
     return check_launch("conv_gemm_kernel");
@@ -636,6 +624,7 @@ constexpr int B_ROWS = 4 * 64;               // (tap, co) rows of one phase pane
 constexpr int B_FLOATS = B_ROWS * LDK;       // 5120
 constexpr size_t LDS_BYTES = (size_t)2 * (A_FLOATS + B_FLOATS) * sizeof(float);   // 69,760: two workgroups per CU
 constexpr int SOOB = 0x7F000000;
+constexpr long REACH = SOOB / 4;     // elements: the out-of-range sentinel must stay above every tensor
 }  // namespace sp
 
 template <bool RELU_IN>
@@ -817,11 +806,9 @@ __global__ __launch_bounds__(256, 2) void subpixel_conv_kernel(const ConvGemmPar
     }
 }
 
-static int launch_subpixel(const ConvGemmParams &P, hipStream_t s) {
+static int launch_subpixel(const ConvPlan &, const ConvGemmParams &P, const char *name, hipStream_t s) {
     const int tiles = ((P.W + sp::TW - 1) / sp::TW) * ((P.H + sp::TH - 1) / sp::TH);
     dim3 grid(P.N * tiles * (P.Co / 64));
-    const char *name = "subpixel_conv";
-    if (prof_enabled()) name = prof_label("subpixel_conv|M=%d,N=%d,K=%d,ph4", P.M, P.Co, P.K);
     ProfScope prof(name, P.flops, P.bytes, s);
     auto kern = P.relu_in ? subpixel_conv_kernel<true> : subpixel_conv_kernel<false>;
     allow_big_lds(kern, sp::LDS_BYTES);
@@ -845,6 +832,7 @@ constexpr int PH = 2 * TH + 2, PW = 2 * TW + 2;   // input patch
 constexpr int NP = PH * PW;                       // 612 pixels of 16 bytes
 constexpr int P_LD = (NP + 255) / 256;            // 3 patch loads per thread
 constexpr int COOB = 0x7F000000;
+constexpr long REACH = COOB / 4;                  // elements: the out-of-range sentinel must stay above every tensor
 }  // namespace c4
 
 template <bool HAS_MASK, bool C4>
@@ -1127,115 +1115,231 @@ __global__ __launch_bounds__(512, 2) void conv1x1_k64_kernel(const ConvGemmParam
     }
 }
 
-static bool conv_k64_ok(const ConvGemmParams &P) {
-    const long gib = 1L << 30;
-    return P.phases == 1 && P.KH == 1 && P.KW == 1 && P.stride == 1 && P.pad_h == 0 && P.pad_w == 0 && P.Ci == 64 &&
-           P.K == 64 && P.Co % 32 == 0 && P.Co >= 64 && P.Co <= 192 && P.M >= 16384 && P.ldx % 4 == 0 &&
-           (long)P.M * P.ldx * 4 < gib && (long)P.M * P.ldy * 4 < gib && (long)P.M * (P.ldm > P.ldr ? P.ldm : P.ldr) * 4 < gib;
-}
-
 template <int NB>
-static int launch_conv_k64_nb(const ConvGemmParams &P, hipStream_t s) {
+static int launch_conv_k64(const ConvPlan &, const ConvGemmParams &P, const char *name, hipStream_t s) {
     auto kern = P.relu_in ? conv1x1_k64_kernel<NB, true> : conv1x1_k64_kernel<NB, false>;
     const size_t lds = k64::lds_bytes<NB>();
     allow_big_lds(kern, lds);
     const int nblk = (P.M + 31) / 32;
     int grid = 256;                               // one 8-wave workgroup per CU, each wave walks nblk / 2048 row blocks
     if (grid * k64::NWAVES > nblk) grid = (nblk + k64::NWAVES - 1) / k64::NWAVES;
-    const char *name = "conv1x1_k64";
-    if (prof_enabled()) name = prof_label("conv1x1_k64|M=%d,N=%d,K=64", P.M, P.Co);
     ProfScope prof(name, P.flops, P.bytes, s);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * k64::NWAVES), lds, s, P);
     return check_launch("conv1x1_k64_kernel");
 }
 
-static int launch_conv_k64(const ConvGemmParams &P, hipStream_t s) {
-    switch (P.Co / 32) {
-        case 2: return launch_conv_k64_nb<2>(P, s);
-        case 3: return launch_conv_k64_nb<3>(P, s);
-        case 4: return launch_conv_k64_nb<4>(P, s);
-        case 5: return launch_conv_k64_nb<5>(P, s);
-        default: return launch_conv_k64_nb<6>(P, s);
-    }
-}
-
-static bool conv_c4_ok(const ConvGemmParams &P) {
-    const long big = 0x7F000000L / 4;
-    return P.phases == 1 && P.KH == 4 && P.KW == 4 && P.stride == 2 && P.pad_h == 1 && P.pad_w == 1 && P.Ci == 4 &&
-           P.Co == 64 && !P.res && P.H % 2 == 0 && P.W % 2 == 0 && P.ldy % 4 == 0 && (!P.mask || P.ldm % 4 == 0) &&
-           (long)P.N * P.H * P.W * P.ldx < big && (long)P.N * P.Ho * P.Wo * (P.ldy > P.ldm ? P.ldy : P.ldm) < big &&
-           (reinterpret_cast<uintptr_t>(P.y) & 15u) == 0 && (!P.mask || (reinterpret_cast<uintptr_t>(P.mask) & 15u) == 0);
-}
-
-static int launch_conv_c4(const ConvGemmParams &P, hipStream_t s) {
+static int launch_conv_c4(const ConvPlan &pl, const ConvGemmParams &P, const char *name, hipStream_t s) {
     const int tiles = ((P.Wo + c4::TW - 1) / c4::TW) * ((P.Ho + c4::TH - 1) / c4::TH) * P.N;
-    const char *name = "conv_k4s2_c4";
-    if (prof_enabled()) name = prof_label("conv_k4s2_c4|M=%d,N=%d,K=%d%s", P.M, P.Co, P.K, P.mask ? ",mask" : "");
     ProfScope prof(name, P.flops, P.bytes, s);
-    // measured (scripts/microbench.py c4s2_3_64 / t_64_3; generic tile: 75 / 88 us): the plain layer streams best with
-    // coalesced 4-byte stores and 4 tiles per workgroup (45 us, 3.7 TB/s of algorithmic bytes); the masked one with the
-    // 16-byte form whose mask loads sit behind the MFMAs and 8 tiles per workgroup (72 us, 4.2 TB/s)
-    const bool c4 = !(P.ci_real > 0 && P.ci_real <= 3);
-    auto kern = P.mask ? (c4 ? conv_k4s2_c4_kernel<true, true> : conv_k4s2_c4_kernel<true, false>)
-                       : (c4 ? conv_k4s2_c4_kernel<false, true> : conv_k4s2_c4_kernel<false, false>);
+    void (*kern)(const ConvGemmParams);
+    switch ((P.mask ? 2 : 0) | (pl.c4 ? 1 : 0)) {
+        case 2 | 1: kern = conv_k4s2_c4_kernel<true, true>; break;
+        case 2:     kern = conv_k4s2_c4_kernel<true, false>; break;
+        case 1:     kern = conv_k4s2_c4_kernel<false, true>; break;
+        default:    kern = conv_k4s2_c4_kernel<false, false>; break;
+    }
     ConvGemmParams Q = P;
-    Q.c4_tpw = P.mask ? 8 : 4;
+    Q.c4_tpw = pl.tpw;
     hipLaunchKernelGGL(kern, dim3((tiles + Q.c4_tpw - 1) / Q.c4_tpw), dim3(256), 0, s, Q);
     return check_launch("conv_k4s2_c4_kernel");
 }
 
-static int run_conv_gemm(const ConvGemmParams &P, hipStream_t s) {
+// ====================================================================== the plan: which kernel, which instantiation
+// The tile tables: every tile of a family once, with the launcher of its instantiations (a plan's `tile` is the position).
+template <int WAVES_M, int WAVES_N, int MT, int NT, int BK, bool OCC4 = false>
+static constexpr ConvTile fast_tile() {
+    return {{WAVES_M * MT * 32, WAVES_N * NT * 32, BK}, launch_conv_gemm_fast<WAVES_M, WAVES_N, MT, NT, BK, OCC4>};
+}
+template <int WAVES_M, int WAVES_N, int MT, int NT, int BK>
+static constexpr ConvTile gen_tile() {
+    return {{WAVES_M * MT * 32, WAVES_N * NT * 32, BK}, launch_conv_gemm<WAVES_M, WAVES_N, MT, NT, BK>};
+}
+template <int NB>
+static constexpr ConvTile k64_tile() { return {{NB, 0, 0}, launch_conv_k64<NB>}; }
+
+static const ConvTile GEN_TILES[] = {
+    gen_tile<2, 2, 1, 2, 16>(),         // 64 x 128
+    gen_tile<2, 2, 1, 1, 16>(),         // 64 x 64
+    gen_tile<2, 2, 2, 2, 32>(),         // 128 x 128
+    gen_tile<2, 2, 2, 1, 16>(),         // 128 x 64
+    gen_tile<4, 1, 1, 1, 16>(),         // 128 x 32
+};
+static const ConvTile FAST_TILES[] = {
+    fast_tile<2, 2, 1, 2, 32>(),        // 64 x 128
+    fast_tile<2, 2, 1, 1, 32>(),        // 64 x 64
+    fast_tile<2, 2, 1, 3, 16>(),        // 64 x 192
+    fast_tile<2, 2, 1, 2, 16>(),        // 64 x 128, short chunks
+    fast_tile<2, 2, 2, 2, 16, true>(),  // 128 x 128, four workgroups per CU (OCC4): the only tile with BM = BN = 128, BK = 16
+    fast_tile<2, 2, 2, 2, 32>(),        // 128 x 128
+    fast_tile<2, 2, 2, 1, 16>(),        // 128 x 64
+    fast_tile<4, 1, 1, 1, 32>(),        // 128 x 32
+};
+static const ConvTile K64_TILES[] = {k64_tile<2>(), k64_tile<3>(), k64_tile<4>(), k64_tile<5>(), k64_tile<6>()};
+static const ConvTile C4_TILES[] = {{{c4::TH, c4::TW, 0}, launch_conv_c4}};
+static const ConvTile SUBPIXEL_TILES[] = {{{sp::TH, sp::TW, 0}, launch_subpixel}};
+
+ConvTiles conv_tiles(int family) {
+    switch (family) {
+        case CONV_GEMM_GEN:  return {GEN_TILES, sizeof(GEN_TILES) / sizeof(ConvTile)};
+        case CONV_GEMM_FAST: return {FAST_TILES, sizeof(FAST_TILES) / sizeof(ConvTile)};
+        case CONV_K4S2_C4:   return {C4_TILES, 1};
+        case CONV_1X1_K64:   return {K64_TILES, sizeof(K64_TILES) / sizeof(ConvTile)};
+        case CONV_SUBPIXEL:  return {SUBPIXEL_TILES, 1};
+        default:             return wino_tiles(family);
+    }
+}
+
+// position of the tile with these dimensions in its family's table, -1 if the family has none (launch_conv refuses that)
+static int tile_of(int family, int d0, int d1, int d2) {
+    const ConvTiles t = conv_tiles(family);
+    for (int i = 0; i < t.n; ++i)
+        if (t.tile[i].dim[0] == d0 && t.tile[i].dim[1] == d1 && t.tile[i].dim[2] == d2) return i;
+    return -1;
+}
+
+// Shapes the Winograd kernels (vq2_wino.hip) take: 3x3, stride 1, pad 1, output the size of the input, whole 64-channel
+// output tiles, 8-channel input blocks (at least 32 channels), rows of whole 64-pixel segments (or 32-pixel ones with
+// H % 4 == 0), tensors below 1 GiB (32-bit offsets with an additive out-of-range penalty); likewise the 4x4 stride-2 and
+// sub-pixel forms.  The rows of the tile follow from the segment width: 64 pixels x 2 rows or 32 x 4 (sub-pixel: x 4 or x 8).
+static bool plan_wino(const ConvGemmParams &P, const ConvExtents &E, ConvPlan &pl) {
+    if (forms() < FORMS_ALL) return false;
+    if (!(P.Ci % wino::BK == 0 && P.Ci >= 32 && P.Co % 64 == 0 && P.ldx % 4 == 0 && E.all_fit(PENALTY_REACH))) return false;
+    // 128-channel tiles where they still give every CU two workgroups; 64-channel tiles otherwise (64-channel outputs, the
+    // 32x32 level)
+    pl.wide = P.Co % 128 == 0 && (long)P.N * P.Ho * P.Wo / 128 * (P.Co / 128) >= 400;
+    if (P.phases == 4) {   // sub-pixel conv-transpose: F(2,2) per output phase
+        pl.rows64 = P.W % 64 == 0 && P.H % 4 == 0;
+        if (!(P.KH == 2 && P.KW == 2 && P.K == 4 * P.Ci && P.Hy == 2 * P.H && P.Wy == 2 * P.W &&
+              (pl.rows64 || (P.W % 32 == 0 && P.H % 8 == 0))))
+            return false;
+        pl.family = CONV_WINO_SUBPIXEL;
+        pl.wide = false;   // (one tile width)
+        pl.tile = pl.rows64 ? tile_of(pl.family, 4, 64, 0) : tile_of(pl.family, 8, 32, 0);
+        return true;
+    }
+    if (P.KH == 4 && P.KW == 4 && P.stride == 2 && P.pad_h == 1 && P.pad_w == 1 && P.phases == 1) {   // F(2,2) by parity
+        pl.rows64 = P.Wo % 64 == 0 && P.Ho % 2 == 0;
+        if (!(2 * P.Ho == P.H && 2 * P.Wo == P.W && P.Hy == P.Ho && P.Wy == P.Wo &&
+              (pl.rows64 || (P.Wo % 32 == 0 && P.Ho % 4 == 0)) &&
+              // (64-channel outputs on 32-pixel rows lose to the direct 64-row tiles -- 128 -> 64 at 32x32 and batch 32: one tile
+              //  per CU, 94.5 vs 84.3 us.  The rule must not look at the batch size: results do not depend on it.)
+              (P.Co % 128 == 0 || P.Wo % 64 == 0)))
+            return false;
+        pl.family = CONV_WINO_K4S2;
+    } else {
+        pl.rows64 = P.W % 64 == 0 && P.H % 2 == 0;
+        // (from 32 input channels: 3x3 32 -> 128 at 64x64, 89.6 -> 74.5 us)
+        if (!(P.KH == 3 && P.KW == 3 && P.stride == 1 && P.pad_h == 1 && P.pad_w == 1 && P.phases == 1 &&
+              P.Ho == P.H && P.Wo == P.W && P.Hy == P.H && P.Wy == P.W && (pl.rows64 || (P.W % 32 == 0 && P.H % 4 == 0))))
+            return false;
+        pl.family = CONV_WINO3;
+    }
+    pl.tile = tile_of(pl.family, pl.rows64 ? 2 : 4, pl.rows64 ? 64 : 32, pl.wide ? 2 : 1);
+    return true;
+}
+
+ConvPlan plan_conv(const ConvGemmParams &P) {
+    ConvPlan pl{};
+    const ConvExtents E = conv_extents(P);
     // Tile by output-channel count (GEMM N).  Chunk depth per tile measured on MI355X: the 128x128 tile is
     // register-bound at 2 waves/SIMD and prefers BK=32; the narrower tiles run 4+ waves/SIMD with BK=16.
     // few row tiles (the 32x32-resolution layers): halve the tile height so every CU still holds >= 2
     // workgroups and the matrix pipe of a SIMD always has a second wave to switch to
     const long wgs128 = (long)((P.M + 127) / 128) * ((P.Co + 127) / 128) * P.phases;
-    const long lim = (1L << 29);  // elements: every tensor below 2 GiB so that 32-bit byte offsets suffice
-    const bool fast_ok = forms() > FORMS_GENERAL && P.KH * P.KW <= 32 && (long)P.N * P.H * P.W * P.ldx < lim &&
-                         (long)P.N * P.Hy * P.Wy * P.ldy < lim && (long)P.N * P.Hy * P.Wy * (P.ldm > P.ldr ? P.ldm : P.ldr) < lim &&
-                         (long)P.Co * P.K * P.phases < lim;
-    if (fast_ok && conv_c4_ok(P)) return launch_conv_c4(P, s);
-    if (fast_ok && conv_k64_ok(P)) return launch_conv_k64(P, s);
-    if (fast_ok && wino3_ok(P)) return launch_wino3(P, s);   // vq2_wino.hip
-    const long big = 0x7F000000L / 4;   // the patch kernel's out-of-range sentinel must stay above every tensor
+    const bool half = wgs128 < 400 && P.Co > 32;
+    // every tensor below 2 GiB so that 32-bit byte offsets suffice
+    const bool fast_ok = forms() > FORMS_GENERAL && P.KH * P.KW <= 32 && E.all_fit(FAST_REACH);
+    if (!fast_ok) {
+        pl.family = CONV_GEMM_GEN;
+        if (half) pl.tile = P.Co > 64 ? tile_of(pl.family, 64, 128, 16) : tile_of(pl.family, 64, 64, 16);
+        else if (P.Co > 64) pl.tile = tile_of(pl.family, 128, 128, 32);
+        else pl.tile = P.Co > 32 ? tile_of(pl.family, 128, 64, 16) : tile_of(pl.family, 128, 32, 16);
+        return pl;
+    }
+    if (P.phases == 1 && P.KH == 4 && P.KW == 4 && P.stride == 2 && P.pad_h == 1 && P.pad_w == 1 && P.Ci == 4 &&
+        P.Co == 64 && !P.res && P.H % 2 == 0 && P.W % 2 == 0 && P.ldy % 4 == 0 && (!P.mask || P.ldm % 4 == 0) &&
+        E.x < c4::REACH && (E.y > E.mask ? E.y : E.mask) < c4::REACH && aligned16(P.y) && (!P.mask || aligned16(P.mask))) {
+        pl.family = CONV_K4S2_C4;
+        // measured (scripts/microbench.py c4s2_3_64 / t_64_3; generic tile: 75 / 88 us): the plain layer streams best with
+        // coalesced 4-byte stores and 4 tiles per workgroup (45 us, 3.7 TB/s of algorithmic bytes); the masked one with the
+        // 16-byte form whose mask loads sit behind the MFMAs and 8 tiles per workgroup (72 us, 4.2 TB/s)
+        pl.c4 = !(P.ci_real > 0 && P.ci_real <= 3);
+        pl.tpw = P.mask ? 8 : 4;
+        return pl;
+    }
+    if (P.phases == 1 && P.KH == 1 && P.KW == 1 && P.stride == 1 && P.pad_h == 0 && P.pad_w == 0 && P.Ci == 64 &&
+        P.K == 64 && P.Co % 32 == 0 && P.Co >= 64 && P.Co <= 192 && P.M >= 16384 && P.ldx % 4 == 0 &&
+        E.acts_fit(PENALTY_REACH)) {
+        pl.family = CONV_1X1_K64;
+        pl.nb = P.Co / 32;
+        pl.tile = tile_of(pl.family, pl.nb, 0, 0);
+        return pl;
+    }
+    ConvPlan w{};
+    if (plan_wino(P, E, w)) return w;
     // (a launch of <= 256 workgroups with a short depth is better off with the 64-row GEMM tiles: measured)
     const long sp_wgs = (long)P.N * ((P.W + sp::TW - 1) / sp::TW) * ((P.H + sp::TH - 1) / sp::TH) * (P.Co / 64);
-    if (fast_ok && P.phases == 4 && P.Co % 64 == 0 && P.Ci % 16 == 0 && P.K == 4 * P.Ci &&
-        (sp_wgs >= 512 || P.K >= 512) &&
-        (long)P.N * P.H * P.W * P.ldx < big && (long)P.N * P.Hy * P.Wy * P.ldy < big &&
-        (long)P.N * P.Hy * P.Wy * (P.ldm > P.ldr ? P.ldm : P.ldr) < big)
-        return launch_subpixel(P, s);
-    if (fast_ok) {
-        if (wgs128 < 400 && P.Co > 32) {
-            if (P.Co > 64) return launch_conv_gemm_fast<2, 2, 1, 2, 32>(P, s);
-            return launch_conv_gemm_fast<2, 2, 1, 1, 32>(P, s);
-        }
-        if (P.Co > 64) {
-            // K <= 64 (the 1x1 convs out of 32/64 channels): one or two chunks, HBM/epilogue-bound ->
-            // 64-row tiles double the workgroups in flight (measured +12 % on 32 -> 128)
-            if (P.K <= 64) {
-                // N = 192 (data gradient of quantize_conv_b, vqvae.py:189): a 192-wide tile covers the row in ONE pass --
-                // with 128-wide tiles the second column tile is half empty (a quarter of the MFMAs wasted) and the dy
-                // rows are read twice
-                if (P.Co > 128 && P.Co <= 192) return launch_conv_gemm_fast<2, 2, 1, 3, 16>(P, s);
-                return launch_conv_gemm_fast<2, 2, 1, 2, 16>(P, s);
-            }
-            // 513..1024 tiles (every 64x64-resolution layer at batch 32): four workgroups per CU hold ALL tiles at
-            // once -- one round instead of two in lock-step (measured +1..3 % per launch, 7.30 -> 7.23 ms/step)
-            const bool below_gib = (long)P.N * P.H * P.W * P.ldx * 4 < (1L << 30) && (long)P.Co * P.K * P.phases * 4 < (1L << 30);
-            if (P.Ci % 16 == 0 && below_gib && wgs128 > 512 && wgs128 <= 1024) return launch_conv_gemm_fast<2, 2, 2, 2, 16, true>(P, s);
-            return launch_conv_gemm_fast<2, 2, 2, 2, 32>(P, s);
-        }
-        if (P.Co > 32) return launch_conv_gemm_fast<2, 2, 2, 1, 16>(P, s);
-        return launch_conv_gemm_fast<4, 1, 1, 1, 32>(P, s);
+    if (P.phases == 4 && P.Co % 64 == 0 && P.Ci % 16 == 0 && P.K == 4 * P.Ci && (sp_wgs >= 512 || P.K >= 512) &&
+        E.acts_fit(sp::REACH)) {
+        pl.family = CONV_SUBPIXEL;
+        return pl;
     }
-    if (wgs128 < 400 && P.Co > 32) {
-        if (P.Co > 64) return launch_conv_gemm<2, 2, 1, 2, 16>(P, s);      // 64 x 128
-        return launch_conv_gemm<2, 2, 1, 1, 16>(P, s);                     // 64 x 64
+    pl.family = CONV_GEMM_FAST;
+    // uniform k tracking whenever a chunk never straddles two taps (every layer except the 3-channel ones), on tensors
+    // the additive out-of-range penalty reaches
+    const bool small = E.x < PENALTY_REACH && E.w < PENALTY_REACH;
+    if (half) {
+        pl.tile = P.Co > 64 ? tile_of(pl.family, 64, 128, 32) : tile_of(pl.family, 64, 64, 32);
+    } else if (P.Co > 64) {
+        // K <= 64 (the 1x1 convs out of 32/64 channels): one or two chunks, HBM/epilogue-bound ->
+        // 64-row tiles double the workgroups in flight (measured +12 % on 32 -> 128)
+        if (P.K <= 64)
+            // N = 192 (data gradient of quantize_conv_b, vqvae.py:189): a 192-wide tile covers the row in ONE pass --
+            // with 128-wide tiles the second column tile is half empty (a quarter of the MFMAs wasted) and the dy
+            // rows are read twice
+            pl.tile = (P.Co > 128 && P.Co <= 192) ? tile_of(pl.family, 64, 192, 16) : tile_of(pl.family, 64, 128, 16);
+        // 513..1024 tiles (every 64x64-resolution layer at batch 32): four workgroups per CU hold ALL tiles at
+        // once -- one round instead of two in lock-step (measured +1..3 % per launch, 7.30 -> 7.23 ms/step)
+        else if (P.Ci % 16 == 0 && small && wgs128 > 512 && wgs128 <= 1024) pl.tile = tile_of(pl.family, 128, 128, 16);
+        else pl.tile = tile_of(pl.family, 128, 128, 32);
+    } else {
+        pl.tile = P.Co > 32 ? tile_of(pl.family, 128, 64, 16) : tile_of(pl.family, 128, 32, 32);
     }
-    if (P.Co > 64) return launch_conv_gemm<2, 2, 2, 2, 32>(P, s);          // 128 x 128
-    if (P.Co > 32) return launch_conv_gemm<2, 2, 2, 1, 16>(P, s);          // 128 x 64
-    return launch_conv_gemm<4, 1, 1, 1, 16>(P, s);                         // 128 x 32
+    if (pl.tile < 0) return pl;
+    const int bk = FAST_TILES[pl.tile].dim[2];
+    pl.occ4 = FAST_TILES[pl.tile].dim[0] == 128 && FAST_TILES[pl.tile].dim[1] == 128 && bk == 16;
+    pl.uni = small && (pl.occ4 || (P.Ci % bk == 0 && P.K % bk == 0));
+    pl.tap_inner = pl.uni && P.KH * P.KW > 1 && P.Ci > 32 && P.Ci % 32 == 0;
+    return pl;
+}
+
+// The profiler label of a planned launch, "<family><tile>|<shape>,<variant>": formatted here and nowhere else.
+static const char *conv_label(const ConvPlan &pl, const int *d, const ConvGemmParams &P) {
+    switch (pl.family) {
+        case CONV_GEMM_GEN:
+        case CONV_GEMM_FAST:
+            // (the last field names the instantiation: tap = uniform chunks with the taps innermost, uni = uniform chunks,
+            //  var = chunks that may straddle taps; conv_gemm_kernel says gen)
+            return prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d,%s", d[0], d[1], d[2], P.M, P.Co, P.K, P.KH,
+                              P.stride, P.phases,
+                              pl.family == CONV_GEMM_GEN ? "gen" : pl.tap_inner ? "tap" : pl.uni ? "uni" : "var");
+        case CONV_K4S2_C4:  return prof_label("conv_k4s2_c4|M=%d,N=%d,K=%d%s", P.M, P.Co, P.K, P.mask ? ",mask" : "");
+        case CONV_1X1_K64:  return prof_label("conv1x1_k64|M=%d,N=%d,K=64", P.M, P.Co);
+        case CONV_SUBPIXEL: return prof_label("subpixel_conv|M=%d,N=%d,K=%d,ph4", P.M, P.Co, P.K);
+        case CONV_WINO3:    return prof_label("conv_wino3<%dx%d,nt%d>|M=%d,N=%d,K=%d", d[0], d[1], d[2], P.M, P.Co, P.K);
+        case CONV_WINO_K4S2:
+            return prof_label("conv_wino_k4s2<%dx%d,nt%d>|M=%d,N=%d,K=%d", d[0], d[1], d[2], P.M, P.Co, P.K);
+        default:            return prof_label("conv_wino_subpixel<%dx%d>|M=%d,N=%d,K=%d,ph4", d[0], d[1], P.M, P.Co, P.K);
+    }
+}
+
+int launch_conv(const ConvPlan &pl, const ConvGemmParams &P, hipStream_t s) {
+    static const char *const family_name[CONV_FAMILIES] = {"conv_gemm", "conv_gemm", "conv_k4s2_c4", "conv1x1_k64",
+                                                           "subpixel_conv", "conv_wino", "conv_wino_k4s2", "conv_wino_subpixel"};
+    const ConvTiles t = conv_tiles(pl.family);
+    if (pl.tile < 0 || pl.tile >= t.n) return set_error(VQ2_ERR_INVALID, "conv: the plan names no tile of family %d", pl.family);
+    const ConvTile &tile = t.tile[pl.tile];
+    return tile.launch(pl, P, prof_enabled() ? conv_label(pl, tile.dim, P) : family_name[pl.family], s);
 }
 
 // ------------------------------------------------------------------ conv-transpose to <= 4 channels
@@ -1257,6 +1361,7 @@ constexpr int CS = 8, LD = CS + 4;          // 48-byte LDS rows: conflict-free d
 constexpr int X_FLOATS = NP * LD, W_FLOATS = 64 * LD;
 constexpr size_t LDS_BYTES = (size_t)2 * (X_FLOATS + W_FLOATS) * sizeof(float);   // 64,896: two workgroups per CU
 constexpr int COOB = 0x7F000000;
+constexpr long REACH = COOB / 4;            // elements: the out-of-range sentinel must stay above every tensor
 }  // namespace ctm
 
 // Each wave owns TWO sets of 64 input positions (rows 4*wq + 2u + lane/32): a weight fragment read from LDS is
@@ -1409,18 +1514,11 @@ static int check_desc(const vq2_conv_desc *d) {
         if (d->stride == 2) VQ2_REQUIRE(d->KH == 4 && d->pad == 1 && d->H % 2 == 0 && d->W % 2 == 0,
                                         "stride-2 conv supports k4 p1 on even sizes (vqvae.py:105,107,114)");
     }
-    int Ho, Wo;
-    if (d->transposed) { Ho = 2 * d->H; Wo = 2 * d->W; }
-    else { Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1; Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1; }
+    const ConvHW o = out_hw(d);
     const int64_t lim = (int64_t)1 << 31;
-    VQ2_REQUIRE((int64_t)d->N * d->H * d->W * d->ldx < lim && (int64_t)d->N * Ho * Wo * d->ldy < lim,
+    VQ2_REQUIRE((int64_t)d->N * d->H * d->W * d->ldx < lim && (int64_t)d->N * o.h * o.w * d->ldy < lim,
                 "conv: tensor exceeds 2^31 elements (int32 indexing)");
     return VQ2_OK;
-}
-
-static void out_dims(const vq2_conv_desc *d, int &Ho, int &Wo) {
-    if (d->transposed) { Ho = 2 * d->H; Wo = 2 * d->W; }
-    else { Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1; Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1; }
 }
 
 }  // namespace vq2
@@ -1429,7 +1527,7 @@ using namespace vq2;
 
 // mode 3 = pack_convT_small layout
 static int pack_job_of(const vq2_conv_desc *d, int which, vq2_pack_job *j) {
-    const int cir = d->Cir ? d->Cir : d->Ci, cor = d->Cor ? d->Cor : d->Co;
+    const int cir = real_ci(d), cor = real_co(d);
     j->KH = d->KH; j->KW = d->KW;
     if (which == VQ2_PACK_FWD && use_convT_small(d)) {
         j->mode = 3; j->Or = d->Ci; j->Ir = cor; j->Op = d->Ci; j->Ip = 4;
@@ -1516,17 +1614,35 @@ extern "C" int vq2_conv_fwd(const vq2_conv_desc *d, int flags, const float *x, c
     VQ2_REQUIRE(x && wp && y, "conv_fwd: null pointer");
     VQ2_REQUIRE(aligned16(x) && aligned16(wp) && aligned16(y), "conv_fwd: pointers must be 16-byte aligned");
     VQ2_REQUIRE(!residual || (ldres >= d->Co), "conv_fwd: ldres < Co");
+    ConvGemmParams P{};
+    P.x = x; P.w = wp; P.bias = bias; P.mask = nullptr; P.res = residual; P.y = y;
+    P.N = d->N; P.H = d->H; P.W = d->W; P.Ci = d->Ci; P.ldx = d->ldx;
+    P.Co = d->Co; P.ldy = d->ldy; P.ldr = ldres; P.ldm = 0;
+    P.relu_in = (flags & VQ2_RELU_IN) != 0; P.relu_out = (flags & VQ2_RELU_OUT) != 0;
+    P.nbias = real_co(d);
+    P.ci_real = real_ci(d);
+    const ConvHW o = out_hw(d);
+    P.Hy = o.h; P.Wy = o.w;
+    if (!d->transposed) {
+        P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = P.pad_w = d->pad;
+        P.Ho = P.Hy; P.Wo = P.Wy; P.phases = 1;
+    } else {
+        P.KH = 2; P.KW = 2; P.stride = 1; P.pad_h = P.pad_w = 1;
+        P.Ho = d->H; P.Wo = d->W; P.phases = 4;
+    }
+    P.K = P.KH * P.KW * P.Ci; P.M = P.N * P.Ho * P.Wo;
+    hipStream_t s = to_stream(stream);
     if (use_convT_small(d)) {
         // (the weight panel of this layer is packed for THIS kernel: there is no other path to fall through to, and the
         //  general kernels would read the panel in their own layout -- a launch this kernel cannot take is refused)
         if (residual || (flags & VQ2_RELU_OUT) || d->N > 65535)
             return set_error(VQ2_ERR_UNSUPPORTED, "conv_fwd: a conv-transpose to <= 3 channels takes neither a residual nor "
                              "ReLU-out, and at most 65535 images per launch (split the batch)");
-        if (!((double)d->N * 4 * d->H * d->W * d->ldy * 4 < (double)ctm::COOB && (double)d->N * d->H * d->W * d->ldx * 4 < (double)ctm::COOB))
+        const ConvExtents E = conv_extents(P);
+        if (!(E.y < ctm::REACH && E.x < ctm::REACH))
             return set_error(VQ2_ERR_UNSUPPORTED, "conv_fwd: a conv-transpose to <= 4 channels is limited to tensors below %d bytes "
                              "(split the batch)", ctm::COOB);
-        hipStream_t s = to_stream(stream);
-        const int cor = d->Cor ? d->Cor : d->Co;
+        const int cor = real_co(d);
         const char *name = "convT_small";
         if (prof_enabled()) name = prof_label("convT_small|N=%d,H=%d,W=%d,Ci=%d", d->N, d->H, d->W, d->Ci);
         ProfScope prof(name, 2.0 * d->N * d->H * d->W * 16.0 * d->Ci * cor,
@@ -1537,30 +1653,9 @@ extern "C" int vq2_conv_fwd(const vq2_conv_desc *d, int flags, const float *x, c
                            d->ldy, d->N, d->H, d->W, d->Ci, (flags & VQ2_RELU_IN) != 0);
         return check_launch("convT_small_mfma_kernel");
     }
-    ConvGemmParams P{};
-    P.x = x; P.w = wp; P.bias = bias; P.mask = nullptr; P.res = residual; P.y = y;
-    P.N = d->N; P.H = d->H; P.W = d->W; P.Ci = d->Ci; P.ldx = d->ldx;
-    P.Co = d->Co; P.ldy = d->ldy; P.ldr = ldres; P.ldm = 0;
-    P.relu_in = (flags & VQ2_RELU_IN) != 0; P.relu_out = (flags & VQ2_RELU_OUT) != 0;
-    P.nbias = d->Cor ? d->Cor : d->Co;
-    P.ci_real = d->Cir ? d->Cir : d->Ci;
-    out_dims(d, P.Hy, P.Wy);
-    if (!d->transposed) {
-        P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = P.pad_w = d->pad;
-        P.Ho = P.Hy; P.Wo = P.Wy; P.phases = 1;
-    } else {
-        P.KH = 2; P.KW = 2; P.stride = 1; P.pad_h = P.pad_w = 1;
-        P.Ho = d->H; P.Wo = d->W; P.phases = 4;
-    }
-    P.K = P.KH * P.KW * P.Ci; P.M = P.N * P.Ho * P.Wo;
-    {   // algorithmic work: real channels, every tap once; x read once, y written once (+ residual read)
-        const double cir = d->Cir ? d->Cir : d->Ci, cor = d->Cor ? d->Cor : d->Co;
-        const double pix_in = (double)d->N * d->H * d->W, pix_out = (double)d->N * P.Hy * P.Wy;
-        const double macs = d->transposed ? pix_in * 16.0 * cir * cor : pix_out * d->KH * d->KW * cir * cor;
-        P.flops = 2.0 * macs;
-        P.bytes = 4.0 * (pix_in * cir + pix_out * cor * (residual ? 2.0 : 1.0) + cir * cor * d->KH * d->KW);
-    }
-    return run_conv_gemm(P, to_stream(stream));
+    const ConvWork work = conv_work(d, 0, residual ? 1 : 0);   // x read once, y written once (+ residual read)
+    P.flops = work.flops; P.bytes = work.bytes;
+    return launch_conv(plan_conv(P), P, s);
 }
 
 extern "C" int vq2_conv_dgrad(const vq2_conv_desc *d, const float *dy, const float *wp, const float *mask,
@@ -1578,15 +1673,14 @@ extern "C" int vq2_conv_dgrad_ex(const vq2_conv_desc *d, int flags, const float 
     VQ2_REQUIRE(aligned16(dy) && aligned16(wp) && aligned16(dx), "conv_dgrad: pointers must be 16-byte aligned");
     VQ2_REQUIRE(lddx >= d->Ci && lddx % 4 == 0, "conv_dgrad: lddx=%d must be >= Ci and a multiple of 4", lddx);
     VQ2_REQUIRE((!mask || ldmask >= d->Ci) && (!residual || ldres >= d->Ci), "conv_dgrad: ldmask/ldres < Ci");
-    int Hy, Wy;
-    out_dims(d, Hy, Wy);
+    const int Hy = out_hw(d).h, Wy = out_hw(d).w;
     ConvGemmParams P{};
     // the gradient GEMM reads dy [N,Hy,Wy,Co] and produces dx [N,H,W,Ci]
     P.x = dy; P.w = wp; P.bias = nullptr; P.mask = mask; P.res = residual; P.y = dx;
     P.N = d->N; P.H = Hy; P.W = Wy; P.Ci = d->Co; P.ldx = d->ldy;
     P.Co = d->Ci; P.ldy = lddx; P.ldm = ldmask; P.ldr = ldres;
     P.relu_in = 0; P.relu_out = 0;
-    P.ci_real = d->Cor ? d->Cor : d->Co;   // the gradient GEMM's input channels are the forward op's output channels
+    P.ci_real = real_co(d);   // the gradient GEMM's input channels are the forward op's output channels
     P.mask_after = (flags & VQ2_MASK_AFTER_RESIDUAL) != 0;
     P.Hy = d->H; P.Wy = d->W;
     if (!d->transposed && d->stride == 1) {
@@ -1603,13 +1697,7 @@ extern "C" int vq2_conv_dgrad_ex(const vq2_conv_desc *d, int flags, const float 
         P.Ho = d->H; P.Wo = d->W; P.phases = 1;
     }
     P.K = P.KH * P.KW * P.Ci; P.M = P.N * P.Ho * P.Wo;
-    {
-        const double cir = d->Cir ? d->Cir : d->Ci, cor = d->Cor ? d->Cor : d->Co;
-        const double pix_in = (double)d->N * d->H * d->W, pix_out = (double)d->N * Hy * Wy;
-        const double macs = d->transposed ? pix_in * 16.0 * cir * cor : pix_out * d->KH * d->KW * cir * cor;
-        P.flops = 2.0 * macs;
-        P.bytes = 4.0 * (pix_out * cor + pix_in * cir * (1.0 + (mask ? 1.0 : 0.0) + (residual ? 1.0 : 0.0)) +
-                         cir * cor * d->KH * d->KW);
-    }
-    return run_conv_gemm(P, to_stream(stream));
+    const ConvWork work = conv_work(d, (mask ? 1 : 0) + (residual ? 1 : 0), 0);   // dy read once, dx written once (+ mask, residual)
+    P.flops = work.flops; P.bytes = work.bytes;
+    return launch_conv(plan_conv(P), P, to_stream(stream));
 }

@@ -253,9 +253,8 @@ __global__ __launch_bounds__(256, 2) void rbw_fwd_kernel(const RbwFwdParams P) {
 }  // namespace rbw
 
 bool rbw_fwd_ok(const RbwFwdParams &P) {
-    const long gib = 1L << 30;
     const int ldmax = P.ldx > P.ldy ? P.ldx : P.ldy;
-    return forms() == FORMS_ALL && P.W % 64 == 0 && P.H % rbw::TR == 0 && (long)P.N * P.H * P.W * ldmax * 4 < gib && P.ldx % 4 == 0;
+    return forms() == FORMS_ALL && P.W % 64 == 0 && P.H % rbw::TR == 0 && (long)P.N * P.H * P.W * ldmax < PENALTY_REACH && P.ldx % 4 == 0;
 }
 
 int launch_rbw_fwd(const RbwFwdParams &P, hipStream_t s) {

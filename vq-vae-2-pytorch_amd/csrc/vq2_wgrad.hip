@@ -12,7 +12,7 @@
 // into the reference weight layout.  Both operands are consumed "reduction-major" straight
 // from NHWC memory: v_mfma_f32_32x32x2_f32 wants A[i][k] / B[k][j] with lanes along i / j,
 // and consecutive lanes read consecutive channels -> conflict-free ds_read_b32, no transposes.
-#include "vq2_common.h"
+#include "vq2_conv.h"
 
 namespace vq2 {
 
@@ -801,6 +801,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const vq2_wgr
 
 struct WgradPlan {
     int O, I, K, M, S, rows_per_split, bmo, bnk;
+    int tile;     // position of (bmo, bnk) in the candidate list
     int swapped;  // roles of x and dy exchanged (see plan_wgrad)
     int wino;     // F(2,3) Winograd along the rows: K = 12 * I (kh, v, i), M in column pairs (wgrad_fast_kernel<..., WINO>)
 };
@@ -814,15 +815,18 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     // gathers the NARROW tensor dy instead (flipped taps, pad' = K-1-p) and streams x once.
     // (Exchanged roles and the Winograd modes below are fast-kernel forms: VQ2_FORMS=general plans neither, =direct no
     // Winograd mode.)
-    const bool fast = forms() > FORMS_GENERAL, wino = forms() == FORMS_ALL;
+    const bool fast = forms() > FORMS_GENERAL;
+    // Winograd modes: tensors that the 32-bit byte offsets of wgrad_fast_kernel reach (x and dy counted over the INPUT grid)
+    const long pix = (long)d->N * d->H * d->W;
+    const bool wino = forms() == FORMS_ALL && pix * d->ldx < FAST_REACH && pix * d->ldy * (d->transposed ? 4 : 1) < FAST_REACH;
+    const ConvHW o = out_hw(d);
     if (fast && !d->transposed && d->stride == 1 && 2 * d->pad == d->KH - 1 && d->KH > 1 && d->Co <= 32 && d->Ci >= 64) {
         p.swapped = 1;
         p.O = d->Ci; p.I = d->Co;
         p.M = d->N * d->H * d->W;
     } else if (!d->transposed) {
         p.O = d->Co; p.I = d->Ci;
-        const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-        p.M = d->N * Ho * Wo;
+        p.M = d->N * o.h * o.w;
     } else {
         p.O = d->Ci; p.I = d->Co;
         p.M = d->N * d->H * d->W;
@@ -830,9 +834,7 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     p.K = d->KH * d->KW * p.I;
     p.wino = 0;
     if (wino && !p.swapped && !d->transposed && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 &&
-        p.O % 128 == 0 && p.I % 128 == 0 && (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0)) &&
-        (long)d->N * d->H * d->W * d->ldx < (1L << 29) &&
-        (long)d->N * d->H * d->W * d->ldy < (1L << 29)) {
+        p.O % 128 == 0 && p.I % 128 == 0 && (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0))) {
         p.wino = 1;
         p.K = 12 * p.I;
         p.M = p.M / 2;
@@ -841,9 +843,7 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
         const int wo = d->transposed ? d->W : d->W / 2;       // width of the G operand's grid
         if (wino && !p.swapped && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad == 1 && d->H % 2 == 0 &&
             d->W % 2 == 0 && p.O % 128 == 0 && (p.I == 64 || p.I % 128 == 0) &&
-            (wo % 64 == 0 || (wo == 32 && (d->transposed ? d->H : d->H / 2) % 2 == 0)) &&
-            (long)d->N * d->H * d->W * d->ldx < (1L << 29) &&
-            (long)d->N * d->H * d->W * d->ldy * (d->transposed ? 4 : 1) < (1L << 29)) {
+            (wo % 64 == 0 || (wo == 32 && (d->transposed ? d->H : d->H / 2) % 2 == 0))) {
             p.wino = 2;
             p.K = 24 * p.I;
             p.M = p.M / 2;
@@ -859,16 +859,16 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
         const long po = (p.O + cand[c][0] - 1) / cand[c][0] * cand[c][0];
         const long pk = (p.K + cand[c][1] - 1) / cand[c][1] * cand[c][1];
         const long work = po * pk;
-        if (best < 0 || work < best) { best = work; p.bmo = cand[c][0]; p.bnk = cand[c][1]; }
+        if (best < 0 || work < best) { best = work; p.tile = c; }
     }
     if (wino && p.swapped && d->KH == 3 && d->pad == 1 && p.I == 32 && p.O % 128 == 0 &&
-        (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0)) &&
-        (long)d->N * d->H * d->W * d->ldx < (1L << 29) && (long)d->N * d->H * d->W * d->ldy < (1L << 29)) {
+        (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0))) {
         p.wino = 3;                 // exchanged roles + F(2,3): four 128 x 96 tiles (v) of three kernel rows each
         p.K = 4 * 96;
         p.M = p.M / 2;
-        p.bmo = 128; p.bnk = 96;
+        p.tile = 3;                 // 128 x 96
     }
+    p.bmo = cand[p.tile][0]; p.bnk = cand[p.tile][1];
     const int tiles = ((p.K + p.bnk - 1) / p.bnk) * ((p.O + p.bmo - 1) / p.bmo);
     const int lds = 2 * WG_BKR * (p.bmo + p.bnk) * 4;
     int per_cu = (160 * 1024) / lds;                 // resident workgroups per CU (LDS-bound), at most 4
@@ -900,23 +900,27 @@ static size_t bias_ws_floats(const vq2_conv_desc *d, const WgradPlan &p) {
     return taps ? (size_t)p.S * nslots * p.I : (size_t)p.S * p.O;
 }
 
+// Element counts of the two operands of a launch as the kernels index them
+struct WgradExtents { long x, g; };
+static WgradExtents wgrad_extents(const WgradParams &P) { return {(long)P.N * P.H * P.W * P.ldx, (long)P.M * P.ldg}; }
+
 // wgrad_fast_kernel in its direct forms: rows of whole 32-pixel chunks, tensors that 32-bit byte offsets reach
 static bool wgrad_fast_ok(const WgradParams &P) {
-    const long lim = 1L << 29;
-    return forms() > FORMS_GENERAL && P.Wo % WG_BKR == 0 && P.rows_per_split % WG_BKR == 0 &&
-           (long)P.N * P.H * P.W * P.ldx < lim && (long)P.M * P.ldg < lim;
+    const WgradExtents E = wgrad_extents(P);
+    return forms() > FORMS_GENERAL && P.Wo % WG_BKR == 0 && P.rows_per_split % WG_BKR == 0 && E.x < FAST_REACH && E.g < FAST_REACH;
 }
 
 template <int WAVES_M, int WAVES_N, int MT, int NT>
 static int launch_wgrad(const WgradParams &P, int S, hipStream_t s) {
     constexpr int BMO = WAVES_M * MT * 32, BNK = WAVES_N * NT * 32;
     const size_t lds = (size_t)2 * WG_BKR * (BMO + BNK) * sizeof(float);
-    const bool fast_ok = wgrad_fast_ok(P);
-    auto kern = wgrad_kernel<WAVES_M, WAVES_N, MT, NT>;
-    if (fast_ok) {   // ReLU flags are compile-time in the fast kernel: every vector instruction competes with the MFMAs
-        if (P.relu_x) kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, true, false>;
-        else if (P.relu_g) kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, false, true>;
-        else kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, false, false>;
+    void (*kern)(const WgradParams);
+    // ReLU flags are compile-time in the fast kernel: every vector instruction competes with the MFMAs
+    switch (!wgrad_fast_ok(P) ? 0 : P.relu_x ? 1 : P.relu_g ? 2 : 3) {
+        case 1:  kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, true, false>; break;
+        case 2:  kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, false, true>; break;
+        case 3:  kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, false, false>; break;
+        default: kern = wgrad_kernel<WAVES_M, WAVES_N, MT, NT>; break;
     }
     allow_big_lds(kern, lds);
     dim3 grid(((P.K + BNK - 1) / BNK) * ((P.O + BMO - 1) / BMO) * S);
@@ -1039,7 +1043,7 @@ static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const f
     } else if (!d->transposed) {
         P.x = x; P.ldx = d->ldx; P.H = d->H; P.W = d->W;
         P.g = dy; P.ldg = d->ldy;
-        P.Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1; P.Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
+        P.Ho = out_hw(d).h; P.Wo = out_hw(d).w;
         P.relu_x = (flags & VQ2_RELU_IN) != 0; P.relu_g = 0;
     } else {
         P.x = dy; P.ldx = d->ldy; P.H = 2 * d->H; P.W = 2 * d->W;
@@ -1047,46 +1051,48 @@ static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const f
         P.Ho = d->H; P.Wo = d->W;
         P.relu_x = 0; P.relu_g = (flags & VQ2_RELU_IN) != 0;
     }
-    VQ2_REQUIRE((int64_t)P.N * P.H * P.W * P.ldx < ((int64_t)1 << 31) && (int64_t)P.M * P.ldg < ((int64_t)1 << 31),
-                "conv_wgrad: tensor exceeds 2^31 elements");
+    VQ2_REQUIRE(wgrad_extents(P).x < (1L << 31) && wgrad_extents(P).g < (1L << 31), "conv_wgrad: tensor exceeds 2^31 elements");
     hipStream_t s = to_stream(stream);
     int e;
-    const double cir_ = d->Cir ? d->Cir : d->Ci, cor_ = d->Cor ? d->Cor : d->Co;
-    const double pix_in_ = (double)d->N * d->H * d->W;
-    const double pix_out_ = d->transposed ? 4.0 * pix_in_ : (double)P.M * (p.wino ? 2.0 : 1.0);
-    const double macs_ = d->transposed ? pix_in_ * 16.0 * cir_ * cor_ : pix_out_ * d->KH * d->KW * cir_ * cor_;
+    const ConvWork work = conv_work(d, 0, 0);
     const char *pname = "wgrad";
     if (prof_enabled()) pname = prof_label("wgrad<%dx%d>%s|O=%d,K=%d,M=%d,S=%d,k%d,%s", p.bmo, p.bnk, p.wino == 3 ? "swwino" : p.swapped ? "sw" : (p.wino == 1 ? "wino" : p.wino == 2 ? "wino4" : ""), p.O, p.K, p.M, p.S, d->KH,
                                             p.wino || wgrad_fast_ok(P) ? "fast" : "gen");   // wgrad_fast_kernel or wgrad_kernel
-    ProfScope prof(pname, 2.0 * macs_, 4.0 * (pix_in_ * cir_ + pix_out_ * cor_ + cir_ * cor_ * d->KH * d->KW), s);
-    if (p.wino == 3) {
-        auto kern = P.relu_g ? wgrad_fast_kernel<4, 1, 1, 3, false, true, 3> : wgrad_fast_kernel<4, 1, 1, 3, false, false, 3>;
-        const size_t lds = (size_t)2 * WG_BKR * (128 + 96) * sizeof(float);
+    ProfScope prof(pname, work.flops, work.bytes, s);
+    if (p.wino) {
+        // Winograd forms: one tile each (128 x 96 with exchanged roles, else 128 x 128); the ReLU sits on the operand that is x
+        void (*kern)(const WgradParams);
+        switch (p.wino * 4 + (P.relu_x ? 2 : P.relu_g ? 1 : 0)) {
+            case 1 * 4 + 2: kern = wgrad_fast_kernel<2, 2, 2, 2, true, false, 1>; break;
+            case 1 * 4 + 0:
+            case 1 * 4 + 1: kern = wgrad_fast_kernel<2, 2, 2, 2, false, false, 1>; break;
+            case 2 * 4 + 2: kern = wgrad_fast_kernel<2, 2, 2, 2, true, false, 2>; break;
+            case 2 * 4 + 1: kern = wgrad_fast_kernel<2, 2, 2, 2, false, true, 2>; break;
+            case 2 * 4 + 0: kern = wgrad_fast_kernel<2, 2, 2, 2, false, false, 2>; break;
+            case 3 * 4 + 1: kern = wgrad_fast_kernel<4, 1, 1, 3, false, true, 3>; break;
+            default:        kern = wgrad_fast_kernel<4, 1, 1, 3, false, false, 3>; break;
+        }
+        const size_t lds = (size_t)2 * WG_BKR * (p.bmo + p.bnk) * sizeof(float);
         allow_big_lds(kern, lds);
-        hipLaunchKernelGGL(kern, dim3(4 * (P.O / 128) * p.S), dim3(256), lds, s, P);
-        e = check_launch("wgrad_fast_kernel<wino sw>");
-    } else if (p.wino) {
-        auto kern = P.relu_x ? wgrad_fast_kernel<2, 2, 2, 2, true, false, 1> : wgrad_fast_kernel<2, 2, 2, 2, false, false, 1>;
-        if (p.wino == 2)
-            kern = P.relu_x ? wgrad_fast_kernel<2, 2, 2, 2, true, false, 2>
-                            : (P.relu_g ? wgrad_fast_kernel<2, 2, 2, 2, false, true, 2> : wgrad_fast_kernel<2, 2, 2, 2, false, false, 2>);
-        const size_t lds = (size_t)2 * WG_BKR * 256 * sizeof(float);
-        allow_big_lds(kern, lds);
-        hipLaunchKernelGGL(kern, dim3((P.K / 128) * ((P.O + 127) / 128) * p.S), dim3(256), lds, s, P);
-        e = check_launch("wgrad_fast_kernel<wino>");
-    } else if (p.bmo == 128 && p.bnk == 128) e = launch_wgrad<2, 2, 2, 2>(P, p.S, s);
-    else if (p.bmo == 64 && p.bnk == 128) e = launch_wgrad<1, 4, 2, 1>(P, p.S, s);
-    else if (p.bmo == 32) e = launch_wgrad<1, 4, 1, 2>(P, p.S, s);      // 32 x 256
-    else if (p.bmo == 128 && p.bnk == 96) e = launch_wgrad<4, 1, 1, 3>(P, p.S, s);
-    else if (p.bmo == 128) e = launch_wgrad<4, 1, 1, 1>(P, p.S, s);     // 128 x 32 (1x1 convs with few inputs)
-    else e = launch_wgrad<2, 2, 1, 1>(P, p.S, s);                       // 64 x 64
+        const int ktiles = p.wino == 3 ? 4 : P.K / 128;
+        hipLaunchKernelGGL(kern, dim3(ktiles * ((P.O + 127) / 128) * p.S), dim3(256), lds, s, P);
+        e = check_launch(p.wino == 3 ? "wgrad_fast_kernel<wino sw>" : "wgrad_fast_kernel<wino>");
+    } else {
+        switch (p.tile) {   // the candidates of plan_wgrad, in their order
+            case 0:  e = launch_wgrad<2, 2, 2, 2>(P, p.S, s); break;     // 128 x 128
+            case 1:  e = launch_wgrad<1, 4, 2, 1>(P, p.S, s); break;     // 64 x 128
+            case 2:  e = launch_wgrad<1, 4, 1, 2>(P, p.S, s); break;     // 32 x 256
+            case 3:  e = launch_wgrad<4, 1, 1, 3>(P, p.S, s); break;     // 128 x 96
+            case 4:  e = launch_wgrad<4, 1, 1, 1>(P, p.S, s); break;     // 128 x 32 (1x1 convs with few inputs)
+            default: e = launch_wgrad<2, 2, 1, 1>(P, p.S, s); break;     // 64 x 64
+        }
+    }
     if (e) return e;
     if (!reduce) return VQ2_OK;
     const int total = p.O * p.K;
     const int blocks = (total + 31) / 32 < 4096 ? (total + 31) / 32 : 4096;
-    const int cir = d->Cir ? d->Cir : d->Ci, cor = d->Cor ? d->Cor : d->Co;
     const bool sw = d->transposed || p.swapped;
-    const int Or = sw ? cir : cor, Ir = sw ? cor : cir;
+    const int Or = sw ? real_ci(d) : real_co(d), Ir = sw ? real_co(d) : real_ci(d);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, P.ws, dw, p.O, p.I, Or, Ir, d->KH * d->KW,
                        p.S, P.bias_ws, db, p.swapped | (p.wino << 1), P.bias_taps ? p.S * P.bias_nslots : 0);
     return check_launch("wgrad_reduce_kernel");
@@ -1106,7 +1112,7 @@ extern "C" int vq2_wgrad_job_init(const vq2_conv_desc *d, const void *ws, float 
     VQ2_REQUIRE(d && ws && dw && job, "wgrad_job_init: null pointer");
     if (int e = check_forms()) return e;
     const WgradPlan p = plan_wgrad(d);
-    const int cir = d->Cir ? d->Cir : d->Ci, cor = d->Cor ? d->Cor : d->Co;
+    const int cir = real_ci(d), cor = real_co(d);
     const float *w = static_cast<const float *>(ws);
     job->ws = w; job->dw = dw; job->db = nullptr; job->bias_ws = nullptr;
     const bool sw = d->transposed || p.swapped;

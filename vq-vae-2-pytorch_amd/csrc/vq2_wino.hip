@@ -25,7 +25,7 @@ namespace wino {
 
 constexpr int TP = 64;             // column pairs per workgroup
 constexpr int BN = 128;            // output channels per workgroup
-constexpr int BK = 8, LDK = BK + 4;   // 48-byte LDS rows: conflict-free ds_read_b128 (vq2_conv.hip)
+constexpr int LDK = BK + 4;       // BK = 8 (vq2_conv.h); 48-byte LDS rows: conflict-free ds_read_b128 (vq2_conv.hip)
 
 // TPW: pairs per tile row (32: rows of whole 64-pixel segments, 2-row tiles; 16: 32-pixel segments, 4-row tiles -- a wave's
 // 32 pairs are then two rows).  (NT, BNT): a wave owns 32 pairs x 32*NT channels of a BNT-channel tile -- (2, 128), or (1, 64)
@@ -443,13 +443,11 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void wino_k4s2_kernel(const C
 }
 
 template <int TPW, int NT, int BNT>
-static int launch_k4s2(const ConvGemmParams &P, hipStream_t s) {
+static int launch_k4s2(const ConvPlan &, const ConvGemmParams &P, const char *name, hipStream_t s) {
     using G = K4<TPW, BNT>;
     auto kern = P.relu_in ? wino_k4s2_kernel<TPW, NT, BNT, true> : wino_k4s2_kernel<TPW, NT, BNT, false>;
     allow_big_lds(kern, G::LDS_BYTES);
     const unsigned nwg = (unsigned)(P.N * (P.Ho / G::TRO) * (P.Wo / (2 * TPW)) * (P.Co / BNT));
-    const char *name = "conv_wino_k4s2";
-    if (prof_enabled()) name = prof_label("conv_wino_k4s2<%dx%d,nt%d>|M=%d,N=%d,K=%d", G::TRO, 2 * TPW, NT, P.M, P.Co, P.K);
     ProfScope prof(name, P.flops, P.bytes, s, true);
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), G::LDS_BYTES, s, P);
     return check_launch("wino_k4s2_kernel");
@@ -618,75 +616,48 @@ __global__ __launch_bounds__(256, 2) void wino_subpixel_kernel(const ConvGemmPar
 }
 
 template <int TPW>
-static int launch_subpixel2(const ConvGemmParams &P, hipStream_t s) {
+static int launch_subpixel2(const ConvPlan &, const ConvGemmParams &P, const char *name, hipStream_t s) {
     using G = Sp2<TPW>;
     auto kern = P.relu_in ? wino_subpixel_kernel<TPW, true> : wino_subpixel_kernel<TPW, false>;
     allow_big_lds(kern, G::LDS_BYTES);
     const unsigned nwg = (unsigned)(4 * P.N * (P.H / G::TR) * (P.W / (2 * TPW)) * (P.Co / BN2));
-    const char *name = "conv_wino_subpixel";
-    if (prof_enabled()) name = prof_label("conv_wino_subpixel<%dx%d>|M=%d,N=%d,K=%d,ph4", G::TR, 2 * TPW, P.M, P.Co, P.K);
     ProfScope prof(name, P.flops, P.bytes, s, true);
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), G::LDS_BYTES, s, P);
     return check_launch("wino_subpixel_kernel");
 }
 
 template <int TPW, int NT, int BNT>
-static int launch(const ConvGemmParams &P, hipStream_t s) {
+static int launch(const ConvPlan &, const ConvGemmParams &P, const char *name, hipStream_t s) {
     using G = Geo<TPW, NT, BNT>;
     auto kern = P.relu_in ? wino3_kernel<TPW, NT, BNT, true> : wino3_kernel<TPW, NT, BNT, false>;
     allow_big_lds(kern, G::LDS_BYTES);
     const unsigned nwg = (unsigned)(P.N * (P.H / G::TR) * (P.W / (2 * TPW)) * (P.Co / BNT));
-    const char *name = "conv_wino";
-    if (prof_enabled()) name = prof_label("conv_wino3<%dx%d,nt%d>|M=%d,N=%d,K=%d", G::TR, 2 * TPW, NT, P.M, P.Co, P.K);
     ProfScope prof(name, P.flops, P.bytes, s, true);
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(G::NTHR), G::LDS_BYTES, s, P);
     return check_launch("wino3_kernel");
 }
 
+// The tiles of the three families (plan_conv, vq2_conv.hip, chooses among them): image rows x pixels per row, NT.
+template <int TPW, int NT, int BNT>
+static constexpr ConvTile wino3_tile() { return {{Geo<TPW, NT, BNT>::TR, 2 * TPW, NT}, launch<TPW, NT, BNT>}; }
+template <int TPW, int NT, int BNT>
+static constexpr ConvTile k4s2_tile() { return {{K4<TPW, BNT>::TRO, 2 * TPW, NT}, launch_k4s2<TPW, NT, BNT>}; }
+template <int TPW>
+static constexpr ConvTile subpixel2_tile() { return {{Sp2<TPW>::TR, 2 * TPW, 0}, launch_subpixel2<TPW>}; }
+
+static const ConvTile WINO3_TILES[] = {wino3_tile<32, 2, 128>(), wino3_tile<32, 1, 64>(), wino3_tile<16, 2, 128>(), wino3_tile<16, 1, 64>()};
+static const ConvTile K4S2_TILES[] = {k4s2_tile<32, 2, 128>(), k4s2_tile<32, 1, 64>(), k4s2_tile<16, 2, 128>(), k4s2_tile<16, 1, 64>()};
+static const ConvTile SUBPIXEL2_TILES[] = {subpixel2_tile<32>(), subpixel2_tile<16>()};
+
 }  // namespace wino
 
-// Shapes the Winograd kernels take: 3x3, stride 1, pad 1, output the size of the input, whole 64-channel output tiles,
-// 8-channel input blocks (at least 32 channels), rows of whole 64-pixel segments (or 32-pixel ones with H % 4 == 0), tensors
-// below 1 GiB (32-bit offsets with an additive out-of-range penalty); likewise the 4x4 stride-2 and sub-pixel forms.
-bool wino3_ok(const ConvGemmParams &P) {
-    if (forms() < FORMS_ALL) return false;
-    const long gib = 1L << 30;
-    if (P.phases == 4)   // sub-pixel conv-transpose: F(2,2) per output phase
-        return P.KH == 2 && P.KW == 2 && P.K == 4 * P.Ci && P.Hy == 2 * P.H && P.Wy == 2 * P.W &&
-               ((P.W % 64 == 0 && P.H % 4 == 0) || (P.W % 32 == 0 && P.H % 8 == 0)) && P.Ci % wino::BK == 0 && P.Ci >= 32 && P.Co % 64 == 0 && P.ldx % 4 == 0 &&
-               (long)P.N * P.H * P.W * P.ldx * 4 < gib && (long)P.N * P.Hy * P.Wy * P.ldy * 4 < gib &&
-               (long)P.N * P.Hy * P.Wy * (P.ldm > P.ldr ? P.ldm : P.ldr) * 4 < gib && (long)4 * P.Co * P.K * 4 < gib;
-    if (P.KH == 4 && P.KW == 4 && P.stride == 2 && P.pad_h == 1 && P.pad_w == 1 && P.phases == 1)   // F(2,2) by parity
-        return 2 * P.Ho == P.H && 2 * P.Wo == P.W && P.Hy == P.Ho && P.Wy == P.Wo &&
-               ((P.Wo % 64 == 0 && P.Ho % 2 == 0) || (P.Wo % 32 == 0 && P.Ho % 4 == 0)) &&
-               P.Ci % wino::BK == 0 && P.Ci >= 32 && P.Co % 64 == 0 && P.ldx % 4 == 0 &&
-               // (64-channel outputs on 32-pixel rows lose to the direct 64-row tiles -- 128 -> 64 at 32x32 and batch 32: one tile
-               //  per CU, 94.5 vs 84.3 us.  The rule must not look at the batch size: results do not depend on it.)
-               (P.Co % 128 == 0 || P.Wo % 64 == 0) &&
-               (long)P.N * P.H * P.W * P.ldx * 4 < gib && (long)P.N * P.Ho * P.Wo * P.ldy * 4 < gib &&
-               (long)P.N * P.Ho * P.Wo * (P.ldm > P.ldr ? P.ldm : P.ldr) * 4 < gib && (long)P.Co * P.K * 4 < gib;
-    const bool rows64 = P.W % 64 == 0 && P.H % 2 == 0, rows32 = P.W % 32 == 0 && P.H % 4 == 0;
-    // (from 32 input channels: 3x3 32 -> 128 at 64x64, 89.6 -> 74.5 us)
-    return P.KH == 3 && P.KW == 3 && P.stride == 1 && P.pad_h == 1 && P.pad_w == 1 && P.phases == 1 &&
-           P.Ho == P.H && P.Wo == P.W && P.Hy == P.H && P.Wy == P.W && P.Ci % wino::BK == 0 && P.Ci >= 32 &&
-           P.Co % 64 == 0 && (rows64 || rows32) && P.ldx % 4 == 0 &&
-           (long)P.N * P.H * P.W * P.ldx * 4 < gib && (long)P.N * P.H * P.W * P.ldy * 4 < gib &&
-           (long)P.N * P.H * P.W * (P.ldm > P.ldr ? P.ldm : P.ldr) * 4 < gib && (long)P.Co * P.K * 4 < gib;
-}
-
-int launch_wino3(const ConvGemmParams &P, hipStream_t s) {
-    if (P.phases == 4) return P.W % 64 == 0 && P.H % 4 == 0 ? wino::launch_subpixel2<32>(P, s) : wino::launch_subpixel2<16>(P, s);
-    // 128-channel tiles where they still give every CU two workgroups; 64-channel tiles otherwise (64-channel outputs, the
-    // 32x32 level)
-    const long wgs128 = (long)P.N * P.Ho * P.Wo / 128 * (P.Co / 128);
-    const bool wide = P.Co % 128 == 0 && wgs128 >= 400;
-    if (P.KH == 4) {
-        if (P.Wo % 64 == 0 && P.Ho % 2 == 0)
-            return wide ? wino::launch_k4s2<32, 2, 128>(P, s) : wino::launch_k4s2<32, 1, 64>(P, s);
-        return wide ? wino::launch_k4s2<16, 2, 128>(P, s) : wino::launch_k4s2<16, 1, 64>(P, s);
+ConvTiles wino_tiles(int family) {
+    switch (family) {
+        case CONV_WINO3:         return {wino::WINO3_TILES, 4};
+        case CONV_WINO_K4S2:     return {wino::K4S2_TILES, 4};
+        case CONV_WINO_SUBPIXEL: return {wino::SUBPIXEL2_TILES, 2};
+        default:                 return {nullptr, 0};
     }
-    if (P.W % 64 == 0 && P.H % 2 == 0) return wide ? wino::launch<32, 2, 128>(P, s) : wino::launch<32, 1, 64>(P, s);
-    return wide ? wino::launch<16, 2, 128>(P, s) : wino::launch<16, 1, 64>(P, s);
 }
 
 }  // namespace vq2
