@@ -4,7 +4,7 @@ form of the reference's samples (train_vqvae.py:120-139: inputs on the top row, 
 
 --ckpt is a checkpoint/vqvae_XXX.pt as examples/train_stage1.py (or the reference) saves it, or a trainer_XXX.pt.
 --path is a directory of .npy image batches, uint8 [N,H,W,3] pixels (normalised on the GPU with --norm, centre-cropped
-to --size) or float32 [N,3,H,W], already normalised.
+to --size) or float32 [N,3,H,W], already normalised.  --image_metrics adds PSNR and SSIM of the 8-bit reconstructions.
 
     python examples/eval_stage1.py --ckpt checkpoint/vqvae_001.pt --path /data/ffhq_val_u8 --size 256 --dump recon
 """
@@ -41,6 +41,7 @@ def main():
     ap.add_argument("--norm", choices=sorted(NORMS), default="half")
     ap.add_argument("--dump", type=str, default="", help="directory for one reconstruction grid per batch")
     ap.add_argument("--dump_images", type=int, default=8, help="images of each batch that go into its grid")
+    ap.add_argument("--image_metrics", action="store_true", help="also PSNR and SSIM of the 8-bit reconstructions")
     args = ap.parse_args()
 
     device = torch.device("cuda", 0)
@@ -52,7 +53,7 @@ def main():
     model.to(device).eval()
 
     normalizer = vqvae2_amd.ImageNormalizer(*NORMS[args.norm], layout="hwc", crop=(args.size, args.size))
-    ev = vqvae2_amd.Evaluator(model, normalizer)
+    ev = vqvae2_amd.Evaluator(model, normalizer, image_metrics=args.image_metrics)
     denorm = normalizer.inverse()
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)
@@ -68,7 +69,8 @@ def main():
     r = ev.result()
     print(f"images: {r['images']}; mse: {r['mse']:.6f}; latent: {r['latent']:.4f}; "
           f"perplexity t/b: {r['perplexity_t']:.2f}/{r['perplexity_b']:.2f}; "
-          f"used codes t/b: {r['used_t']}/{r['used_b']} of {r['n_embed']}")
+          f"used codes t/b: {r['used_t']}/{r['used_b']} of {r['n_embed']}"
+          + (f"; psnr: {r['psnr']:.2f} dB; ssim: {r['ssim']:.4f}" if args.image_metrics else ""))
 
 
 if __name__ == "__main__":

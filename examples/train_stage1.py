@@ -101,7 +101,8 @@ def val_batches(args, plan, device):
 def print_validation(epoch, i, r):
     print(f"epoch: {epoch + 1}; it {i}; val images: {r['images']}; val mse: {r['mse']:.5f}; val latent: {r['latent']:.3f}; "
           f"perplexity t/b: {r['perplexity_t']:.1f}/{r['perplexity_b']:.1f}; "
-          f"used codes t/b: {r['used_t']}/{r['used_b']} of {r['n_embed']}", flush=True)
+          f"used codes t/b: {r['used_t']}/{r['used_b']} of {r['n_embed']}"
+          + (f"; psnr: {r['psnr']:.2f} dB; ssim: {r['ssim']:.4f}" if "psnr" in r else ""), flush=True)
 
 
 def main():
@@ -122,6 +123,8 @@ def main():
     ap.add_argument("--val_path", type=str, default="", help="held-out batches, same file format as --path")
     ap.add_argument("--eval_every", type=int, default=0, help="steps between evaluations of --val_path (0 = never)")
     ap.add_argument("--sample_every", type=int, default=0, help="steps between sample grids under sample/ (0 = never)")
+    ap.add_argument("--image_metrics", action="store_true",
+                    help="with --val_path: also PSNR and SSIM of the 8-bit reconstructions of the held-out set")
     args = ap.parse_args()
     if args.eval_every and not args.val_path:
         raise SystemExit("--eval_every needs --val_path")
@@ -157,7 +160,8 @@ def main():
             mse_sum[0] += out["recon"] * img.shape[0]
             mse_sum[1] += img.shape[0]
             if args.eval_every and (i + 1) % args.eval_every == 0:       # every rank: result() sums over the group
-                r = trainer.evaluate(val_batches(args, val_plan, device))
+                evaluate = trainer.evaluate_image_metrics if args.image_metrics else trainer.evaluate
+                r = evaluate(val_batches(args, val_plan, device))
                 if dist.is_primary():
                     print_validation(epoch, i, r)
             if args.sample_every and i % args.sample_every == 0 and dist.is_primary():   # train_vqvae.py:120-139

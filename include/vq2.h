@@ -43,11 +43,12 @@ typedef void *vq2_stream_t;
  * argument / workspace (revision 2: vq2_vq_fwd lost its counts/sumsT arguments and vq2_vq_fwd_workspace_floats
  * went from (M) to (M, D, K); revision 3: round-3 additions; revision 4: the two diagnostic probe exports removed;
  * revision 5: vq2_u8_to_nhwc4 added; revision 6: the evaluation entry points added (vq2_nhwc_to_u8, vq2_sse_per_image,
- * vq2_index_hist, vq2_eval_accumulate);
+ * vq2_index_hist, vq2_eval_accumulate); revision 7: vq2_image_metrics, vq2_image_metrics_workspace_bytes and
+ * vq2_image_metrics_accumulate added;
  * see INTEGRATION.md "ABI history").  vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 6
+#define VQ2_API_VERSION 7
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -340,6 +341,31 @@ int vq2_sse_per_image(const float *a, const float *b, int32_t N, int32_t H, int3
 int vq2_index_hist(const int64_t *idx, int64_t M, int32_t K, int64_t *counts, int32_t *flag, vq2_stream_t stream);
 int vq2_eval_accumulate(const float *sse, int32_t N, int64_t elems_per_image, const float *diff, double *acc,
                         vq2_stream_t stream);
+
+/* ------------------------------------------------------------------ quality of the 8-bit reconstruction
+ * Squared error and SSIM between the two 8-bit images that vq2_nhwc_to_u8 would write from a (reconstruction) and b
+ * (target): fp32 NHWC tensors [N,H,W,>=C] with pixel strides lda, ldb >= C, each element turned into a byte by the
+ * arithmetic documented at vq2_nhwc_to_u8 (inv_s, mean: HOST arrays of C floats).  1 <= C <= 4, 1 <= N <= 65535,
+ * H >= 11 and W >= 11 (else VQ2_ERR_INVALID).
+ *   sse_u8[n] (device int64)  sum over the H * W * C elements of image n of (byte_a - byte_b)^2: exact.
+ *   ssim[n]   (device double) Wang et al. 2004 with data range 255: window w = g x g, g[k] = exp(-(k - 5)^2 / (2 * 1.5^2))
+ *             for k = 0..10 normalised to sum 1; at each of the (H - 10) * (W - 10) window positions that lie wholly
+ *             inside the image and for each channel, mu_a = sum w a, mu_b = sum w b, var_a = sum w a^2 - mu_a^2,
+ *             var_b = sum w b^2 - mu_b^2, cov = sum w a b - mu_a mu_b and
+ *             S = ((2 mu_a mu_b + C1) (2 cov + C2)) / ((mu_a^2 + mu_b^2 + C1) (var_a + var_b + C2)),
+ *             C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2; ssim[n] is the mean of S over positions and channels.  Moments
+ *             and S are fp64 (the window applied along rows, then along columns); identical images give exactly 1.0.
+ * Fixed reduction tree that depends on (C, H, W) only, no floating-point atomics: image i of a launch of 9 is bit for
+ * bit image i of a launch of 5.  ws: 8-byte aligned, >= vq2_image_metrics_workspace_bytes (0 for invalid arguments).
+ * vq2_image_metrics_accumulate: one workgroup; acc_d[0] (device double) += ssim[0], += ssim[1], ... in image order,
+ *             acc_i[0] (device int64) += sum of sse_u8: totals do not depend on how a set was cut into batches.
+ * No synchronisation; the caller owns all memory. */
+size_t vq2_image_metrics_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int vq2_image_metrics(const float *a, int32_t lda, const float *b, int32_t ldb, int32_t N, int32_t C, int32_t H, int32_t W,
+                      const float *inv_s, const float *mean, int64_t *sse_u8, double *ssim, void *ws, size_t ws_bytes,
+                      vq2_stream_t stream);
+int vq2_image_metrics_accumulate(const int64_t *sse_u8, const double *ssim, int32_t N, int64_t *acc_i, double *acc_d,
+                                 vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ data-parallel exchange (RCCL over xGMI)
  * One communicator per process (= per GPU), owned by the library -- its only persistent state.  Replaces what

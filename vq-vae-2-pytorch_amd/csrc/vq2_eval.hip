@@ -3,6 +3,8 @@
 //   sse_per_image    one sum of squared differences per image, fixed reduction tree
 //   index_hist       code-usage histogram of a quantizer's indices (integer atomics only)
 //   eval_accumulate  folds a batch into a device accumulator of doubles, so that an evaluation loop never syncs
+//   image_metrics    per image: integer squared error and Gaussian-window SSIM of the two 8-bit images nhwc_to_u8 writes
+#include <math.h>
 #include "vq2_common.h"
 
 namespace vq2 {
@@ -209,6 +211,200 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(const float *__res
     }
 }
 
+// ------------------------------------------------------------------ 8-bit squared error and SSIM per image
+// Both tensors become bytes through to_byte (the bytes nhwc_to_u8 writes); everything after that is integer (the
+// squared error) or fp64 (SSIM, Wang et al. 2004: 11x11 Gaussian window of sigma 1.5, valid region, data range 255).
+// One workgroup per tile of IM_T x IM_T window positions of one image:
+//   1. the IM_P x IM_P pixel patch of both tensors -> one dword of <= 4 bytes per pixel in LDS.  A lane whose pixel is
+//      outside the image loads nothing and stores 0.  A pixel's squared error is counted by the tile that owns it: the
+//      tile of its own window position, the last tile of a row / column taking the 10 trailing pixels as well.
+//   2. per channel: horizontal 11-tap pass of a, b, a^2, b^2, ab into an fp64 LDS tile (IM_P rows x IM_T columns),
+//      vertical pass with consecutive lanes on consecutive columns, then the SSIM map value; positions outside the
+//      valid region add nothing.
+//   3. fixed tree: a thread adds its positions channel after channel, wave butterfly, the four waves in order; the
+//      tile's partials go to the workspace and image_metrics_final_kernel folds them in tile order.  The tree depends on
+//      (C, H, W) alone.
+// In fp64 with separately rounded operations a == b gives mu_a == mu_b and var_a == var_b == cov bit for bit, so that
+// numerator and denominator below are the same number and S == 1.0 exactly.
+constexpr int IM_T = 32, IM_WIN = 11, IM_P = IM_T + IM_WIN - 1, IM_PIX = IM_P * IM_P;
+constexpr int IM_LOADS = (IM_PIX + 255) / 256;
+
+struct ImParams {
+    const float *a, *b;
+    int64_t lda, ldb;
+    int C, H, W, tiles_x, tiles_y, veca, vecb;
+    float inv_s[4], m[4];
+    double g[IM_WIN];
+    double *part_s;                 // [N * tiles] SSIM map sums
+    unsigned long long *part_e;     // [N * tiles] squared errors
+};
+
+__device__ __forceinline__ uint32_t pack_bytes(const float x[4], const ImParams &P) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) w |= (c < P.C ? to_byte(x[c], P.inv_s[c], P.m[c]) : 0u) << (8 * c);
+    return w;
+}
+
+__device__ __forceinline__ uint32_t sq_diff_bytes(uint32_t wa, uint32_t wb) {
+    uint32_t e = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int d = (int)((wa >> (8 * c)) & 255u) - (int)((wb >> (8 * c)) & 255u);
+        e += (uint32_t)(d * d);
+    }
+    return e;
+}
+
+__global__ __launch_bounds__(256) void image_metrics_kernel(const ImParams P) {
+    __shared__ uint32_t pa[IM_PIX], pb[IM_PIX];
+    __shared__ double hd[5][IM_P][IM_T];
+    __shared__ double wsum[4];
+    __shared__ uint32_t wsum_e[4];
+    const int t = threadIdx.x, n = blockIdx.y, H = P.H, W = P.W;
+    const int tyi = blockIdx.x / P.tiles_x, txi = blockIdx.x - tyi * P.tiles_x;
+    const int ty0 = tyi * IM_T, tx0 = txi * IM_T;
+    const bool last_y = tyi == P.tiles_y - 1, last_x = txi == P.tiles_x - 1;
+    const int64_t img0 = (int64_t)n * H * W;
+
+    // ---- 1. patch -> bytes.  All of the thread's 16-byte loads are issued before the first one is waited for.
+    float4 va[IM_LOADS], vb[IM_LOADS];
+#pragma unroll
+    for (int j = 0; j < IM_LOADS; ++j) {
+        const int p = j * 256 + t, py = p / IM_P, px = p - py * IM_P;
+        const int gy = ty0 + py, gx = tx0 + px;
+        const bool in = p < IM_PIX && gy < H && gx < W;
+        const int64_t g = img0 + (int64_t)gy * W + gx;
+        va[j] = (in && P.veca) ? reinterpret_cast<const float4 *>(P.a)[g] : make_float4(0.f, 0.f, 0.f, 0.f);
+        vb[j] = (in && P.vecb) ? reinterpret_cast<const float4 *>(P.b)[g] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    uint32_t err = 0;
+#pragma unroll
+    for (int j = 0; j < IM_LOADS; ++j) {
+        const int p = j * 256 + t, py = p / IM_P, px = p - py * IM_P;
+        const int gy = ty0 + py, gx = tx0 + px;
+        if (p < IM_PIX) {
+            uint32_t wa = 0, wb = 0;
+            if (gy < H && gx < W) {
+                const int64_t g = img0 + (int64_t)gy * W + gx;
+                float xa[4] = {va[j].x, va[j].y, va[j].z, va[j].w}, xb[4] = {vb[j].x, vb[j].y, vb[j].z, vb[j].w};
+                if (!P.veca) for (int c = 0; c < P.C; ++c) xa[c] = P.a[g * P.lda + c];
+                if (!P.vecb) for (int c = 0; c < P.C; ++c) xb[c] = P.b[g * P.ldb + c];
+                wa = pack_bytes(xa, P);
+                wb = pack_bytes(xb, P);
+                if ((py < IM_T || last_y) && (px < IM_T || last_x)) err += sq_diff_bytes(wa, wb);
+            }
+            pa[p] = wa;
+            pb[p] = wb;
+        }
+    }
+    // a tile's squared error is at most 42 * 42 * 4 * 255^2 < 2^29: 32 bits hold every partial sum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) err += (uint32_t)__shfl_xor((int)err, o, 64);
+    if ((t & 63) == 0) wsum_e[t >> 6] = err;
+    __syncthreads();
+
+    // ---- 2. per channel: horizontal pass, vertical pass, map value
+    const double C1 = (0.01 * 255.0) * (0.01 * 255.0), C2 = (0.03 * 255.0) * (0.03 * 255.0);
+    const int vy = H - (IM_WIN - 1) - ty0, vx = W - (IM_WIN - 1) - tx0;   // valid positions of this tile: oy < vy, ox < vx
+    double acc = 0.0;
+    for (int c = 0; c < P.C; ++c) {
+        const int sh = 8 * c;
+        for (int i = t; i < IM_P * IM_T; i += 256) {
+            const int row = i >> 5, col = i & 31;
+            const uint32_t *ra = pa + row * IM_P + col, *rb = pb + row * IM_P + col;
+            double sa = 0.0, sb = 0.0, saa = 0.0, sbb = 0.0, sab = 0.0;
+#pragma unroll
+            for (int k = 0; k < IM_WIN; ++k) {
+                const double da = (double)((ra[k] >> sh) & 255u), db = (double)((rb[k] >> sh) & 255u);
+                sa += P.g[k] * da;
+                sb += P.g[k] * db;
+                saa += P.g[k] * (da * da);
+                sbb += P.g[k] * (db * db);
+                sab += P.g[k] * (da * db);
+            }
+            hd[0][row][col] = sa; hd[1][row][col] = sb; hd[2][row][col] = saa; hd[3][row][col] = sbb; hd[4][row][col] = sab;
+        }
+        __syncthreads();
+        for (int i = t; i < IM_T * IM_T; i += 256) {
+            const int oy = i >> 5, ox = i & 31;
+            double mua = 0.0, mub = 0.0, eaa = 0.0, ebb = 0.0, eab = 0.0;
+#pragma unroll
+            for (int k = 0; k < IM_WIN; ++k) {
+                mua += P.g[k] * hd[0][oy + k][ox];
+                mub += P.g[k] * hd[1][oy + k][ox];
+                eaa += P.g[k] * hd[2][oy + k][ox];
+                ebb += P.g[k] * hd[3][oy + k][ox];
+                eab += P.g[k] * hd[4][oy + k][ox];
+            }
+            const double maa = mua * mua, mbb = mub * mub, mab = mua * mub;
+            const double va2 = eaa - maa, vb2 = ebb - mbb, cov = eab - mab;
+            const double s = ((2.0 * mab + C1) * (2.0 * cov + C2)) / ((maa + mbb + C1) * (va2 + vb2 + C2));
+            acc += (oy < vy && ox < vx) ? s : 0.0;
+        }
+        __syncthreads();   // the fp64 tile is refilled by the next channel
+    }
+    // ---- 3. fixed tree
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((t & 63) == 0) wsum[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) {
+        const int64_t slot = (int64_t)n * gridDim.x + blockIdx.x;
+        P.part_s[slot] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        P.part_e[slot] = ((unsigned long long)wsum_e[0] + wsum_e[1]) + ((unsigned long long)wsum_e[2] + wsum_e[3]);
+    }
+}
+
+// image n: thread t adds the tiles t, t + 64, ... in order, then the butterfly; ssim = sum / count
+__global__ __launch_bounds__(64) void image_metrics_final_kernel(const double *__restrict__ part_s,
+                                                                 const unsigned long long *__restrict__ part_e, int tiles,
+                                                                 double count, long long *__restrict__ sse_u8,
+                                                                 double *__restrict__ ssim) {
+    const int n = blockIdx.x, t = threadIdx.x;
+    double s = 0.0;
+    unsigned long long e = 0;
+    for (int i = t; i < tiles; i += 64) {
+        s += part_s[(int64_t)n * tiles + i];
+        e += part_e[(int64_t)n * tiles + i];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, 64);
+        e += __shfl_xor(e, o, 64);
+    }
+    if (t == 0) {
+        ssim[n] = s / count;
+        sse_u8[n] = (long long)e;
+    }
+}
+
+// acc_d[0] += ssim[0], then ssim[1], ... in image order (as eval_accumulate_kernel does); acc_i[0] += sum of sse_u8
+__global__ __launch_bounds__(256) void image_metrics_accumulate_kernel(const long long *__restrict__ sse_u8,
+                                                                       const double *__restrict__ ssim, int N,
+                                                                       long long *__restrict__ acc_i, double *__restrict__ acc_d) {
+    __shared__ double buf[256];
+    __shared__ long long ebuf[256];
+    double s = threadIdx.x == 0 ? acc_d[0] : 0.0;
+    long long e = threadIdx.x == 0 ? acc_i[0] : 0;
+    for (int base = 0; base < N; base += 256) {
+        if (base + (int)threadIdx.x < N) {
+            buf[threadIdx.x] = ssim[base + threadIdx.x];
+            ebuf[threadIdx.x] = sse_u8[base + threadIdx.x];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = N - base < 256 ? N - base : 256;
+            for (int i = 0; i < m; ++i) { s += buf[i]; e += ebuf[i]; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        acc_d[0] = s;
+        acc_i[0] = e;
+    }
+}
+
 }  // namespace vq2
 
 using namespace vq2;
@@ -296,4 +492,63 @@ extern "C" int vq2_eval_accumulate(const float *sse, int32_t N, int64_t elems_pe
     hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(256), 0, to_stream(stream), sse, N, (double)elems_per_image,
                        diff, acc);
     return check_launch("eval_accumulate_kernel");
+}
+
+static inline int64_t im_tiles(int32_t H, int32_t W, int *tx, int *ty) {
+    const int x = (W - (IM_WIN - 1) + IM_T - 1) / IM_T, y = (H - (IM_WIN - 1) + IM_T - 1) / IM_T;
+    if (tx) *tx = x;
+    if (ty) *ty = y;
+    return (int64_t)x * y;
+}
+
+extern "C" size_t vq2_image_metrics_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W) {
+    if (N <= 0 || N > 65535 || C < 1 || C > 4 || H < IM_WIN || W < IM_WIN) return 0;
+    return (size_t)N * (size_t)im_tiles(H, W, nullptr, nullptr) * (sizeof(double) + sizeof(unsigned long long));
+}
+
+extern "C" int vq2_image_metrics(const float *a, int32_t lda, const float *b, int32_t ldb, int32_t N, int32_t C, int32_t H,
+                                 int32_t W, const float *inv_s, const float *mean, int64_t *sse_u8, double *ssim, void *ws,
+                                 size_t ws_bytes, vq2_stream_t stream) {
+    VQ2_REQUIRE(a && b && inv_s && mean && sse_u8 && ssim && ws, "image_metrics: null pointer");
+    VQ2_REQUIRE(C >= 1 && C <= 4, "image_metrics: %d channels (1..4)", C);
+    VQ2_REQUIRE(N >= 1 && N <= 65535, "image_metrics: %d images (1..65535)", N);
+    VQ2_REQUIRE(lda >= C && ldb >= C, "image_metrics: pixel strides %d and %d are shorter than %d channels", lda, ldb, C);
+    VQ2_REQUIRE(H >= IM_WIN && W >= IM_WIN, "image_metrics: a %dx%d image is smaller than the %dx%d window", H, W, IM_WIN, IM_WIN);
+    for (int c = 0; c < C; ++c) VQ2_REQUIRE(inv_s[c] != 0.f, "image_metrics: inv_s[%d] is zero", c);
+    ImParams P;
+    const int64_t tiles = im_tiles(H, W, &P.tiles_x, &P.tiles_y);
+    VQ2_REQUIRE(tiles < ((int64_t)1 << 31), "image_metrics: a %dx%d image has 2^31 tiles or more", H, W);
+    const size_t slots = (size_t)N * (size_t)tiles;
+    if (ws_bytes < slots * (sizeof(double) + sizeof(unsigned long long)))
+        return set_error(VQ2_ERR_WORKSPACE, "image_metrics: workspace too small");
+    VQ2_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, "image_metrics: the workspace must be 8-byte aligned");
+    P.a = a; P.b = b; P.lda = lda; P.ldb = ldb;
+    P.C = C; P.H = H; P.W = W;
+    P.veca = lda == 4 && aligned16(a);
+    P.vecb = ldb == 4 && aligned16(b);
+    for (int c = 0; c < 4; ++c) { P.inv_s[c] = c < C ? inv_s[c] : 1.f; P.m[c] = c < C ? mean[c] : 0.f; }
+    double gsum = 0.0;
+    for (int k = 0; k < IM_WIN; ++k) {
+        const double d = k - IM_WIN / 2;
+        P.g[k] = exp(-(d * d) / (2.0 * 1.5 * 1.5));
+        gsum += P.g[k];
+    }
+    for (int k = 0; k < IM_WIN; ++k) P.g[k] /= gsum;
+    P.part_s = static_cast<double *>(ws);
+    P.part_e = reinterpret_cast<unsigned long long *>(P.part_s + slots);
+    hipStream_t s = to_stream(stream);
+    hipLaunchKernelGGL(image_metrics_kernel, dim3((unsigned)tiles, (unsigned)N), dim3(256), 0, s, P);
+    if (int e = check_launch("image_metrics_kernel")) return e;
+    hipLaunchKernelGGL(image_metrics_final_kernel, dim3((unsigned)N), dim3(64), 0, s, P.part_s, P.part_e, (int)tiles,
+                       (double)(H - (IM_WIN - 1)) * (double)(W - (IM_WIN - 1)) * (double)C,
+                       reinterpret_cast<long long *>(sse_u8), ssim);
+    return check_launch("image_metrics_final_kernel");
+}
+
+extern "C" int vq2_image_metrics_accumulate(const int64_t *sse_u8, const double *ssim, int32_t N, int64_t *acc_i,
+                                            double *acc_d, vq2_stream_t stream) {
+    VQ2_REQUIRE(sse_u8 && ssim && acc_i && acc_d && N > 0, "image_metrics_accumulate: bad arguments");
+    hipLaunchKernelGGL(image_metrics_accumulate_kernel, dim3(1), dim3(256), 0, to_stream(stream),
+                       reinterpret_cast<const long long *>(sse_u8), ssim, N, reinterpret_cast<long long *>(acc_i), acc_d);
+    return check_launch("image_metrics_accumulate_kernel");
 }

@@ -2,8 +2,10 @@
 `mse_sum / mse_n` of train_vqvae.py:93-100 and the sample grid of :120-139 -- plus the health of both EMA codebooks
 (codes in use, perplexity), gathered on the GPU without a host synchronisation per batch.
 
-Evaluator               accumulates reconstruction error, latent loss and both code histograms over batches
+Evaluator               accumulates reconstruction error, latent loss and both code histograms over batches; with
+                        image_metrics=True also the squared error and SSIM of the 8-bit reconstructions (PSNR, SSIM)
 perplexity_from_counts  exp(entropy) of a code histogram, fp64 on the host
+psnr_from_mse_u8        10 log10(255^2 / mse) of 8-bit images, fp64 on the host
 """
 import contextlib
 import math
@@ -23,6 +25,14 @@ def perplexity_from_counts(counts):
         return float("nan")
     p = c[c > 0] / total
     return float(math.exp(-float((p * p.log()).sum())))
+
+
+def psnr_from_mse_u8(mse_u8):
+    """PSNR in dB of 8-bit images (data range 255) from their mean squared error in byte units; inf for identical images."""
+    mse_u8 = float(mse_u8)
+    if mse_u8 == 0.0:
+        return float("inf")
+    return 10.0 * math.log10(255.0 ** 2 / mse_u8)
 
 
 @contextlib.contextmanager
@@ -53,24 +63,39 @@ class Evaluator:
                   (train_vqvae.py:83 averaged as :93-100 does), latent the image-weighted mean of the batches' latent
                   losses.  With a process group the totals and the histograms are summed over the ranks first, on
                   float64 / int64 tensors.  Raises RuntimeError if a quantizer ever produced an index outside its codebook.
-    reset()       clears the accumulators."""
+    reset()       clears the accumulators.
 
-    def __init__(self, model, normalizer=None):
+    image_metrics=True (needs the normalizer): the quality of the 8-bit reconstruction, i.e. of the bytes that
+    update(..., return_u8=True) returns against the bytes of the input (a uint8 batch returns to its own source bytes
+    exactly; a float batch is quantised the same way).  update() adds the launches of vq2_image_metrics and its
+    accumulate on the tensors it already holds, and result() gains "mse_u8" (mean squared byte difference over every
+    element seen), "psnr" (10 log10(255^2 / mse_u8) dB, inf for mse_u8 == 0) and "ssim" (mean over the images of the
+    Gaussian-window SSIM, see include/vq2.h).  They do not depend on the normaliser's statistics in any other way.  The
+    integer total is summed over the ranks as int64, the SSIM total as float64."""
+
+    def __init__(self, model, normalizer=None, image_metrics=False):
         if not hasattr(model, "forward_nhwc"):
             raise TypeError(f"Evaluator: {type(model).__name__} has no forward_nhwc (VQVAE_Deep's decoder needs a style "
                             "input that a held-out pass does not have); evaluate a VQVAE")
-        self.model, self.normalizer = model, normalizer
+        if image_metrics and normalizer is None:
+            raise TypeError("Evaluator(image_metrics=True) needs normalizer=ImageNormalizer(...): its statistics define the "
+                            "8-bit images that PSNR and SSIM compare")
+        self.model, self.normalizer, self.image_metrics = model, normalizer, bool(image_metrics)
         self.denormalizer = normalizer.inverse() if normalizer is not None else None
         self.k_t, self.k_b = model.quantize_t.n_embed, model.quantize_b.n_embed
         self._state = None
 
+    def _state_len(self):
+        return 4 + self.k_t + self.k_b + 1 + (2 if self.image_metrics else 0)
+
     def _buffers(self, device):
-        """One int64 buffer [accumulator (4 doubles, as bits) | counts_t | counts_b | flag], so that result() is one copy."""
+        """One int64 buffer [accumulator (4 doubles, as bits) | counts_t | counts_b | flag], so that result() is one copy;
+        with image_metrics two more words follow: the int64 squared-error total and the SSIM total (a double, as bits)."""
         if self._state is None or self._state.device != device:
-            self._state = torch.zeros(4 + self.k_t + self.k_b + 1, device=device, dtype=torch.int64)
+            self._state = torch.zeros(self._state_len(), device=device, dtype=torch.int64)
         s = self._state
-        return (s[:4].view(torch.float64), s[4:4 + self.k_t], s[4 + self.k_t:4 + self.k_t + self.k_b],
-                s[4 + self.k_t + self.k_b:].view(torch.int32)[:1])
+        hist = 4 + self.k_t + self.k_b
+        return (s[:4].view(torch.float64), s[4:4 + self.k_t], s[4 + self.k_t:hist], s[hist:hist + 1].view(torch.int32)[:1])
 
     def reset(self):
         if self._state is not None:
@@ -94,6 +119,10 @@ class Evaluator:
         ops.eval_accumulate(ops.sse_per_image(dec, ops.packed(x)), channels * h * w, diff, acc)
         ops.index_hist(id_t, counts_t, flag)
         ops.index_hist(id_b, counts_b, flag)
+        if self.image_metrics:
+            d = self.denormalizer
+            sse_u8, ssim = ops.image_metrics(dec, x, channels, d.inv_s, d.m)
+            ops.image_metrics_accumulate(sse_u8, ssim, self._state[-2:-1], self._state[-1:].view(torch.float64))
         if return_u8:
             d = self.denormalizer
             return ops.nhwc_to_u8(dec, channels, d.inv_s, d.m, d.layout if u8 else "chw")
@@ -103,20 +132,30 @@ class Evaluator:
         state = self._state
         if state is None:       # no batch yet: empty totals (a rank whose share of the data is empty still joins the sums)
             dev = next(self.model.parameters()).device
-            state = self._state = torch.zeros(4 + self.k_t + self.k_b + 1, device=dev, dtype=torch.int64)
+            state = self._state = torch.zeros(self._state_len(), device=dev, dtype=torch.int64)
+        ints = len(state) - 1 if self.image_metrics else len(state)     # the SSIM total is the last word, a double
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             state = state.clone()
             dist.all_reduce(state[:4].view(torch.float64))       # the four totals, float64
-            dist.all_reduce(state[4:])                           # both histograms (and the flag), int64
+            dist.all_reduce(state[4:ints])                       # both histograms, the flag (and the squared bytes), int64
+            if self.image_metrics:
+                dist.all_reduce(state[ints:].view(torch.float64))
         host = state.cpu()
         acc = host[:4].view(torch.float64)
         counts_t, counts_b = host[4:4 + self.k_t].clone(), host[4 + self.k_t:4 + self.k_t + self.k_b].clone()
-        if int(host[-1]) != 0:
+        if int(host[4 + self.k_t + self.k_b]) != 0:
             raise RuntimeError("Evaluator: a quantizer produced a code index outside [0, n_embed) (vq2_index_hist flag)")
         images = int(acc[3])
-        return {"mse": float(acc[0] / acc[1]) if images else float("nan"),
-                "latent": float(acc[2] / acc[3]) if images else float("nan"),
-                "images": images,
-                "perplexity_t": perplexity_from_counts(counts_t), "perplexity_b": perplexity_from_counts(counts_b),
-                "used_t": int((counts_t > 0).sum()), "used_b": int((counts_b > 0).sum()),
-                "n_embed": self.k_t if self.k_t == self.k_b else (self.k_t, self.k_b), "counts_t": counts_t, "counts_b": counts_b}
+        out = {"mse": float(acc[0] / acc[1]) if images else float("nan"),
+               "latent": float(acc[2] / acc[3]) if images else float("nan"),
+               "images": images,
+               "perplexity_t": perplexity_from_counts(counts_t), "perplexity_b": perplexity_from_counts(counts_b),
+               "used_t": int((counts_t > 0).sum()), "used_b": int((counts_b > 0).sum()),
+               "n_embed": self.k_t if self.k_t == self.k_b else (self.k_t, self.k_b), "counts_t": counts_t, "counts_b": counts_b}
+        if self.image_metrics:
+            nan = float("nan")
+            mse_u8 = int(host[-2]) / float(acc[1]) if images else nan
+            out["mse_u8"] = mse_u8
+            out["psnr"] = psnr_from_mse_u8(mse_u8) if images else nan
+            out["ssim"] = float(host[-1:].view(torch.float64)[0] / acc[3]) if images else nan
+        return out

@@ -545,6 +545,44 @@ def eval_accumulate(sse, elems_per_image, diff, acc):
     check(lib.vq2_eval_accumulate(_p(sse), sse.numel(), int(elems_per_image), _p(d), _p(acc), _stream()), "eval_accumulate")
 
 
+def image_metrics(a, b, c, inv_s, mean):
+    """Per image, between the 8-bit images nhwc_to_u8 would write from a (reconstruction) and b (target), dense NHWC
+    tensors [N,H,W,>=c] (vq2_image_metrics): sse_u8 int64 [N], the exact sum of squared byte differences over the
+    H * W * c elements, and ssim float64 [N], Gaussian-window SSIM (11x11, sigma 1.5, valid region, data range 255) in
+    fp64.  inv_s / mean as for nhwc_to_u8.  Nothing is read back."""
+    _require_cuda(a, "reconstruction")
+    _require_cuda(b, "target")
+    if not (is_nhwc_dense(a) and is_nhwc_dense(b)) or a.shape[:3] != b.shape[:3] or a.device != b.device:
+        raise RuntimeError("image_metrics: two dense NHWC tensors of one [N,H,W] on one GPU expected")
+    n, h, w, _ = a.shape
+    if not 1 <= c <= min(a.shape[3], b.shape[3], 4) or len(inv_s) != c or len(mean) != c:
+        raise RuntimeError(f"image_metrics: {c} channels with {len(inv_s)} / {len(mean)} statistics from tensors of "
+                           f"{a.shape[3]} and {b.shape[3]} lanes")
+    sse = torch.empty(n, device=a.device, dtype=torch.int64)
+    ssim = torch.empty(n, device=a.device, dtype=torch.float64)
+    nbytes = lib.vq2_image_metrics_workspace_bytes(n, c, h, w)
+    ws = torch.empty(max(nbytes // 8, 1), device=a.device, dtype=torch.float64)
+    fa = (C.c_float * c)(*inv_s)
+    fm = (C.c_float * c)(*mean)
+    check(lib.vq2_image_metrics(_p(a), ld_of(a), _p(b), ld_of(b), n, c, h, w, fa, fm, _p(sse), _p(ssim), _p(ws), nbytes,
+                                _stream()), "image_metrics")
+    return sse, ssim
+
+
+def image_metrics_accumulate(sse_u8, ssim, acc_i, acc_d):
+    """acc_i (int64 [1]) += sum of sse_u8; acc_d (float64 [1]) += ssim[0], then ssim[1], ... in image order, on the
+    device (vq2_image_metrics_accumulate)."""
+    if not (sse_u8.is_cuda and sse_u8.dtype == torch.int64 and ssim.dtype == torch.float64 and ssim.device == sse_u8.device
+            and sse_u8.is_contiguous() and ssim.is_contiguous() and sse_u8.dim() == 1 and sse_u8.shape == ssim.shape):
+        raise RuntimeError("image_metrics_accumulate: int64 [N] squared errors and float64 [N] SSIM values on one GPU "
+                           "expected; no CPU path")
+    if not (acc_i.dtype == torch.int64 and acc_d.dtype == torch.float64 and acc_i.numel() == 1 and acc_d.numel() == 1
+            and acc_i.device == ssim.device and acc_d.device == ssim.device):
+        raise RuntimeError("image_metrics_accumulate: the accumulators are an int64 [1] and a float64 [1] tensor on the GPU")
+    check(lib.vq2_image_metrics_accumulate(_p(sse_u8), _p(ssim), sse_u8.numel(), _p(acc_i), _p(acc_d), _stream()),
+          "image_metrics_accumulate")
+
+
 def from_nhwc(y, c):
     """Internal NHWC -> NCHW-shaped result (zero-copy channels-last view when C % 4 == 0)."""
     if y.shape[3] == c:

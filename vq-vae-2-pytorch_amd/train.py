@@ -239,8 +239,16 @@ class Stage1Trainer:
         parameter, so the steps that follow are bit for bit those of a run that never evaluated; every module's
         train / eval flag is restored.  Data parallel: every rank calls it (result() sums over the group).  sample: a
         batch (same forms) whose grid (sample_grid) is returned under "sample"."""
+        return self._evaluate(batches, sample, False)
+
+    def evaluate_image_metrics(self, batches, sample=None):
+        """evaluate() with Evaluator(image_metrics=True): the result also holds "psnr", "ssim" and "mse_u8" of the 8-bit
+        reconstructions.  Needs the trainer's normalizer; leaves trainer and model alone as evaluate() does."""
+        return self._evaluate(batches, sample, True)
+
+    def _evaluate(self, batches, sample, image_metrics):
         from .evaluate import Evaluator
-        ev = Evaluator(self.model, self.normalizer)
+        ev = Evaluator(self.model, self.normalizer, image_metrics=image_metrics)
         for img in batches:
             ev.update(img)
         out = ev.result()
