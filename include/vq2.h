@@ -44,11 +44,12 @@ typedef void *vq2_stream_t;
  * went from (M) to (M, D, K); revision 3: round-3 additions; revision 4: the two diagnostic probe exports removed;
  * revision 5: vq2_u8_to_nhwc4 added; revision 6: the evaluation entry points added (vq2_nhwc_to_u8, vq2_sse_per_image,
  * vq2_index_hist, vq2_eval_accumulate); revision 7: vq2_image_metrics, vq2_image_metrics_workspace_bytes and
- * vq2_image_metrics_accumulate added;
+ * vq2_image_metrics_accumulate added; revision 8: the causal-attention and weight-norm entry points added
+ * (vq2_causal_attn_fwd, vq2_causal_attn_bwd, vq2_causal_attn_keep_mask, vq2_weight_norm_fwd, vq2_weight_norm_bwd);
  * see INTEGRATION.md "ABI history").  vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 7
+#define VQ2_API_VERSION 8
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -366,6 +367,50 @@ int vq2_image_metrics(const float *a, int32_t lda, const float *b, int32_t ldb, 
                       vq2_stream_t stream);
 int vq2_image_metrics_accumulate(const int64_t *sse_u8, const double *ssim, int32_t N, int64_t *acc_i, double *acc_d,
                                  vq2_stream_t stream);
+
+/* ------------------------------------------------------------------ causal self-attention (stage-2 prior)
+ * CausalAttention of the reference (pixelsnail.py:195-234) after its three projections: q, k, v, o are [B, L, n_head *
+ * dim_head] fp32 with pixel strides ldq / ldk / ldv / ldo (NHWC activations flattened over H * W); head h owns channels
+ * h * dim_head .. (h + 1) * dim_head - 1.
+ *     S = Q K^T / sqrt(dim_head);  query i attends to keys j < i only (the diagonal is masked, pixelsnail.py:185,224);
+ *     P = softmax over the visible keys;  row 0 sees nothing and its output is exactly 0 (start_mask, pixelsnail.py:225);
+ *     O = dropout(P) V (pixelsnail.py:226-228), dropout scaled by 1 / (1 - p_drop) like nn.Dropout; p_drop = 0: none.
+ * Masked scores are excluded, where the reference fills them with -1e4: the two agree to the last bit of every
+ * exponential while each unmasked score of a row exceeds about -9,896 (exp of anything below -103.97 is 0 in fp32);
+ * the other regime is not reproduced.
+ * Geometry: any B <= 65535, L >= 1, 1 <= n_head <= 65535, dim_head % 4 == 0 in 4..64; anything else VQ2_ERR_INVALID.
+ * Nothing of size L * L is read or written: scores live in registers.  No floating-point atomics, fixed accumulation
+ * orders: results are bit-reproducible.
+ * vq2_causal_attn_fwd: o and lse[B, n_head, L], the base-2 log-sum-exp of the scaled scores of each row (0 for a row
+ *              that sees no key).
+ * vq2_causal_attn_bwd: dq, dk, dv (pixel strides lddq / lddk / lddv) from dO (lddo), the forward operands and lse (o is not
+ *              needed; ldo of the descriptor is only checked).  delta_ws: B * n_head * L floats (receives the row term of the
+ *              softmax backward, sum_j P dP = sum_d dO * O, formed from the recomputed P and dP so that it cancels against dP
+ *              as it does in a plain fp32 evaluation).  Same seed and p_drop as the forward call.
+ * Dropout: keep(seed, b, h, i, j) = word (j & 3) of Philox4x32 (7 rounds) with counter (j >> 2, i, b, h) and the
+ *              64-bit seed as key, compared >= floor(p_drop * 2^32).  It depends on nothing else.
+ * vq2_causal_attn_keep_mask: that decision for every (b, h, i, j) as bytes [B, n_head, L, L] (1 = keep; the causal mask
+ *              is not applied) -- the only way to check the dropout path against a reference; for small L. */
+typedef struct vq2_attn_desc {
+    int32_t B, L, n_head, dim_head;
+    int32_t ldq, ldk, ldv, ldo; /* pixel strides (elements) of q, k, v, o */
+    float p_drop;               /* dropout probability in [0, 1); 0 = no dropout */
+    int32_t reserved;
+    uint64_t seed;
+} vq2_attn_desc;
+int vq2_causal_attn_fwd(const vq2_attn_desc *d, const float *q, const float *k, const float *v, float *o, float *lse,
+                        vq2_stream_t stream);
+int vq2_causal_attn_bwd(const vq2_attn_desc *d, const float *q, const float *k, const float *v,
+                        const float *lse, const float *dO, int32_t lddo, float *dq, int32_t lddq, float *dk, int32_t lddk,
+                        float *dv, int32_t lddv, float *delta_ws, vq2_stream_t stream);
+int vq2_causal_attn_keep_mask(const vq2_attn_desc *d, uint8_t *mask, vq2_stream_t stream);
+
+/* weight_norm(nn.Linear) (pixelsnail.py:17-18): w[r][c] = g[r] * v[r][c] / ||v[r]||_2 over `rows` output rows of `cols`
+ * floats, and its backward: dg[r] = (dw[r] . v[r]) / ||v[r]||, dv[r] = (g[r] / ||v[r]||) * (dw[r] - v[r] * (dw[r] . v[r]) /
+ * ||v[r]||^2).  One wave per row, fixed reduction order. */
+int vq2_weight_norm_fwd(const float *v, const float *g, float *w, int32_t rows, int32_t cols, vq2_stream_t stream);
+int vq2_weight_norm_bwd(const float *dw, const float *v, const float *g, float *dv, float *dg, int32_t rows, int32_t cols,
+                        vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ data-parallel exchange (RCCL over xGMI)
  * One communicator per process (= per GPU), owned by the library -- its only persistent state.  Replaces what

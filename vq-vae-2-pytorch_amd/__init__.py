@@ -6,6 +6,8 @@ Public surface mirrors /root/reference/vqvae.py and distributed/__init__.py:1-13
 from .vqvae import VQVAE, Quantize, ResBlock, Encoder, Decoder, Conv2d, ConvTranspose2d, ReLU  # noqa: F401
 from . import vqvae_deep  # noqa: F401
 from .vqvae_deep import VQVAE_Deep  # noqa: F401
+from . import pixelsnail  # noqa: F401
+from .pixelsnail import CausalAttention  # noqa: F401
 from . import distributed  # noqa: F401
 from . import ops  # noqa: F401
 from . import codes  # noqa: F401

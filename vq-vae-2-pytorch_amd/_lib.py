@@ -27,6 +27,11 @@ class WgradJob(C.Structure):
                [(n, C.c_int32) for n in ("O", "I", "Or", "Ir", "taps", "S", "n_units_w", "n_units_b", "swapped", "bias_splits")]
 
 
+class AttnDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "L", "n_head", "dim_head", "ldq", "ldk", "ldv", "ldo")] + \
+               [("p_drop", C.c_float), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -92,6 +97,11 @@ def _load():
         "vq2_adam_step": (C.c_int, [P, P, P, P, I64, D, D, D, D, I32, D, P]),
         "vq2_axpby": (C.c_int, [P, P, F, P, I64, P]),
         "vq2_scale": (C.c_int, [P, P, F, P, I64, P]),
+        "vq2_causal_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P, P]),
+        "vq2_causal_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P, I32, P, I32, P, I32, P, I32, P, P]),
+        "vq2_causal_attn_keep_mask": (C.c_int, [C.POINTER(AttnDesc), P, P]),
+        "vq2_weight_norm_fwd": (C.c_int, [P, P, P, I32, I32, P]),
+        "vq2_weight_norm_bwd": (C.c_int, [P, P, P, P, P, I32, I32, P]),
         "vq2_comm_unique_id": (C.c_int, [P]),
         "vq2_comm_init": (C.c_int, [P, I32, I32]),
         "vq2_comm_world": (C.c_int, []),

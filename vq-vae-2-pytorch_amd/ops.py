@@ -12,7 +12,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check, ConvDesc, PackJob, WgradJob
+from ._lib import lib, check, AttnDesc, ConvDesc, PackJob, WgradJob
 
 VQ2_RELU_IN = 1
 VQ2_RELU_OUT = 2
@@ -866,6 +866,113 @@ class AddScalarsFn(Function):
     @staticmethod
     def backward(ctx, g):
         return g.reshape(()), g.reshape(())
+
+
+# ----------------------------------------------------------------------------- causal attention (stage-2 prior)
+ATTN_BQ = 64   # query / key tile lengths of csrc/vq2_attn.hip (AT_BQ, AT_BK): tests place their lengths around them
+ATTN_BK = 64
+
+
+def attn_check_geometry(channel, n_head):
+    """The geometries vq2_causal_attn_* accept: dim_head = channel / n_head a multiple of 4 in 4..64."""
+    if n_head < 1 or channel < 1 or channel % n_head:
+        raise NotImplementedError(f"vqvae2_amd causal attention: channel ({channel}) must be a positive multiple of "
+                                  f"n_head ({n_head})")
+    dh = channel // n_head
+    if not (4 <= dh <= 64 and dh % 4 == 0):
+        raise NotImplementedError(f"vqvae2_amd causal attention: dim_head must be a multiple of 4 in 4..64 (got {dh})")
+    return dh
+
+
+def _attn_desc(b, l, n_head, dh, q, k, v, o, p, seed):
+    d = AttnDesc()
+    d.B, d.L, d.n_head, d.dim_head = b, l, n_head, dh
+    d.ldq, d.ldk, d.ldv, d.ldo = ld_of(q), ld_of(k), ld_of(v), ld_of(o)
+    d.p_drop, d.seed = float(p), int(seed) & 0xFFFFFFFFFFFFFFFF
+    return d
+
+
+def _attn_operand(t, what):
+    """A dense NHWC [B,H,W,channel] tensor is the [B, L, channel] matrix with row stride ld the kernels take."""
+    _require_cuda(t, what)
+    return as_nhwc(t)
+
+
+class CausalAttnFn(Function):
+    """pixelsnail.py:220-228 for projected q, k, v ([B,H,W,n_head * dim_head] NHWC): strictly causal softmax(QK^T /
+    sqrt(dim_head)) V over the H * W positions, dropout p on the probabilities keyed by `seed`.  Saves q, k, v and
+    one log-sum-exp per (b, h, i); nothing of size L^2 exists in either pass."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, n_head, p, seed):
+        q, k, v = _attn_operand(q, "q"), _attn_operand(k, "k"), _attn_operand(v, "v")
+        b, hh, w, c = q.shape
+        if k.shape != q.shape or v.shape != q.shape:
+            raise RuntimeError("CausalAttnFn: q, k and v must have one shape")
+        dh = attn_check_geometry(c, n_head)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"dropout probability must be in [0, 1), got {p}")
+        l = hh * w
+        o = torch.empty((b, hh, w, c), device=q.device, dtype=torch.float32)
+        lse = torch.empty((b, n_head, l), device=q.device, dtype=torch.float32)
+        d = _attn_desc(b, l, n_head, dh, q, k, v, o, p, seed)
+        check(lib.vq2_causal_attn_fwd(C.byref(d), _p(q), _p(k), _p(v), _p(o), _p(lse), _stream()), "causal_attn_fwd")
+        ctx.save_for_backward(q, k, v, lse)   # the backward kernels recompute P and need neither o nor anything of size L^2
+        ctx.n_head, ctx.p, ctx.seed = n_head, p, seed
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, lse = ctx.saved_tensors
+        b, hh, w, c = q.shape
+        l = hh * w
+        do = _attn_operand(do, "dO")
+        dq, dk, dv = (torch.empty((b, hh, w, c), device=q.device, dtype=torch.float32) for _ in range(3))
+        delta = torch.empty_like(lse)
+        d = _attn_desc(b, l, ctx.n_head, c // ctx.n_head, q, k, v, dq, ctx.p, ctx.seed)
+        check(lib.vq2_causal_attn_bwd(C.byref(d), _p(q), _p(k), _p(v), _p(lse), _p(do), ld_of(do), _p(dq), c, _p(dk), c,
+                                      _p(dv), c, _p(delta), _stream()), "causal_attn_bwd")
+        return dq, dk, dv, None, None, None
+
+
+def causal_attn_keep_mask(b, n_head, l, p, seed, device):
+    """The dropout keep decisions of CausalAttnFn for (p, seed) as a bool tensor [B, n_head, L, L] (the causal mask is
+    not applied).  For tests at small L: this IS of size L^2."""
+    mask = torch.empty((b, n_head, l, l), device=device, dtype=torch.uint8)
+    d = AttnDesc()
+    d.B, d.L, d.n_head, d.dim_head = b, l, n_head, 4
+    d.ldq = d.ldk = d.ldv = d.ldo = 4 * n_head
+    d.p_drop, d.seed = float(p), int(seed) & 0xFFFFFFFFFFFFFFFF
+    check(lib.vq2_causal_attn_keep_mask(C.byref(d), _p(mask), _stream()), "causal_attn_keep_mask")
+    return mask.bool()
+
+
+class WeightNormFn(Function):
+    """weight_norm(nn.Linear) (pixelsnail.py:17-18): w = g * v / ||v||_2 per output row; v [out, in], g [out, 1]."""
+
+    @staticmethod
+    def forward(ctx, v, g):
+        _require_cuda(v, "weight_v")
+        _require_cuda(g, "weight_g")
+        rows, cols = v.shape
+        if g.numel() != rows:
+            raise RuntimeError("WeightNormFn: weight_g must hold one value per output row")
+        vc = v if v.is_contiguous() else v.contiguous()
+        gc = g if g.is_contiguous() else g.contiguous()
+        w = torch.empty_like(vc)
+        check(lib.vq2_weight_norm_fwd(_p(vc), _p(gc), _p(w), rows, cols, _stream()), "weight_norm_fwd")
+        ctx.save_for_backward(vc, gc)
+        return w
+
+    @staticmethod
+    def backward(ctx, dw):
+        v, g = ctx.saved_tensors
+        rows, cols = v.shape
+        dwc = dw if dw.is_contiguous() else dw.contiguous()
+        dv = torch.empty_like(v)
+        dg = torch.empty_like(g)
+        check(lib.vq2_weight_norm_bwd(_p(dwc), _p(v), _p(g), _p(dv), _p(dg), rows, cols, _stream()), "weight_norm_bwd")
+        return dv, dg
 
 
 # ----------------------------------------------------------------------------- Quantize
