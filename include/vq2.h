@@ -46,10 +46,12 @@ typedef void *vq2_stream_t;
  * vq2_index_hist, vq2_eval_accumulate); revision 7: vq2_image_metrics, vq2_image_metrics_workspace_bytes and
  * vq2_image_metrics_accumulate added; revision 8: the causal-attention and weight-norm entry points added
  * (vq2_causal_attn_fwd, vq2_causal_attn_bwd, vq2_causal_attn_keep_mask, vq2_weight_norm_fwd, vq2_weight_norm_bwd);
+ * revision 9: additions only -- the second conv descriptor vq2_conv_geom with its vq2_convg_* entry points (rectangular
+ * kernels, top / left padding) and the ELU / ELU+dropout / GLU+residual kernels of the stage-2 GatedResBlock;
  * see INTEGRATION.md "ABI history").  vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 8
+#define VQ2_API_VERSION 9
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -411,6 +413,76 @@ int vq2_causal_attn_keep_mask(const vq2_attn_desc *d, uint8_t *mask, vq2_stream_
 int vq2_weight_norm_fwd(const float *v, const float *g, float *w, int32_t rows, int32_t cols, vq2_stream_t stream);
 int vq2_weight_norm_bwd(const float *dw, const float *v, const float *g, float *dv, float *dg, int32_t rows, int32_t cols,
                         vq2_stream_t stream);
+
+/* ------------------------------------------------------------------ conv, second geometry (stage-2 prior)
+ * Rectangular kernels with top / left padding: WNConv2d and CausalConv2d of the reference (pixelsnail.py:21-119, whose
+ * nn.ZeroPad2d + unpadded conv is one op here).  Non-transposed, stride 1, output the size of the input:
+ *     y[n,h,w,co] = bias[co] + sum_{kh<KH, kw<KW, ci} w[co,ci,kh,kw] * x[n, h - pad_top + kh, w - pad_left + kw, ci]
+ * with reads outside the image taken as 0.  1 <= KH, KW <= 7, KH * KW <= 32, 0 <= pad_top < KH, 0 <= pad_left < KW;
+ * anything else is VQ2_ERR_INVALID (a malformed descriptor) or VQ2_ERR_UNSUPPORTED (more than 32 taps) and reaches no kernel.
+ * 'downright' is (pad_top, pad_left) = (KH - 1, KW - 1); 'down' and 'causal' are (KH - 1, KW / 2) with odd KW; a
+ * size-preserving WNConv2d is ((KH - 1) / 2, (KW - 1) / 2) with odd KH and KW.
+ * Everything else is as for vq2_conv_desc and each vq2_convg_* function is its vq2_conv_* namesake on this descriptor:
+ * flags, bias, residual epilogue, Cir / Cor channel padding, pixel strides, the two weight panels packed from OIHW, the
+ * mask / residual / VQ2_MASK_AFTER_RESIDUAL of the data gradient (vq2_convg_dgrad takes the flags of vq2_conv_dgrad_ex), the
+ * immediate and the deferred weight gradient with their workspace and reduction job (every tap is computed, also those a
+ * 'causal' layer zeroes in its weight: the reference's gradient there is the full correlation), and the 2^31-element checks.
+ * The data gradient is the correlation with the flipped kernel at (KH - 1 - pad_top, KW - 1 - pad_left).  The kernel is
+ * chosen by the same plan as for vq2_conv_desc, so a square kernel with pad_top == pad_left == (KH - 1) / 2 gives bit for
+ * bit what the old descriptor gives; geometries the Winograd and fused forms do not name take the general GEMM tiles. */
+typedef struct vq2_conv_geom {
+    int32_t N, H, W, Ci; /* input, NHWC                                         */
+    int32_t Co;          /* output channels                                     */
+    int32_t KH, KW;      /* kernel rows and columns                             */
+    int32_t pad_top, pad_left;
+    int32_t ldx, ldy;    /* pixel strides of x and y buffers (elements)         */
+    int32_t Cir, Cor;    /* real channel counts, as in vq2_conv_desc            */
+    int32_t reserved;    /* must be 0                                           */
+} vq2_conv_geom;
+int vq2_convg_pack_weight(const vq2_conv_geom *d, int which, const float *w, float *packed, vq2_stream_t stream);
+int vq2_convg_pack_job_init(const vq2_conv_geom *d, int which, const float *w, float *packed, vq2_pack_job *job);
+int vq2_convg_fwd(const vq2_conv_geom *d, int flags, const float *x, const float *wp, const float *bias,
+                  const float *residual, int32_t ldres, float *y, vq2_stream_t stream);
+int vq2_convg_dgrad(const vq2_conv_geom *d, int flags, const float *dy, const float *wp, const float *mask, int32_t ldmask,
+                    const float *residual, int32_t ldres, float *dx, int32_t lddx, vq2_stream_t stream);
+size_t vq2_convg_wgrad_workspace_bytes(const vq2_conv_geom *d);
+int vq2_convg_wgrad(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
+                    size_t ws_bytes, vq2_stream_t stream);
+int vq2_convg_wgrad_partial(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *db, void *ws,
+                            size_t ws_bytes, vq2_stream_t stream);
+int vq2_convg_wgrad_job_init(const vq2_conv_geom *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job);
+
+/* ------------------------------------------------------------------ ELU, dropout and GLU of GatedResBlock (pixelsnail.py:122-179)
+ * All over [pixels, C] NHWC rows with pixel strides (multiples of 4, >= ceil4(C); 16-byte aligned pointers), any C >= 1;
+ * the pad lanes C .. ceil4(C) - 1 of every output are written as 0.  Deterministic: no reductions, no atomics.
+ * vq2_elu_fwd:  y = x > 0 ? x : expm1(x)                                (nn.ELU, alpha 1; pixelsnail.py:162,165,167)
+ * vq2_elu_bwd:  dx = dy * (y > 0 ? 1 : y + 1), from the OUTPUT y so that x need not be kept
+ * vq2_elu_dropout_fwd: y = keep * ELU(x) / (1 - p)                      (activation then nn.Dropout, pixelsnail.py:167-168)
+ * vq2_elu_dropout_bwd: dx = dy * keep / (1 - p) * (x > 0 ? 1 : exp(x)), from the INPUT x (y / (1 - p) would not give
+ *               y + 1 back to the last bit)
+ *               keep(seed, e) for the element with flat index e = pixel * C + c of the unpadded [pixels, C] tensor is
+ *               word (e & 3) of Philox4x32 (7 rounds, the generator of vq2_causal_attn_fwd) with counter (low and high
+ *               half of e >> 2, 0, 0) and the 64-bit seed as key, compared >= floor(p * 2^32).  0 <= p < 1; p = 0: no
+ *               dropout, the seed is not read.
+ * vq2_dropout_keep_mask: that decision as bytes [pixels, C] (1 = keep), the only way to check the dropout path.
+ * vq2_glu_res_fwd: out[c] = t[c] * sigmoid(t[Ch + c]) + res[c], c < Ch  (nn.GLU(1) and `out += input`, pixelsnail.py:176-177)
+ *               t holds 2 * Ch real channels (ldt >= ceil4(2 * Ch)), res and out Ch.  Ch % 4 != 0 (the 514-channel key
+ *               block): the second half starts at an unaligned channel and is read and written dword by dword.
+ * vq2_glu_res_bwd: dt[c] = dout[c] * sigmoid(b), dt[Ch + c] = dout[c] * a * sigmoid(b) * (1 - sigmoid(b)) with a = t[c],
+ *               b = t[Ch + c] (the sigmoid recomputed from t); lanes 2 * Ch .. ceil4(2 * Ch) - 1 of dt are 0.  The
+ *               gradient of res is dout itself. */
+int vq2_elu_fwd(const float *x, int32_t ldx, float *y, int32_t ldy, int64_t pixels, int32_t C, vq2_stream_t stream);
+int vq2_elu_bwd(const float *dy, int32_t lddy, const float *y, int32_t ldy, float *dx, int32_t lddx, int64_t pixels,
+                int32_t C, vq2_stream_t stream);
+int vq2_elu_dropout_fwd(const float *x, int32_t ldx, float *y, int32_t ldy, int64_t pixels, int32_t C, float p,
+                        uint64_t seed, vq2_stream_t stream);
+int vq2_elu_dropout_bwd(const float *dy, int32_t lddy, const float *x, int32_t ldx, float *dx, int32_t lddx,
+                        int64_t pixels, int32_t C, float p, uint64_t seed, vq2_stream_t stream);
+int vq2_dropout_keep_mask(uint8_t *mask, int64_t pixels, int32_t C, float p, uint64_t seed, vq2_stream_t stream);
+int vq2_glu_res_fwd(const float *t, int32_t ldt, const float *res, int32_t ldres, float *out, int32_t ldo, int64_t pixels,
+                    int32_t Ch, vq2_stream_t stream);
+int vq2_glu_res_bwd(const float *dout, int32_t lddo, const float *t, int32_t ldt, float *dt, int32_t lddt, int64_t pixels,
+                    int32_t Ch, vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ data-parallel exchange (RCCL over xGMI)
  * One communicator per process (= per GPU), owned by the library -- its only persistent state.  Replaces what

@@ -1,0 +1,132 @@
+"""GatedResBlock of the stage-2 prior against the same formula in eager torch (tests/_pixelsnail_ref.py), on one MI355X,
+timed with device events.
+
+Shapes: the top prior's causal 5x5 block (256 channels, B = 32, 32 x 32), the 1x1 block with an auxiliary input of 128
+channels at the same size, and the 5x5 block with a 256-channel condition at B = 8, 64 x 64; forward and forward +
+backward, eval mode (no dropout) and training mode (p = 0.1).  The two paths alternate inside every repeat, the first
+repeat of a series is discarded (warm-up), and the spread of the others is reported with the medians.  Writes one JSON
+document (default profiles/gated_resblock.json).  No GPU: fails.
+
+Counted from the shapes (not measured): conv FLOP = 2 * pixels * KH * KW * (in * channel + channel * 2 in) per forward,
+every tap (also the ones a 'causal' layer zeroes), three times that for forward + backward; the rate is taken over the
+time of the WHOLE block call, so it is a lower bound for the conv kernels, against the 157.3 TFLOP/s fp32 matrix peak."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+PEAK_TFLOPS = 157.3
+
+CASES = [dict(cin=256, ch=256, k=5, conv="causal", aux=0, cond=0, b=32, hw=32),
+         dict(cin=256, ch=256, k=1, conv="wnconv2d", aux=128, cond=0, b=32, hw=32),
+         dict(cin=256, ch=256, k=5, conv="causal", aux=0, cond=256, b=8, hw=64)]
+
+
+def time_ms(fn, inner):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(inner):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / inner
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gated_resblock.json"))
+    ap.add_argument("--repeats", type=int, default=5, help="timed repeats per path (one more is run first and discarded)")
+    ap.add_argument("--inner", type=int, default=10)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_gated_resblock.py needs the MI355X")
+    import vqvae2_amd
+    import _pixelsnail_ref as R
+    dev = torch.device("cuda:0")
+    results = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "inner": args.inner,
+               "peak_tflops": PEAK_TFLOPS, "cases": []}
+    for c in CASES:
+        b, hw, cin, ch = c["b"], c["hw"], c["cin"], c["ch"]
+        torch.manual_seed(0)
+        mod = vqvae2_amd.GatedResBlock(cin, ch, c["k"], conv=c["conv"], dropout=0.1, auxiliary_channel=c["aux"],
+                                       condition_dim=c["cond"]).to(dev)
+        sd = {k: v.detach().clone().requires_grad_(True) for k, v in mod.state_dict().items()}
+
+        def act(channels):
+            return torch.randn(b, channels, hw, hw, device=dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+
+        x = act(cin)
+        aux = act(c["aux"]) if c["aux"] else None
+        cond = act(c["cond"]) if c["cond"] else None
+        gout = act(cin).detach()
+
+        def eager(training):
+            keep = (torch.rand(b, ch, hw, hw, device=dev) >= 0.1) if training else None
+            return R.gated_resblock(x, sd, c["conv"], aux, cond, keep=keep, p=0.1)
+
+        # faster and different is not faster: the two paths must agree in eval mode at the timed size
+        mod.eval()
+        with torch.no_grad():
+            want = eager(False)
+            diff = float((mod(x, aux, cond) - want).abs().max())
+            bound = 1e-4 * float(want.abs().max())      # fp32 sums of up to 6,400 products in two orders: ~1e-5 relative
+        if not diff <= bound:
+            raise SystemExit(f"case {c}: the fused block differs from the eager formula by {diff:.3e} (bound {bound:.3e}); not timed")
+        conv_flop = 2.0 * b * hw * hw * c["k"] ** 2 * (cin * ch + ch * 2 * cin)
+        for training in (False, True):
+            mod.train(training)
+
+            def fused_f():
+                with torch.no_grad():
+                    mod(x, aux, cond)
+
+            def eager_f():
+                with torch.no_grad():
+                    eager(training)
+
+            def fused_fb():
+                mod(x, aux, cond).backward(gout)
+
+            def eager_fb():
+                eager(training).backward(gout)
+
+            row = {**c, "training": training, "eval_max_abs_diff": diff, "eval_diff_bound": bound}
+            for tag, ff, ef, flop in (("fwd", fused_f, eager_f, conv_flop), ("fwd_bwd", fused_fb, eager_fb, 3 * conv_flop)):
+                for fn in (ff, ef):      # warm every shape the timed window uses
+                    fn()
+                    fn()
+                torch.cuda.synchronize()
+                tf, te = [], []
+                for _ in range(args.repeats + 1):   # alternate the two paths
+                    tf.append(time_ms(ff, args.inner))
+                    te.append(time_ms(ef, args.inner))
+                tf, te = tf[1:], te[1:]              # the first window of a series still carries warm-up
+                mf, me = statistics.median(tf), statistics.median(te)
+                row[tag] = {"fused_ms": tf, "eager_ms": te, "fused_median_ms": mf, "eager_median_ms": me,
+                            "fused_spread": (max(tf) - min(tf)) / mf, "eager_spread": (max(te) - min(te)) / me,
+                            "eager_over_fused": me / mf, "counted_conv_flop": flop,
+                            "fused_conv_tflops": flop / (mf * 1e-3) / 1e12,
+                            "fused_fraction_of_peak": flop / (mf * 1e-3) / 1e12 / PEAK_TFLOPS}
+                print(json.dumps({"case": f"{c['conv']} k{c['k']} B{b} {hw}x{hw}", "training": training, "pass": tag,
+                                  "fused_ms": round(mf, 4), "eager_ms": round(me, 4),
+                                  "tflops": round(row[tag]["fused_conv_tflops"], 2),
+                                  "spread": [round(row[tag]["fused_spread"], 3), round(row[tag]["eager_spread"], 3)]}), flush=True)
+            results["cases"].append(row)
+            for t in (x, aux, cond, *sd.values(), *mod.parameters()):
+                if t is not None:
+                    t.grad = None
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(results, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()

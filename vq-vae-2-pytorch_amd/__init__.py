@@ -7,7 +7,7 @@ from .vqvae import VQVAE, Quantize, ResBlock, Encoder, Decoder, Conv2d, ConvTran
 from . import vqvae_deep  # noqa: F401
 from .vqvae_deep import VQVAE_Deep  # noqa: F401
 from . import pixelsnail  # noqa: F401
-from .pixelsnail import CausalAttention  # noqa: F401
+from .pixelsnail import CausalAttention, WNConv2d, CausalConv2d, GatedResBlock  # noqa: F401
 from . import distributed  # noqa: F401
 from . import ops  # noqa: F401
 from . import codes  # noqa: F401

@@ -16,6 +16,12 @@ class ConvDesc(C.Structure):
                 ("N", "H", "W", "Ci", "Co", "KH", "KW", "stride", "pad", "transposed", "ldx", "ldy", "Cir", "Cor")]
 
 
+class ConvGeom(C.Structure):
+    """vq2_conv_geom: rectangular kernels with top / left padding, output the size of the input."""
+    _fields_ = [(n, C.c_int32) for n in
+                ("N", "H", "W", "Ci", "Co", "KH", "KW", "pad_top", "pad_left", "ldx", "ldy", "Cir", "Cor", "reserved")]
+
+
 class PackJob(C.Structure):
     _fields_ = [("w", C.c_void_p), ("packed", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int64)] + \
                [(n, C.c_int32) for n in ("Or", "Ir", "Op", "Ip", "KH", "KW", "mode", "reserved")]
@@ -41,6 +47,8 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     P, I32, I64, SZ, F, D = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_double
     DP = C.POINTER(ConvDesc)
+    GP = C.POINTER(ConvGeom)
+    U64 = C.c_uint64
     sig = {
         "vq2_version": (C.c_int, []),
         "vq2_last_error": (C.c_char_p, []),
@@ -102,6 +110,21 @@ def _load():
         "vq2_causal_attn_keep_mask": (C.c_int, [C.POINTER(AttnDesc), P, P]),
         "vq2_weight_norm_fwd": (C.c_int, [P, P, P, I32, I32, P]),
         "vq2_weight_norm_bwd": (C.c_int, [P, P, P, P, P, I32, I32, P]),
+        "vq2_convg_pack_weight": (C.c_int, [GP, C.c_int, P, P, P]),
+        "vq2_convg_pack_job_init": (C.c_int, [GP, C.c_int, P, P, C.POINTER(PackJob)]),
+        "vq2_convg_fwd": (C.c_int, [GP, C.c_int, P, P, P, P, I32, P, P]),
+        "vq2_convg_dgrad": (C.c_int, [GP, C.c_int, P, P, P, I32, P, I32, P, I32, P]),
+        "vq2_convg_wgrad_workspace_bytes": (SZ, [GP]),
+        "vq2_convg_wgrad": (C.c_int, [GP, C.c_int, P, P, P, P, P, SZ, P]),
+        "vq2_convg_wgrad_partial": (C.c_int, [GP, C.c_int, P, P, P, P, SZ, P]),
+        "vq2_convg_wgrad_job_init": (C.c_int, [GP, P, P, P, C.POINTER(WgradJob)]),
+        "vq2_elu_fwd": (C.c_int, [P, I32, P, I32, I64, I32, P]),
+        "vq2_elu_bwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
+        "vq2_elu_dropout_fwd": (C.c_int, [P, I32, P, I32, I64, I32, F, U64, P]),
+        "vq2_elu_dropout_bwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, F, U64, P]),
+        "vq2_dropout_keep_mask": (C.c_int, [P, I64, I32, F, U64, P]),
+        "vq2_glu_res_fwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
+        "vq2_glu_res_bwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
         "vq2_comm_unique_id": (C.c_int, [P]),
         "vq2_comm_init": (C.c_int, [P, I32, I32]),
         "vq2_comm_world": (C.c_int, []),

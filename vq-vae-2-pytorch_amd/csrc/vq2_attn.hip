@@ -25,6 +25,7 @@
 // seed, >= floor(p * 2^32).  Nothing else enters (no tile size, no launch geometry, same in forward and backward);
 // attn_keep_mask_kernel writes it out as bytes for tests.
 #include "vq2_common.h"
+#include "vq2_philox.h"
 
 namespace {
 
@@ -46,16 +47,7 @@ struct AttnParams {
     int dropout;
 };
 
-__device__ __forceinline__ uint4 philox4x32_7(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 7; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
+using vq2::philox4x32_7;
 // the four keep words of keys 4 * jq .. 4 * jq + 3 for query i
 __device__ __forceinline__ uint4 keep_words(const AttnParams &P, int b, int h, int i, int jq) {
     return philox4x32_7((uint32_t)jq, (uint32_t)i, (uint32_t)b, (uint32_t)h, P.seed_lo, P.seed_hi);

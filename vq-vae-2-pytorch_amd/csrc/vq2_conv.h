@@ -48,17 +48,52 @@ __device__ __forceinline__ float4 as_f4(u32x4 v) {
 static inline int real_ci(const vq2_conv_desc *d) { return d->Cir ? d->Cir : d->Ci; }
 static inline int real_co(const vq2_conv_desc *d) { return d->Cor ? d->Cor : d->Co; }
 
+// What every conv entry point plans from: the layer as a vq2_conv_desc plus the top and left padding on their own.
+//   vq2_conv_desc:  pad_h = pad_w = pad, the output size follows from pad, kernel and stride
+//   vq2_conv_geom:  stride 1, not transposed, pad_h = pad_top, pad_w = pad_left, `same`: output the size of the input
+// (the `pad` member is not read past geo_of)
+struct ConvGeo : vq2_conv_desc {
+    int pad_h, pad_w;
+    bool same;
+};
+static inline ConvGeo geo_of(const vq2_conv_desc *d) {
+    ConvGeo g;
+    static_cast<vq2_conv_desc &>(g) = *d;
+    g.pad_h = g.pad_w = d->pad; g.same = false;
+    return g;
+}
+// The contract of the second descriptor (include/vq2.h), checked by every vq2_convg_* entry point before geo_of: the one
+// copy of it.  The checks shared with vq2_conv_desc (dims, multiples of 4, strides, Cir / Cor, 2^31) follow in the callers.
+static inline int check_geom(const vq2_conv_geom *d) {
+    VQ2_REQUIRE(d != nullptr, "conv geometry is null");
+    VQ2_REQUIRE(d->reserved == 0, "conv geometry: the reserved word must be 0");
+    VQ2_REQUIRE(d->KH >= 1 && d->KH <= 7 && d->KW >= 1 && d->KW <= 7, "conv geometry: KH=%d, KW=%d must lie in 1..7", d->KH, d->KW);
+    VQ2_REQUIRE(d->pad_top >= 0 && d->pad_top < d->KH && d->pad_left >= 0 && d->pad_left < d->KW,
+                "conv geometry: 0 <= pad_top < KH and 0 <= pad_left < KW required (got %d, %d)", d->pad_top, d->pad_left);
+    if (d->KH * d->KW > 32) return set_error(VQ2_ERR_UNSUPPORTED, "conv geometry: %d x %d has more than 32 taps", d->KH, d->KW);
+    VQ2_REQUIRE(d->Cir >= 0 && d->Cir <= d->Ci && d->Cor >= 0 && d->Cor <= d->Co, "conv geometry: Cir/Cor out of range");
+    return VQ2_OK;
+}
+static inline ConvGeo geo_of(const vq2_conv_geom *d) {
+    ConvGeo g;
+    g.N = d->N; g.H = d->H; g.W = d->W; g.Ci = d->Ci; g.Co = d->Co; g.KH = d->KH; g.KW = d->KW;
+    g.stride = 1; g.pad = d->pad_top; g.transposed = 0; g.ldx = d->ldx; g.ldy = d->ldy; g.Cir = d->Cir; g.Cor = d->Cor;
+    g.pad_h = d->pad_top; g.pad_w = d->pad_left; g.same = true;
+    return g;
+}
+
 struct ConvHW { int h, w; };
-static inline ConvHW out_hw(const vq2_conv_desc *d) {
+static inline ConvHW out_hw(const ConvGeo *d) {
     if (d->transposed) return {2 * d->H, 2 * d->W};
-    return {(d->H + 2 * d->pad - d->KH) / d->stride + 1, (d->W + 2 * d->pad - d->KW) / d->stride + 1};
+    if (d->same) return {d->H, d->W};
+    return {(d->H + 2 * d->pad_h - d->KH) / d->stride + 1, (d->W + 2 * d->pad_w - d->KW) / d->stride + 1};
 }
 
 // Algorithmic work of a layer, the same for its forward, data-gradient and weight-gradient launches (for the profiler only):
 // real channels, every tap once; the input-sized and the output-sized tensor cross memory once each, plus `more_in` /
 // `more_out` further tensors of those sizes (residual, mask), plus the weights.
 struct ConvWork { double flops, bytes; };
-static inline ConvWork conv_work(const vq2_conv_desc *d, int more_in, int more_out) {
+static inline ConvWork conv_work(const ConvGeo *d, int more_in, int more_out) {
     const double cir = real_ci(d), cor = real_co(d);
     const ConvHW o = out_hw(d);
     const double pix_in = (double)d->N * d->H * d->W, pix_out = (double)d->N * o.h * o.w;

@@ -27,7 +27,7 @@ struct WgradParams {
     int bias_nslots; // popcount(bias_taps): bias_ws is [S][nslots][I]
     int N, H, W, I, ldx;
     int Ho, Wo, O, ldg;
-    int KH, KW, stride, pad;
+    int KH, KW, stride, pad_h, pad_w;
     int K, M;
     int rows_per_split;  // multiple of 32
     int relu_x, relu_g;
@@ -110,8 +110,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams P) {
             const int m = mbase + x_r + j * X_RSTEP;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (x_kv && m < m_end) {
-                const int ih = xho[j] * P.stride - P.pad + kh;
-                const int iw = xwo[j] * P.stride - P.pad + kw;
+                const int ih = xho[j] * P.stride - P.pad_h + kh;
+                const int iw = xwo[j] * P.stride - P.pad_w + kw;
                 if ((unsigned)ih < (unsigned)P.H && (unsigned)iw < (unsigned)P.W)
                     v = *reinterpret_cast<const float4 *>(P.x + ((size_t)(xn[j] * P.H + ih) * P.W + iw) * P.ldx + ci);
             }
@@ -376,7 +376,7 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
             x_iw[j] = CS * tj;                               // + CS * pair0 + xo = input column
             x_const[j] = (((WINO == 3 ? -kh : kh) + RS * r2) * P.W + CS * tj) * P.ldx * 4 + ci * 4;
         } else {
-        x_iw[j] = rj * P.stride - P.pad + kw;                // + wo0*stride = input column
+        x_iw[j] = rj * P.stride - P.pad_w + kw;               // + wo0*stride = input column
         x_const[j] = ((kh * P.W + kw + rj * P.stride) * P.ldx + ci) * 4;
         }
     }
@@ -445,8 +445,8 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
             const bool v = g_cv && (g_r + j * G_RSTEP) < rows_left;
             rgv[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, v ? gbase + g_const[j] : WOOB, 0, 0);
         }
-        const int ihu = uho * P.stride - P.pad;               // uniform
-        const int xbase = ((un * P.H + ihu) * P.W + uwo * P.stride - P.pad) * P.ldx * 4;  // uniform
+        const int ihu = uho * P.stride - P.pad_h;             // uniform
+        const int xbase = ((un * P.H + ihu) * P.W + uwo * P.stride - P.pad_w) * P.ldx * 4;  // uniform
         const bool hv = x_kv && (unsigned)(ihu + kh) < (unsigned)P.H;
         const int iwu = uwo * P.stride;
 #pragma unroll
@@ -806,13 +806,14 @@ struct WgradPlan {
     int wino;     // F(2,3) Winograd along the rows: K = 12 * I (kh, v, i), M in column pairs (wgrad_fast_kernel<..., WINO>)
 };
 
-static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
+static WgradPlan plan_wgrad(const ConvGeo *d) {
     WgradPlan p;
     p.swapped = 0;
     // A stride-1 "same" conv with few output channels (the ResBlock 3x3, 128 -> 32): gathering the im2col
     // of the WIDE tensor x re-reads it KH*KW times through L2.  The same sum with the roles exchanged,
     //   dw[co][ci][kh][kw] = sum_q relu(x)[q][ci] * dy[q - (kh-p, kw-p)][co],
-    // gathers the NARROW tensor dy instead (flipped taps, pad' = K-1-p) and streams x once.
+    // gathers the NARROW tensor dy instead (flipped taps, pad' = K-1-p) and streams x once.  Square kernels with the
+    // same centred padding on both axes only.
     // (Exchanged roles and the Winograd modes below are fast-kernel forms: VQ2_FORMS=general plans neither, =direct no
     // Winograd mode.)
     const bool fast = forms() > FORMS_GENERAL;
@@ -820,7 +821,8 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     const long pix = (long)d->N * d->H * d->W;
     const bool wino = forms() == FORMS_ALL && pix * d->ldx < FAST_REACH && pix * d->ldy * (d->transposed ? 4 : 1) < FAST_REACH;
     const ConvHW o = out_hw(d);
-    if (fast && !d->transposed && d->stride == 1 && 2 * d->pad == d->KH - 1 && d->KH > 1 && d->Co <= 32 && d->Ci >= 64) {
+    if (fast && !d->transposed && d->stride == 1 && d->KH == d->KW && d->pad_h == d->pad_w && 2 * d->pad_h == d->KH - 1 &&
+        d->KH > 1 && d->Co <= 32 && d->Ci >= 64) {
         p.swapped = 1;
         p.O = d->Ci; p.I = d->Co;
         p.M = d->N * d->H * d->W;
@@ -833,7 +835,7 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     }
     p.K = d->KH * d->KW * p.I;
     p.wino = 0;
-    if (wino && !p.swapped && !d->transposed && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 &&
+    if (wino && !p.swapped && !d->transposed && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 &&
         p.O % 128 == 0 && p.I % 128 == 0 && (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0))) {
         p.wino = 1;
         p.K = 12 * p.I;
@@ -841,7 +843,7 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     }
     {   // 4x4 stride-2 conv / conv-transpose: F(2,2) by column parity over output column pairs
         const int wo = d->transposed ? d->W : d->W / 2;       // width of the G operand's grid
-        if (wino && !p.swapped && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad == 1 && d->H % 2 == 0 &&
+        if (wino && !p.swapped && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_h == 1 && d->H % 2 == 0 &&
             d->W % 2 == 0 && p.O % 128 == 0 && (p.I == 64 || p.I % 128 == 0) &&
             (wo % 64 == 0 || (wo == 32 && (d->transposed ? d->H : d->H / 2) % 2 == 0))) {
             p.wino = 2;
@@ -861,7 +863,7 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
         const long work = po * pk;
         if (best < 0 || work < best) { best = work; p.tile = c; }
     }
-    if (wino && p.swapped && d->KH == 3 && d->pad == 1 && p.I == 32 && p.O % 128 == 0 &&
+    if (wino && p.swapped && d->KH == 3 && d->pad_h == 1 && p.I == 32 && p.O % 128 == 0 &&
         (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0))) {
         p.wino = 3;                 // exchanged roles + F(2,3): four 128 x 96 tiles (v) of three kernel rows each
         p.K = 4 * 96;
@@ -887,14 +889,14 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
 // Which taps of the gathered operand cover every dy pixel exactly once (bias gradient = their column sums):
 // exchanged roles -> the centre tap (its own flip); conv-transpose k4 s2 p1 -> taps (1,1),(1,2),(2,1),(2,2),
 // one per output phase, never out of bounds.
-static void bias_taps_of(const vq2_conv_desc *d, const WgradPlan &p, int &taps, int &nslots) {
+static void bias_taps_of(const ConvGeo *d, const WgradPlan &p, int &taps, int &nslots) {
     taps = 0; nslots = 0;
     if (p.wino == 2 && d->transposed) { taps = 1; nslots = 4; return; }    // flag only: see wgrad_fast_kernel<..., 2>
     if (p.swapped) { taps = 1 << ((d->KH / 2) * d->KW + d->KW / 2); nslots = 1; }
     else if (d->transposed) { taps = (1 << 5) | (1 << 6) | (1 << 9) | (1 << 10); nslots = 4; }
 }
 
-static size_t bias_ws_floats(const vq2_conv_desc *d, const WgradPlan &p) {
+static size_t bias_ws_floats(const ConvGeo *d, const WgradPlan &p) {
     int taps, nslots;
     bias_taps_of(d, p, taps, nslots);
     return taps ? (size_t)p.S * nslots * p.I : (size_t)p.S * p.O;
@@ -1004,14 +1006,26 @@ static int colsum_impl(const float *dy, int64_t rows, int C, int ld, float *db, 
 
 using namespace vq2;
 
-extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) {
-    if (!d || check_forms() || d->N <= 0 || d->Ci <= 0 || d->Co <= 0) return 0;
+static size_t wgrad_ws_bytes(const ConvGeo *d) {
+    if (check_forms() || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Ci <= 0 || d->Co <= 0 || d->KH <= 0 || d->KW <= 0) return 0;
     const WgradPlan p = plan_wgrad(d);
     return ((size_t)p.S * p.O * p.K + bias_ws_floats(d, p)) * sizeof(float);
 }
 
+extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) {
+    if (!d) return 0;
+    const ConvGeo g = geo_of(d);
+    return wgrad_ws_bytes(&g);
+}
+
+extern "C" size_t vq2_convg_wgrad_workspace_bytes(const vq2_conv_geom *d) {
+    if (check_geom(d)) return 0;
+    const ConvGeo g = geo_of(d);
+    return wgrad_ws_bytes(&g);
+}
+
 // slabs (+ bias partials); reduce == true also runs the per-layer reduction into dw/db
-static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
+static int wgrad_impl(const ConvGeo *d, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
                       size_t ws_bytes, vq2_stream_t stream, bool reduce) {
     VQ2_REQUIRE(d && x && dy && ws && (dw || !reduce), "conv_wgrad: null pointer");
     if (int e = check_forms()) return e;
@@ -1020,25 +1034,25 @@ static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const f
     VQ2_REQUIRE(d->ldx >= d->Ci && d->ldy >= d->Co && d->ldx % 4 == 0 && d->ldy % 4 == 0, "conv_wgrad: bad strides");
     VQ2_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(ws), "conv_wgrad: pointers must be 16-byte aligned");
     if (d->transposed)
-        VQ2_REQUIRE(d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad == 1, "conv_wgrad: convT must be k4 s2 p1");
-    else
-        VQ2_REQUIRE(d->KH == d->KW && d->KH >= 1 && d->KH <= 7 && (d->stride == 1 || d->stride == 2) && d->pad >= 0,
+        VQ2_REQUIRE(d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_h == 1, "conv_wgrad: convT must be k4 s2 p1");
+    else if (!d->same)   // (the second descriptor was checked by check_geom)
+        VQ2_REQUIRE(d->KH == d->KW && d->KH >= 1 && d->KH <= 7 && (d->stride == 1 || d->stride == 2) && d->pad_h >= 0,
                     "conv_wgrad: unsupported conv geometry");
     const WgradPlan p = plan_wgrad(d);
-    VQ2_REQUIRE(ws_bytes >= vq2_conv_wgrad_workspace_bytes(d), "conv_wgrad: workspace too small");
+    VQ2_REQUIRE(ws_bytes >= wgrad_ws_bytes(d), "conv_wgrad: workspace too small");
     WgradParams P{};
     P.ws = static_cast<float *>(ws);
     float *bias_ws = P.ws + (size_t)p.S * p.O * p.K;       // bias partials: [S][O], or [S][nslots][I] from the gathered operand
     bias_taps_of(d, p, P.bias_taps, P.bias_nslots);
     P.bias_ws = db ? bias_ws : nullptr;
-    P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad = d->pad;
+    P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = d->pad_h; P.pad_w = d->pad_w;
     P.O = p.O; P.I = p.I; P.K = p.K; P.M = p.M; P.rows_per_split = p.rows_per_split;
     P.N = d->N;
     if (p.swapped) {
         P.x = dy; P.ldx = d->ldy; P.H = d->H; P.W = d->W;       // gathered operand: dy (same spatial size as x)
         P.g = x; P.ldg = d->ldx;
         P.Ho = d->H; P.Wo = d->W;
-        P.stride = 1; P.pad = d->KH - 1 - d->pad;
+        P.stride = 1; P.pad_h = P.pad_w = d->KH - 1 - d->pad_h;
         P.relu_x = 0; P.relu_g = (flags & VQ2_RELU_IN) != 0;
     } else if (!d->transposed) {
         P.x = x; P.ldx = d->ldx; P.H = d->H; P.W = d->W;
@@ -1100,16 +1114,49 @@ static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const f
 
 extern "C" int vq2_conv_wgrad(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *dw, float *db,
                               void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    return wgrad_impl(d, flags, x, dy, dw, db, ws, ws_bytes, stream, true);
+    VQ2_REQUIRE(d, "conv_wgrad: null pointer");
+    const ConvGeo g = geo_of(d);
+    return wgrad_impl(&g, flags, x, dy, dw, db, ws, ws_bytes, stream, true);
 }
 
 extern "C" int vq2_conv_wgrad_partial(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *db,
                                       void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    return wgrad_impl(d, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
+    VQ2_REQUIRE(d, "conv_wgrad: null pointer");
+    const ConvGeo g = geo_of(d);
+    return wgrad_impl(&g, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
 }
+
+extern "C" int vq2_convg_wgrad(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *dw, float *db,
+                               void *ws, size_t ws_bytes, vq2_stream_t stream) {
+    if (int e = check_geom(d)) return e;
+    const ConvGeo g = geo_of(d);
+    return wgrad_impl(&g, flags, x, dy, dw, db, ws, ws_bytes, stream, true);
+}
+
+extern "C" int vq2_convg_wgrad_partial(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *db,
+                                       void *ws, size_t ws_bytes, vq2_stream_t stream) {
+    if (int e = check_geom(d)) return e;
+    const ConvGeo g = geo_of(d);
+    return wgrad_impl(&g, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
+}
+
+static int wgrad_job_init_impl(const ConvGeo *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job);
 
 extern "C" int vq2_wgrad_job_init(const vq2_conv_desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
     VQ2_REQUIRE(d && ws && dw && job, "wgrad_job_init: null pointer");
+    const ConvGeo g = geo_of(d);
+    return wgrad_job_init_impl(&g, ws, dw, db, job);
+}
+
+extern "C" int vq2_convg_wgrad_job_init(const vq2_conv_geom *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
+    if (int e = check_geom(d)) return e;
+    VQ2_REQUIRE(ws && dw && job, "wgrad_job_init: null pointer");
+    VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0, "wgrad_job_init: non-positive dims");
+    const ConvGeo g = geo_of(d);
+    return wgrad_job_init_impl(&g, ws, dw, db, job);
+}
+
+static int wgrad_job_init_impl(const ConvGeo *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
     if (int e = check_forms()) return e;
     const WgradPlan p = plan_wgrad(d);
     const int cir = real_ci(d), cor = real_co(d);

@@ -6,13 +6,14 @@ wider buffer).  PyTorch is used for device memory, streams and autograd bookkeep
 every FLOP and every byte moved on this path is a libvq2 kernel.
 """
 from dataclasses import dataclass
+from types import SimpleNamespace
 import ctypes as C
 import os
 
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check, AttnDesc, ConvDesc, PackJob, WgradJob
+from ._lib import lib, check, AttnDesc, ConvDesc, ConvGeom, PackJob, WgradJob
 
 VQ2_RELU_IN = 1
 VQ2_RELU_OUT = 2
@@ -99,6 +100,25 @@ class ConvSpec:
     k: int
     stride: int
     pad: int
+    # The second geometry (vq2_conv_geom of include/vq2.h; WNConv2d / CausalConv2d of the stage-2 prior): kernel columns
+    # and top / left padding on their own, output the size of the input.  All None (the default): the square, symmetric
+    # layer that `k` and `pad` describe, through vq2_conv_desc as before.  Set together by ConvSpec.geom().
+    kw: int = None
+    pad_top: int = None
+    pad_left: int = None
+
+    @classmethod
+    def geom(cls, cin, cout, kh, kw, pad_top, pad_left):
+        """A stride-1 conv with a kh x kw kernel that reads from row h - pad_top and column w - pad_left on."""
+        return cls(False, cin, cout, kh, 1, pad_top, kw, pad_top, pad_left)
+
+    @property
+    def is_geom(self):
+        return self.kw is not None
+
+    @property
+    def taps(self):
+        return self.k * (self.kw if self.is_geom else self.k)
 
     @property
     def ci(self):
@@ -111,10 +131,19 @@ class ConvSpec:
     def out_hw(self, h, w):
         if self.transposed:
             return 2 * h, 2 * w
+        if self.is_geom:
+            return h, w
         return (h + 2 * self.pad - self.k) // self.stride + 1, (w + 2 * self.pad - self.k) // self.stride + 1
 
 
 def _desc(spec, n, h, w, ldx, ldy):
+    if spec.is_geom:
+        d = ConvGeom()
+        d.N, d.H, d.W, d.Ci, d.Co = n, h, w, spec.ci, spec.co
+        d.KH, d.KW, d.pad_top, d.pad_left = spec.k, spec.kw, spec.pad_top, spec.pad_left
+        d.ldx, d.ldy = ldx, ldy
+        d.Cir, d.Cor = spec.cin, spec.cout
+        return d
     d = ConvDesc()
     d.N, d.H, d.W, d.Ci, d.Co = n, h, w, spec.ci, spec.co
     d.KH = d.KW = spec.k
@@ -129,6 +158,21 @@ def touch_weights(params):
     does not bump tensor._version."""
     for p in params:
         p._vq2_epoch = getattr(p, "_vq2_epoch", 0) + 1
+
+
+# The entry points of the two descriptor types (vq2_conv_desc, vq2_conv_geom) under one set of names
+_ABI_DESC = SimpleNamespace(
+    pack_weight=lib.vq2_pack_weight, pack_job_init=lib.vq2_pack_job_init, fwd=lib.vq2_conv_fwd, dgrad=lib.vq2_conv_dgrad_ex,
+    wgrad_workspace_bytes=lib.vq2_conv_wgrad_workspace_bytes, wgrad=lib.vq2_conv_wgrad,
+    wgrad_partial=lib.vq2_conv_wgrad_partial, wgrad_job_init=lib.vq2_wgrad_job_init)
+_ABI_GEOM = SimpleNamespace(
+    pack_weight=lib.vq2_convg_pack_weight, pack_job_init=lib.vq2_convg_pack_job_init, fwd=lib.vq2_convg_fwd,
+    dgrad=lib.vq2_convg_dgrad, wgrad_workspace_bytes=lib.vq2_convg_wgrad_workspace_bytes, wgrad=lib.vq2_convg_wgrad,
+    wgrad_partial=lib.vq2_convg_wgrad_partial, wgrad_job_init=lib.vq2_convg_wgrad_job_init)
+
+
+def _abi(spec):
+    return _ABI_GEOM if spec.is_geom else _ABI_DESC
 
 
 def _pack_version(spec, weight):
@@ -146,11 +190,11 @@ def packed_weight(spec, weight, which):
     wsrc = weight.detach()
     if not wsrc.is_contiguous():
         wsrc = wsrc.contiguous()
-    n = spec.ci * spec.co * spec.k * spec.k
+    n = spec.ci * spec.co * spec.taps
     buf = hit[1] if (hit is not None and hit[1].numel() == n and hit[1].device == weight.device) else \
         torch.empty(n, device=weight.device, dtype=torch.float32)
     d = _desc(spec, 1, max(spec.k, 2), max(spec.k, 2), spec.ci, spec.co)
-    check(lib.vq2_pack_weight(C.byref(d), which, _p(wsrc), _p(buf), _stream()), "pack_weight")
+    check(_abi(spec).pack_weight(C.byref(d), which, _p(wsrc), _p(buf), _stream()), "pack_weight")
     packs[which] = (ver, buf)
     return buf
 
@@ -167,19 +211,19 @@ class PackPlan:
         for spec, weight, needs_dgrad in layers:
             for which in ((PACK_FWD, PACK_DGRAD) if needs_dgrad else (PACK_FWD,)):
                 jobs.append((spec, weight, which))
-        n = sum(s.ci * s.co * s.k * s.k for s, _, _ in jobs)
+        n = sum(s.ci * s.co * s.taps for s, _, _ in jobs)
         dev = jobs[0][1].device
         self.flat = torch.empty(n, device=dev, dtype=torch.float32)
         self.entries = []
         arr = (PackJob * len(jobs))()
         off = 0
         for i, (spec, weight, which) in enumerate(jobs):
-            numel = spec.ci * spec.co * spec.k * spec.k
+            numel = spec.ci * spec.co * spec.taps
             buf = self.flat[off:off + numel]
             d = _desc(spec, 1, max(spec.k, 2), max(spec.k, 2), spec.ci, spec.co)
             if not weight.is_contiguous():
                 raise RuntimeError("PackPlan: weights must be contiguous")
-            check(lib.vq2_pack_job_init(C.byref(d), which, _p(weight), _p(buf), C.byref(arr[i])), "pack_job_init")
+            check(_abi(spec).pack_job_init(C.byref(d), which, _p(weight), _p(buf), C.byref(arr[i])), "pack_job_init")
             arr[i].offset = off
             assert arr[i].numel == numel
             self.entries.append((spec, weight, which, buf))
@@ -210,7 +254,7 @@ def conv_forward(spec, x, weight, bias, flags=0, residual=None, out=None):
     d = _desc(spec, n, h, w, ld_of(x), ld_of(out))
     wp = packed_weight(spec, weight, PACK_FWD)
     ldres = ld_of(residual) if residual is not None else 0
-    check(lib.vq2_conv_fwd(C.byref(d), flags, _p(x), _p(wp), _p(bias), _p(residual), ldres, _p(out), _stream()),
+    check(_abi(spec).fwd(C.byref(d), flags, _p(x), _p(wp), _p(bias), _p(residual), ldres, _p(out), _stream()),
           "conv_fwd")
     return out
 
@@ -221,7 +265,7 @@ def conv_dgrad(spec, xshape, dy, weight, mask=None, residual=None, out=None, mas
         out = torch.empty((n, h, w, spec.ci), device=dy.device, dtype=torch.float32)
     d = _desc(spec, n, h, w, spec.ci, ld_of(dy))
     wp = packed_weight(spec, weight, PACK_DGRAD)
-    check(lib.vq2_conv_dgrad_ex(C.byref(d), VQ2_MASK_AFTER_RESIDUAL if mask_after else 0, _p(dy), _p(wp), _p(mask),
+    check(_abi(spec).dgrad(C.byref(d), VQ2_MASK_AFTER_RESIDUAL if mask_after else 0, _p(dy), _p(wp), _p(mask),
                                 ld_of(mask) if mask is not None else 0, _p(residual),
                                 ld_of(residual) if residual is not None else 0, _p(out), ld_of(out), _stream()),
           "conv_dgrad")
@@ -253,12 +297,12 @@ class WgradBatch:
         d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
         ent = self.entries.get(key)
         if ent is None:
-            nbytes = lib.vq2_conv_wgrad_workspace_bytes(C.byref(d))
+            nbytes = _abi(spec).wgrad_workspace_bytes(C.byref(d))
             ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
             dw = weight._vq2_grad
             db = bias._vq2_grad if (bias is not None and want_db) else None
             job = WgradJob()
-            check(lib.vq2_wgrad_job_init(C.byref(d), _p(ws), _p(dw), _p(db), C.byref(job)), "wgrad_job_init")
+            check(_abi(spec).wgrad_job_init(C.byref(d), _p(ws), _p(dw), _p(db), C.byref(job)), "wgrad_job_init")
             ent = {"ws": ws, "nbytes": nbytes, "job": job, "dw": dw, "db": db, "used": False}
             self.entries[key] = ent
             self.dirty = True
@@ -267,12 +311,12 @@ class WgradBatch:
         if n * h * w <= WGRAD_STREAM_MAX_PIXELS:
             side.wait_event(torch.cuda.current_stream().record_event())
             with torch.cuda.stream(side):
-                check(lib.vq2_conv_wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
+                check(_abi(spec).wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
                                                  _p(ent["ws"]), ent["nbytes"], _stream()), "conv_wgrad_partial")
             x.record_stream(side)
             dy.record_stream(side)
         else:
-            check(lib.vq2_conv_wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
+            check(_abi(spec).wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
                                              _p(ent["ws"]), ent["nbytes"], _stream()), "conv_wgrad_partial")
         if not ent["used"]:
             ent["used"] = True
@@ -354,7 +398,7 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
     """(dw, db) in the reference layouts; the bias gradient is fused into the same launches."""
     n, h, w, _ = x.shape
     d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
-    nbytes = lib.vq2_conv_wgrad_workspace_bytes(C.byref(d))
+    nbytes = _abi(spec).wgrad_workspace_bytes(C.byref(d))
     sc = _step_ctx(weight)
     if sc is not None and getattr(weight, "_vq2_grad", None) is not None and weight.grad is None and \
             (bias is None or (getattr(bias, "_vq2_grad", None) is not None and bias.grad is None)) and \
@@ -368,13 +412,13 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
         side.wait_event(torch.cuda.current_stream().record_event())
         with torch.cuda.stream(side):
             ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
-            check(lib.vq2_conv_wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws),
+            check(_abi(spec).wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws),
                                      nbytes, _stream()), "conv_wgrad")
         x.record_stream(side)   # keep the caching allocator from recycling these while the side stream reads
         dy.record_stream(side)
         return (dw if want_dw else None), db
     ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
-    check(lib.vq2_conv_wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes,
+    check(_abi(spec).wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes,
                              _stream()), "conv_wgrad")
     return (dw if want_dw else None), db
 
@@ -973,6 +1017,104 @@ class WeightNormFn(Function):
         dg = torch.empty_like(g)
         check(lib.vq2_weight_norm_bwd(_p(dwc), _p(v), _p(g), _p(dv), _p(dg), rows, cols, _stream()), "weight_norm_bwd")
         return dv, dg
+
+
+# ----------------------------------------------------------------------------- GatedResBlock pieces (stage-2 prior)
+def _rows(t, c):
+    """Dense NHWC operand of an elementwise kernel: real channels c, ceil4(c) stored."""
+    t = as_nhwc(t)
+    if t.shape[3] != ceil4(c):
+        raise RuntimeError(f"expected {ceil4(c)} stored channels for {c} real ones, got {t.shape[3]}")
+    return t
+
+
+class EluFn(Function):
+    """y = ELU(x) (alpha 1) over NHWC with `c` real channels; pad lanes of y are 0.  Saves y only: the backward is
+    dx = dy * (y > 0 ? 1 : y + 1)."""
+
+    @staticmethod
+    def forward(ctx, x, c):
+        x = _rows(x, c)
+        n, h, w, cp = x.shape
+        y = torch.empty((n, h, w, cp), device=x.device, dtype=torch.float32)
+        check(lib.vq2_elu_fwd(_p(x), ld_of(x), _p(y), cp, n * h * w, c, _stream()), "elu_fwd")
+        ctx.save_for_backward(y)
+        ctx.c = c
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy = _rows(dy, ctx.c)
+        n, h, w, cp = y.shape
+        dx = torch.empty_like(y)
+        check(lib.vq2_elu_bwd(_p(dy), ld_of(dy), _p(y), cp, _p(dx), cp, n * h * w, ctx.c, _stream()), "elu_bwd")
+        return dx, None
+
+
+class EluDropoutFn(Function):
+    """y = dropout(ELU(x)) in one pass (pixelsnail.py:167-168): keep decisions are a function of (seed, flat index of the
+    element in the unpadded tensor) alone, survivors are scaled by 1 / (1 - p).  Saves x: the backward recomputes the
+    decisions and the derivative exp(x) from it."""
+
+    @staticmethod
+    def forward(ctx, x, c, p, seed):
+        x = _rows(x, c)
+        n, h, w, cp = x.shape
+        y = torch.empty((n, h, w, cp), device=x.device, dtype=torch.float32)
+        check(lib.vq2_elu_dropout_fwd(_p(x), ld_of(x), _p(y), cp, n * h * w, c, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                      _stream()), "elu_dropout_fwd")
+        ctx.save_for_backward(x)
+        ctx.c, ctx.p, ctx.seed = c, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dy = _rows(dy, ctx.c)
+        n, h, w, cp = x.shape
+        dx = torch.empty((n, h, w, cp), device=x.device, dtype=torch.float32)
+        check(lib.vq2_elu_dropout_bwd(_p(dy), ld_of(dy), _p(x), ld_of(x), _p(dx), cp, n * h * w, ctx.c, ctx.p, ctx.seed,
+                                      _stream()), "elu_dropout_bwd")
+        return dx, None, None, None
+
+
+def dropout_keep_mask(pixels, c, p, seed, device):
+    """The keep decisions of EluDropoutFn for (p, seed) as a bool tensor [pixels, c] (for tests)."""
+    mask = torch.empty((pixels, c), device=device, dtype=torch.uint8)
+    check(lib.vq2_dropout_keep_mask(_p(mask), pixels, c, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
+          "dropout_keep_mask")
+    return mask.bool()
+
+
+class GluResFn(Function):
+    """out = t[..., :ch] * sigmoid(t[..., ch:2ch]) + res (pixelsnail.py:176-177), t with 2 * ch real channels, res and out
+    with ch.  Saves t; the backward recomputes the sigmoid and hands dout on as the gradient of res."""
+
+    @staticmethod
+    def forward(ctx, t, res, ch):
+        t, res = _rows(t, 2 * ch), _rows(res, ch)
+        n, h, w, _ = t.shape
+        if tuple(res.shape[:3]) != (n, h, w):
+            raise RuntimeError("GluResFn: t and res must cover the same pixels")
+        out = torch.empty((n, h, w, ceil4(ch)), device=t.device, dtype=torch.float32)
+        check(lib.vq2_glu_res_fwd(_p(t), ld_of(t), _p(res), ld_of(res), _p(out), ceil4(ch), n * h * w, ch, _stream()),
+              "glu_res_fwd")
+        ctx.save_for_backward(t)
+        ctx.ch = ch
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (t,) = ctx.saved_tensors
+        dout = _rows(dout, ctx.ch)
+        n, h, w, cp = t.shape
+        dt = None
+        if ctx.needs_input_grad[0]:
+            dt = torch.empty((n, h, w, cp), device=t.device, dtype=torch.float32)
+            check(lib.vq2_glu_res_bwd(_p(dout), ld_of(dout), _p(t), ld_of(t), _p(dt), cp, n * h * w, ctx.ch, _stream()),
+                  "glu_res_bwd")
+        return dt, (dout if ctx.needs_input_grad[1] else None), None
 
 
 # ----------------------------------------------------------------------------- Quantize
