@@ -1,0 +1,95 @@
+"""Train a PixelSNAIL prior on extracted codes: the reference's train_pixelsnail.py on one MI355X.
+
+    python examples/train_pixelsnail.py --hier top    [--batch 32 --epoch 420 --lr 3e-4 --sched cycle ...] CODES
+    python examples/train_pixelsnail.py --hier bottom [...] CODES
+
+CODES is what examples/extract_code.py wrote (vqvae2_amd.codes.CodeDataset reads it).  The command line is the
+reference's; `--amp` is accepted only as O0 (this path is fp32).  The reference wraps the model in nn.DataParallel; that is
+not mirrored: this script drives a single GPU.  Every epoch whose number is 1 modulo 10, and the last, saves
+{'model': state_dict, 'args': args} as <ckpt_dir>/pixelsnail_<hier>_<NNN>.pt, the reference's file.
+
+Extra arguments of this script (all default to the reference's fixed values): --size H W of the top codes (the bottom codes
+are twice that), --n_class, --n_block, --kernel_size, --max_steps to stop early, --ckpt_dir, --workers."""
+import argparse
+import os
+import sys
+
+import torch
+from torch.utils.data import DataLoader
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument('--batch', type=int, default=32)
+    parser.add_argument('--epoch', type=int, default=420)
+    parser.add_argument('--hier', type=str, default='top', choices=['top', 'bottom'])
+    parser.add_argument('--lr', type=float, default=3e-4)
+    parser.add_argument('--channel', type=int, default=256)
+    parser.add_argument('--n_res_block', type=int, default=4)
+    parser.add_argument('--n_res_channel', type=int, default=256)
+    parser.add_argument('--n_out_res_block', type=int, default=0)
+    parser.add_argument('--n_cond_res_block', type=int, default=3)
+    parser.add_argument('--dropout', type=float, default=0.1)
+    parser.add_argument('--amp', type=str, default='O0', choices=['O0'])
+    parser.add_argument('--sched', type=str, choices=['cycle'])
+    parser.add_argument('--ckpt', type=str)
+    parser.add_argument('path', type=str)
+    # not in the reference
+    parser.add_argument('--size', type=int, nargs=2, default=[32, 32], metavar=('H', 'W'))
+    parser.add_argument('--n_class', type=int, default=512)
+    parser.add_argument('--n_block', type=int, default=4)
+    parser.add_argument('--kernel_size', type=int, default=5)
+    parser.add_argument('--max_steps', type=int, default=0)
+    parser.add_argument('--ckpt_dir', type=str, default='checkpoint')
+    parser.add_argument('--workers', type=int, default=4)
+    return parser.parse_args(argv)
+
+
+def build_model(args):
+    import vqvae2_amd
+    h, w = args.size
+    if args.hier == 'top':
+        return vqvae2_amd.PixelSNAIL([h, w], args.n_class, args.channel, args.kernel_size, args.n_block, args.n_res_block,
+                                     args.n_res_channel, dropout=args.dropout, n_out_res_block=args.n_out_res_block)
+    return vqvae2_amd.PixelSNAIL([2 * h, 2 * w], args.n_class, args.channel, args.kernel_size, args.n_block, args.n_res_block,
+                                 args.n_res_channel, attention=False, dropout=args.dropout,
+                                 n_cond_res_block=args.n_cond_res_block, cond_res_channel=args.n_res_channel)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    print(args)
+    import vqvae2_amd
+    device = 'cuda'
+    dataset = vqvae2_amd.codes.CodeDataset(args.path)
+    loader = DataLoader(dataset, batch_size=args.batch, shuffle=True, num_workers=args.workers, drop_last=True)
+    ckpt = {}
+    if args.ckpt is not None:
+        ckpt = torch.load(args.ckpt, weights_only=False)
+        args = ckpt['args']
+    model = build_model(args)
+    if 'model' in ckpt:
+        model.load_state_dict(ckpt['model'])
+    model = model.to(device).train()
+    trainer = vqvae2_amd.Stage2Trainer(model, args.hier, lr=args.lr, sched=args.sched, n_iter=len(loader) * args.epoch)
+    os.makedirs(args.ckpt_dir, exist_ok=True)
+    steps = 0
+    for i in range(args.epoch):
+        for top, bottom, _ in loader:
+            r = trainer.step(top.to(device), bottom.to(device) if args.hier == 'bottom' else None)
+            steps += 1
+            print(f"epoch: {i + 1}; loss: {r['loss'].item():.5f}; acc: {r['accuracy'].item():.5f}; lr: {r['lr']:.5f}")
+            if args.max_steps and steps >= args.max_steps:
+                break
+        done = bool(args.max_steps and steps >= args.max_steps)
+        if i % 10 == 0 or i >= args.epoch - 1 or done:
+            torch.save({'model': model.state_dict(), 'args': args},
+                       os.path.join(args.ckpt_dir, f'pixelsnail_{args.hier}_{str(i + 1).zfill(3)}.pt'))
+        if done:
+            break
+
+
+if __name__ == '__main__':
+    main()

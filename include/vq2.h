@@ -48,10 +48,11 @@ typedef void *vq2_stream_t;
  * (vq2_causal_attn_fwd, vq2_causal_attn_bwd, vq2_causal_attn_keep_mask, vq2_weight_norm_fwd, vq2_weight_norm_bwd);
  * revision 9: additions only -- the second conv descriptor vq2_conv_geom with its vq2_convg_* entry points (rectangular
  * kernels, top / left padding) and the ELU / ELU+dropout / GLU+residual kernels of the stage-2 GatedResBlock;
- * see INTEGRATION.md "ABI history").  vq2_version()
+ * revision 10: additions only -- the one-hot convolution, cross-entropy and x2-upsample entry points of the stage-2 prior
+ * (csrc/vq2_prior.hip); see INTEGRATION.md "ABI history").  vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 9
+#define VQ2_API_VERSION 10
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -483,6 +484,51 @@ int vq2_glu_res_fwd(const float *t, int32_t ldt, const float *res, int32_t ldres
                     int32_t Ch, vq2_stream_t stream);
 int vq2_glu_res_bwd(const float *dout, int32_t lddo, const float *t, int32_t ldt, float *dt, int32_t lddt, int64_t pixels,
                     int32_t Ch, vq2_stream_t stream);
+
+/* ------------------------------------------------------------------ the two ends of PixelSNAIL (pixelsnail.py:397-431)
+ * One-hot convolution (pixelsnail.py:401-406, :416-421): y = shift(conv(one_hot(idx), w) + bias) [+ acc] without a one-hot
+ * tensor.  idx [N,H,W] int64 as torch holds it; w [Co, n_class, KH, KW]; the conv reads from (h - pad_top, w - pad_left) on
+ * as in vq2_conv_geom; the result is moved shift_down rows down and shift_right columns right (each 0 or 1), the row / column
+ * that enters is 0 (bias included, as F.pad of the conv output makes it); `acc` (optional, NHWC, pixel stride ldacc) is added
+ * everywhere.  y is NHWC [N,H,W,ldy >= ceil4(Co)], pad lanes 0.  An index outside [0, n_class) contributes nothing and no
+ * address is formed from it (the reference's F.one_hot raises there; this does not).
+ * 1 <= KH, KW <= 7, KH * KW <= 32, 1 <= n_class <= 16384, Co >= 1, N * H * W < 2^31; anything else: VQ2_ERR_INVALID.
+ *   vq2_onehot_pack_weight: w -> wp [KH * KW][n_class][ceil4(Co)] floats (pad lanes 0), the layout the forward reads.
+ *   vq2_onehot_conv_wgrad:  dw [Co, n_class, KH, KW] (dense; exact 0 for classes that do not occur) and, when db is not
+ *       NULL, db [Co] = sum of dy over the pixels that were not shifted in; `ldy` of the descriptor is dy's pixel stride.
+ *       Sums run in double in one fixed order (no atomics): bit-reproducible.  The workspace is needed for db only. */
+typedef struct vq2_onehot_desc {
+    int32_t N, H, W;
+    int32_t Co, n_class;
+    int32_t KH, KW, pad_top, pad_left;
+    int32_t shift_down, shift_right;
+    int32_t ldy; /* pixel stride of y (forward) or dy (weight gradient) */
+} vq2_onehot_desc;
+int vq2_onehot_pack_weight(const float *w, float *wp, int32_t Co, int32_t n_class, int32_t KH, int32_t KW,
+                           vq2_stream_t stream);
+int vq2_onehot_conv_fwd(const vq2_onehot_desc *d, const int64_t *idx, const float *wp, const float *bias, const float *acc,
+                        int32_t ldacc, float *y, vq2_stream_t stream);
+size_t vq2_onehot_conv_wgrad_workspace_bytes(const vq2_onehot_desc *d);
+int vq2_onehot_conv_wgrad(const vq2_onehot_desc *d, const int64_t *idx, const float *dy, float *dw, float *db, void *ws,
+                          size_t ws_bytes, vq2_stream_t stream);
+
+/* Cross-entropy over rows of logits (nn.CrossEntropyLoss and out.max(1), train_pixelsnail.py:39,46-48): logits [M, ld] with
+ * n_class real channels (NHWC rows), target [M] int64.  Per row: stat[2 * row] = max, stat[2 * row + 1] = log(sum exp(l - max))
+ * (kept apart so that the backward forms (l - max) - log_sum as the forward did), row_nll, row_ok = (arg-max == target) with
+ * the LOWEST index winning a tie.  loss[0] = mean of row_nll, accuracy[0] = hits / M, correct[0] = hits, summed in one
+ * fixed order.  A target outside [0, n_class) gives that row no loss term, no hit and no gradient; M still counts it.
+ * vq2_xent_bwd: dlogits = (exp((l - max) - log_sum) - [c == target]) * gout[0] / M, pad lanes 0; gout is a device scalar. */
+int vq2_xent_fwd(const float *logits, int32_t ld, const int64_t *target, int64_t M, int32_t n_class, float *stat,
+                 float *row_nll, int32_t *row_ok, float *loss, float *accuracy, int32_t *correct, vq2_stream_t stream);
+int vq2_xent_bwd(const float *logits, int32_t ld, const int64_t *target, const float *stat, const float *gout, int64_t M,
+                 int32_t n_class, float *dlogits, int32_t lddl, vq2_stream_t stream);
+
+/* Nearest x2 upsample over NHWC (F.interpolate(condition, scale_factor=2), pixelsnail.py:422): x [N,H,W,C] -> y [N,2H,2W,C];
+ * backward dx = ((dy[2h,2w] + dy[2h,2w+1]) + dy[2h+1,2w]) + dy[2h+1,2w+1].  H and W are the SMALL image's in both. */
+int vq2_upsample2_fwd(const float *x, int32_t ldx, float *y, int32_t ldy, int32_t N, int32_t H, int32_t W, int32_t C,
+                      vq2_stream_t stream);
+int vq2_upsample2_bwd(const float *dy, int32_t lddy, float *dx, int32_t lddx, int32_t N, int32_t H, int32_t W, int32_t C,
+                      vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ data-parallel exchange (RCCL over xGMI)
  * One communicator per process (= per GPU), owned by the library -- its only persistent state.  Replaces what

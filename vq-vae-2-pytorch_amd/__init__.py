@@ -7,11 +7,13 @@ from .vqvae import VQVAE, Quantize, ResBlock, Encoder, Decoder, Conv2d, ConvTran
 from . import vqvae_deep  # noqa: F401
 from .vqvae_deep import VQVAE_Deep  # noqa: F401
 from . import pixelsnail  # noqa: F401
-from .pixelsnail import CausalAttention, WNConv2d, CausalConv2d, GatedResBlock  # noqa: F401
+from .pixelsnail import (CausalAttention, WNConv2d, CausalConv2d, GatedResBlock, PixelBlock, CondResNet,  # noqa: F401
+                         PixelSNAIL)
+from .ops import prior_loss  # noqa: F401
 from . import distributed  # noqa: F401
 from . import ops  # noqa: F401
 from . import codes  # noqa: F401
 from .optim import FusedAdam, CycleScheduler  # noqa: F401
-from .train import Stage1Trainer, stage1_loss  # noqa: F401
+from .train import Stage1Trainer, Stage2Trainer, stage1_loss  # noqa: F401
 from .data import ImageNormalizer, ImageDenormalizer, HostBatchPrefetcher, grid_layout, save_u8_image  # noqa: F401
 from .evaluate import Evaluator, perplexity_from_counts, psnr_from_mse_u8  # noqa: F401

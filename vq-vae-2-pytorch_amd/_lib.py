@@ -33,6 +33,12 @@ class WgradJob(C.Structure):
                [(n, C.c_int32) for n in ("O", "I", "Or", "Ir", "taps", "S", "n_units_w", "n_units_b", "swapped", "bias_splits")]
 
 
+class OneHotDesc(C.Structure):
+    """vq2_onehot_desc: the conv over one_hot(idx) with its output shift."""
+    _fields_ = [(n, C.c_int32) for n in
+                ("N", "H", "W", "Co", "n_class", "KH", "KW", "pad_top", "pad_left", "shift_down", "shift_right", "ldy")]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "L", "n_head", "dim_head", "ldq", "ldk", "ldv", "ldo")] + \
                [("p_drop", C.c_float), ("reserved", C.c_int32), ("seed", C.c_uint64)]
@@ -125,6 +131,14 @@ def _load():
         "vq2_dropout_keep_mask": (C.c_int, [P, I64, I32, F, U64, P]),
         "vq2_glu_res_fwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
         "vq2_glu_res_bwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
+        "vq2_onehot_pack_weight": (C.c_int, [P, P, I32, I32, I32, I32, P]),
+        "vq2_onehot_conv_fwd": (C.c_int, [C.POINTER(OneHotDesc), P, P, P, P, I32, P, P]),
+        "vq2_onehot_conv_wgrad_workspace_bytes": (SZ, [C.POINTER(OneHotDesc)]),
+        "vq2_onehot_conv_wgrad": (C.c_int, [C.POINTER(OneHotDesc), P, P, P, P, P, SZ, P]),
+        "vq2_xent_fwd": (C.c_int, [P, I32, P, I64, I32, P, P, P, P, P, P, P]),
+        "vq2_xent_bwd": (C.c_int, [P, I32, P, P, P, I64, I32, P, I32, P]),
+        "vq2_upsample2_fwd": (C.c_int, [P, I32, P, I32, I32, I32, I32, I32, P]),
+        "vq2_upsample2_bwd": (C.c_int, [P, I32, P, I32, I32, I32, I32, I32, P]),
         "vq2_comm_unique_id": (C.c_int, [P]),
         "vq2_comm_init": (C.c_int, [P, I32, I32]),
         "vq2_comm_world": (C.c_int, []),

@@ -13,7 +13,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check, AttnDesc, ConvDesc, ConvGeom, PackJob, WgradJob
+from ._lib import lib, check, AttnDesc, ConvDesc, ConvGeom, OneHotDesc, PackJob, WgradJob
 
 VQ2_RELU_IN = 1
 VQ2_RELU_OUT = 2
@@ -1115,6 +1115,202 @@ class GluResFn(Function):
             check(lib.vq2_glu_res_bwd(_p(dout), ld_of(dout), _p(t), ld_of(t), _p(dt), cp, n * h * w, ctx.ch, _stream()),
                   "glu_res_bwd")
         return dt, (dout if ctx.needs_input_grad[1] else None), None
+
+
+# ----------------------------------------------------------------------------- the two ends of PixelSNAIL (stage-2 prior)
+ONEHOT_MAX_CLASSES = 16384
+
+
+def _require_codes(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64):
+        raise RuntimeError(f"vqvae2_amd: {what} must be an int64 tensor on the MI355X (got "
+                           f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')})")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def onehot_check_geometry(n_class, kh, kw):
+    """What vq2_onehot_conv_* accept: kernel sides in 1..7 with at most 32 taps, 1..16,384 classes."""
+    if not (1 <= kh <= 7 and 1 <= kw <= 7 and kh * kw <= 32):
+        raise NotImplementedError(f"vqvae2_amd one-hot conv: kernel sides in 1..7 with at most 32 taps, got {kh} x {kw}")
+    if not 1 <= n_class <= ONEHOT_MAX_CLASSES:
+        raise NotImplementedError(f"vqvae2_amd: n_class must be in 1..{ONEHOT_MAX_CLASSES}, got {n_class}")
+
+
+def _onehot_desc(n, h, w, cout, n_class, geom, shift, ldy):
+    d = OneHotDesc()
+    d.N, d.H, d.W, d.Co, d.n_class = n, h, w, cout, n_class
+    d.KH, d.KW, d.pad_top, d.pad_left = geom
+    d.shift_down, d.shift_right = shift
+    d.ldy = ldy
+    return d
+
+
+class OneHotConvFn(Function):
+    """shift(conv_at(one_hot(idx), weight, bias, pad_top, pad_left)) [+ acc] over integer codes idx [N,H,W] (pixelsnail.py:
+    401-406): no one-hot tensor, no separate shift or add pass.  weight [Co, n_class, KH, KW] is the effective (already
+    weight-normed) weight; geom = (KH, KW, pad_top, pad_left); shift = (shift_down, shift_right), each 0 or 1 -- the row /
+    column that enters is 0, bias included; acc: an NHWC tensor [N,H,W,ceil4(Co)] added everywhere, or None.  Returns NHWC
+    [N,H,W,ceil4(Co)].  An index outside [0, n_class) contributes nothing (the reference's F.one_hot raises; this does
+    not).  Backward: the dense weight gradient (exact zeros for absent classes), the bias gradient over the pixels that
+    were not shifted in, and dy itself for acc; no gradient for the integer input."""
+
+    @staticmethod
+    def forward(ctx, idx, weight, bias, geom, shift, acc):
+        idx = _require_codes(idx, "codes")
+        _require_cuda(weight, "weight")
+        if idx.dim() != 3 or weight.dim() != 4 or tuple(weight.shape[2:]) != tuple(geom[:2]):
+            raise RuntimeError("OneHotConvFn: codes [N,H,W] and weight [Co, n_class, KH, KW] expected")
+        n, h, w = idx.shape
+        cout, n_class, kh, kw = weight.shape
+        onehot_check_geometry(n_class, kh, kw)
+        wsrc = weight.detach()
+        wsrc = wsrc if wsrc.is_contiguous() else wsrc.contiguous()
+        cp = ceil4(cout)
+        wp = torch.empty(kh * kw * n_class * cp, device=idx.device, dtype=torch.float32)
+        check(lib.vq2_onehot_pack_weight(_p(wsrc), _p(wp), cout, n_class, kh, kw, _stream()), "onehot_pack_weight")
+        if acc is not None:
+            acc = _rows(acc, cout)
+            if tuple(acc.shape[:3]) != (n, h, w):
+                raise RuntimeError("OneHotConvFn: acc must cover the same pixels")
+        y = torch.empty((n, h, w, cp), device=idx.device, dtype=torch.float32)
+        d = _onehot_desc(n, h, w, cout, n_class, geom, shift, cp)
+        check(lib.vq2_onehot_conv_fwd(C.byref(d), _p(idx), _p(wp), _p(bias), _p(acc), ld_of(acc) if acc is not None else 0,
+                                      _p(y), _stream()), "onehot_conv_fwd")
+        ctx.save_for_backward(idx)
+        ctx.geom, ctx.shift, ctx.wshape, ctx.has_bias = tuple(geom), tuple(shift), tuple(weight.shape), bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        n, h, w = idx.shape
+        cout, n_class, kh, kw = ctx.wshape
+        dy = _rows(dy, cout)
+        dw = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            d = _onehot_desc(n, h, w, cout, n_class, ctx.geom, ctx.shift, ld_of(dy))
+            dw = torch.empty(ctx.wshape, device=dy.device, dtype=torch.float32)
+            ws = nbytes = None
+            if ctx.has_bias and ctx.needs_input_grad[2]:
+                db = torch.empty(cout, device=dy.device, dtype=torch.float32)
+                nbytes = lib.vq2_onehot_conv_wgrad_workspace_bytes(C.byref(d))
+                ws = torch.empty(max(nbytes // 8, 1), device=dy.device, dtype=torch.float64)
+            check(lib.vq2_onehot_conv_wgrad(C.byref(d), _p(idx), _p(dy), _p(dw), _p(db), _p(ws), nbytes or 0, _stream()),
+                  "onehot_conv_wgrad")
+        return None, dw, db, None, None, (dy if ctx.needs_input_grad[5] else None)
+
+
+def onehot_conv(idx, weight, bias, geom, shift=(0, 0), acc=None):
+    return OneHotConvFn.apply(idx, weight, bias, tuple(geom), tuple(shift), acc)
+
+
+class Upsample2Fn(Function):
+    """Nearest x2 upsample of an NHWC tensor with `c` real channels (F.interpolate(condition, scale_factor=2),
+    pixelsnail.py:422); backward: the sum of each 2x2 block in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, x, c):
+        x = _rows(x, c)
+        n, h, w, cp = x.shape
+        y = torch.empty((n, 2 * h, 2 * w, cp), device=x.device, dtype=torch.float32)
+        check(lib.vq2_upsample2_fwd(_p(x), ld_of(x), _p(y), cp, n, h, w, c, _stream()), "upsample2_fwd")
+        ctx.c, ctx.shape = c, (n, h, w, cp)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _rows(dy, ctx.c)
+        n, h, w, cp = ctx.shape
+        dx = torch.empty((n, h, w, cp), device=dy.device, dtype=torch.float32)
+        check(lib.vq2_upsample2_bwd(_p(dy), ld_of(dy), _p(dx), cp, n, h, w, ctx.c, _stream()), "upsample2_bwd")
+        return dx, None
+
+
+class CrossEntropyFn(Function):
+    """(mean cross-entropy, accuracy, hit count) of NHWC logits [N,H,W,ceil4(n_class)] against int64 targets [N,H,W]
+    (nn.CrossEntropyLoss and out.max(1), train_pixelsnail.py:39,46-48).  One pass reads each row for the loss, the hit and
+    the two saved row values (maximum, log of the sum of exponentials); the backward writes the gradient from the logits
+    and those.  The lowest index wins an arg-max tie.  A target outside [0, n_class) gives its row no loss term, no hit and
+    no gradient, and still counts in the mean (the reference raises there)."""
+
+    @staticmethod
+    def forward(ctx, x, target, n_class):
+        x = _rows(x, n_class)
+        target = _require_codes(target, "target")
+        n, h, w, _ = x.shape
+        m = n * h * w
+        if target.numel() != m:
+            raise RuntimeError("prior_loss: one target per pixel expected")
+        if not 1 <= n_class <= ONEHOT_MAX_CLASSES:
+            raise NotImplementedError(f"vqvae2_amd: n_class must be in 1..{ONEHOT_MAX_CLASSES}, got {n_class}")
+        dev = x.device
+        stat = torch.empty((m, 2), device=dev, dtype=torch.float32)
+        nll = torch.empty(m, device=dev, dtype=torch.float32)
+        ok = torch.empty(m, device=dev, dtype=torch.int32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        acc = torch.empty((), device=dev, dtype=torch.float32)
+        count = torch.empty((), device=dev, dtype=torch.int32)
+        check(lib.vq2_xent_fwd(_p(x), ld_of(x), _p(target), m, n_class, _p(stat), _p(nll), _p(ok), _p(loss), _p(acc),
+                               _p(count), _stream()), "xent_fwd")
+        ctx.save_for_backward(x, target, stat)
+        ctx.n_class = n_class
+        ctx.mark_non_differentiable(acc, count)
+        return loss, acc, count
+
+    @staticmethod
+    def backward(ctx, g, _gacc, _gcount):
+        x, target, stat = ctx.saved_tensors
+        n, h, w, cp = x.shape
+        _require_cuda(g, "loss gradient")
+        gc = g.reshape(1)
+        gc = gc if gc.is_contiguous() else gc.contiguous()
+        dx = torch.empty((n, h, w, cp), device=x.device, dtype=torch.float32)
+        check(lib.vq2_xent_bwd(_p(x), ld_of(x), _p(target), _p(stat), _p(gc), n * h * w, ctx.n_class, _p(dx), cp, _stream()),
+              "xent_bwd")
+        return dx, None, None
+
+
+def prior_loss(out, target, return_count=False):
+    """(loss, accuracy) of PixelSNAIL's output `out` [B,n_class,H,W] against the codes `target` [B,H,W]: both 0-dim device
+    tensors, the loss differentiable, accuracy = hits / target.numel() (train_pixelsnail.py:39,46-48).  The channels-last
+    view the model returns is read in place.  The lowest class index wins an arg-max tie; 1 <= n_class <= 16,384; a target
+    outside [0, n_class) is skipped as CrossEntropyFn describes."""
+    _require_cuda(out, "out")
+    if out.dim() != 4 or target.dim() != 3 or out.shape[0] != target.shape[0] or tuple(out.shape[2:]) != tuple(target.shape[1:]):
+        raise RuntimeError("prior_loss: out [B,n_class,H,W] and target [B,H,W] expected")
+    loss, acc, count = CrossEntropyFn.apply(to_nhwc(out), target, out.shape[1])
+    return (loss, acc, count) if return_count else (loss, acc)
+
+
+class CatNFn(Function):
+    """torch.cat(parts, channel) of NHWC tensors whose stored widths are multiples of 4 and of which only the LAST may carry
+    pad lanes (PixelBlock's [input, out, background]: 256 + 256 + 2 real channels in 516 stored): one slice copy per part
+    forward, slices of the gradient backward."""
+
+    @staticmethod
+    def forward(ctx, *parts):
+        parts = [as_nhwc(t) for t in parts]
+        n, h, w, _ = parts[0].shape
+        if any(tuple(t.shape[:3]) != (n, h, w) for t in parts):
+            raise RuntimeError("CatNFn: spatial sizes differ")
+        widths = [t.shape[3] for t in parts]
+        total = sum(widths)
+        out = torch.empty((n, h, w, total), device=parts[0].device, dtype=torch.float32)
+        off = 0
+        for t, c in zip(parts, widths):
+            check(lib.vq2_slice_copy(_p(t), ld_of(t), _p(out[..., off:]), total, n * h * w, c, 0, _stream()), "slice_copy")
+            off += c
+        ctx.widths = widths
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = as_nhwc(g)
+        outs, off = [], 0
+        for i, c in enumerate(ctx.widths):
+            outs.append(g[..., off:off + c] if ctx.needs_input_grad[i] else None)
+            off += c
+        return tuple(outs)
 
 
 # ----------------------------------------------------------------------------- Quantize

@@ -1,12 +1,14 @@
-"""Stage-2 prior pieces (drop-in for the reference's pixelsnail.py).  So far: WNConv2d, CausalConv2d and GatedResBlock
-(pixelsnail.py:21-179) and CausalAttention (pixelsnail.py:195-234); PixelBlock and PixelSNAIL are assembled from these in
-later work."""
+"""The stage-2 prior (drop-in for the reference's pixelsnail.py): WNConv2d, CausalConv2d and GatedResBlock
+(pixelsnail.py:21-179), CausalAttention (pixelsnail.py:195-234), and PixelBlock, CondResNet and PixelSNAIL
+(pixelsnail.py:237-431) assembled from them.  Inside a model everything stays NHWC; the integer codes enter through the
+one-hot convolution kernels and the logits leave as a channels-last view."""
 import math
 
 import torch
 from torch import nn
 
 from . import ops
+from ._lib import lib, check
 from .ops import ConvSpec
 
 BQ = ops.ATTN_BQ   # query and key tile lengths of the attention kernels
@@ -67,6 +69,15 @@ class CausalAttention(nn.Module):
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
         o = ops.CausalAttnFn.apply(q, k, v, self.n_head, p, seed)
         return ops.from_nhwc(o, self.channel)
+
+    def nhwc(self, qx, kx):
+        """forward() on NHWC operands [B,H,W,ceil4(Cq)] and [B,H,W,ceil4(Ck)] -> NHWC [B,H,W,channel]: what PixelBlock
+        calls, without the layout round trip at the module boundary."""
+        kx1, kx2 = ops.FanOutFn.apply(kx)        # the key and value projections read one tensor: their gradients meet in a library kernel
+        q, k, v = self.query.nhwc(qx), self.key.nhwc(kx1), self.value.nhwc(kx2)
+        p = self.p if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
+        return ops.CausalAttnFn.apply(q, k, v, self.n_head, p, seed)
 
 
 # ----------------------------------------------------------------------------- weight-normed convs and the gated block
@@ -143,6 +154,15 @@ class WNConv2d(nn.Module):
         y = ops.conv_op(x, w, c.bias, s, residual=residual)
         return ops.EluFn.apply(y, s.cout) if self.elu else y
 
+    def onehot(self, codes, shift=(0, 0), acc=None):
+        """This layer applied to one_hot(codes) (codes int64 [N,H,W], in_channel classes) -> NHWC [N,H,W,ceil4(out)], the
+        result moved shift = (down, right) pixels and `acc` added, all in ops.OneHotConvFn's one launch."""
+        c = self.conv
+        s = self.spec
+        w = ops.WeightNormFn.apply(c.weight_v.view(s.cout, -1), c.weight_g).view(s.cout, s.cin, s.k, s.kw)
+        y = ops.onehot_conv(codes, w, c.bias, (s.k, s.kw, s.pad_top, s.pad_left), shift, acc)
+        return ops.EluFn.apply(y, s.cout) if self.elu else y
+
     def forward(self, input):
         return ops.from_nhwc(self.nhwc(ops.to_nhwc(input)), self.out_channel)
 
@@ -179,6 +199,11 @@ class CausalConv2d(nn.Module):
             # (a parameter edit, not part of the graph: the reference's own statement)
             self.conv.conv.weight_v.data[:, :, -1, self.causal:].zero_()
         return self.conv.nhwc(x, residual)
+
+    def onehot(self, codes, shift=(0, 0), acc=None):
+        if self.padding == 'causal':
+            self.conv.conv.weight_v.data[:, :, -1, self.causal:].zero_()
+        return self.conv.onehot(codes, shift, acc)
 
     def forward(self, input):
         return ops.from_nhwc(self.nhwc(ops.to_nhwc(input)), self.conv.out_channel)
@@ -259,3 +284,194 @@ class GatedResBlock(nn.Module):
         aux = ops.to_nhwc(aux_input) if aux_input is not None else None
         cond = ops.to_nhwc(condition) if condition is not None else None
         return ops.from_nhwc(self.nhwc(x, aux, cond), self.in_channel)
+
+
+# ----------------------------------------------------------------------------- PixelBlock, CondResNet, PixelSNAIL
+def _fan(x, k):
+    """k aliases of x whose gradients are summed by library kernels (chained ops.FanOutFn), not by autograd's own adds."""
+    outs = []
+    for _ in range(k - 1):
+        a, x = ops.FanOutFn.apply(x)
+        outs.append(a)
+    outs.append(x)
+    return outs
+
+
+def _repeat_batch(x1, batch):
+    """NHWC [1,H,W,C] -> [batch,H,W,C], one slice copy per image (the coordinate planes: made once and cached)."""
+    _, h, w, c = x1.shape
+    out = torch.empty((batch, h, w, c), device=x1.device, dtype=torch.float32)
+    for b in range(batch):
+        check(lib.vq2_slice_copy(ops._p(x1), c, ops._p(out[b]), c, h * w, c, 0, ops._stream()), "slice_copy")
+    return out
+
+
+class PixelBlock(nn.Module):
+    """PixelBlock(in_channel, channel, kernel_size, n_res_block, attention=True, dropout=0.1, condition_dim=0) of the
+    reference (pixelsnail.py:237-308): n_res_block 'causal' GatedResBlocks, then either the attention branch (key and query
+    blocks over the concatenations with the two coordinate planes, CausalAttention, and a block that takes the attention
+    output as its auxiliary input) or a 1x1 WNConv2d over [out, background].  in_channel must be a multiple of 4 (the
+    concatenations are slice copies of whole 16-byte groups) and kernel_size odd."""
+
+    def __init__(self, in_channel, channel, kernel_size, n_res_block, attention=True, dropout=0.1, condition_dim=0):
+        super().__init__()
+        if in_channel % 4 != 0:
+            raise NotImplementedError(f"vqvae2_amd.PixelBlock: in_channel must be a multiple of 4, got {in_channel}")
+        if not isinstance(kernel_size, int) or kernel_size % 2 == 0:
+            raise NotImplementedError(f"vqvae2_amd.PixelBlock: kernel_size must be an odd int, got {kernel_size} (the "
+                                      "reference's 'causal' blocks change the width with an even one)")
+        if attention:
+            ops.attn_check_geometry(in_channel // 2, 8)
+        self.in_channel = in_channel
+        self.resblocks = nn.ModuleList([
+            GatedResBlock(in_channel, channel, kernel_size, conv='causal', dropout=dropout, condition_dim=condition_dim)
+            for _ in range(n_res_block)])
+        self.attention = attention
+        if attention:
+            self.key_resblock = GatedResBlock(in_channel * 2 + 2, in_channel, 1, dropout=dropout)
+            self.query_resblock = GatedResBlock(in_channel + 2, in_channel, 1, dropout=dropout)
+            self.causal_attention = CausalAttention(in_channel + 2, in_channel * 2 + 2, in_channel // 2, dropout=dropout)
+            self.out_resblock = GatedResBlock(in_channel, in_channel, 1, auxiliary_channel=in_channel // 2, dropout=dropout)
+        else:
+            self.out = WNConv2d(in_channel + 2, in_channel, 1)
+
+    def nhwc(self, x, background, conditions=None):
+        """x [N,H,W,in_channel], background [N,H,W,4] (two real channels); conditions: None or one NHWC alias of the
+        condition per res block."""
+        if self.attention:
+            x, x_key = ops.FanOutFn.apply(x)
+        out = x
+        for i, resblock in enumerate(self.resblocks):
+            out = resblock.nhwc(out, condition=None if conditions is None else conditions[i])
+        if self.attention:
+            out_key, out_query, out = _fan(out, 3)
+            key = self.key_resblock.nhwc(ops.CatNFn.apply(x_key, out_key, background))
+            query = self.query_resblock.nhwc(ops.CatNFn.apply(out_query, background))
+            attn_out = self.causal_attention.nhwc(query, key)
+            return self.out_resblock.nhwc(out, aux=attn_out)
+        return self.out.nhwc(ops.CatNFn.apply(out, background))
+
+    def forward(self, input, background, condition=None):
+        cond = None
+        if condition is not None:
+            cond = _fan(ops.to_nhwc(condition), len(self.resblocks)) if len(self.resblocks) else None
+        return ops.from_nhwc(self.nhwc(ops.to_nhwc(input), ops.to_nhwc(background), cond), self.in_channel)
+
+
+class CondResNet(nn.Module):
+    """CondResNet(in_channel, channel, kernel_size, n_res_block) of the reference (pixelsnail.py:311-323): a size-preserving
+    WNConv2d and n_res_block plain GatedResBlocks.  forward takes what the reference takes (a float [B,in_channel,H,W]
+    tensor, one-hot there) or the int64 codes [B,H,W] themselves, which go through the one-hot convolution kernel."""
+
+    def __init__(self, in_channel, channel, kernel_size, n_res_block):
+        super().__init__()
+        if not isinstance(kernel_size, int) or kernel_size % 2 == 0:
+            raise NotImplementedError(f"vqvae2_amd.CondResNet: kernel_size must be an odd int, got {kernel_size}")
+        self.channel = channel
+        blocks = [WNConv2d(in_channel, channel, kernel_size, padding=kernel_size // 2)]
+        for _ in range(n_res_block):
+            blocks.append(GatedResBlock(channel, channel, kernel_size))
+        self.blocks = nn.Sequential(*blocks)
+
+    def nhwc(self, input):
+        first = self.blocks[0]
+        x = first.onehot(input) if input.dtype == torch.int64 else first.nhwc(ops.to_nhwc(input))
+        for block in list(self.blocks)[1:]:
+            x = block.nhwc(x)
+        return x
+
+    def forward(self, input):
+        return ops.from_nhwc(self.nhwc(input), self.channel)
+
+
+class PixelSNAIL(nn.Module):
+    """PixelSNAIL(shape, n_class, channel, kernel_size, n_block, n_res_block, res_channel, attention=True, dropout=0.1,
+    n_cond_res_block=0, cond_res_channel=0, cond_res_kernel=3, n_out_res_block=0) of the reference (pixelsnail.py:326-431),
+    with its parameter and buffer names.
+
+    forward(input [B,H,W] int64, condition=None [B,H/2,W/2] int64, cache=None) -> (out, cache): out is a channels-last view
+    of shape [B,n_class,H,W] (a copy when n_class is no multiple of 4); cache['condition'] is a detached clone of the
+    upsampled condition features and is used instead of running cond_resnet when present; an input of fewer rows than
+    shape[0] uses the first rows of the coordinate planes and of the condition.  A code outside [0, n_class) contributes
+    nothing (the reference raises).  Refused at construction: channel % 4 != 0, an even kernel_size or cond_res_kernel,
+    and with attention a channel whose half the 8-head attention kernels do not take."""
+
+    def __init__(self, shape, n_class, channel, kernel_size, n_block, n_res_block, res_channel, attention=True,
+                 dropout=0.1, n_cond_res_block=0, cond_res_channel=0, cond_res_kernel=3, n_out_res_block=0):
+        super().__init__()
+        height, width = shape
+        if channel % 4 != 0:
+            raise NotImplementedError(f"vqvae2_amd.PixelSNAIL: channel must be a multiple of 4, got {channel}")
+        if not isinstance(kernel_size, int) or kernel_size % 2 == 0:
+            raise NotImplementedError(f"vqvae2_amd.PixelSNAIL: kernel_size must be an odd int, got {kernel_size} (the "
+                                      "reference's 'causal' blocks change the width with an even one)")
+        if not isinstance(cond_res_kernel, int) or cond_res_kernel % 2 == 0:
+            raise NotImplementedError(f"vqvae2_amd.PixelSNAIL: cond_res_kernel must be an odd int, got {cond_res_kernel}")
+        if attention:
+            ops.attn_check_geometry(channel // 2, 8)
+        kernel = kernel_size
+        ops.onehot_check_geometry(n_class, (kernel + 1) // 2, kernel)
+        self.n_class = n_class
+        self.channel = channel
+        self.cond_res_channel = cond_res_channel
+        self.horizontal = CausalConv2d(n_class, channel, [kernel // 2, kernel], padding='down')
+        self.vertical = CausalConv2d(n_class, channel, [(kernel + 1) // 2, kernel // 2], padding='downright')
+        coord_x = (torch.arange(height).float() - height / 2) / height
+        coord_x = coord_x.view(1, 1, height, 1).expand(1, 1, height, width)
+        coord_y = (torch.arange(width).float() - width / 2) / width
+        coord_y = coord_y.view(1, 1, 1, width).expand(1, 1, height, width)
+        self.register_buffer('background', torch.cat([coord_x, coord_y], 1))
+        self.blocks = nn.ModuleList([
+            PixelBlock(channel, res_channel, kernel_size, n_res_block, attention=attention, dropout=dropout,
+                       condition_dim=cond_res_channel) for _ in range(n_block)])
+        if n_cond_res_block > 0:
+            self.cond_resnet = CondResNet(n_class, cond_res_channel, cond_res_kernel, n_cond_res_block)
+        out = [GatedResBlock(channel, res_channel, 1) for _ in range(n_out_res_block)]
+        out.extend([nn.ELU(inplace=True), WNConv2d(channel, n_class, 1)])
+        self.out = nn.Sequential(*out)
+        self._bg = None      # (key, NHWC coordinate planes repeated over the batch)
+
+    def _background(self, batch, height):
+        bg = self.background
+        key = (batch, height, bg.data_ptr(), bg._version)
+        if self._bg is None or self._bg[0] != key:
+            planes = ops.to_nhwc(bg[:, :, :height, :].contiguous())            # [1, height, W, 4], two real channels
+            self._bg = (key, _repeat_batch(planes, batch))
+        return self._bg[1]
+
+    def forward(self, input, condition=None, cache=None):
+        if cache is None:
+            cache = {}
+        if input.dim() != 3:
+            raise RuntimeError("PixelSNAIL: input [B,H,W] of int64 codes expected")
+        batch, height, width = input.shape
+        if height > self.background.shape[2] or width != self.background.shape[3]:
+            raise RuntimeError(f"PixelSNAIL: input of {height} x {width} does not fit shape "
+                               f"{tuple(self.background.shape[2:])} (fewer rows are allowed, other widths are not)")
+        horizontal = self.horizontal.onehot(input, shift=(1, 0))                # shift_down(horizontal(one_hot))
+        out = self.vertical.onehot(input, shift=(0, 1), acc=horizontal)         # + shift_right(vertical(one_hot))
+        background = self._background(batch, height)
+        conditions = None
+        if condition is not None:
+            if 'condition' in cache:
+                cond = ops.to_nhwc(cache['condition'])
+            else:
+                # (through the module's __call__, so that forward hooks see it; the NCHW-shaped view comes back without a copy)
+                cond = ops.Upsample2Fn.apply(ops.to_nhwc(self.cond_resnet(condition)), self.cond_res_channel)
+                cache['condition'] = ops.from_nhwc(cond, self.cond_res_channel).detach().clone()
+            if height < cond.shape[1]:
+                cond = cond[:, :height]
+            n_use = sum(len(b.resblocks) for b in self.blocks)
+            conditions = _fan(cond, n_use) if n_use else None
+        for block in self.blocks:
+            n = len(block.resblocks)
+            mine = None
+            if conditions is not None:
+                mine, conditions = conditions[:n], conditions[n:]
+            out = block.nhwc(out, background, mine)
+        for layer in self.out:
+            if isinstance(layer, nn.ELU):
+                out = ops.EluFn.apply(out, self.channel)       # nn.ELU(inplace=True) of the reference
+            else:
+                out = layer.nhwc(out)
+        return ops.from_nhwc(out, self.n_class), cache

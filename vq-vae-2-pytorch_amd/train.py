@@ -313,3 +313,36 @@ class Stage1Trainer:
             if self.scheduler is not None:
                 self.scheduler.load_state_dict(sd["scheduler"])
         self.pack_plan.run()
+
+
+class Stage2Trainer:
+    """The train step of the reference's train_pixelsnail.py:20-57 for one PixelSNAIL on one GPU: zero_grad, forward,
+    cross-entropy with accuracy (ops.prior_loss), backward, scheduler step, Adam step (FusedAdam, one launch per
+    parameter).  `hier` is 'top' (the model sees the top codes) or 'bottom' (the bottom codes, conditioned on the top
+    ones).  step() returns {'loss', 'accuracy'} as 0-dim device tensors and 'lr'; nothing is copied to the host."""
+
+    def __init__(self, model, hier="top", lr=3e-4, sched=None, n_iter=None):
+        if hier not in ("top", "bottom"):
+            raise ValueError(f"Stage2Trainer: hier must be 'top' or 'bottom', got {hier!r}")
+        self.model, self.hier = model, hier
+        self.optimizer = FusedAdam(model.parameters(), lr=lr)
+        self.scheduler = None
+        if sched == "cycle":
+            self.scheduler = CycleScheduler(self.optimizer, lr, n_iter=n_iter, momentum=None)
+        elif sched is not None:
+            raise ValueError(f"Stage2Trainer: sched must be None or 'cycle', got {sched!r}")
+
+    def step(self, top, bottom=None):
+        self.model.zero_grad(set_to_none=True)
+        if self.hier == "top":
+            target = top
+            out, _ = self.model(top)
+        else:
+            target = bottom
+            out, _ = self.model(bottom, condition=top)
+        loss, accuracy = ops.prior_loss(out, target)
+        loss.backward()
+        if self.scheduler is not None:
+            self.scheduler.step()
+        self.optimizer.step()
+        return {"loss": loss.detach(), "accuracy": accuracy, "lr": self.optimizer.param_groups[0]["lr"]}
