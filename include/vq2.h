@@ -49,10 +49,12 @@ typedef void *vq2_stream_t;
  * revision 9: additions only -- the second conv descriptor vq2_conv_geom with its vq2_convg_* entry points (rectangular
  * kernels, top / left padding) and the ELU / ELU+dropout / GLU+residual kernels of the stage-2 GatedResBlock;
  * revision 10: additions only -- the one-hot convolution, cross-entropy and x2-upsample entry points of the stage-2 prior
- * (csrc/vq2_prior.hip); see INTEGRATION.md "ABI history").  vq2_version()
+ * (csrc/vq2_prior.hip); revision 11: additions only -- the row-incremental sampling entry points (vq2_convg_fwd_row with its
+ * workspace query, vq2_causal_attn_fwd_rows, vq2_sample_categorical, vq2_sample_uniforms); see INTEGRATION.md "ABI history").
+ * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 10
+#define VQ2_API_VERSION 11
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -529,6 +531,47 @@ int vq2_upsample2_fwd(const float *x, int32_t ldx, float *y, int32_t ldy, int32_
                       vq2_stream_t stream);
 int vq2_upsample2_bwd(const float *dy, int32_t lddy, float *dx, int32_t lddx, int32_t N, int32_t H, int32_t W, int32_t C,
                       vq2_stream_t stream);
+
+/* ------------------------------------------------------------------ sampling from the prior, one image row at a time
+ * The reference's sample_model (sample.py:17-29) runs the whole model on rows 0..i for every pixel (i, j).  Every layer is
+ * causal in raster order, so a sampler keeps what earlier rows produced and computes row i only; the two layer kinds that
+ * look at earlier rows get entry points that read a history in place, and the draw is one launch.
+ *
+ * vq2_convg_fwd_row: output row `row` of what vq2_convg_fwd computes for the same descriptor (d->H is the number of rows
+ *              the image has; 0 <= row < H; pad_top == KH - 1 is required, else VQ2_ERR_INVALID).  Input pixel (n, r, w) is at
+ *              x + n * x_image_stride + r * x_row_stride + w * ldx (strides in elements, multiples of 4); rows r < 0 read as
+ *              0, rows > row are never read.  y and residual are dense [N, W, ldy] / [N, W, ldres] single rows.  wp is the
+ *              VQ2_PACK_FWD panel; bias, VQ2_RELU_IN / VQ2_RELU_OUT, the residual and the Cir / Cor padding are those of
+ *              vq2_convg_fwd.  VQ2_ROW_CAUSAL_TAPS: the caller states that the weight is 0 at the taps a 'causal' layer
+ *              zeroes (last kernel row, columns KW / 2 .. KW - 1) and those taps are skipped.  K is split over taps: one
+ *              [N * W, Co] slab per split in `ws` (>= vq2_convg_fwd_row_workspace_bytes(d, flags), 16-byte aligned), then the
+ *              slabs are added in ascending order with the epilogue.  fp32-input MFMA, fp32 accumulation, no atomics:
+ *              bit-reproducible.  The sums run in another order than vq2_convg_fwd's, so the two agree to rounding only.
+ * vq2_causal_attn_fwd_rows: vq2_causal_attn_fwd for the queries at raster positions q0 .. q0 + nq - 1 (q0 + nq <= d->L).
+ *              q and o are dense [B, nq, ldq / ldo]; the key or value at position p of image b is at
+ *              base + b * kv_image_stride + (p / W) * kv_row_stride + (p % W) * ldk (ldv); positions < q0 + nq - 1 are read, the last
+ *              query's own position and later ones never (they may be unwritten).
+ *              Masking, scaling and the exact-zero output of position 0 are those of vq2_causal_attn_fwd, and every query
+ *              gets the bits that function gives it.  p_drop must be 0 (VQ2_ERR_INVALID otherwise); there is no lse.
+ * vq2_sample_categorical: for each of M rows of logits (row r at logits + r * row_stride, n_class values read, pad lanes
+ *              never): u = (w0 >> 8) * 2^-24 with w0 = word 0 of Philox4x32 (7 rounds) at counter (low and high half of
+ *              `position`, r, 0) and the 64-bit seed as key; e_k = exp(l_k / temperature - max), summed in one fixed order
+ *              (64 contiguous chunks, then a scan over the chunks); the drawn class is the smallest c whose running sum
+ *              e_0 + .. + e_c exceeds u * sum (the rule cumsum(softmax) > u, scaled by the sum), or n_class - 1 if rounding
+ *              leaves none.  Written as int64 to out[r * out_stride].  temperature <= 0 or n_class outside 1..16384:
+ *              VQ2_ERR_INVALID.
+ * vq2_sample_uniforms: those u values, u[r] for r < M -- the only way to check the draw against a reference. */
+#define VQ2_ROW_CAUSAL_TAPS 8
+size_t vq2_convg_fwd_row_workspace_bytes(const vq2_conv_geom *d, int flags);
+int vq2_convg_fwd_row(const vq2_conv_geom *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
+                      const float *x, const float *wp, const float *bias, const float *residual, int32_t ldres, float *y,
+                      void *ws, size_t ws_bytes, vq2_stream_t stream);
+int vq2_causal_attn_fwd_rows(const vq2_attn_desc *d, int32_t q0, int32_t nq, int32_t W, int64_t kv_image_stride,
+                             int64_t kv_row_stride, const float *q, const float *k, const float *v, float *o,
+                             vq2_stream_t stream);
+int vq2_sample_categorical(const float *logits, int64_t row_stride, int32_t M, int32_t n_class, float temperature,
+                           uint64_t seed, uint64_t position, int64_t *out, int64_t out_stride, vq2_stream_t stream);
+int vq2_sample_uniforms(float *u, int32_t M, uint64_t seed, uint64_t position, vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ data-parallel exchange (RCCL over xGMI)
  * One communicator per process (= per GPU), owned by the library -- its only persistent state.  Replaces what

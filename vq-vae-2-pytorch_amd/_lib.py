@@ -139,6 +139,11 @@ def _load():
         "vq2_xent_bwd": (C.c_int, [P, I32, P, P, P, I64, I32, P, I32, P]),
         "vq2_upsample2_fwd": (C.c_int, [P, I32, P, I32, I32, I32, I32, I32, P]),
         "vq2_upsample2_bwd": (C.c_int, [P, I32, P, I32, I32, I32, I32, I32, P]),
+        "vq2_convg_fwd_row_workspace_bytes": (SZ, [GP, C.c_int]),
+        "vq2_convg_fwd_row": (C.c_int, [GP, I32, I64, I64, C.c_int, P, P, P, P, I32, P, P, SZ, P]),
+        "vq2_causal_attn_fwd_rows": (C.c_int, [C.POINTER(AttnDesc), I32, I32, I32, I64, I64, P, P, P, P, P]),
+        "vq2_sample_categorical": (C.c_int, [P, I64, I32, I32, F, U64, U64, P, I64, P]),
+        "vq2_sample_uniforms": (C.c_int, [P, I32, U64, U64, P]),
         "vq2_comm_unique_id": (C.c_int, [P]),
         "vq2_comm_init": (C.c_int, [P, I32, I32]),
         "vq2_comm_world": (C.c_int, []),

@@ -208,6 +208,106 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams P, const float
     if (g == 0 && i < L) lse[((size_t)b * P.nh + h) * L + i] = lsum > 0.f ? m + log2f(lsum) : 0.f;   // base-2 log-sum-exp
 }
 
+// ---------------------------------------------------------------- a window of queries over keys kept by image row
+// The forward loop for the queries at raster positions q0 .. q0 + nq - 1 only (the sampler's current row, vq2.h
+// vq2_causal_attn_fwd_rows): q and o are dense [B, nq, ld], the key / value at position p lives at image row p / W of a
+// buffer with its own image and row strides, so that a history of rows in any layout is read in place.  Key blocks start
+// at multiples of AT_BK from position 0 as in attn_fwd_kernel and each query's statistics are its own lane's, so a query
+// gets bit for bit what the full-sequence kernel gives it.  No dropout, no log-sum-exp.
+struct AttnRows {
+    int q0, nq, W;
+    long long kv_image_stride, kv_row_stride;
+};
+
+// positions [r0, r0 + 64) of one head -> LDS tile [64][DP + 4]; positions >= Lk and channels >= dh read as 0
+template <int DP>
+__device__ __forceinline__ void stage_tile_rows(float *tile, const float *base, int ld, int r0, int Lk, int dh, int W,
+                                                long long row_stride) {
+    constexpr int LDR = DP + 4, V4 = DP / 4;
+    for (int idx = threadIdx.x; idx < 64 * V4; idx += 256) {
+        const int r = idx / V4, c = (idx - r * V4) * 4;
+        const int p = r0 + r;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p < Lk && c < dh) {
+            const int pr = p / W, pc = p - pr * W;
+            v = *reinterpret_cast<const float4 *>(base + (long long)pr * row_stride + (long long)pc * ld + c);
+        }
+        *reinterpret_cast<float4 *>(tile + r * LDR + c) = v;
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void attn_fwd_rows_kernel(AttnParams P, AttnRows R, const float *__restrict__ q,
+                                                            const float *__restrict__ k, const float *__restrict__ v,
+                                                            float *__restrict__ o) {
+    constexpr int DP = 16 * DT, LDR = DP + 4;
+    __shared__ __attribute__((aligned(16))) float Ks[AT_BK * LDR];
+    __shared__ __attribute__((aligned(16))) float Vs[AT_BK * LDR];
+    const int qt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
+    const int dh = P.dh, nq = R.nq;
+    const int lq = qt * AT_BQ + wave * 16 + col;        // index inside the window
+    const int iw0 = R.q0 + qt * AT_BQ + wave * 16, i = iw0 + col;   // raster positions
+    const int Lk = R.q0 + nq - 1;                       // the last query's own position and everything past it is visible to no query: never read
+    const float *kb_ = k + (long long)b * R.kv_image_stride + h * dh;
+    const float *vb = v + (long long)b * R.kv_image_stride + h * dh;
+    float4 qf[DT];
+    load_frag<DT>(qf, q + (size_t)b * nq * P.ldq + h * dh, P.ldq, lq, nq, dh, g);
+    f32x4 oacc[DT];
+#pragma unroll
+    for (int t = 0; t < DT; ++t) oacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, lsum = 0.f;
+    const int imax = R.q0 + min(nq - 1, qt * AT_BQ + AT_BQ - 1);
+    const int nkb = imax >= 1 ? (imax - 1) / AT_BK + 1 : 0;
+    for (int kb = 0; kb < nkb; ++kb) {
+        __syncthreads();
+        stage_tile_rows<DP>(Ks, kb_, P.ldk, kb * AT_BK, Lk, dh, R.W, R.kv_row_stride);
+        stage_tile_rows<DP>(Vs, vb, P.ldv, kb * AT_BK, Lk, dh, R.W, R.kv_row_stride);
+        __syncthreads();
+        const int j0 = kb * AT_BK;
+        if (j0 >= iw0 + 15) continue;   // wave-uniform: none of this wave's queries sees this block
+        f32x4 s[4];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            if (j0 + 16 * kt >= iw0 + 15) { s[kt] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY}; continue; }
+            s[kt] = dot_tile<DT>(Ks, kt, qf, col, g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = j0 + 16 * kt + 4 * g + r;
+                s[kt][r] = j < i ? s[kt][r] * P.scale2 : -INFINITY;
+                mx = fmaxf(mx, s[kt][r]);
+            }
+        }
+        mx = group_max(mx);
+        const float m_new = fmaxf(m, mx);
+        const float m_use = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = exp2_fast(m - m_use);
+        m = m_new;
+        lsum *= alpha;
+#pragma unroll
+        for (int t = 0; t < DT; ++t) oacc[t] *= alpha;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            if (j0 + 16 * kt >= iw0 + 15) continue;
+            f32x4 p;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { p[r] = exp2_fast(s[kt][r] - m_use); lsum += p[r]; }
+            accum_tile<DT>(oacc, Vs, kt, p, col, g);
+        }
+    }
+    lsum = group_sum(lsum);
+    float *ob = o + (size_t)b * nq * P.ldo + h * dh;
+#pragma unroll
+    for (int t = 0; t < DT; ++t) {
+        const int d = 16 * t + 4 * g;
+        if (lq < nq && d < dh)
+            *reinterpret_cast<float4 *>(ob + (size_t)lq * P.ldo + d) =
+                lsum > 0.f ? make_float4(oacc[t][0] / lsum, oacc[t][1] / lsum, oacc[t][2] / lsum, oacc[t][3] / lsum)
+                           : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
 // delta[b][h][i] = sum_j P_ij dP_ij (with dropout: of the kept, rescaled dP), the row term D_i of the softmax backward
 // dS = P (dP - D).  In exact arithmetic D_i = sum_d dO_id O_id, and that form needs no pass over the keys; but it is
 // rounded independently of dP, and where a row sees only a few keys dP - D cancels: at L = 3 the dK error came out at 5.4 x
@@ -466,6 +566,25 @@ extern "C" int vq2_causal_attn_fwd(const vq2_attn_desc *d, const float *q, const
     const dim3 grid((P.L + AT_BQ - 1) / AT_BQ, P.nh, P.B);
     ATTN_BY_DT(P.dh, hipLaunchKernelGGL((attn_fwd_kernel<DT>), grid, dim3(256), 0, vq2::to_stream(stream), P, q, k, v, o, lse));
     return vq2::check_launch("attn_fwd_kernel");
+}
+
+extern "C" int vq2_causal_attn_fwd_rows(const vq2_attn_desc *d, int32_t q0, int32_t nq, int32_t W, int64_t kv_image_stride,
+                                        int64_t kv_row_stride, const float *q, const float *k, const float *v, float *o,
+                                        vq2_stream_t stream) {
+    AttnParams P;
+    if (int e = fill_params(d, P, "causal_attn_fwd_rows")) return e;
+    VQ2_REQUIRE(!P.dropout, "causal_attn_fwd_rows: p_drop must be 0");
+    VQ2_REQUIRE(q && k && v && o, "causal_attn_fwd_rows: null pointer");
+    VQ2_REQUIRE(vq2::aligned16(q) && vq2::aligned16(k) && vq2::aligned16(v) && vq2::aligned16(o),
+                "causal_attn_fwd_rows: pointers must be 16-byte aligned");
+    VQ2_REQUIRE(q0 >= 0 && nq >= 1 && W >= 1 && (int64_t)q0 + nq <= (int64_t)d->L,
+                "causal_attn_fwd_rows: the window q0=%d, nq=%d must lie inside the L=%d positions", q0, nq, d->L);
+    VQ2_REQUIRE(kv_image_stride % 4 == 0 && kv_row_stride % 4 == 0 && kv_image_stride >= 0 && kv_row_stride >= 0,
+                "causal_attn_fwd_rows: key / value strides must be non-negative multiples of 4");
+    const AttnRows R{q0, nq, W, (long long)kv_image_stride, (long long)kv_row_stride};
+    const dim3 grid((nq + AT_BQ - 1) / AT_BQ, P.nh, P.B);
+    ATTN_BY_DT(P.dh, hipLaunchKernelGGL((attn_fwd_rows_kernel<DT>), grid, dim3(256), 0, vq2::to_stream(stream), P, R, q, k, v, o));
+    return vq2::check_launch("attn_fwd_rows_kernel");
 }
 
 extern "C" int vq2_causal_attn_bwd(const vq2_attn_desc *d, const float *q, const float *k, const float *v,

@@ -1,0 +1,288 @@
+// Sampling from the stage-2 prior one image row at a time (the reference's sample.py:17-29 evaluates the whole model on
+// rows 0..i for every pixel; every layer is causal in raster order, so only row i is new).
+//
+//   row convolution    output row `row` of a causal conv (pad_top == KH - 1) from input rows kept in a history with its own
+//                      image and row strides.  The GEMM is small in M (N * W pixels) and long in K (KH * KW * Ci), so K is
+//                      split over taps: convg_row_partial_kernel writes one [M][Co] slab per split, convg_row_reduce_kernel
+//                      adds the slabs in ascending order and applies the epilogue of vq2_convg_fwd.  No atomics: two runs
+//                      give the same bits.  v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation) with the
+//                      weight panel rows on the A side and the pixels on the B side: a lane then holds 4 consecutive output
+//                      channels of one pixel and stores 16 bytes.  Both operands come straight from global memory as float4
+//                      reads of 4 consecutive input channels (k step s of an MFMA quadruple takes channel 4 * g + s from
+//                      both sides, as in vq2_attn.hip); the four waves of a workgroup share the panel rows through the
+//                      vector cache and differ in their 32 pixels.  It reads the VQ2_PACK_FWD panel [Co][tap][Ci].
+//   categorical draw   one wave per row of logits: maximum, sum of exponentials over lane-contiguous chunks, a fixed-order
+//                      scan over the lanes, then every lane walks its chunk for the first class whose running sum passes
+//                      u * sum; the lowest such lane wins.  u comes from Philox4x32-7 keyed by (seed, position, row).
+#include "vq2_conv.h"
+#include "vq2_philox.h"
+
+namespace {
+
+using vq2::philox4x32_7;
+
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+constexpr int RC_BM = 128;   // pixels per workgroup: 4 waves x 32
+constexpr int RC_BN = 64;    // output channels per workgroup (every wave computes all of them)
+
+struct RowConv {
+    const float *x, *w;
+    float *ws;
+    long long x_image_stride, x_row_stride;
+    int W, Ci, Co, KH, KW, pad_left, ldx, row, M, K;
+    int relu_in;
+    unsigned tap_mask;   // bit t: tap t = kh * KW + kw is computed
+    int tps;             // active taps per split
+};
+
+// which taps are computed and how they are cut into splits: a function of the shape and the flags alone
+struct RowPlan { unsigned mask; int ntaps, tps, splits; };
+static RowPlan row_plan(const vq2_conv_geom *d, int flags) {
+    RowPlan p{0u, 0, 1, 1};
+    for (int kh = 0; kh < d->KH; ++kh)
+        for (int kw = 0; kw < d->KW; ++kw) {
+            if ((flags & VQ2_ROW_CAUSAL_TAPS) && kh == d->KH - 1 && kw >= d->KW / 2) continue;
+            p.mask |= 1u << (kh * d->KW + kw);
+            ++p.ntaps;
+        }
+    if (p.ntaps == 0) return p;   // a 1 x 1 'causal' kernel: nothing but the bias
+    const long tiles = (((long)d->N * d->W + RC_BM - 1) / RC_BM) * ((d->Co + RC_BN - 1) / RC_BN);
+    long want = (512 + tiles - 1) / tiles;          // about two workgroups per compute unit
+    if (want > p.ntaps) want = p.ntaps;
+    p.tps = (int)((p.ntaps + want - 1) / want);
+    p.splits = (p.ntaps + p.tps - 1) / p.tps;
+    return p;
+}
+
+__global__ __launch_bounds__(256) void convg_row_partial_kernel(const RowConv P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
+    const int m0 = blockIdx.x * RC_BM + wave * 32, co0 = blockIdx.y * RC_BN, split = blockIdx.z;
+    int pn[2], pw[2], pp[2];
+    bool pv[2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        pp[mt] = m0 + 16 * mt + col;
+        pv[mt] = pp[mt] < P.M;
+        pn[mt] = pp[mt] / P.W;
+        pw[mt] = pp[mt] - pn[mt] * P.W;
+    }
+    const float *wrow[4];
+    bool wv[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int co = co0 + 16 * nt + col;
+        wv[nt] = co < P.Co;
+        wrow[nt] = P.w + (size_t)(wv[nt] ? co : 0) * P.K;
+    }
+    f32x4 acc[4][2];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) acc[nt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int t0 = split * P.tps, t1 = t0 + P.tps;
+    const int T = P.KH * P.KW;
+    int active = 0;
+    for (int tap = 0; tap < T; ++tap) {
+        if (!((P.tap_mask >> tap) & 1u)) continue;
+        const int ai = active++;
+        if (ai < t0 || ai >= t1) continue;
+        const int kh = tap / P.KW, kw = tap - kh * P.KW;
+        const int r = P.row - (P.KH - 1) + kh;
+        if (r < 0) continue;                                   // above the image: zeros (workgroup-uniform)
+        const float *xp[2];
+        bool xv[2];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const int wi = pw[mt] - P.pad_left + kw;
+            xv[mt] = pv[mt] && wi >= 0 && wi < P.W;
+            xp[mt] = P.x + (xv[mt] ? (long long)pn[mt] * P.x_image_stride + (long long)r * P.x_row_stride + (long long)wi * P.ldx : 0ll);
+        }
+        const int koff = tap * P.Ci;
+        for (int c0 = 0; c0 < P.Ci; c0 += 16) {
+            const int c = c0 + 4 * g;
+            const bool cv = c < P.Ci;
+            float4 a[4], b[2];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+                a[nt] = (wv[nt] && cv) ? *reinterpret_cast<const float4 *>(wrow[nt] + koff + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                b[mt] = (xv[mt] && cv) ? *reinterpret_cast<const float4 *>(xp[mt] + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (P.relu_in) b[mt] = vq2::relu4(b[mt]);
+            }
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    acc[nt][mt] = mfma4(a[nt].x, b[mt].x, acc[nt][mt]);
+                    acc[nt][mt] = mfma4(a[nt].y, b[mt].y, acc[nt][mt]);
+                    acc[nt][mt] = mfma4(a[nt].z, b[mt].z, acc[nt][mt]);
+                    acc[nt][mt] = mfma4(a[nt].w, b[mt].w, acc[nt][mt]);
+                }
+        }
+    }
+    // accumulator register r of lane (col, g) is output channel 16 * nt + 4 * g + r of pixel col
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        if (!pv[mt]) continue;
+        float *dst = P.ws + ((size_t)split * P.M + pp[mt]) * P.Co;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const int co = co0 + 16 * nt + 4 * g;
+            if (co < P.Co)
+                *reinterpret_cast<float4 *>(dst + co) = make_float4(acc[nt][mt][0], acc[nt][mt][1], acc[nt][mt][2], acc[nt][mt][3]);
+        }
+    }
+}
+
+// y = [relu](((slab 0 + slab 1) + ...) + bias [+ residual]), pad lanes Cor .. Co - 1 written as 0
+__global__ __launch_bounds__(256) void convg_row_reduce_kernel(const float *__restrict__ ws, int splits, int M, int Co, int Cor,
+                                                               const float *__restrict__ bias, const float *__restrict__ res,
+                                                               int ldres, float *__restrict__ y, int ldy, int relu_out) {
+    const int G = Co / 4;
+    const long total = (long)M * G;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int p = (int)(t / G), c = (int)(t - (long)p * G) * 4;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < splits; ++k) {
+        const float4 v = *reinterpret_cast<const float4 *>(ws + ((size_t)k * M + p) * Co + c);
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    float o[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (c + k >= Cor) { o[k] = 0.f; continue; }
+        if (bias) o[k] += bias[c + k];
+        if (res) o[k] += res[(size_t)p * ldres + c + k];
+        if (relu_out) o[k] = fmaxf(o[k], 0.f);
+    }
+    *reinterpret_cast<float4 *>(y + (size_t)p * ldy + c) = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// ----------------------------------------------------------------------------- categorical draw
+__device__ __forceinline__ float uniform_of(uint32_t seed_lo, uint32_t seed_hi, uint32_t pos_lo, uint32_t pos_hi, uint32_t row) {
+    const uint4 w = philox4x32_7(pos_lo, pos_hi, row, 0u, seed_lo, seed_hi);
+    return (float)(w.x >> 8) * 5.9604644775390625e-08f;   // 2^-24: u in [0, 1), exact
+}
+
+__global__ __launch_bounds__(256) void sample_categorical_kernel(const float *__restrict__ logits, long long row_stride, int M,
+                                                                 int n_class, float temperature, uint32_t seed_lo,
+                                                                 uint32_t seed_hi, uint32_t pos_lo, uint32_t pos_hi,
+                                                                 long long *__restrict__ out, long long out_stride) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;                                      // whole waves leave: no shuffle crosses a wave
+    const float *l = logits + (long long)row * row_stride;
+    const int chunk = (n_class + 63) / 64;
+    const int c0 = min(lane * chunk, n_class), c1 = min(c0 + chunk, n_class);
+    float mx = -INFINITY;
+    for (int c = c0; c < c1; ++c) mx = fmaxf(mx, l[c] / temperature);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    float s = 0.f;
+    for (int c = c0; c < c1; ++c) s += expf(l[c] / temperature - mx);
+    float incl = s;                                            // inclusive scan over the lanes, one fixed tree
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.f;
+    const float total = __shfl(incl, 63, 64);
+    const float thr = uniform_of(seed_lo, seed_hi, pos_lo, pos_hi, (uint32_t)row) * total;
+    // running sum at class c of this lane: excl + (own exponentials up to c, in order); first class that passes thr
+    int found = -1;
+    float run = 0.f;
+    for (int c = c0; c < c1; ++c) {
+        run += expf(l[c] / temperature - mx);
+        if (excl + run > thr) { found = c; break; }
+    }
+    const unsigned long long hit = __ballot(found >= 0);
+    int cls = n_class - 1;                                     // rounding left no class above thr: the last one
+    if (hit) cls = __shfl(found, __ffsll((long long)hit) - 1, 64);
+    if (lane == 0) out[(long long)row * out_stride] = (long long)cls;
+}
+
+__global__ __launch_bounds__(256) void sample_uniforms_kernel(float *__restrict__ u, int M, uint32_t seed_lo, uint32_t seed_hi,
+                                                              uint32_t pos_lo, uint32_t pos_hi) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row < M) u[row] = uniform_of(seed_lo, seed_hi, pos_lo, pos_hi, (uint32_t)row);
+}
+
+int check_row_geom(const vq2_conv_geom *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags) {
+    if (int e = vq2::check_geom(d)) return e;
+    VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0, "convg_fwd_row: non-positive dims");
+    VQ2_REQUIRE(d->Ci % 4 == 0 && d->Co % 4 == 0, "convg_fwd_row: Ci=%d, Co=%d must be multiples of 4", d->Ci, d->Co);
+    VQ2_REQUIRE(d->ldx >= d->Ci && d->ldx % 4 == 0, "convg_fwd_row: ldx=%d must be >= Ci and a multiple of 4", d->ldx);
+    VQ2_REQUIRE(d->ldy >= d->Co && d->ldy % 4 == 0, "convg_fwd_row: ldy=%d must be >= Co and a multiple of 4", d->ldy);
+    VQ2_REQUIRE(d->pad_top == d->KH - 1, "convg_fwd_row: pad_top == KH - 1 required (the kernel must end at the output row)");
+    VQ2_REQUIRE(row >= 0 && row < d->H, "convg_fwd_row: row %d outside the %d rows", row, d->H);
+    VQ2_REQUIRE(x_image_stride >= 0 && x_row_stride >= 0 && x_image_stride % 4 == 0 && x_row_stride % 4 == 0,
+                "convg_fwd_row: input strides must be non-negative multiples of 4");
+    VQ2_REQUIRE((flags & ~(VQ2_RELU_IN | VQ2_RELU_OUT | VQ2_ROW_CAUSAL_TAPS)) == 0, "convg_fwd_row: unknown flag");
+    VQ2_REQUIRE((int64_t)d->N * d->W * (d->ldy > d->Co ? d->ldy : d->Co) < ((int64_t)1 << 31) &&
+                    (int64_t)d->Co * d->KH * d->KW * d->Ci < ((int64_t)1 << 31),
+                "convg_fwd_row: tensor exceeds 2^31 elements");
+    return VQ2_OK;
+}
+
+}  // namespace
+
+extern "C" size_t vq2_convg_fwd_row_workspace_bytes(const vq2_conv_geom *d, int flags) {
+    if (!d || d->N <= 0 || d->W <= 0 || d->Co <= 0 || d->KH < 1 || d->KW < 1 || d->KH * d->KW > 32) return 0;
+    const RowPlan p = row_plan(d, flags);
+    return (size_t)p.splits * d->N * d->W * d->Co * sizeof(float);
+}
+
+extern "C" int vq2_convg_fwd_row(const vq2_conv_geom *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
+                                 const float *x, const float *wp, const float *bias, const float *residual, int32_t ldres,
+                                 float *y, void *ws, size_t ws_bytes, vq2_stream_t stream) {
+    if (int e = check_row_geom(d, row, x_image_stride, x_row_stride, flags)) return e;
+    VQ2_REQUIRE(x && wp && y && ws, "convg_fwd_row: null pointer");
+    VQ2_REQUIRE(vq2::aligned16(x) && vq2::aligned16(wp) && vq2::aligned16(y) && vq2::aligned16(ws) &&
+                    (!residual || vq2::aligned16(residual)),
+                "convg_fwd_row: pointers must be 16-byte aligned");
+    VQ2_REQUIRE(!residual || (ldres >= d->Co && ldres % 4 == 0), "convg_fwd_row: ldres must be >= Co and a multiple of 4");
+    const RowPlan pl = row_plan(d, flags);
+    if (ws_bytes < vq2_convg_fwd_row_workspace_bytes(d, flags))
+        return vq2::set_error(VQ2_ERR_WORKSPACE, "convg_fwd_row: workspace of %zu bytes, %zu needed", ws_bytes,
+                              vq2_convg_fwd_row_workspace_bytes(d, flags));
+    hipStream_t s = vq2::to_stream(stream);
+    RowConv P{};
+    P.x = x; P.w = wp; P.ws = static_cast<float *>(ws);
+    P.x_image_stride = x_image_stride; P.x_row_stride = x_row_stride;
+    P.W = d->W; P.Ci = d->Ci; P.Co = d->Co; P.KH = d->KH; P.KW = d->KW; P.pad_left = d->pad_left; P.ldx = d->ldx;
+    P.row = row; P.M = d->N * d->W; P.K = d->KH * d->KW * d->Ci;
+    P.relu_in = (flags & VQ2_RELU_IN) != 0;
+    P.tap_mask = pl.mask; P.tps = pl.tps;
+    const dim3 grid((P.M + RC_BM - 1) / RC_BM, (P.Co + RC_BN - 1) / RC_BN, pl.splits);
+    hipLaunchKernelGGL(convg_row_partial_kernel, grid, dim3(256), 0, s, P);
+    if (int e = vq2::check_launch("convg_row_partial_kernel")) return e;
+    const long total = (long)P.M * (P.Co / 4);
+    hipLaunchKernelGGL(convg_row_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P.ws, pl.splits, P.M, P.Co,
+                       d->Cor ? d->Cor : d->Co, bias, residual, ldres, y, d->ldy, (flags & VQ2_RELU_OUT) != 0);
+    return vq2::check_launch("convg_row_reduce_kernel");
+}
+
+extern "C" int vq2_sample_categorical(const float *logits, int64_t row_stride, int32_t M, int32_t n_class, float temperature,
+                                      uint64_t seed, uint64_t position, int64_t *out, int64_t out_stride, vq2_stream_t stream) {
+    VQ2_REQUIRE(logits && out, "sample_categorical: null pointer");
+    VQ2_REQUIRE(M >= 1 && row_stride >= n_class && out_stride >= 1, "sample_categorical: M >= 1, row_stride >= n_class and out_stride >= 1 required");
+    VQ2_REQUIRE(temperature > 0.f, "sample_categorical: temperature must be positive");
+    VQ2_REQUIRE(n_class >= 1 && n_class <= 16384, "sample_categorical: n_class must be in 1..16384 (got %d)", n_class);
+    hipLaunchKernelGGL(sample_categorical_kernel, dim3((M + 3) / 4), dim3(256), 0, vq2::to_stream(stream), logits,
+                       (long long)row_stride, M, n_class, temperature, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32),
+                       (uint32_t)(position & 0xFFFFFFFFu), (uint32_t)(position >> 32), reinterpret_cast<long long *>(out),
+                       (long long)out_stride);
+    return vq2::check_launch("sample_categorical_kernel");
+}
+
+extern "C" int vq2_sample_uniforms(float *u, int32_t M, uint64_t seed, uint64_t position, vq2_stream_t stream) {
+    VQ2_REQUIRE(u && M >= 1, "sample_uniforms: null pointer or M < 1");
+    hipLaunchKernelGGL(sample_uniforms_kernel, dim3((M + 255) / 256), dim3(256), 0, vq2::to_stream(stream), u, M,
+                       (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (uint32_t)(position & 0xFFFFFFFFu),
+                       (uint32_t)(position >> 32));
+    return vq2::check_launch("sample_uniforms_kernel");
+}

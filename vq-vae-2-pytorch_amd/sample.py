@@ -1,0 +1,485 @@
+"""Sampling from a trained PixelSNAIL prior (drop-in for the reference's sample.py: sample_model, load_model).
+
+The reference draws pixel (i, j) from model(row[:, :i + 1])[..., i, j]: H * W forward passes over ever more rows.  Every layer
+of the model is causal in raster order, so rows < i never change.  PriorSampler computes row i only:
+
+    row-local layers     (ELU, GLU, 1x1 convs, the concatenations with the coordinate planes, the condition) run the
+                         library's kernels on a dense [B, 1, W, C] row
+    'causal' convs       keep their input rows in a history [H, B, W, C] and compute output row i with vq2_convg_fwd_row
+    CausalAttention      keeps the projected keys and values [H, B, W, C / 2]; row i's W queries go through
+                         vq2_causal_attn_fwd_rows
+    the input convs      run vq2_onehot_conv_fwd on the band of code rows that ends at row i (-1 above the image: such a code
+                         contributes nothing); at row 0 the shifted-down branch is left out, because the row a shift brings in
+                         is 0 without the bias
+    the condition        cond_resnet and the x2 upsample run once per call
+
+Histories are row-outer so that every row slice is dense.  Effective weights (g * v / ||v|| after the 'causal' zeroing) and
+their packed panels are formed once, when the sampler is built; the launches of a row are recorded once per (batch, rows) as a
+list of library calls with their arguments and replayed W times, without autograd, dropout or a host synchronisation.  Step
+(i, j) recomputes the whole row: columns <= j are exact, later ones are placeholders nothing reads.  The integer code map
+is moved by torch copies once per row (band of row i + 1 from band of row i); everything else is a libvq2 kernel."""
+import ctypes as C
+import os
+import weakref
+
+import torch
+
+from . import ops
+from ._lib import lib, check, AttnDesc, ConvGeom
+from .evaluate import eval_mode
+from .pixelsnail import CausalConv2d, GatedResBlock, PixelSNAIL, WNConv2d, _WNLinear
+
+VQ2_ROW_CAUSAL_TAPS = 8
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _ptr(t, offset=0):
+    """Device pointer `offset` elements into t."""
+    return C.c_void_p(t.data_ptr() + offset * t.element_size())
+
+
+class _Program:
+    """Library calls recorded with their arguments; run() replays them in order."""
+
+    def __init__(self):
+        self.calls = []
+
+    def add(self, what, fn, *args):
+        self.calls.append((fn, args, what))
+
+    def run(self):
+        for fn, args, what in self.calls:
+            rc = fn(*args)
+            if rc:
+                check(rc, what)
+
+
+class _Conv:
+    """One weight-normed conv with its effective weight, formed and packed once."""
+
+    def __init__(self, mod, pack=True):
+        causal_cols = None
+        if isinstance(mod, CausalConv2d):
+            if mod.padding == 'causal':
+                causal_cols = mod.causal
+            mod = mod.conv
+        if isinstance(mod, WNConv2d):
+            if mod.elu:
+                raise NotImplementedError("vqvae2_amd.PriorSampler: a WNConv2d with an activation of its own")
+            par, self.spec = mod.conv, mod.spec
+        elif isinstance(mod, _WNLinear):
+            par, self.spec = mod, mod.spec
+        else:
+            raise NotImplementedError(f"vqvae2_amd.PriorSampler: cannot step through {type(mod).__name__}")
+        s = self.spec
+        v = par.weight_v.detach().clone().contiguous()
+        if causal_cols is not None:
+            v[:, :, -1, causal_cols:] = 0
+        g = par.weight_g.detach().contiguous()
+        w = torch.empty_like(v)
+        check(lib.vq2_weight_norm_fwd(ops._p(v), ops._p(g), ops._p(w), s.cout, v.numel() // s.cout, ops._stream()), "weight_norm_fwd")
+        self.kh = s.k
+        self.kw = s.kw if s.is_geom else s.k
+        self.weight = w.view(s.cout, s.cin, self.kh, self.kw)
+        self.bias = None if par.bias is None else par.bias.detach()
+        self.row_flags = VQ2_ROW_CAUSAL_TAPS if causal_cols is not None else 0
+        if self.kh > 1 and not (s.is_geom and s.pad_top == self.kh - 1):
+            raise NotImplementedError("vqvae2_amd.PriorSampler: a conv over several rows must end at its output row")
+        self.wp = ops.packed_weight(s, self.weight, ops.PACK_FWD) if pack else None
+        self.hist = None
+
+    def row_desc(self, batch, rows, width):
+        s = self.spec
+        d = ConvGeom()
+        d.N, d.H, d.W, d.Ci, d.Co = batch, rows, width, s.ci, s.co
+        d.KH, d.KW, d.pad_top, d.pad_left = s.k, s.kw, s.pad_top, s.pad_left
+        d.ldx, d.ldy, d.Cir, d.Cor = s.ci, s.co, s.cin, s.cout
+        return d
+
+    def workspace_bytes(self, batch, rows, width):
+        if self.kh == 1:
+            return 0
+        return lib.vq2_convg_fwd_row_workspace_bytes(C.byref(self.row_desc(batch, rows, width)), self.row_flags)
+
+
+class _Plan:
+    """Buffers, histories and the recorded launches of every row for one (batch, rows, condition?) on one stream."""
+
+    def __init__(self, sampler, batch, rows, with_condition):
+        self.s, self.B, self.H, self.W = sampler, batch, rows, sampler.width
+        self.dev = sampler.device
+        self.stream = ops._stream()
+        self.stream_id = torch.cuda.current_stream().cuda_stream
+        self.bufs = {}
+        m = sampler.model
+        ws_bytes = max([c.workspace_bytes(batch, rows, self.W) for c in sampler.convs] + [16])
+        self.ws = torch.empty((ws_bytes + 3) // 4, device=self.dev, dtype=torch.float32)
+        self.ws_bytes = ws_bytes
+        self.R = sampler.band_rows
+        # band i: code rows i - R + 1 .. i as the input convs see them at row i; -1 above the image
+        self.bands = torch.empty((rows, batch, self.R, self.W), device=self.dev, dtype=torch.int64)
+        self.cond_rows = None
+        if with_condition:
+            self.cond_rows = torch.empty((rows, batch, self.W, ops.ceil4(m.cond_res_channel)), device=self.dev, dtype=torch.float32)
+        bg = m._background(batch, rows)                                   # [B, rows, W, 4]
+        self.bg_rows = torch.empty((rows, batch, self.W, 4), device=self.dev, dtype=torch.float32)
+        self.to_row_outer(bg, self.bg_rows)
+        self.logits = None
+        self.programs = [self.record(i) for i in range(rows)]
+
+    # -- buffers
+    def buf(self, name, c):
+        t = self.bufs.get(name)
+        if t is None:
+            t = self.bufs[name] = torch.empty((self.B, 1, self.W, c), device=self.dev, dtype=torch.float32)
+        return t
+
+    def hist(self, name, c):
+        t = self.bufs.get(name)
+        if t is None:
+            t = self.bufs[name] = torch.empty((self.H, self.B, self.W, c), device=self.dev, dtype=torch.float32)
+        return t
+
+    def to_row_outer(self, src, dst):
+        """NHWC [B, >= rows, W, C] -> [rows, B, W, C]: one slice copy per row (an image's row is one run of W * C floats)."""
+        b, h, w, c = src.shape
+        for i in range(self.H):
+            check(lib.vq2_slice_copy(_ptr(src, i * w * c), h * w * c, _ptr(dst, i * b * w * c), w * c, b, w * c, 0, self.stream),
+                  "slice_copy")
+
+    def reset_codes(self):
+        self.bands.zero_()
+        for r in range(self.R - 1):
+            self.bands[:self.R - 1 - r, :, r].fill_(-1)
+
+    def end_row(self, i):
+        if i + 1 < self.H:
+            self.bands[i + 1, :, :self.R - 1].copy_(self.bands[i, :, 1:])
+
+    def codes(self):
+        return self.bands[:, :, self.R - 1].permute(1, 0, 2).contiguous()
+
+    # -- recording
+    def record(self, i):
+        self.prog = _Program()
+        self.row = i
+        s, m = self.s, self.s.model
+        x = self.input_stage()
+        bg = self.bg_rows[i].view(self.B, 1, self.W, 4)
+        cond = None if self.cond_rows is None else self.cond_rows[i].view(self.B, 1, self.W, -1)
+        for bi, block in enumerate(m.blocks):
+            x = self.pixel_block(f"b{bi}", block, x, bg, cond)
+        n_out = len(m.out) - 2
+        for k in range(n_out):
+            x = self.gated(f"o{k}", m.out[k], x)
+        e = self.buf("head.elu", m.channel)
+        self.elu(x, m.channel, e)
+        self.logits = self.buf("head.logits", ops.ceil4(m.n_class))
+        self.conv(s.conv_of[m.out[n_out + 1]], e, None, self.logits)
+        return self.prog
+
+    def add(self, what, fn, *args):
+        self.prog.add(what, fn, *(args + (self.stream,)))
+
+    def elu(self, x, c, out):
+        self.add("elu_fwd", lib.vq2_elu_fwd, _ptr(x), x.shape[3], _ptr(out), out.shape[3], self.B * self.W, c)
+
+    def copy(self, src, dst, dst_off):
+        self.add("slice_copy", lib.vq2_slice_copy, _ptr(src), src.shape[3], _ptr(dst, dst_off), dst.shape[3], self.B * self.W,
+                 src.shape[3], 0)
+
+    def conv_input(self, name, conv):
+        """Where the input row of `conv` is to be written: its history's row, or a plain row buffer."""
+        if conv.kh > 1:
+            return self.hist(name + ".hist", conv.spec.ci)[self.row].view(self.B, 1, self.W, conv.spec.ci)
+        return self.buf(name + ".in", conv.spec.ci)
+
+    def conv(self, conv, x, residual, out, name=None):
+        sp = conv.spec
+        ldres = residual.shape[3] if residual is not None else 0
+        if conv.kh == 1:
+            d = ops._desc(sp, self.B, 1, self.W, x.shape[3], out.shape[3])
+            self.add("conv_fwd", ops._abi(sp).fwd, d, 0, _ptr(x), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres, _ptr(out))
+            return
+        hist = self.hist(name + ".hist", sp.ci)
+        assert x.data_ptr() == hist[self.row].data_ptr() and out.shape[3] == sp.co
+        d = conv.row_desc(self.B, self.H, self.W)
+        self.add("convg_fwd_row", lib.vq2_convg_fwd_row, d, self.row, self.W * sp.ci, self.B * self.W * sp.ci, conv.row_flags,
+                 _ptr(hist), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres, _ptr(out), _ptr(self.ws), self.ws_bytes)
+
+    def input_stage(self):
+        s, m, i = self.s, self.s.model, self.row
+        cp = ops.ceil4(m.channel)
+        band = self.bands[i]
+        acc = None
+        if i > 0:       # at row 0 the shift brings in a row of zeros (no bias); the band would give the bias
+            acc = self.bufs.setdefault("in.h", torch.empty((self.B, self.R, self.W, cp), device=self.dev, dtype=torch.float32))
+            sp = s.horizontal.spec
+            d = ops._onehot_desc(self.B, self.R, self.W, sp.cout, sp.cin, (sp.k, sp.kw, sp.pad_top, sp.pad_left), (1, 0), cp)
+            self.add("onehot_conv_fwd", lib.vq2_onehot_conv_fwd, d, _ptr(band), _ptr(s.horizontal_wp), ops._p(s.horizontal.bias),
+                     None, 0, _ptr(acc))
+        y = self.bufs.setdefault("in.v", torch.empty((self.B, self.R, self.W, cp), device=self.dev, dtype=torch.float32))
+        sp = s.vertical.spec
+        d = ops._onehot_desc(self.B, self.R, self.W, sp.cout, sp.cin, (sp.k, sp.kw, sp.pad_top, sp.pad_left), (0, 1), cp)
+        self.add("onehot_conv_fwd", lib.vq2_onehot_conv_fwd, d, _ptr(band), _ptr(s.vertical_wp), ops._p(s.vertical.bias),
+                 ops._p(acc), cp if acc is not None else 0, _ptr(y))
+        x = self.buf("in.x", cp)
+        # the band's last row of every image: B runs of W * cp floats
+        self.add("slice_copy", lib.vq2_slice_copy, _ptr(y, (self.R - 1) * self.W * cp), self.R * self.W * cp, _ptr(x), self.W * cp,
+                 self.B, self.W * cp, 0)
+        return x
+
+    def gated(self, name, block, x, aux=None, cond=None):
+        s = self.s
+        conv1, conv2 = s.conv_of[block.conv1], s.conv_of[block.conv2]
+        r = None
+        if aux is not None:
+            ea = self.buf(name + ".ea", aux.shape[3])
+            self.elu(aux, block.auxiliary_channel, ea)
+            r = self.buf(name + ".aux", conv1.spec.co)
+            self.conv(s.conv_of[block.aux_conv], ea, None, r)
+        e = self.conv_input(name + ".c1", conv1)
+        self.elu(x, block.in_channel, e)
+        h = self.buf(name + ".h", conv1.spec.co)
+        self.conv(conv1, e, r, h, name + ".c1")
+        e2 = self.conv_input(name + ".c2", conv2)
+        self.elu(h, block.channel, e2)
+        r = None
+        if cond is not None:
+            r = self.buf(name + ".cond", conv2.spec.co)
+            self.conv(s.conv_of[block.condition], cond, None, r)
+        t = self.buf(name + ".t", conv2.spec.co)
+        self.conv(conv2, e2, r, t, name + ".c2")
+        out = self.buf(name + ".out", ops.ceil4(block.in_channel))
+        self.add("glu_res_fwd", lib.vq2_glu_res_fwd, _ptr(t), t.shape[3], _ptr(x), x.shape[3], _ptr(out), out.shape[3],
+                 self.B * self.W, block.in_channel)
+        return out
+
+    def cat(self, name, parts):
+        out = self.buf(name, sum(p.shape[3] for p in parts))
+        off = 0
+        for p in parts:
+            self.copy(p, out, off)
+            off += p.shape[3]
+        return out
+
+    def pixel_block(self, name, block, x, bg, cond):
+        s = self.s
+        out = x
+        for k, rb in enumerate(block.resblocks):
+            out = self.gated(f"{name}.r{k}", rb, out, cond=cond)
+        if not block.attention:
+            o = self.buf(name + ".o", s.conv_of[block.out].spec.co)
+            self.conv(s.conv_of[block.out], self.cat(name + ".cat", [out, bg]), None, o)
+            return o
+        key = self.gated(name + ".key", block.key_resblock, self.cat(name + ".kcat", [x, out, bg]))
+        query = self.gated(name + ".query", block.query_resblock, self.cat(name + ".qcat", [out, bg]))
+        att = block.causal_attention
+        ch = att.channel
+        q = self.buf(name + ".q", ch)
+        kh, vh = self.hist(name + ".khist", ch), self.hist(name + ".vhist", ch)
+        self.conv(s.conv_of[att.query], query, None, q)
+        self.conv(s.conv_of[att.key], key, None, kh[self.row].view(self.B, 1, self.W, ch))
+        self.conv(s.conv_of[att.value], key, None, vh[self.row].view(self.B, 1, self.W, ch))
+        o = self.buf(name + ".att", ch)
+        d = AttnDesc()
+        d.B, d.L, d.n_head, d.dim_head = self.B, self.H * self.W, att.n_head, att.dim_head
+        d.ldq = d.ldk = d.ldv = d.ldo = ch
+        self.add("causal_attn_fwd_rows", lib.vq2_causal_attn_fwd_rows, d, self.row * self.W, self.W, self.W, self.W * ch,
+                 self.B * self.W * ch, _ptr(q), _ptr(kh), _ptr(vh), _ptr(o))
+        return self.gated(name + ".outb", block.out_resblock, out, aux=o)
+
+
+class PriorSampler:
+    """PriorSampler(model): a row-incremental sampler over a vqvae2_amd.PixelSNAIL on the GPU.
+
+    sample(batch, temperature=1.0, condition=None, seed=None, rows=None) -> int64 [B, rows, W] on the device.  condition: the
+        int64 top codes [B, H / 2, W / 2] for a model built with a condition network.  seed None takes one integer from torch's
+        default CPU generator (as the dropout layers do), so torch.manual_seed makes a run repeatable.  The code of pixel (i, j)
+        of image b is drawn by vq2_sample_categorical at position i * W + j, row b.
+    logits_given(codes, condition=None) -> [B, n_class, H, W]: the same stepping with `codes` written where sample() draws;
+        entry (i, j) is what step (i, j) saw, which by causality is the model's own output for those codes.
+    The weights are those of the moment of construction: a model whose parameters changed since is refused until refresh().
+    One set of histories and recorded launches is kept, for the last (batch, rows, condition or not, stream): a call with
+    another combination frees it and builds a new one (alternating sample() and logits_given() of different sizes rebuilds
+    every time).  The sampler holds device pointers: it cannot be pickled or deep-copied, and nothing of it is stored on the
+    model."""
+
+    def __init__(self, model, _weak=False):
+        if not isinstance(model, PixelSNAIL):
+            raise TypeError("vqvae2_amd.PriorSampler: a vqvae2_amd.PixelSNAIL expected")
+        # _weak: sample_model's cache is keyed weakly by the model; its samplers must not keep the model alive themselves
+        self._model_ref = weakref.ref(model)
+        self._model = None if _weak else model
+        self.refresh()
+
+    @property
+    def model(self):
+        m = self._model_ref()
+        if m is None:
+            raise RuntimeError("vqvae2_amd.PriorSampler: the model is gone")
+        return m
+
+    def refresh(self):
+        m = self.model
+        par = next(m.parameters())
+        ops._require_cuda(par, "the model's parameters")
+        self.device = par.device
+        self.width = m.background.shape[3]
+        with torch.no_grad():
+            self.conv_of = {}
+            for mod in self._gated_blocks():
+                names = ["conv1", "conv2"] + (["aux_conv"] if mod.auxiliary_channel > 0 else []) + \
+                        (["condition"] if mod.condition_dim > 0 else [])
+                for n in names:
+                    self.conv_of[getattr(mod, n)] = _Conv(getattr(mod, n))
+            for block in m.blocks:
+                if block.attention:
+                    for lin in (block.causal_attention.query, block.causal_attention.key, block.causal_attention.value):
+                        self.conv_of[lin] = _Conv(lin)
+                else:
+                    self.conv_of[block.out] = _Conv(block.out)
+            self.conv_of[m.out[-1]] = _Conv(m.out[-1])
+            self.convs = list(self.conv_of.values())
+            self.horizontal, self.vertical = _Conv(m.horizontal, pack=False), _Conv(m.vertical, pack=False)
+            self.horizontal_wp, self.vertical_wp = self._onehot_panel(self.horizontal), self._onehot_panel(self.vertical)
+        self.band_rows = max(self.horizontal.kh + 1, self.vertical.kh)
+        self._versions = self._snapshot()
+        self._plan = None
+
+    def _gated_blocks(self):
+        """The gated blocks the stepping runs (cond_resnet's run through the module itself, once per call)."""
+        for block in self.model.blocks:
+            yield from block.resblocks
+            if block.attention:
+                yield from (block.key_resblock, block.query_resblock, block.out_resblock)
+        yield from list(self.model.out)[:-2]
+
+    def _onehot_panel(self, conv):
+        cout, n_class, kh, kw = conv.weight.shape
+        wp = torch.empty(kh * kw * n_class * ops.ceil4(cout), device=self.device, dtype=torch.float32)
+        check(lib.vq2_onehot_pack_weight(ops._p(conv.weight), ops._p(wp), cout, n_class, kh, kw, ops._stream()), "onehot_pack_weight")
+        return wp
+
+    def _snapshot(self):
+        return [(p.data_ptr(), p._version, getattr(p, "_vq2_epoch", 0)) for p in self.model.parameters()]
+
+    def _plan_for(self, batch, rows, condition):
+        if self._snapshot() != self._versions:
+            raise RuntimeError("vqvae2_amd.PriorSampler: the model's parameters changed since the sampler was built; call refresh()")
+        m = self.model
+        if not 1 <= rows <= m.background.shape[2]:
+            raise RuntimeError(f"PriorSampler: {rows} rows do not fit the model's {m.background.shape[2]}")
+        key = (batch, rows, condition is not None, torch.cuda.current_stream().cuda_stream)
+        if self._plan is None or self._plan[0] != key:
+            self._plan = None       # free the old histories before the new ones are allocated
+            self._plan = (key, _Plan(self, batch, rows, condition is not None))
+        plan = self._plan[1]
+        if condition is not None:
+            if not hasattr(m, "cond_resnet"):
+                raise RuntimeError("PriorSampler: condition given to a model built without a condition network")
+            condition = ops._require_codes(condition, "condition")
+            if condition.dim() != 3 or condition.shape[0] != batch or 2 * condition.shape[1] < rows or 2 * condition.shape[2] != self.width:
+                raise RuntimeError("PriorSampler: condition [B, H / 2, W / 2] of int64 codes expected")
+            with eval_mode(m.cond_resnet):
+                cond = ops.Upsample2Fn.apply(m.cond_resnet.nhwc(condition), m.cond_res_channel)
+            plan.to_row_outer(cond, plan.cond_rows)
+        plan.reset_codes()
+        return plan
+
+    @torch.no_grad()
+    def sample(self, batch, temperature=1.0, condition=None, seed=None, rows=None):
+        rows = self.model.background.shape[2] if rows is None else int(rows)
+        if not temperature > 0:
+            raise ValueError(f"PriorSampler: temperature must be positive, got {temperature}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = int(seed) & _MASK64
+        plan = self._plan_for(int(batch), rows, condition)
+        b, w, r = plan.B, plan.W, plan.R
+        n_class, ld = self.model.n_class, ops.ceil4(self.model.n_class)
+        draw, t = lib.vq2_sample_categorical, float(temperature)
+        for i in range(rows):
+            prog = plan.programs[i]
+            band = plan.bands[i]
+            for j in range(w):
+                prog.run()
+                check(draw(_ptr(plan.logits, j * ld), w * ld, b, n_class, t, seed, i * w + j, _ptr(band, (r - 1) * w + j), r * w,
+                           plan.stream), "sample_categorical")
+            plan.end_row(i)
+        return plan.codes()
+
+    @torch.no_grad()
+    def logits_given(self, codes, condition=None):
+        codes = ops._require_codes(codes, "codes")
+        if codes.dim() != 3 or codes.shape[2] != self.width:
+            raise RuntimeError("PriorSampler: codes [B, H, W] of int64 expected")
+        batch, rows, w = codes.shape
+        plan = self._plan_for(batch, rows, condition)
+        ld = ops.ceil4(self.model.n_class)
+        out = torch.zeros((batch, rows, w, ld), device=self.device, dtype=torch.float32)
+        for i in range(rows):
+            prog = plan.programs[i]
+            for j in range(w):
+                prog.run()
+                check(lib.vq2_slice_copy(_ptr(plan.logits, j * ld), w * ld, _ptr(out, (i * w + j) * ld), rows * w * ld, batch, ld, 0,
+                                         plan.stream), "slice_copy")
+                plan.bands[i, :, plan.R - 1, j] = codes[:, i, j]
+            plan.end_row(i)
+        return ops.from_nhwc(out, self.model.n_class)
+
+
+_SAMPLERS = weakref.WeakKeyDictionary()      # model -> its PriorSampler (which refers to the model weakly)
+
+
+def sample_model(model, device, batch, size, temperature, condition=None):
+    """The reference's sample_model (sample.py:12-24): int64 codes [batch, size[0], size[1]] on `device`, drawn from `model`
+    pixel by pixel in raster order.  One PriorSampler per model is kept in this module, keyed weakly by the model (it goes
+    when the model goes, and the model itself carries nothing: it still pickles and deep-copies), and is rebuilt when the
+    model's parameters change."""
+    if tuple(size)[1] != model.background.shape[3]:
+        raise RuntimeError(f"sample_model: width {size[1]} does not fit the model's {model.background.shape[3]}")
+    model = model.to(device)
+    sampler = _SAMPLERS.get(model)
+    if sampler is None or sampler._snapshot() != sampler._versions:
+        sampler = _SAMPLERS[model] = PriorSampler(model, _weak=True)
+    return sampler.sample(batch, temperature, condition, rows=int(size[0]))
+
+
+def _arg(args, name, default):
+    if isinstance(args, dict):
+        return args.get(name, default)
+    return getattr(args, name, default)
+
+
+def load_model(model, checkpoint, device, ckpt_dir='checkpoint', **overrides):
+    """The reference's load_model (sample.py:27-68): model is 'vqvae', 'pixelsnail_top' or 'pixelsnail_bottom', `checkpoint`
+    a file under `ckpt_dir`.  Constructor arguments come from ckpt['args'] where the checkpoint has them (what
+    examples/train_pixelsnail.py saves, including its extras size / n_class / n_block / kernel_size), then from `overrides`.
+    Returns the model on `device` in eval mode."""
+    from .vqvae import VQVAE
+    ckpt = torch.load(os.path.join(ckpt_dir, checkpoint), map_location='cpu', weights_only=False)
+    args = ckpt.get('args', {}) if isinstance(ckpt, dict) else {}
+
+    def get(name, default):
+        return overrides.get(name, _arg(args, name, default))
+
+    if model == 'vqvae':
+        keys = ('in_channel', 'channel', 'n_res_block', 'n_res_channel', 'embed_dim', 'n_embed', 'decay')
+        net = VQVAE(**{k: get(k, None) for k in keys if get(k, None) is not None})
+    elif model in ('pixelsnail_top', 'pixelsnail_bottom'):
+        h, w = get('size', [32, 32])
+        n_class, kernel, n_block = get('n_class', 512), get('kernel_size', 5), get('n_block', 4)
+        if model == 'pixelsnail_top':
+            net = PixelSNAIL([h, w], n_class, get('channel', 256), kernel, n_block, get('n_res_block', 4), get('n_res_channel', 256),
+                             dropout=get('dropout', 0.1), n_out_res_block=get('n_out_res_block', 0))
+        else:
+            net = PixelSNAIL([2 * h, 2 * w], n_class, get('channel', 256), kernel, n_block, get('n_res_block', 4),
+                             get('n_res_channel', 256), attention=False, dropout=get('dropout', 0.1),
+                             n_cond_res_block=get('n_cond_res_block', 3), cond_res_channel=get('n_res_channel', 256))
+    else:
+        raise ValueError(f"load_model: model must be 'vqvae', 'pixelsnail_top' or 'pixelsnail_bottom', got {model!r}")
+    if isinstance(ckpt, dict) and 'model' in ckpt:
+        ckpt = ckpt['model']
+    net.load_state_dict(ckpt)
+    return net.to(device).eval()
