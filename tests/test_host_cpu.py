@@ -273,6 +273,21 @@ def test_dispatch_table_tolerances_bite_on_the_cpu():
     assert len(done) >= 12
 
 
+def test_geom_dispatch_table_tolerances_bite_on_the_cpu():
+    """The same for the table of the second descriptor (tests/test_gpu_geom_dispatch.py): the cheapest case of EVERY label
+    of EXPECTED_GEOM_LABELS["all"]; and the literal label sets are what the table says, for every value of VQ2_FORMS."""
+    import test_gpu_geom_dispatch as G
+    for forms, col in (("all", 8), ("direct", 9), ("general", 10)):
+        assert set(c[col] for c in G.GEOM_CASES) == G.EXPECTED_GEOM_LABELS[forms], forms
+    assert len(set(G.case_id(c) for c in G.GEOM_CASES)) == len(G.GEOM_CASES)
+    done = set()
+    for c in sorted(G.GEOM_CASES, key=G.cost):
+        if c[8] not in done:
+            done.add(c[8])
+            G._bites(c)
+    assert done == G.EXPECTED_GEOM_LABELS["all"]
+
+
 def test_state_dict_layout_matches_reference(amd):
     m = amd.VQVAE()
     spec = O.state_spec(O.DEFAULT)
