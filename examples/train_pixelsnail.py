@@ -1,15 +1,20 @@
-"""Train a PixelSNAIL prior on extracted codes: the reference's train_pixelsnail.py on one MI355X.
+"""Train a PixelSNAIL prior on extracted codes: the reference's train_pixelsnail.py on one MI355X or several.
 
     python examples/train_pixelsnail.py --hier top    [--batch 32 --epoch 420 --lr 3e-4 --sched cycle ...] CODES
     python examples/train_pixelsnail.py --hier bottom [...] CODES
+    python -m torch.distributed.run --nproc-per-node N examples/train_pixelsnail.py [...] CODES
 
 CODES is what examples/extract_code.py wrote (vqvae2_amd.codes.CodeDataset reads it).  The command line is the
-reference's; `--amp` is accepted only as O0 (this path is fp32).  The reference wraps the model in nn.DataParallel; that is
-not mirrored: this script drives a single GPU.  Every epoch whose number is 1 modulo 10, and the last, saves
-{'model': state_dict, 'args': args} as <ckpt_dir>/pixelsnail_<hier>_<NNN>.pt, the reference's file.
+reference's; `--amp` is accepted only as O0 (this path is fp32).  The reference wraps the model in nn.DataParallel; here
+data parallelism is one process per GPU under torch.distributed.run: every rank takes its shard of each epoch (--batch is
+per rank), Stage2Trainer all-reduces the gradients, and only the primary rank prints and saves.  Every epoch whose number
+is 1 modulo 10, and the last, saves {'model': state_dict, 'args': args} as <ckpt_dir>/pixelsnail_<hier>_<NNN>.pt, the
+reference's file, and beside it trainer_<hier>_<NNN>.pt: Stage2Trainer.state_dict() plus the epoch, which --resume
+continues from exactly (model, Adam moments, schedule position).
 
 Extra arguments of this script (all default to the reference's fixed values): --size H W of the top codes (the bottom codes
-are twice that), --n_class, --n_block, --kernel_size, --max_steps to stop early, --ckpt_dir, --workers."""
+are twice that), --n_class, --n_block, --kernel_size, --max_steps to stop early, --ckpt_dir, --workers, --seed (the torch
+generator is seeded with seed + rank: it draws the shuffle and the dropout seeds), --resume FILE."""
 import argparse
 import os
 import sys
@@ -44,6 +49,8 @@ def parse_args(argv=None):
     parser.add_argument('--max_steps', type=int, default=0)
     parser.add_argument('--ckpt_dir', type=str, default='checkpoint')
     parser.add_argument('--workers', type=int, default=4)
+    parser.add_argument('--seed', type=int, default=None)
+    parser.add_argument('--resume', type=str, default=None)
     return parser.parse_args(argv)
 
 
@@ -60,11 +67,23 @@ def build_model(args):
 
 def main(argv=None):
     args = parse_args(argv)
-    print(args)
     import vqvae2_amd
+    from vqvae2_amd import distributed as dist_fn
+    rank, _, world = dist_fn.bringup()       # joins the launcher's job; a no-op without one
+    primary = dist_fn.is_primary()
+    if primary:
+        print(args)
+    if args.seed is not None:
+        torch.manual_seed(args.seed + rank)
     device = 'cuda'
     dataset = vqvae2_amd.codes.CodeDataset(args.path)
-    loader = DataLoader(dataset, batch_size=args.batch, shuffle=True, num_workers=args.workers, drop_last=True)
+    distributed = dist_fn.get_world_size() > 1
+    sampler = dist_fn.data_sampler(dataset, shuffle=True, distributed=distributed)
+    # (the DistributedSampler pads every shard to the same length and drop_last cuts whole batches: every rank takes the
+    # same number of steps)
+    loader = DataLoader(dataset, batch_size=args.batch, sampler=sampler, num_workers=args.workers, drop_last=True)
+    # (--resume keeps this command line: give the run's own arguments again)
+    resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume is not None else None
     ckpt = {}
     if args.ckpt is not None:
         ckpt = torch.load(args.ckpt, weights_only=False)
@@ -74,21 +93,34 @@ def main(argv=None):
         model.load_state_dict(ckpt['model'])
     model = model.to(device).train()
     trainer = vqvae2_amd.Stage2Trainer(model, args.hier, lr=args.lr, sched=args.sched, n_iter=len(loader) * args.epoch)
-    os.makedirs(args.ckpt_dir, exist_ok=True)
+    first_epoch = 0
+    if resume is not None:
+        trainer.load_state_dict(resume['trainer'] if 'trainer' in resume else resume)
+        first_epoch = int(resume.get('epoch', 0))
+    if primary:
+        os.makedirs(args.ckpt_dir, exist_ok=True)
     steps = 0
-    for i in range(args.epoch):
+    for i in range(first_epoch, args.epoch):
+        if distributed:
+            sampler.set_epoch(i)
         for top, bottom, _ in loader:
             r = trainer.step(top.to(device), bottom.to(device) if args.hier == 'bottom' else None)
             steps += 1
-            print(f"epoch: {i + 1}; loss: {r['loss'].item():.5f}; acc: {r['accuracy'].item():.5f}; lr: {r['lr']:.5f}")
+            if primary:
+                print(f"epoch: {i + 1}; loss: {r['loss'].item():.5f}; acc: {r['accuracy'].item():.5f}; lr: {r['lr']:.5f}")
             if args.max_steps and steps >= args.max_steps:
                 break
         done = bool(args.max_steps and steps >= args.max_steps)
-        if i % 10 == 0 or i >= args.epoch - 1 or done:
-            torch.save({'model': model.state_dict(), 'args': args},
-                       os.path.join(args.ckpt_dir, f'pixelsnail_{args.hier}_{str(i + 1).zfill(3)}.pt'))
+        if primary and (i % 10 == 0 or i >= args.epoch - 1 or done):
+            tag = f'{args.hier}_{str(i + 1).zfill(3)}.pt'
+            torch.save({'model': model.state_dict(), 'args': args}, os.path.join(args.ckpt_dir, 'pixelsnail_' + tag))
+            torch.save({'trainer': trainer.state_dict(), 'args': args, 'epoch': i + 1},
+                       os.path.join(args.ckpt_dir, 'trainer_' + tag))
         if done:
             break
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        dist_fn.synchronize()
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == '__main__':

@@ -50,11 +50,13 @@ typedef void *vq2_stream_t;
  * kernels, top / left padding) and the ELU / ELU+dropout / GLU+residual kernels of the stage-2 GatedResBlock;
  * revision 10: additions only -- the one-hot convolution, cross-entropy and x2-upsample entry points of the stage-2 prior
  * (csrc/vq2_prior.hip); revision 11: additions only -- the row-incremental sampling entry points (vq2_convg_fwd_row with its
- * workspace query, vq2_causal_attn_fwd_rows, vq2_sample_categorical, vq2_sample_uniforms); see INTEGRATION.md "ABI history").
+ * workspace query, vq2_causal_attn_fwd_rows, vq2_sample_categorical, vq2_sample_uniforms); revision 12: additions only -- the table-driven
+ * weight-norm entry points vq2_wn_table_fwd and vq2_wn_table_bwd with their table entry vq2_wn_entry; see INTEGRATION.md
+ * "ABI history").
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 11
+#define VQ2_API_VERSION 12
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -416,6 +418,27 @@ int vq2_causal_attn_keep_mask(const vq2_attn_desc *d, uint8_t *mask, vq2_stream_
 int vq2_weight_norm_fwd(const float *v, const float *g, float *w, int32_t rows, int32_t cols, vq2_stream_t stream);
 int vq2_weight_norm_bwd(const float *dw, const float *v, const float *g, float *dv, float *dg, int32_t rows, int32_t cols,
                         vq2_stream_t stream);
+
+/* The same two operations for EVERY weight-normed tensor of a model in one launch each (Stage2Trainer's arena path).  The
+ * table lives in device memory, is written once and holds offsets in floats, not pointers: `v_off` / `g_off` place weight_v
+ * [rows][cols] and weight_g [rows] in the parameter arena (and dv / dg in the gradient arena), `w_off` places the effective
+ * weight in a flat buffer of its own (and dW in one of the same layout).  With a row of v read as [cin][kh][kw], the elements
+ * of kernel row kh - 1 and kernel column >= mask_from are the ones the reference's 'causal' CausalConv2d zeroes
+ * (pixelsnail.py:108-110); mask_from == kw: none.  `row_start` is the number of rows of all earlier entries, and the table
+ * ends with one more entry that carries only the total in `row_start`: a table of n entries has n + 1 elements.
+ *
+ * vq2_wn_table_fwd writes 0 into the masked elements of v IN PLACE, then w = g * v / ||v|| per row, for all n entries.
+ * vq2_wn_table_bwd reads dW and v, g and writes dv, dg for the entries [first, last) only; first == last launches nothing.
+ * Every row has exactly the bits vq2_weight_norm_fwd / vq2_weight_norm_bwd give for it; floats of the flat buffers that
+ * belong to no tensor are not touched.  Offsets and sizes are the caller's to get right: they are not checked on the device. */
+typedef struct vq2_wn_entry {
+    int64_t v_off, g_off, w_off;
+    int32_t rows, cols, kh, kw, mask_from, row_start;
+} vq2_wn_entry;
+
+int vq2_wn_table_fwd(const vq2_wn_entry *table, int32_t n_entries, float *params, float *w, vq2_stream_t stream);
+int vq2_wn_table_bwd(const vq2_wn_entry *table, int32_t first, int32_t last, const float *params, const float *dw,
+                     float *grads, vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ conv, second geometry (stage-2 prior)
  * Rectangular kernels with top / left padding: WNConv2d and CausalConv2d of the reference (pixelsnail.py:21-119, whose

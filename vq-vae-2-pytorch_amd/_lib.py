@@ -44,6 +44,12 @@ class AttnDesc(C.Structure):
                [("p_drop", C.c_float), ("reserved", C.c_int32), ("seed", C.c_uint64)]
 
 
+class WnEntry(C.Structure):
+    """vq2_wn_entry: one weight-normed tensor of a vq2_wn_table_* table (offsets in floats)."""
+    _fields_ = [("v_off", C.c_int64), ("g_off", C.c_int64), ("w_off", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("rows", "cols", "kh", "kw", "mask_from", "row_start")]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -116,6 +122,8 @@ def _load():
         "vq2_causal_attn_keep_mask": (C.c_int, [C.POINTER(AttnDesc), P, P]),
         "vq2_weight_norm_fwd": (C.c_int, [P, P, P, I32, I32, P]),
         "vq2_weight_norm_bwd": (C.c_int, [P, P, P, P, P, I32, I32, P]),
+        "vq2_wn_table_fwd": (C.c_int, [P, I32, P, P, P]),
+        "vq2_wn_table_bwd": (C.c_int, [P, I32, I32, P, P, P, P]),
         "vq2_convg_pack_weight": (C.c_int, [GP, C.c_int, P, P, P]),
         "vq2_convg_pack_job_init": (C.c_int, [GP, C.c_int, P, P, C.POINTER(PackJob)]),
         "vq2_convg_fwd": (C.c_int, [GP, C.c_int, P, P, P, P, I32, P, P]),

@@ -496,30 +496,85 @@ __global__ __launch_bounds__(256) void attn_keep_mask_kernel(AttnParams P, uint8
 }
 
 // ---------------------------------------------------------------- weight norm (one wave per output row)
+// The row routines: lane c takes columns c, c + 64, ... in order, then the butterfly of wave_sum.  The per-layer kernels
+// and the table-driven ones both run exactly these, so a row has one set of bits whichever launch formed it.
+__device__ __forceinline__ void wn_row_fwd(const float *vr, const float *g, float *wr, int cols, int lane) {
+    float ss = 0.f;
+    for (int c = lane; c < cols; c += 64) ss += vr[c] * vr[c];
+    ss = vq2::wave_sum(ss);
+    const float f = g[0] / sqrtf(ss);
+    for (int c = lane; c < cols; c += 64) wr[c] = vr[c] * f;
+}
+
+__device__ __forceinline__ void wn_row_bwd(const float *wr, const float *vr, const float *g, float *dvr, float *dg, int cols,
+                                           int lane) {
+    float ss = 0.f, dot = 0.f;
+    for (int c = lane; c < cols; c += 64) { ss += vr[c] * vr[c]; dot += wr[c] * vr[c]; }
+    ss = vq2::wave_sum(ss);
+    dot = vq2::wave_sum(dot);
+    const float n = sqrtf(ss);
+    const float f = g[0] / n, e = dot / ss;   // dv = (g / n) * (dw - v * (dw . v) / n^2)
+    for (int c = lane; c < cols; c += 64) dvr[c] = f * (wr[c] - vr[c] * e);
+    if (lane == 0) dg[0] = dot / n;
+}
+
 __global__ __launch_bounds__(64) void weight_norm_fwd_kernel(const float *__restrict__ v, const float *__restrict__ g,
                                                              float *__restrict__ w, int cols) {
     const int row = blockIdx.x;
-    const float *vr = v + (size_t)row * cols;
-    float ss = 0.f;
-    for (int c = threadIdx.x; c < cols; c += 64) ss += vr[c] * vr[c];
-    ss = vq2::wave_sum(ss);
-    const float f = g[row] / sqrtf(ss);
-    for (int c = threadIdx.x; c < cols; c += 64) w[(size_t)row * cols + c] = vr[c] * f;
+    wn_row_fwd(v + (size_t)row * cols, g + row, w + (size_t)row * cols, cols, threadIdx.x);
 }
 
 __global__ __launch_bounds__(64) void weight_norm_bwd_kernel(const float *__restrict__ dw, const float *__restrict__ v,
                                                              const float *__restrict__ g, float *__restrict__ dv,
                                                              float *__restrict__ dg, int cols) {
     const int row = blockIdx.x;
-    const float *vr = v + (size_t)row * cols, *wr = dw + (size_t)row * cols;
-    float ss = 0.f, dot = 0.f;
-    for (int c = threadIdx.x; c < cols; c += 64) { ss += vr[c] * vr[c]; dot += wr[c] * vr[c]; }
-    ss = vq2::wave_sum(ss);
-    dot = vq2::wave_sum(dot);
-    const float n = sqrtf(ss);
-    const float f = g[row] / n, e = dot / ss;   // dv = (g / n) * (dw - v * (dw . v) / n^2)
-    for (int c = threadIdx.x; c < cols; c += 64) dv[(size_t)row * cols + c] = f * (wr[c] - vr[c] * e);
-    if (threadIdx.x == 0) dg[row] = dot / n;
+    wn_row_bwd(dw + (size_t)row * cols, v + (size_t)row * cols, g + row, dv + (size_t)row * cols, dg + row, cols, threadIdx.x);
+}
+
+// Table-driven forms: every weight-normed tensor of a model in one launch.  A workgroup is four waves, a wave takes one row
+// at a time; the rows [tab[first].row_start, tab[last].row_start) are dealt to the waves of a fixed grid, and each wave finds
+// the entry of its row by bisection over row_start (a handful of cached loads against one read of the row itself).
+constexpr int WN_WAVES = 4;
+constexpr int WN_GRID = 2048;      // 256 CUs x 8 workgroups: enough rows in flight for a kernel bound by one read of v
+
+__device__ __forceinline__ int wn_find(const vq2_wn_entry *tab, int first, int last, int r) {
+    int lo = first, hi = last - 1;            // the largest index whose row_start is <= r
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].row_start <= r) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(64 * WN_WAVES) void wn_table_fwd_kernel(const vq2_wn_entry *tab, int first, int last,
+                                                                     float *params, float *w) {
+    const int lane = threadIdx.x & 63;
+    const int r1 = tab[last].row_start;
+    for (int r = tab[first].row_start + blockIdx.x * WN_WAVES + (threadIdx.x >> 6); r < r1; r += gridDim.x * WN_WAVES) {
+        const vq2_wn_entry e = tab[wn_find(tab, first, last, r)];
+        const int row = r - e.row_start;
+        float *vr = params + e.v_off + (int64_t)row * e.cols;
+        if (e.mask_from < e.kw) {
+            // the 'causal' edit of the parameter itself: last kernel row, columns from mask_from on.  The lane that zeroes
+            // column c is the lane that reads it below
+            for (int c = lane; c < e.cols; c += 64)
+                if ((c / e.kw) % e.kh == e.kh - 1 && c % e.kw >= e.mask_from) vr[c] = 0.f;
+        }
+        wn_row_fwd(vr, params + e.g_off + row, w + e.w_off + (int64_t)row * e.cols, e.cols, lane);
+    }
+}
+
+__global__ __launch_bounds__(64 * WN_WAVES) void wn_table_bwd_kernel(const vq2_wn_entry *tab, int first, int last,
+                                                                     const float *params, const float *dw, float *grads) {
+    const int lane = threadIdx.x & 63;
+    const int r1 = tab[last].row_start;
+    for (int r = tab[first].row_start + blockIdx.x * WN_WAVES + (threadIdx.x >> 6); r < r1; r += gridDim.x * WN_WAVES) {
+        const vq2_wn_entry e = tab[wn_find(tab, first, last, r)];
+        const int row = r - e.row_start;
+        const int64_t o = (int64_t)row * e.cols;
+        wn_row_bwd(dw + e.w_off + o, params + e.v_off + o, params + e.g_off + row, grads + e.v_off + o, grads + e.g_off + row,
+                   e.cols, lane);
+    }
 }
 
 int fill_params(const vq2_attn_desc *d, AttnParams &P, const char *what) {
@@ -632,4 +687,24 @@ extern "C" int vq2_weight_norm_bwd(const float *dw, const float *v, const float 
     VQ2_REQUIRE(rows >= 1 && cols >= 1, "weight_norm_bwd: non-positive size");
     hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(rows), dim3(64), 0, vq2::to_stream(stream), dw, v, g, dv, dg, cols);
     return vq2::check_launch("weight_norm_bwd_kernel");
+}
+
+extern "C" int vq2_wn_table_fwd(const vq2_wn_entry *table, int32_t n_entries, float *params, float *w, vq2_stream_t stream) {
+    VQ2_REQUIRE(table && params && w, "wn_table_fwd: null pointer");
+    VQ2_REQUIRE(n_entries >= 1, "wn_table_fwd: the table needs at least one entry");
+    VQ2_REQUIRE(vq2::aligned16(table), "wn_table_fwd: the table must be 16-byte aligned");
+    hipLaunchKernelGGL(wn_table_fwd_kernel, dim3(WN_GRID), dim3(64 * WN_WAVES), 0, vq2::to_stream(stream), table, 0, n_entries,
+                       params, w);
+    return vq2::check_launch("wn_table_fwd_kernel");
+}
+
+extern "C" int vq2_wn_table_bwd(const vq2_wn_entry *table, int32_t first, int32_t last, const float *params, const float *dw,
+                                float *grads, vq2_stream_t stream) {
+    VQ2_REQUIRE(table && params && dw && grads, "wn_table_bwd: null pointer");
+    VQ2_REQUIRE(first >= 0 && first <= last, "wn_table_bwd: the entry range [%d, %d) is not a range", first, last);
+    VQ2_REQUIRE(vq2::aligned16(table), "wn_table_bwd: the table must be 16-byte aligned");
+    if (first == last) return VQ2_OK;
+    hipLaunchKernelGGL(wn_table_bwd_kernel, dim3(WN_GRID), dim3(64 * WN_WAVES), 0, vq2::to_stream(stream), table, first, last,
+                       params, dw, grads);
+    return vq2::check_launch("wn_table_bwd_kernel");
 }

@@ -13,7 +13,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check, AttnDesc, ConvDesc, ConvGeom, OneHotDesc, PackJob, WgradJob
+from ._lib import lib, check, AttnDesc, ConvDesc, ConvGeom, OneHotDesc, PackJob, WgradJob, WnEntry
 
 VQ2_RELU_IN = 1
 VQ2_RELU_OUT = 2
@@ -275,7 +275,9 @@ def conv_dgrad(spec, xshape, dy, weight, mask=None, residual=None, out=None, mas
 def _grad_slot(param):
     """ParamArena: the gradient of `param` lands directly in the flat gradient buffer."""
     slot = getattr(param, "_vq2_grad", None) if param is not None else None
-    if slot is not None and param.grad is None:   # a second backward (accumulation) must not overwrite the first
+    # a second backward (accumulation) must not overwrite the first; an effective weight handed out by a WeightNormPlan
+    # is no leaf (it has no .grad): its slot is that plan's dW buffer, written once per step
+    if slot is not None and (not param.is_leaf or param.grad is None):
         return slot.view_as(slot)  # fresh tensor object so autograd can adopt it as .grad without a copy
     return None if param is None else torch.empty_like(param, memory_format=torch.contiguous_format)
 
@@ -1019,6 +1021,152 @@ class WeightNormFn(Function):
         return dv, dg
 
 
+class WeightNormPlan:
+    """Every weight-normed tensor of a model whose parameters live in a ParamArena, formed and differentiated by ONE launch
+    each (vq2_wn_table_fwd / vq2_wn_table_bwd) instead of one per layer and pass.  The plan owns the device table (built
+    once, offsets only), a flat buffer of effective weights and one of their gradients; each layer's effective weight is
+    a view of the first whose `_vq2_grad` is the matching view of the second, so the weight-gradient launches write there.
+
+    The layers take their weight from the plan (planned_weight) only while it is `active` (its trainer's step is running) and
+    `current` (prepare() ran after the last change of the parameters); otherwise they run the per-layer kernels as before.
+    Entries are in arena order, so a contiguous slice of the gradient arena is a contiguous range of entries."""
+
+    @staticmethod
+    def layers(model):
+        """[(name, module holding weight_v / weight_g, kh, kw, mask_from)] in registration order.  mask_from < kw only for a
+        CausalConv2d(padding='causal'): the first kernel column of the last kernel row that it zeroes."""
+        causal = {id(m.conv.conv): m.causal for m in model.modules()
+                  if getattr(m, "padding", None) == "causal" and hasattr(m, "causal")}
+        out = []
+        for name, mod in model.named_modules():
+            prm = mod._parameters
+            if prm.get("weight_v") is None or prm.get("weight_g") is None:
+                continue
+            v = mod.weight_v
+            kh, kw = (int(v.shape[2]), int(v.shape[3])) if v.dim() == 4 else (1, 1)
+            out.append((name, mod, kh, kw, causal.get(id(mod), kw)))
+        return out
+
+    @classmethod
+    def entries(cls, model, offset):
+        """The table as a list of dicts (name, rows, cols, kh, kw, mask_from, v_off, g_off, w_off, row_start), in arena
+        order, plus the names of the layers that stay on the per-layer kernels (a weight_v or weight_g outside the arena,
+        or not contiguous).  offset: {id(parameter): offset in floats}, ParamArena.offset or ParamArena.layout()[1].
+        Needs no device."""
+        rows_of, skipped = [], []
+        for name, mod, kh, kw, mask_from in cls.layers(model):
+            v, g = mod.weight_v, mod.weight_g
+            if id(v) not in offset or id(g) not in offset or not v.is_contiguous() or not g.is_contiguous() or \
+                    g.numel() != v.shape[0]:
+                skipped.append(name)
+                continue
+            rows = int(v.shape[0])
+            rows_of.append(dict(name=name, module=mod, rows=rows, cols=v.numel() // rows, kh=kh, kw=kw, mask_from=mask_from,
+                                v_off=offset[id(v)], g_off=offset[id(g)]))
+        rows_of.sort(key=lambda e: e["v_off"])
+        w_off = row_start = 0
+        for e in rows_of:
+            e["w_off"], e["row_start"] = w_off, row_start
+            w_off += ceil4(e["rows"] * e["cols"])       # 16-byte slots, as in the arena
+            row_start += e["rows"]
+        return rows_of, skipped
+
+    def __init__(self, model, arena):
+        import numpy as np
+        self.arena = arena
+        self.table, self.skipped = self.entries(model, arena.offset)
+        if not self.table:
+            raise ValueError("WeightNormPlan: the model has no weight-normed layer inside the arena")
+        n = self.n = len(self.table)
+        total = sum(ceil4(e["rows"] * e["cols"]) for e in self.table)
+        dev = arena.flat_p.device
+        self.w = torch.zeros(total, device=dev, dtype=torch.float32)
+        self.dw = torch.zeros(total, device=dev, dtype=torch.float32)
+        arr = (WnEntry * (n + 1))()
+        self.index, self.vg, self.w_views, self.dw_views = {}, [], [], []
+        for i, e in enumerate(self.table):
+            for k in ("v_off", "g_off", "w_off", "rows", "cols", "kh", "kw", "mask_from", "row_start"):
+                setattr(arr[i], k, e[k])
+            mod = e["module"]
+            numel = e["rows"] * e["cols"]
+            shape = (e["rows"], e["cols"] // (e["kh"] * e["kw"]), e["kh"], e["kw"])
+            self.index[id(mod.weight_v)] = i
+            self.vg.append((mod.weight_v, mod.weight_g))
+            self.w_views.append(self.w[e["w_off"]:e["w_off"] + numel].view(shape))
+            self.dw_views.append(self.dw[e["w_off"]:e["w_off"] + numel].view(shape))
+            mod.weight_v._vq2_wn = self
+        arr[n].row_start = self.table[-1]["row_start"] + self.table[-1]["rows"]      # the terminator: total rows
+        raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
+        self.table_dev = torch.from_numpy(raw).to(dev)
+        self._ptrs = [(v.data_ptr(), g.data_ptr()) for v, g in self.vg]
+        self.active = False
+        self.current = False
+
+    def first_entry_at(self, lo):
+        """Index of the first entry whose parameters start at arena offset >= lo (entries are in arena order)."""
+        return sum(1 for e in self.table if e["v_off"] < lo)
+
+    def prepare(self):
+        """One launch: the 'causal' zeros into weight_v, every effective weight into the flat buffer."""
+        a = self.arena
+        if any((v.data_ptr(), g.data_ptr()) != p for (v, g), p in zip(self.vg, self._ptrs)):
+            raise RuntimeError("WeightNormPlan: a parameter was re-allocated; rebuild the trainer")
+        check(lib.vq2_wn_table_fwd(_p(self.table_dev), self.n, _p(a.flat_p), _p(self.w), _stream()), "wn_table_fwd")
+        self.current = True
+
+    def backward(self, first, last):
+        """One launch: dv, dg of the entries [first, last) from their dW, into the gradient arena."""
+        a = self.arena
+        check(lib.vq2_wn_table_bwd(_p(self.table_dev), first, last, _p(a.flat_p), _p(self.dw), _p(a.gp), _stream()),
+              "wn_table_bwd")
+
+    def invalidate(self):
+        """The parameters changed (optimizer step, load_state_dict, broadcast): the flat buffer is stale."""
+        self.current = False
+
+
+class PlannedWeightFn(Function):
+    """The autograd link between a layer and its WeightNormPlan.  Forward: the prepared view, no launch.  Backward: dW is
+    already in its slot when the weight-gradient kernel honoured `_vq2_grad` (one copy if it could not); the gradients
+    handed to weight_v and weight_g are their arena slots, whose values vq2_wn_table_bwd writes before anything reads them."""
+
+    @staticmethod
+    def forward(ctx, v, g, plan, i):
+        ctx.plan, ctx.i = plan, i
+        w = plan.w_views[i]
+        return w.view_as(w)
+
+    @staticmethod
+    def backward(ctx, dw):
+        plan, i = ctx.plan, ctx.i
+        slot = plan.dw_views[i]
+        if dw.data_ptr() != slot.data_ptr() or not dw.is_contiguous():
+            slot.copy_(dw)
+        v, g = plan.vg[i]
+        if v.grad is not None or g.grad is not None:
+            raise RuntimeError("WeightNormPlan: a second backward inside one trainer step (arena.zero_grad() first)")
+        return v._vq2_grad.view_as(v._vq2_grad), g._vq2_grad.view_as(g._vq2_grad), None, None
+
+
+def plan_ready(weight_v):
+    """The WeightNormPlan that serves this weight_v right now, or None."""
+    plan = getattr(weight_v, "_vq2_wn", None)
+    if plan is not None and plan.active and plan.current and id(weight_v) in plan.index:
+        return plan
+    return None
+
+
+def planned_weight(weight_v, weight_g):
+    """The effective weight [out, in, kh, kw] from the layer's plan, or None when the layer has to form it itself."""
+    plan = plan_ready(weight_v)
+    if plan is None:
+        return None
+    i = plan.index[id(weight_v)]
+    w = PlannedWeightFn.apply(weight_v, weight_g, plan, i)
+    w._vq2_grad = plan.dw_views[i]
+    return w
+
+
 # ----------------------------------------------------------------------------- GatedResBlock pieces (stage-2 prior)
 def _rows(t, c):
     """Dense NHWC operand of an elementwise kernel: real channels c, ceil4(c) stored."""
@@ -1178,6 +1326,8 @@ class OneHotConvFn(Function):
                                       _p(y), _stream()), "onehot_conv_fwd")
         ctx.save_for_backward(idx)
         ctx.geom, ctx.shift, ctx.wshape, ctx.has_bias = tuple(geom), tuple(shift), tuple(weight.shape), bias is not None
+        # where the gradients go: a plan's dW slot for the weight, the arena slot for the bias (None: fresh tensors)
+        ctx.dw_slot, ctx.bias = (None if weight.is_leaf else getattr(weight, "_vq2_grad", None)), bias
         return y
 
     @staticmethod
@@ -1189,10 +1339,12 @@ class OneHotConvFn(Function):
         dw = db = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             d = _onehot_desc(n, h, w, cout, n_class, ctx.geom, ctx.shift, ld_of(dy))
-            dw = torch.empty(ctx.wshape, device=dy.device, dtype=torch.float32)
+            slot = ctx.dw_slot
+            dw = slot.view_as(slot) if slot is not None and tuple(slot.shape) == ctx.wshape and slot.is_contiguous() else \
+                torch.empty(ctx.wshape, device=dy.device, dtype=torch.float32)
             ws = nbytes = None
             if ctx.has_bias and ctx.needs_input_grad[2]:
-                db = torch.empty(cout, device=dy.device, dtype=torch.float32)
+                db = _grad_slot(ctx.bias)
                 nbytes = lib.vq2_onehot_conv_wgrad_workspace_bytes(C.byref(d))
                 ws = torch.empty(max(nbytes // 8, 1), device=dy.device, dtype=torch.float64)
             check(lib.vq2_onehot_conv_wgrad(C.byref(d), _p(idx), _p(dy), _p(dw), _p(db), _p(ws), nbytes or 0, _stream()),

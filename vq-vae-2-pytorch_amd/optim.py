@@ -29,14 +29,11 @@ class ParamArena:
         if not params:
             raise ValueError("ParamArena: no parameters")
         self.registration_order = list(params)
-        tail_ids = {id(p) for p in last}
-        params = [p for p in params if id(p) not in tail_ids] + [p for p in params if id(p) in tail_ids]
+        params, self.offset, self.n = self.layout(params, last)
         dev = params[0].device
         if dev.type != "cuda":
             raise RuntimeError("ParamArena: parameters must live on the MI355X (model.cuda() first)")
         self.params = params
-        sizes = [(p.numel() + 3) // 4 * 4 for p in params]  # keep every slot 16-byte aligned
-        self.n = sum(sizes)
         self.flat_p = torch.zeros(self.n, device=dev, dtype=torch.float32)
         # gradient buffer = [extra (VQ statistics) | parameter gradients in registration order]; backward
         # produces gradients roughly in REVERSE registration order, so the tail of this buffer is
@@ -45,17 +42,26 @@ class ParamArena:
         self.flat_g = torch.zeros(self.n_extra + self.n, device=dev, dtype=torch.float32)
         self.extra = self.flat_g[:extra]
         self.gp = self.flat_g[self.n_extra:]
-        self.offset = {}
-        off = 0
         with torch.no_grad():
-            for p, sz in zip(params, sizes):
+            for p in params:
+                off = self.offset[id(p)]
                 view = self.flat_p[off:off + p.numel()].view(p.shape)
                 view.copy_(p.data)
                 p.data = view
                 p._vq2_grad = self.gp[off:off + p.numel()].view(p.shape)
-                self.offset[id(p)] = off
-                off += sz
         ops.touch_weights(params)
+
+    @staticmethod
+    def layout(params, last=()):
+        """(parameters in arena order, {id(p): offset in floats}, total floats) -- where the arena puts each parameter.
+        Needs no device: the `last` ones go to the end, every slot starts on a 16-byte boundary."""
+        tail_ids = {id(p) for p in last}
+        params = [p for p in params if id(p) not in tail_ids] + [p for p in params if id(p) in tail_ids]
+        offset, off = {}, 0
+        for p in params:
+            offset[id(p)] = off
+            off += (p.numel() + 3) // 4 * 4  # keep every slot 16-byte aligned
+        return params, offset, off
 
     def canonical(self, flat):
         """A per-parameter flat state vector (Adam moments) re-ordered from arena order into REGISTRATION order -- the

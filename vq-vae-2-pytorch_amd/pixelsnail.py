@@ -32,8 +32,11 @@ class _WNLinear(nn.Module):
     def nhwc(self, x):
         # the effective weight is a non-leaf tensor made each forward: its packed panels are cached on that tensor object
         # and die with it, and its gradient takes the immediate (not the deferred) weight-gradient path of conv_wgrad
-        w = ops.WeightNormFn.apply(self.weight_v, self.weight_g)
-        return ops.conv_op(x, w.view(self.spec.cout, self.spec.cin, 1, 1), self.bias, self.spec)
+        # (a trainer's WeightNormPlan, while it is active and current, hands out its prepared view instead: no launch)
+        w = ops.planned_weight(self.weight_v, self.weight_g)
+        if w is None:
+            w = ops.WeightNormFn.apply(self.weight_v, self.weight_g).view(self.spec.cout, self.spec.cin, 1, 1)
+        return ops.conv_op(x, w, self.bias, self.spec)
 
 
 class CausalAttention(nn.Module):
@@ -145,13 +148,20 @@ class WNConv2d(nn.Module):
         self.spec = ConvSpec.geom(in_channel, out_channel, kh, kw, ph, pw)
         self.conv = _WNConvParams(in_channel, out_channel, kh, kw, bias)
 
+    def _weight(self):
+        """The effective weight [out, in, kh, kw]: a non-leaf tensor made each forward (see _WNLinear.nhwc)."""
+        c = self.conv
+        s = self.spec
+        w = ops.planned_weight(c.weight_v, c.weight_g)
+        if w is None:
+            w = ops.WeightNormFn.apply(c.weight_v.view(s.cout, -1), c.weight_g).view(s.cout, s.cin, s.k, s.kw)
+        return w
+
     def nhwc(self, x, residual=None):
         """x [N,H,W,ceil4(in)] -> [N,H,W,ceil4(out)] (+ residual, added in the conv's epilogue)."""
         c = self.conv
         s = self.spec
-        # the effective weight is a non-leaf tensor made each forward (see _WNLinear.nhwc)
-        w = ops.WeightNormFn.apply(c.weight_v.view(s.cout, -1), c.weight_g).view(s.cout, s.cin, s.k, s.kw)
-        y = ops.conv_op(x, w, c.bias, s, residual=residual)
+        y = ops.conv_op(x, self._weight(), c.bias, s, residual=residual)
         return ops.EluFn.apply(y, s.cout) if self.elu else y
 
     def onehot(self, codes, shift=(0, 0), acc=None):
@@ -159,8 +169,7 @@ class WNConv2d(nn.Module):
         result moved shift = (down, right) pixels and `acc` added, all in ops.OneHotConvFn's one launch."""
         c = self.conv
         s = self.spec
-        w = ops.WeightNormFn.apply(c.weight_v.view(s.cout, -1), c.weight_g).view(s.cout, s.cin, s.k, s.kw)
-        y = ops.onehot_conv(codes, w, c.bias, (s.k, s.kw, s.pad_top, s.pad_left), shift, acc)
+        y = ops.onehot_conv(codes, self._weight(), c.bias, (s.k, s.kw, s.pad_top, s.pad_left), shift, acc)
         return ops.EluFn.apply(y, s.cout) if self.elu else y
 
     def forward(self, input):
@@ -194,15 +203,18 @@ class CausalConv2d(nn.Module):
     def extra_repr(self):
         return f"padding={self.padding!r}"
 
-    def nhwc(self, x, residual=None):
-        if self.padding == 'causal':
-            # (a parameter edit, not part of the graph: the reference's own statement)
+    def _mask(self):
+        # (a parameter edit, not part of the graph: the reference's own statement; a trainer's WeightNormPlan has already
+        # made it, for every layer at once, when it formed this step's weights)
+        if self.padding == 'causal' and ops.plan_ready(self.conv.conv.weight_v) is None:
             self.conv.conv.weight_v.data[:, :, -1, self.causal:].zero_()
+
+    def nhwc(self, x, residual=None):
+        self._mask()
         return self.conv.nhwc(x, residual)
 
     def onehot(self, codes, shift=(0, 0), acc=None):
-        if self.padding == 'causal':
-            self.conv.conv.weight_v.data[:, :, -1, self.causal:].zero_()
+        self._mask()
         return self.conv.onehot(codes, shift, acc)
 
     def forward(self, input):

@@ -316,23 +316,158 @@ class Stage1Trainer:
 
 
 class Stage2Trainer:
-    """The train step of the reference's train_pixelsnail.py:20-57 for one PixelSNAIL on one GPU: zero_grad, forward,
-    cross-entropy with accuracy (ops.prior_loss), backward, scheduler step, Adam step (FusedAdam, one launch per
-    parameter).  `hier` is 'top' (the model sees the top codes) or 'bottom' (the bottom codes, conditioned on the top
-    ones).  step() returns {'loss', 'accuracy'} as 0-dim device tensors and 'lr'; nothing is copied to the host."""
+    """The train step of the reference's train_pixelsnail.py:20-57 for one PixelSNAIL: zero_grad, forward, cross-entropy with
+    accuracy (ops.prior_loss), backward, scheduler step, Adam step.  `hier` is 'top' (the model sees the top codes) or
+    'bottom' (the bottom codes, conditioned on the top ones).  step() returns {'loss', 'accuracy'} as 0-dim device tensors
+    and 'lr'; nothing is copied to the host.
 
-    def __init__(self, model, hier="top", lr=3e-4, sched=None, n_iter=None):
+    arena=True (the default): the parameters live in a ParamArena and an ops.WeightNormPlan forms every effective weight
+    with one launch per step and differentiates them with one more, straight into the gradient arena; Adam is one launch.
+    Every element goes through the same kernels in the same order as with arena=False (one weight-norm launch per layer and
+    pass, one Adam launch per tensor), so losses and parameters are bit for bit the same.
+
+    Data parallelism (one process per GPU, in place of the reference's nn.DataParallel, train_pixelsnail.py:141): as
+    Stage1Trainer -- rank 0's parameters and buffers everywhere at construction, the gradient arena SUM-all-reduced in two
+    contiguous slices (Adam divides by the world size), the first of them from a backward hook while the rest still
+    back-propagates.  VQ2_DP_FORCE=1 takes this path whenever a process group exists, also at world size 1.  Dropout seeds
+    come from each rank's own torch generator; the trainer does not touch them."""
+
+    def __init__(self, model, hier="top", lr=3e-4, sched=None, n_iter=None, arena=True):
         if hier not in ("top", "bottom"):
             raise ValueError(f"Stage2Trainer: hier must be 'top' or 'bottom', got {hier!r}")
+        if sched not in (None, "cycle"):
+            raise ValueError(f"Stage2Trainer: sched must be None or 'cycle', got {sched!r}")
         self.model, self.hier = model, hier
-        self.optimizer = FusedAdam(model.parameters(), lr=lr)
+        self.arena = self.plan = None
+        self.plan_info = {"entries": 0, "per_layer": len(ops.WeightNormPlan.layers(model)), "per_layer_names": []}
+        self.world, self.dp = 1, False
+        self.buckets, self.bucket_bytes, self.early_buckets = [], {}, 0
+        if arena:
+            self._init_arena(lr)
+        else:
+            if dist_fn.get_world_size() > 1:
+                raise RuntimeError("Stage2Trainer: data-parallel training needs the arena path (arena=True)")
+            self.optimizer = FusedAdam(model.parameters(), lr=lr)
         self.scheduler = None
         if sched == "cycle":
             self.scheduler = CycleScheduler(self.optimizer, lr, n_iter=n_iter, momentum=None)
-        elif sched is not None:
-            raise ValueError(f"Stage2Trainer: sched must be None or 'cycle', got {sched!r}")
+
+    # ------------------------------------------------------------------ the arena path
+    @staticmethod
+    def _early_modules(model):
+        """The modules whose gradients are complete first: the output head and the later half of the blocks (the backward
+        pass runs out -> blocks[-1] -> ... -> blocks[0] -> cond_resnet, horizontal, vertical)."""
+        blocks = list(getattr(model, "blocks", ()))
+        early = blocks[len(blocks) // 2:] if len(blocks) >= 2 else []
+        if getattr(model, "out", None) is not None:
+            early.append(model.out)
+        return early
+
+    def _init_arena(self, lr):
+        model = self.model
+        live = [p for p in model.parameters() if p.requires_grad]
+        # registration order is horizontal vertical blocks[...] cond_resnet out; with the early modules at the end the
+        # gradient buffer reads [horizontal vertical blocks[:k] cond_resnet | blocks[k:] out]: the tail is complete first
+        early = [p for m in self._early_modules(model) for p in m.parameters() if p.requires_grad]
+        if len(early) == len(live):
+            early = []
+        self.arena = a = ParamArena(live, last=early)
+        self.optimizer = FusedAdam(live, lr=lr, arena=a)
+        self.plan = ops.WeightNormPlan(model, a)
+        self.plan_info = {"entries": self.plan.n, "per_layer": len(self.plan.skipped), "per_layer_names": list(self.plan.skipped),
+                          "w_floats": self.plan.w.numel()}
+        self.world = dist_fn.get_world_size()
+        forced = os.environ.get("VQ2_DP_FORCE", "0") != "0" and dist.is_available() and dist.is_initialized()
+        self.dp = self.world > 1 or forced
+        self.optimizer.grad_scale = 1.0 / self.world       # the all-reduce sums; DataParallel's loss is a mean over the batch
+        self.comm_stream = torch.cuda.Stream() if self.dp else None
+        self.comm = dist_fn.data_comm() if self.dp else None
+        total = a.flat_g.numel()
+        lo = min((a.n_extra + a.offset[id(p)] for p in early), default=total)
+        inside = lambda b, e: [p for p in a.params if b <= a.n_extra + a.offset[id(p)] < e]
+        # (name, lo, hi, parameters, [first, last) entries of the plan): "early" goes out from the backward hook
+        self.buckets = [(name, b, e, inside(b, e), (self.plan.first_entry_at(b), self.plan.first_entry_at(e)))
+                        for name, b, e in (("early", lo, total), ("late", 0, lo)) if e > b]
+        self.bucket_bytes = {name: 4 * (e - b) for name, b, e, _, _ in self.buckets}
+        self._sent, self._seen = [], 0
+        if self.dp:
+            self._sync_initial_state()
+            if len(self.buckets) == 2:
+                for prm in self.buckets[0][3]:
+                    prm.register_post_accumulate_grad_hook(self._early_hook)
+
+    def _sync_initial_state(self):
+        """Rank 0's parameters and buffers everywhere: one broadcast for the arena, one per tensor outside it."""
+        with torch.no_grad():
+            self.comm.broadcast(self.arena.flat_p, 0)
+            inside = {id(p) for p in self.arena.params}
+            for t in list(self.model.parameters()) + list(self.model.buffers()):
+                if id(t) not in inside:
+                    self.comm.broadcast(t.detach(), 0)
+        ops.touch_weights(self.arena.params)
+        self.plan.invalidate()
+        if hasattr(self.model, "_bg"):
+            self.model._bg = None       # the repeated coordinate planes were made from the buffer as it was
+
+    def _early_hook(self, _p):
+        """Post-accumulate hook of every parameter of the early slice: when the last of them has its gradient, form the
+        slice's dv / dg and hand it to the communicator while the rest of the model back-propagates."""
+        if not self.plan.active:
+            return
+        self._seen += 1
+        _, lo, hi, params, (first, last) = self.buckets[0]
+        if self._seen != len(params):
+            return
+        if not all(p.grad is not None and p.grad.data_ptr() == p._vq2_grad.data_ptr() for p in params):
+            return      # a gradient missed its slot: keep the slice for after backward, where FusedAdam reports it
+        self.plan.backward(first, last)
+        ev = torch.cuda.current_stream().record_event()
+        with torch.cuda.stream(self.comm_stream):
+            self.comm_stream.wait_event(ev)
+            self.comm.all_reduce(self.arena.flat_g[lo:hi])
+        self._sent.append((lo, hi))
+        self.early_buckets += 1
+
+    def _step_arena(self, top, bottom):
+        a, plan = self.arena, self.plan
+        a.zero_grad()
+        self._sent, self._seen = [], 0
+        plan.prepare()
+        plan.active = True
+        try:
+            if self.hier == "top":
+                target = top
+                out, _ = self.model(top)
+            else:
+                target = bottom
+                out, _ = self.model(bottom, condition=top)
+            loss, accuracy = ops.prior_loss(out, target)
+            loss.backward()
+        finally:
+            plan.active = False
+            plan.invalidate()
+        # the entries whose slice did not go out early: everything without data parallelism
+        plan.backward(0, self.buckets[0][4][0] if self._sent else plan.n)
+        if self.dp:
+            if not a.grads_ready():
+                raise RuntimeError("Stage2Trainer: a gradient did not land in the flat arena")
+            ev = torch.cuda.current_stream().record_event()
+            with torch.cuda.stream(self.comm_stream):
+                self.comm_stream.wait_event(ev)
+                pos = 0
+                for lo, hi in sorted(self._sent) + [(a.flat_g.numel(), a.flat_g.numel())]:
+                    if lo > pos:
+                        self.comm.all_reduce(a.flat_g[pos:lo])
+                    pos = max(pos, hi)
+            torch.cuda.current_stream().wait_stream(self.comm_stream)
+        if self.scheduler is not None:
+            self.scheduler.step()
+        self.optimizer.step()
+        return {"loss": loss.detach(), "accuracy": accuracy, "lr": self.optimizer.param_groups[0]["lr"]}
 
     def step(self, top, bottom=None):
+        if self.arena is not None:
+            return self._step_arena(top, bottom)
         self.model.zero_grad(set_to_none=True)
         if self.hier == "top":
             target = top
@@ -346,3 +481,45 @@ class Stage2Trainer:
             self.scheduler.step()
         self.optimizer.step()
         return {"loss": loss.detach(), "accuracy": accuracy, "lr": self.optimizer.param_groups[0]["lr"]}
+
+    # ------------------------------------------------------------------ checkpoint / resume
+    def _need_arena(self, what):
+        if self.arena is None:
+            raise RuntimeError(f"Stage2Trainer.{what} needs the arena path (arena=True)")
+
+    def state_dict(self):
+        """As Stage1Trainer.state_dict(): "model" is exactly what the reference saves (train_pixelsnail.py:150-153), then the
+        Adam moments in registration order, the step count, learning rate / betas and the schedule position."""
+        self._need_arena("state_dict")
+        group = self.optimizer.param_groups[0]
+        return {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+                "adam_m": self.arena.canonical(self.optimizer._m), "adam_v": self.arena.canonical(self.optimizer._v),
+                "adam_t": self.optimizer._t,
+                "lr": group["lr"], "betas": tuple(group["betas"]),
+                "scheduler": None if self.scheduler is None else self.scheduler.state_dict()}
+
+    def load_state_dict(self, sd):
+        """Inverse of state_dict(); also accepts a bare model state_dict (the reference's checkpoint['model'], with or
+        without DataParallel's "module." prefix): optimizer state then starts fresh."""
+        self._need_arena("load_state_dict")
+        model_sd = sd["model"] if isinstance(sd.get("model"), dict) else sd      # (the reference's file: {'model', 'args'})
+        full = model_sd is not sd and "adam_m" in sd
+        model_sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in model_sd.items()}
+        if full and (self.scheduler is None) != (sd.get("scheduler") is None):
+            raise RuntimeError("Stage2Trainer.load_state_dict: checkpoint and trainer disagree about --sched")
+        if full and sd["adam_m"].numel() != sum(p.numel() for p in self.arena.params):
+            raise RuntimeError("Stage2Trainer.load_state_dict: optimizer state belongs to a different model")
+        self.model.load_state_dict(model_sd)          # copies INTO the arena views: parameters stay re-homed
+        ops.touch_weights(self.arena.params)
+        self.plan.invalidate()
+        if hasattr(self.model, "_bg"):
+            self.model._bg = None
+        if full:
+            dev = self.optimizer._m.device
+            self.arena.from_canonical(sd["adam_m"].to(dev), self.optimizer._m)
+            self.arena.from_canonical(sd["adam_v"].to(dev), self.optimizer._v)
+            self.optimizer._t = int(sd["adam_t"])
+            for group in self.optimizer.param_groups:
+                group["lr"], group["betas"] = sd["lr"], tuple(sd["betas"])
+            if self.scheduler is not None:
+                self.scheduler.load_state_dict(sd["scheduler"])
