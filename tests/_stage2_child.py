@@ -79,7 +79,7 @@ def run(amd, ci, steps, arena=True, sched="cycle", seed=5, rank=0, dropout=None,
 
 def bucket_facts(tr):
     return {"early": tr.early_buckets, "dp": tr.dp, "world": tr.world, "bucket_bytes": tr.bucket_bytes,
-            "slices": sorted((lo, hi) for _, lo, hi, _, _ in tr.buckets), "total": tr.arena.flat_g.numel(),
+            "slices": sorted((lo, hi) for _, lo, hi, _ in tr.buckets), "total": tr.arena.flat_g.numel(),
             "per_layer": tr.plan_info["per_layer"]}
 
 

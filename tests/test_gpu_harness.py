@@ -55,6 +55,44 @@ def test_resume_continues_the_uninterrupted_trajectory(tmp_path):
     assert tr_c.optimizer._t == 0
 
 
+def test_stage1_load_state_dict_validates_before_it_mutates():
+    """A checkpoint the trainer cannot take (another --sched, Adam moments of another model) is refused before anything
+    is written: model, step count and moments stay bit for bit what they were, and the trainer steps on."""
+    import vqvae2_amd as amd
+    img = O.make_images(2, 32, 960).cuda()
+    _, tr_a = _trainer(amd, 5)
+    tr_a.step(img)
+    ck = tr_a.state_dict()
+    short = dict(ck, scheduler=None, adam_m=ck["adam_m"][:-1])  # agrees about --sched, so that the moments are looked at
+    cfg = O.TINY
+    m = amd.VQVAE(channel=cfg.channel, n_res_block=cfg.n_res_block, n_res_channel=cfg.n_res_channel,
+                  embed_dim=cfg.embed_dim, n_embed=cfg.n_embed)
+    m.load_state_dict(O.make_state(cfg, 779))
+    tr = amd.Stage1Trainer(m.cuda(), lr=1e-3, sched=None)
+    tr.step(img)                                                # non-zero moments and step count to keep
+    for bad, match in ((ck, "sched"), (short, "different model")):
+        before = {k: v.clone() for k, v in m.state_dict().items()}
+        t, mom, var = tr.optimizer._t, tr.optimizer._m.clone(), tr.optimizer._v.clone()
+        with pytest.raises(RuntimeError, match=match):
+            tr.load_state_dict(bad)
+        assert all(torch.equal(v, before[k]) for k, v in m.state_dict().items())
+        assert tr.optimizer._t == t > 0 and torch.equal(tr.optimizer._m, mom) and torch.equal(tr.optimizer._v, var)
+        assert np.isfinite(float(tr.step(img)["loss"]))
+
+
+def test_stage1_accepts_the_reference_style_wrapper():
+    """{'model': state_dict, 'args': ...} (what train_pixelsnail.py:150-153 saves) is a bare model: weights load, the
+    optimizer starts fresh."""
+    import vqvae2_amd as amd
+    m_ref, _ = _trainer(amd, 5)
+    m, tr = _trainer(amd, 780)
+    tr.load_state_dict({"model": m_ref.state_dict(), "args": None})
+    for (k, a), (_, b) in zip(m_ref.state_dict().items(), m.state_dict().items()):
+        assert torch.equal(a, b), k
+    assert tr.optimizer._t == 0
+    assert np.isfinite(float(tr.step(O.make_images(2, 32, 961).cuda())["loss"]))
+
+
 def test_two_models_in_one_process_do_not_share_state():
     """No process-global mutable state on the autograd path: interleaving the steps of two trainers
     gives each the trajectory it has alone."""

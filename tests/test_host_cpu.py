@@ -433,12 +433,10 @@ def test_extract_code_preprocessing_uses_torchvision_integer_rules(amd):
     assert box(256, 256, 256) == ((256, 256), (0, 0, 256, 256))
 
 
-def test_unsent_bucket_slices_cover_the_gradient_buffer(amd):
-    """Stage1Trainer's fallback after backward: whatever slices the backward hooks did NOT hand to the communicator go
-    out then, as maximal contiguous ranges -- never a gap, never a slice twice (no silent un-reduced gradient)."""
+def _check_unsent_slices(trainer_cls):
     import types
     fake = types.SimpleNamespace(arena=types.SimpleNamespace(flat_g=torch.zeros(100)), _sent=[])
-    unsent = lambda: amd.Stage1Trainer._unsent_slices(fake)
+    unsent = lambda: trainer_cls._unsent_slices(fake)
     assert unsent() == [(0, 100)]                       # no hook fired: one collective over everything
     fake._sent = [(60, 90)]                             # tail only
     assert unsent() == [(0, 60), (90, 100)]
@@ -446,6 +444,34 @@ def test_unsent_bucket_slices_cover_the_gradient_buffer(amd):
     assert unsent() == [(90, 100)]
     fake._sent = [(0, 60), (60, 100)]
     assert unsent() == []
+
+
+def test_unsent_bucket_slices_cover_the_gradient_buffer(amd):
+    """Stage1Trainer's fallback after backward: whatever slices the backward hooks did NOT hand to the communicator go
+    out then, as maximal contiguous ranges -- never a gap, never a slice twice (no silent un-reduced gradient)."""
+    _check_unsent_slices(amd.Stage1Trainer)
+
+
+def test_stage2_trainer_runs_the_same_unsent_slices(amd):
+    """Stage2Trainer reduces the rest of its gradient buffer through the routine pinned above, not a copy of it."""
+    _check_unsent_slices(amd.Stage2Trainer)
+    assert amd.Stage2Trainer._unsent_slices is amd.Stage1Trainer._unsent_slices
+
+
+def test_split_checkpoint_recognises_every_accepted_file(amd):
+    """What load_state_dict makes of a checkpoint before it touches anything: the model's state_dict without the
+    "module." prefix of DDP / DataParallel, and whether optimizer state comes with it."""
+    from vqvae2_amd.train import split_checkpoint
+    bare = {"conv.weight": torch.ones(2, 2), "conv.bias": torch.zeros(2)}
+    prefixed = {"module." + k: v for k, v in bare.items()}
+    rest = {"adam_m": torch.zeros(6), "adam_v": torch.zeros(6), "adam_t": 3, "lr": 1e-3, "betas": (0.9, 0.999),
+            "scheduler": None}
+    for sd, want_full in ((bare, False), (prefixed, False),
+                          ({"model": bare, "args": None}, False), ({"model": prefixed, "args": None}, False),
+                          (dict(rest, model=bare), True), (dict(rest, model=prefixed), True)):
+        model_sd, full = split_checkpoint(sd)
+        assert list(model_sd) == list(bare) and full is want_full
+        assert all(model_sd[k] is bare[k] for k in bare)
 
 
 def test_launch_spawns_ranks_and_joins_the_group(amd, tmp_path):

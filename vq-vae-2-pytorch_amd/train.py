@@ -2,8 +2,16 @@
 object: forward, MSE + 0.25*latent, backward, packed all-reduces (gradients + the EMA sums of both
 quantizers) over RCCL on a side stream, deferred EMA update, one-launch Adam, optional CycleScheduler,
 and a checkpoint that resumes the run exactly (model in the reference's format + optimizer + schedule).
+Stage2Trainer is the step of train_pixelsnail.py:20-57 for one PixelSNAIL prior.
+
+Both stand on _ArenaTrainer, the host-side machinery of a trainer whose parameters, gradients and Adam moments live in
+a ParamArena: the data-parallel set-up and initial broadcast, the gradient buffer cut into contiguous Buckets that go
+to the communicator from backward hooks, the all-reduce of whatever did not go out early, and the checkpoint.  A
+trainer adds its own step, what "finish this slice of the gradient buffer" means, and which derived state to drop when
+the parameters are overwritten behind autograd's back.
 """
 import os
+from collections import namedtuple
 
 import torch
 from torch import distributed as dist
@@ -20,7 +28,165 @@ def stage1_loss(dec, diff, img, latent_loss_weight=LATENT_LOSS_WEIGHT):
     return ops.Stage1LossFn.apply(dec, diff, img, latent_loss_weight)
 
 
-class Stage1Trainer:
+# one contiguous slice [lo, hi) of the gradient arena that goes to the communicator in one collective, and its parameters
+Bucket = namedtuple("Bucket", "name lo hi params")
+
+
+def split_checkpoint(sd):
+    """(model state_dict without DDP's / DataParallel's "module." prefix, full) of anything load_state_dict accepts: a
+    bare model state_dict (train_vqvae.py:173-182), the reference's {'model': ..., 'args': ...} file
+    (train_pixelsnail.py:150-153) -- both with full = False: optimizer state starts fresh -- or a trainer's own
+    state_dict() (full = True).  Touches no device."""
+    wrapped = isinstance(sd.get("model"), dict)
+    model_sd = sd["model"] if wrapped else sd
+    strip = lambda k: k[len("module."):] if k.startswith("module.") else k
+    return {strip(k): v for k, v in model_sd.items()}, wrapped and "adam_m" in sd
+
+
+class _ArenaTrainer:
+    """What Stage1Trainer and Stage2Trainer share; needs self.model, self.arena, self.optimizer and self.scheduler."""
+
+    arena = None
+
+    def _need_arena(self, what):
+        if self.arena is None:
+            raise RuntimeError(f"{type(self).__name__}.{what} needs the arena path (arena=True)")
+
+    def _params_overwritten(self):
+        """The parameters and buffers were written behind autograd's back: drop what was derived from the old ones."""
+        raise NotImplementedError
+
+    # ------------------------------------------------------------------ data parallel plumbing
+    def _init_data_parallel(self):
+        """One process per GPU.  Like DDP's constructor (train_vqvae.py:166-171) rank 0's state goes everywhere first;
+        every step then SUM-all-reduces the gradient arena and Adam divides by the world size."""
+        self.world = dist_fn.get_world_size()
+        forced = os.environ.get("VQ2_DP_FORCE", "0") != "0" and dist.is_available() and dist.is_initialized()
+        self.dp = self.world > 1 or forced
+        self.optimizer.grad_scale = 1.0 / self.world
+        self.comm_stream = torch.cuda.Stream() if self.dp else None
+        self.comm = dist_fn.data_comm() if self.dp else None   # torch.distributed group or libvq2's own communicator
+        self.buckets = []           # Buckets that tile flat_g, in the order their gradients are complete
+        self.bucket_bytes = {}      # name -> bytes of the slice (bench line)
+        self.early_buckets = 0      # buckets that went out from a backward hook (all steps)
+        self._sent = []             # [lo, hi) slices of flat_g already handed to the communicator in this step
+        self._hooks_seen = {}       # bucket name -> watched parameters that have reported in this step
+        if self.dp:
+            self._sync_initial_state()
+
+    def _sync_initial_state(self):
+        """Rank 0's parameters and buffers everywhere: one broadcast for the whole arena, one per tensor outside it
+        (dead dec_ir, codebooks, coordinate planes)."""
+        with torch.no_grad():
+            self.comm.broadcast(self.arena.flat_p, 0)
+            inside = {id(p) for p in self.arena.params}
+            for t in list(self.model.parameters()) + list(self.model.buffers()):
+                if id(t) not in inside:
+                    self.comm.broadcast(t.detach(), 0)     # (detach() shares the version counter; .data does not)
+        ops.touch_weights(self.arena.params)
+        self._params_overwritten()      # (NativeComm writes through raw pointers, which no version counter sees)
+
+    def _set_buckets(self, spans):
+        """spans: (name, lo, hi) slices that tile flat_g, in the order their gradients are complete."""
+        a = self.arena
+        inside = lambda lo, hi: [p for p in a.params if lo <= a.n_extra + a.offset[id(p)] < hi]
+        self.buckets = [Bucket(name, lo, hi, inside(lo, hi)) for name, lo, hi in spans]
+        self.bucket_bytes = {b.name: 4 * (b.hi - b.lo) for b in self.buckets}
+
+    def _send_when_reported(self, bucket, watched, finish):
+        """Post-accumulate hooks on `watched`: when the last of them has reported in a step, `bucket` goes out early."""
+        for prm in watched:
+            prm.register_post_accumulate_grad_hook(lambda _p: self._reported(bucket, len(watched), finish))
+
+    def _reported(self, bucket, need, finish):
+        """finish() completes the bucket's slice of flat_g and returns the event the communicator has to wait for; data
+        parallel, the slice is then all-reduced on the communication stream while the rest of the model back-propagates."""
+        seen = self._hooks_seen[bucket.name] = self._hooks_seen.get(bucket.name, 0) + 1
+        if seen != need:
+            return
+        if not all(p.grad is not None and p.grad.data_ptr() == p._vq2_grad.data_ptr() for p in bucket.params):
+            # a gradient is not in its slot (autograd ordered the graph differently, or it missed the arena, which
+            # _reduce_unsent / FusedAdam report): keep the slice for the collective after backward
+            return
+        ev = finish()
+        if not self.dp:
+            return
+        with torch.cuda.stream(self.comm_stream):
+            self.comm_stream.wait_event(ev)
+            self.comm.all_reduce(self.arena.flat_g[bucket.lo:bucket.hi])
+        self._sent.append((bucket.lo, bucket.hi))
+        self.early_buckets += 1
+
+    def _unsent_slices(self):
+        """Complement of the slices already sent, as maximal contiguous [lo, hi) ranges of flat_g."""
+        out, pos = [], 0
+        for lo, hi in sorted(self._sent):
+            if lo > pos:
+                out.append((pos, lo))
+            pos = max(pos, hi)
+        if pos < self.arena.flat_g.numel():
+            out.append((pos, self.arena.flat_g.numel()))
+        return out
+
+    def _reduce_unsent(self):
+        """After backward, data parallel: whatever no hook sent goes out now (everything if none fired), on the side
+        stream so the host can already enqueue what follows; the main stream waits for all of the step's collectives."""
+        if not self.dp:
+            return
+        if not self.arena.grads_ready():
+            raise RuntimeError(f"{type(self).__name__}: a gradient did not land in the flat arena")
+        ev = torch.cuda.current_stream().record_event()
+        with torch.cuda.stream(self.comm_stream):
+            self.comm_stream.wait_event(ev)
+            for lo, hi in self._unsent_slices():
+                self.comm.all_reduce(self.arena.flat_g[lo:hi])
+        torch.cuda.current_stream().wait_stream(self.comm_stream)
+
+    # ------------------------------------------------------------------ checkpoint / resume
+    def state_dict(self):
+        """"model" is exactly what the reference saves (train_vqvae.py:205-206, train_pixelsnail.py:150-153:
+        model.state_dict(), loadable by extract_code.py / sample.py); the rest is what the reference lacks for an exact
+        resume: Adam moments and step count, learning rate / betas, the schedule position."""
+        self._need_arena("state_dict")
+        group = self.optimizer.param_groups[0]
+        return {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+                # Adam moments in REGISTRATION order (the arena's internal order is an implementation detail)
+                "adam_m": self.arena.canonical(self.optimizer._m), "adam_v": self.arena.canonical(self.optimizer._v),
+                "adam_t": self.optimizer._t,
+                "lr": group["lr"], "betas": tuple(group["betas"]),
+                "scheduler": None if self.scheduler is None else self.scheduler.state_dict()}
+
+    def load_state_dict(self, sd):
+        """Inverse of state_dict(); also accepts what split_checkpoint() calls not full (the reference's files):
+        optimizer state then starts fresh.  Raises before it changes anything."""
+        self._need_arena("load_state_dict")
+        who = f"{type(self).__name__}.load_state_dict"
+        model_sd, full = split_checkpoint(sd)
+        if full:
+            if (self.scheduler is None) != (sd.get("scheduler") is None):
+                raise RuntimeError(f"{who}: checkpoint and trainer disagree about --sched")
+            n, n_real = sd["adam_m"].numel(), sum(p.numel() for p in self.arena.params)
+            if n != n_real and n == self.optimizer._m.numel():
+                # a round-2 checkpoint: moments in that arena's padded registration order
+                raise RuntimeError(f"{who}: optimizer state uses the pre-round-3 padded layout; "
+                                   "re-save it with that version or resume from the model weights alone")
+            if n != n_real:
+                raise RuntimeError(f"{who}: optimizer state belongs to a different model")
+        self.model.load_state_dict(model_sd)          # copies INTO the arena views: parameters stay re-homed
+        ops.touch_weights(self.arena.params)
+        if full:
+            dev = self.optimizer._m.device
+            self.arena.from_canonical(sd["adam_m"].to(dev), self.optimizer._m)
+            self.arena.from_canonical(sd["adam_v"].to(dev), self.optimizer._v)
+            self.optimizer._t = int(sd["adam_t"])
+            for group in self.optimizer.param_groups:
+                group["lr"], group["betas"] = sd["lr"], tuple(sd["betas"])
+            if self.scheduler is not None:
+                self.scheduler.load_state_dict(sd["scheduler"])
+        self._params_overwritten()
+
+
+class Stage1Trainer(_ArenaTrainer):
     """Replaces `DistributedDataParallel(model)` + `optim.Adam` + the loop body of train_vqvae.py:83-91.
 
     Data parallelism (one process per GPU): like DDP's constructor (train_vqvae.py:166-171) the trainer first
@@ -74,14 +240,7 @@ class Stage1Trainer:
                 layers.append((mod.spec, mod.weight, name != "enc_b.blocks.0"))
         self.pack_plan = ops.PackPlan(layers)
 
-        self.world = dist_fn.get_world_size()
-        forced = os.environ.get("VQ2_DP_FORCE", "0") != "0" and dist.is_available() and dist.is_initialized()
-        self.dp = self.world > 1 or forced
-        self.optimizer.grad_scale = 1.0 / self.world  # DDP averages gradients (train_vqvae.py:166-171)
-        self.comm_stream = torch.cuda.Stream() if self.dp else None
-        self.comm = dist_fn.data_comm() if self.dp else None   # torch.distributed group or libvq2's own communicator
-        if self.dp:
-            self._sync_initial_state()
+        self._init_data_parallel()
         self.pack_plan.run()
         # Overlap (train_vqvae.py:166-171 is DDP's bucketed all-reduce; vqvae.py:58-59 the EMA sums).  The backward pass
         # produces gradients in the order dec, upsample_t, quantize_conv_b | dec_t, quantize_conv_t, enc_t | enc_b, so
@@ -92,11 +251,6 @@ class Stage1Trainer:
         #   head    [enc_b]                                       after backward: the only exposed part (~1.4 MB)
         # A bucket goes out early only if every parameter of its slice already owns its gradient slot (autograd happens
         # to order the graph this way; nothing else guarantees it) -- whatever was not sent early is sent after backward.
-        self.early_buckets = 0      # buckets that went out from a backward hook (all steps)
-        self.bucket_bytes = {}      # name -> bytes of the slice (bench line)
-        self._sent = []             # [lo, hi) slices of flat_g already handed to the communicator in this step
-        self._hooks_seen = {}
-        self.buckets = []           # (name, lo, hi, params of the slice)
         split = getattr(model, "quantize_conv_b", None)
         enc_t = getattr(model, "enc_t", None)
         if split is not None and enc_b is not None and enc_t is not None:
@@ -104,68 +258,26 @@ class Stage1Trainer:
             off = lambda p: a.n_extra + a.offset[id(p)]
             lo_tail = off(split.weight)
             lo_head = min(off(p) for p in enc_b.parameters())
-            total = a.flat_g.numel()
-            inside = lambda lo, hi: [p for p in a.params if lo <= off(p) < hi]
-            self.buckets = [("tail", lo_tail, lo_head, inside(lo_tail, lo_head)),
-                            ("middle", 0, lo_tail, inside(0, lo_tail)),
-                            ("head", lo_head, total, inside(lo_head, total))]
-            self.bucket_bytes = {name: 4 * (hi - lo) for name, lo, hi, _ in self.buckets}
-            for prm in (split.weight, split.bias):
-                prm.register_post_accumulate_grad_hook(lambda _p: self._group_done("tail", 2))
-            if self.dp:     # (single GPU: one early slab reduction is enough, a second one only adds a launch)
+            self._set_buckets([("tail", lo_tail, lo_head), ("middle", 0, lo_tail), ("head", lo_head, a.flat_g.numel())])
+            tail, middle, _ = self.buckets
+            # each group is watched through its LAST layer; without data parallelism the tail hook still runs, for the
+            # early slab reduction (one is enough on a single GPU, a second one only adds a launch)
+            self._send_when_reported(tail, (split.weight, split.bias), self._flush_slabs)
+            if self.dp:
                 first = enc_t.blocks[0]
-                for prm in (first.weight, first.bias):
-                    prm.register_post_accumulate_grad_hook(lambda _p: self._group_done("middle", 2))
+                self._send_when_reported(middle, (first.weight, first.bias), self._flush_slabs)
 
-    # ------------------------------------------------------------------ data parallel plumbing
-    def _sync_initial_state(self):
-        """What DistributedDataParallel's constructor does (train_vqvae.py:166-171): rank 0's parameters and
-        buffers everywhere.  One broadcast for the whole arena, one per tensor outside it (dead dec_ir, codebooks)."""
-        with torch.no_grad():
-            self.comm.broadcast(self.arena.flat_p, 0)
-            inside = {id(p) for p in self.arena.params}
-            for t in list(self.model.parameters()) + list(self.model.buffers()):
-                if id(t) not in inside:
-                    self.comm.broadcast(t.detach(), 0)     # (detach() shares the version counter; .data does not)
-        ops.touch_weights(self.arena.params)
-        # the codebooks were just overwritten (NativeComm writes through raw pointers, which no version counter sees):
-        # anything a Quantize derived from its OLD codebook is stale now
-        for q in self.quantizers:
+    def _params_overwritten(self):
+        for q in self.quantizers:       # anything a Quantize derived from its OLD codebook is stale now
             q.invalidate_prepared()
 
-    def _group_done(self, name, need):
-        """Post-accumulate hook of the LAST layer of a backward group: reduce the split-K slabs produced so far into the
-        arena (side stream) and, data parallel, hand the group's slice to the communicator while the next group
-        back-propagates."""
-        seen = self._hooks_seen[name] = self._hooks_seen.get(name, 0) + 1
-        if seen != need:
-            return
-        _, lo, hi, params = next(b for b in self.buckets if b[0] == name)
-        if not all(p.grad is not None and p.grad.data_ptr() == p._vq2_grad.data_ptr() for p in params):
-            return      # autograd ordered the graph differently: keep the slice for the collective after backward
+    def _flush_slabs(self):
+        """Finish a slice: reduce the split-K slabs produced so far into the arena, on the side stream."""
         side = self.ctx.stream
         side.wait_event(torch.cuda.current_stream().record_event())
         with torch.cuda.stream(side):
             self.ctx.batch.flush()
-            ev = side.record_event()
-        if not self.dp:
-            return
-        with torch.cuda.stream(self.comm_stream):
-            self.comm_stream.wait_event(ev)
-            self.comm.all_reduce(self.arena.flat_g[lo:hi])
-        self._sent.append((lo, hi))
-        self.early_buckets += 1
-
-    def _unsent_slices(self):
-        """Complement of the slices already sent, as maximal contiguous [lo, hi) ranges of flat_g."""
-        out, pos = [], 0
-        for lo, hi in sorted(self._sent):
-            if lo > pos:
-                out.append((pos, lo))
-            pos = max(pos, hi)
-        if pos < self.arena.flat_g.numel():
-            out.append((pos, self.arena.flat_g.numel()))
-        return out
+            return side.record_event()
 
     # ------------------------------------------------------------------ the step
     def step(self, img, return_dec=False):
@@ -209,17 +321,9 @@ class Stage1Trainer:
             self.ctx.active = False
         torch.cuda.current_stream().wait_stream(self.ctx.stream)   # all slabs written
         self.ctx.batch.flush()   # one launch reduces the split-K slabs of every layer into the arena
-        if self.dp:
-            if not self.arena.grads_ready():
-                raise RuntimeError("Stage1Trainer: a gradient did not land in the flat arena")
-            # gradients (SUM; Adam divides by world) and EMA sums (SUM, vqvae.py:58-59) in one collective,
-            # issued on a side stream so the host can already enqueue the next step's input work
-            ev = torch.cuda.current_stream().record_event()
-            with torch.cuda.stream(self.comm_stream):
-                self.comm_stream.wait_event(ev)
-                for lo, hi in self._unsent_slices():     # normally just enc_b's slice; everything if no hook fired
-                    self.comm.all_reduce(self.arena.flat_g[lo:hi])
-            torch.cuda.current_stream().wait_stream(self.comm_stream)
+        # gradients (SUM; Adam divides by world) and EMA sums (SUM, vqvae.py:58-59) travel together; normally only
+        # enc_b's slice is left
+        self._reduce_unsent()
         for q in self.quantizers:
             q.apply_deferred_update()
         if self.scheduler is not None:
@@ -273,49 +377,12 @@ class Stage1Trainer:
                 dec, _ = model.forward_nhwc(x)
             return self.normalizer.inverse().grid([x, dec], nrow=x.shape[0], nhwc=True)
 
-    # ------------------------------------------------------------------ checkpoint / resume
-    def state_dict(self):
-        """"model" is exactly what the reference saves (train_vqvae.py:205-206: model.state_dict(), loadable by
-        extract_code.py / sample.py); the rest is what the reference lacks for an exact resume: Adam moments and
-        step count, learning rate / betas, the schedule position."""
-        group = self.optimizer.param_groups[0]
-        return {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-                # Adam moments in REGISTRATION order (the arena's internal order is an implementation detail)
-                "adam_m": self.arena.canonical(self.optimizer._m), "adam_v": self.arena.canonical(self.optimizer._v),
-                "adam_t": self.optimizer._t,
-                "lr": group["lr"], "betas": tuple(group["betas"]),
-                "scheduler": None if self.scheduler is None else self.scheduler.state_dict()}
-
     def load_state_dict(self, sd):
-        """Inverse of state_dict(); also accepts a bare model state_dict (the reference's --resume file,
-        train_vqvae.py:173-182, with or without DDP's "module." prefix): optimizer state then starts fresh."""
-        full = "model" in sd and isinstance(sd["model"], dict)
-        model_sd = sd["model"] if full else sd
-        model_sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in model_sd.items()}
-        self.model.load_state_dict(model_sd)          # copies INTO the arena views: parameters stay re-homed
-        ops.touch_weights(self.arena.params)
-        if full:
-            n_real = sum(p.numel() for p in self.arena.params)
-            if sd["adam_m"].numel() == self.optimizer._m.numel() and sd["adam_m"].numel() != n_real:
-                # a round-2 checkpoint: moments in that arena's padded registration order
-                raise RuntimeError("Stage1Trainer.load_state_dict: optimizer state uses the pre-round-3 padded layout; "
-                                   "re-save it with that version or resume from the model weights alone")
-            if sd["adam_m"].numel() != n_real:
-                raise RuntimeError("Stage1Trainer.load_state_dict: optimizer state belongs to a different model")
-            dev = self.optimizer._m.device
-            self.arena.from_canonical(sd["adam_m"].to(dev), self.optimizer._m)
-            self.arena.from_canonical(sd["adam_v"].to(dev), self.optimizer._v)
-            self.optimizer._t = int(sd["adam_t"])
-            for group in self.optimizer.param_groups:
-                group["lr"], group["betas"] = sd["lr"], tuple(sd["betas"])
-            if (self.scheduler is None) != (sd.get("scheduler") is None):
-                raise RuntimeError("Stage1Trainer.load_state_dict: checkpoint and trainer disagree about --sched")
-            if self.scheduler is not None:
-                self.scheduler.load_state_dict(sd["scheduler"])
+        super().load_state_dict(sd)
         self.pack_plan.run()
 
 
-class Stage2Trainer:
+class Stage2Trainer(_ArenaTrainer):
     """The train step of the reference's train_pixelsnail.py:20-57 for one PixelSNAIL: zero_grad, forward, cross-entropy with
     accuracy (ops.prior_loss), backward, scheduler step, Adam step.  `hier` is 'top' (the model sees the top codes) or
     'bottom' (the bottom codes, conditioned on the top ones).  step() returns {'loss', 'accuracy'} as 0-dim device tensors
@@ -340,13 +407,13 @@ class Stage2Trainer:
         self.model, self.hier = model, hier
         self.arena = self.plan = None
         self.plan_info = {"entries": 0, "per_layer": len(ops.WeightNormPlan.layers(model)), "per_layer_names": []}
-        self.world, self.dp = 1, False
-        self.buckets, self.bucket_bytes, self.early_buckets = [], {}, 0
         if arena:
             self._init_arena(lr)
         else:
             if dist_fn.get_world_size() > 1:
                 raise RuntimeError("Stage2Trainer: data-parallel training needs the arena path (arena=True)")
+            self.world, self.dp = 1, False
+            self.buckets, self.bucket_bytes, self.early_buckets = [], {}, 0
             self.optimizer = FusedAdam(model.parameters(), lr=lr)
         self.scheduler = None
         if sched == "cycle":
@@ -376,150 +443,60 @@ class Stage2Trainer:
         self.plan = ops.WeightNormPlan(model, a)
         self.plan_info = {"entries": self.plan.n, "per_layer": len(self.plan.skipped), "per_layer_names": list(self.plan.skipped),
                           "w_floats": self.plan.w.numel()}
-        self.world = dist_fn.get_world_size()
-        forced = os.environ.get("VQ2_DP_FORCE", "0") != "0" and dist.is_available() and dist.is_initialized()
-        self.dp = self.world > 1 or forced
-        self.optimizer.grad_scale = 1.0 / self.world       # the all-reduce sums; DataParallel's loss is a mean over the batch
-        self.comm_stream = torch.cuda.Stream() if self.dp else None
-        self.comm = dist_fn.data_comm() if self.dp else None
+        self._init_data_parallel()      # (the all-reduce sums; DataParallel's loss is a mean over the batch)
         total = a.flat_g.numel()
         lo = min((a.n_extra + a.offset[id(p)] for p in early), default=total)
-        inside = lambda b, e: [p for p in a.params if b <= a.n_extra + a.offset[id(p)] < e]
-        # (name, lo, hi, parameters, [first, last) entries of the plan): "early" goes out from the backward hook
-        self.buckets = [(name, b, e, inside(b, e), (self.plan.first_entry_at(b), self.plan.first_entry_at(e)))
-                        for name, b, e in (("early", lo, total), ("late", 0, lo)) if e > b]
-        self.bucket_bytes = {name: 4 * (e - b) for name, b, e, _, _ in self.buckets}
-        self._sent, self._seen = [], 0
-        if self.dp:
-            self._sync_initial_state()
-            if len(self.buckets) == 2:
-                for prm in self.buckets[0][3]:
-                    prm.register_post_accumulate_grad_hook(self._early_hook)
+        self._set_buckets([(name, b, e) for name, b, e in (("early", lo, total), ("late", 0, lo)) if e > b])
+        # [first, last) entries of the plan that differentiate the "early" slice, the one a backward hook sends
+        self._early_entries = (self.plan.first_entry_at(lo), self.plan.first_entry_at(total))
+        if self.dp and len(self.buckets) == 2:
+            self._send_when_reported(self.buckets[0], self.buckets[0].params, self._finish_early)
 
-    def _sync_initial_state(self):
-        """Rank 0's parameters and buffers everywhere: one broadcast for the arena, one per tensor outside it."""
-        with torch.no_grad():
-            self.comm.broadcast(self.arena.flat_p, 0)
-            inside = {id(p) for p in self.arena.params}
-            for t in list(self.model.parameters()) + list(self.model.buffers()):
-                if id(t) not in inside:
-                    self.comm.broadcast(t.detach(), 0)
-        ops.touch_weights(self.arena.params)
+    def _params_overwritten(self):
         self.plan.invalidate()
         if hasattr(self.model, "_bg"):
             self.model._bg = None       # the repeated coordinate planes were made from the buffer as it was
 
-    def _early_hook(self, _p):
-        """Post-accumulate hook of every parameter of the early slice: when the last of them has its gradient, form the
-        slice's dv / dg and hand it to the communicator while the rest of the model back-propagates."""
-        if not self.plan.active:
-            return
-        self._seen += 1
-        _, lo, hi, params, (first, last) = self.buckets[0]
-        if self._seen != len(params):
-            return
-        if not all(p.grad is not None and p.grad.data_ptr() == p._vq2_grad.data_ptr() for p in params):
-            return      # a gradient missed its slot: keep the slice for after backward, where FusedAdam reports it
-        self.plan.backward(first, last)
-        ev = torch.cuda.current_stream().record_event()
-        with torch.cuda.stream(self.comm_stream):
-            self.comm_stream.wait_event(ev)
-            self.comm.all_reduce(self.arena.flat_g[lo:hi])
-        self._sent.append((lo, hi))
-        self.early_buckets += 1
+    def _reported(self, bucket, need, finish):
+        if self.plan.active:            # a backward pass outside step() sends nothing
+            super()._reported(bucket, need, finish)
 
-    def _step_arena(self, top, bottom):
-        a, plan = self.arena, self.plan
-        a.zero_grad()
-        self._sent, self._seen = [], 0
-        plan.prepare()
-        plan.active = True
-        try:
-            if self.hier == "top":
-                target = top
-                out, _ = self.model(top)
-            else:
-                target = bottom
-                out, _ = self.model(bottom, condition=top)
-            loss, accuracy = ops.prior_loss(out, target)
-            loss.backward()
-        finally:
-            plan.active = False
-            plan.invalidate()
-        # the entries whose slice did not go out early: everything without data parallelism
-        plan.backward(0, self.buckets[0][4][0] if self._sent else plan.n)
-        if self.dp:
-            if not a.grads_ready():
-                raise RuntimeError("Stage2Trainer: a gradient did not land in the flat arena")
-            ev = torch.cuda.current_stream().record_event()
-            with torch.cuda.stream(self.comm_stream):
-                self.comm_stream.wait_event(ev)
-                pos = 0
-                for lo, hi in sorted(self._sent) + [(a.flat_g.numel(), a.flat_g.numel())]:
-                    if lo > pos:
-                        self.comm.all_reduce(a.flat_g[pos:lo])
-                    pos = max(pos, hi)
-            torch.cuda.current_stream().wait_stream(self.comm_stream)
-        if self.scheduler is not None:
-            self.scheduler.step()
-        self.optimizer.step()
-        return {"loss": loss.detach(), "accuracy": accuracy, "lr": self.optimizer.param_groups[0]["lr"]}
+    def _finish_early(self):
+        """Finish the early slice: form its dv / dg while the rest of the model back-propagates."""
+        self.plan.backward(*self._early_entries)
+        return torch.cuda.current_stream().record_event()
 
-    def step(self, top, bottom=None):
-        if self.arena is not None:
-            return self._step_arena(top, bottom)
-        self.model.zero_grad(set_to_none=True)
+    # ------------------------------------------------------------------ the step
+    def _forward_loss(self, top, bottom):
         if self.hier == "top":
             target = top
             out, _ = self.model(top)
         else:
             target = bottom
             out, _ = self.model(bottom, condition=top)
-        loss, accuracy = ops.prior_loss(out, target)
-        loss.backward()
+        return ops.prior_loss(out, target)
+
+    def step(self, top, bottom=None):
+        plan = self.plan
+        if plan is None:                # arena=False: one weight-norm launch per layer and pass, one Adam launch per tensor
+            self.model.zero_grad(set_to_none=True)
+            loss, accuracy = self._forward_loss(top, bottom)
+            loss.backward()
+        else:
+            self.arena.zero_grad()
+            self._sent, self._hooks_seen = [], {}
+            plan.prepare()
+            plan.active = True
+            try:
+                loss, accuracy = self._forward_loss(top, bottom)
+                loss.backward()
+            finally:
+                plan.active = False
+                plan.invalidate()
+            # the entries whose slice did not go out early: everything without data parallelism
+            plan.backward(0, self._early_entries[0] if self._sent else plan.n)
+            self._reduce_unsent()
         if self.scheduler is not None:
             self.scheduler.step()
         self.optimizer.step()
         return {"loss": loss.detach(), "accuracy": accuracy, "lr": self.optimizer.param_groups[0]["lr"]}
-
-    # ------------------------------------------------------------------ checkpoint / resume
-    def _need_arena(self, what):
-        if self.arena is None:
-            raise RuntimeError(f"Stage2Trainer.{what} needs the arena path (arena=True)")
-
-    def state_dict(self):
-        """As Stage1Trainer.state_dict(): "model" is exactly what the reference saves (train_pixelsnail.py:150-153), then the
-        Adam moments in registration order, the step count, learning rate / betas and the schedule position."""
-        self._need_arena("state_dict")
-        group = self.optimizer.param_groups[0]
-        return {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-                "adam_m": self.arena.canonical(self.optimizer._m), "adam_v": self.arena.canonical(self.optimizer._v),
-                "adam_t": self.optimizer._t,
-                "lr": group["lr"], "betas": tuple(group["betas"]),
-                "scheduler": None if self.scheduler is None else self.scheduler.state_dict()}
-
-    def load_state_dict(self, sd):
-        """Inverse of state_dict(); also accepts a bare model state_dict (the reference's checkpoint['model'], with or
-        without DataParallel's "module." prefix): optimizer state then starts fresh."""
-        self._need_arena("load_state_dict")
-        model_sd = sd["model"] if isinstance(sd.get("model"), dict) else sd      # (the reference's file: {'model', 'args'})
-        full = model_sd is not sd and "adam_m" in sd
-        model_sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in model_sd.items()}
-        if full and (self.scheduler is None) != (sd.get("scheduler") is None):
-            raise RuntimeError("Stage2Trainer.load_state_dict: checkpoint and trainer disagree about --sched")
-        if full and sd["adam_m"].numel() != sum(p.numel() for p in self.arena.params):
-            raise RuntimeError("Stage2Trainer.load_state_dict: optimizer state belongs to a different model")
-        self.model.load_state_dict(model_sd)          # copies INTO the arena views: parameters stay re-homed
-        ops.touch_weights(self.arena.params)
-        self.plan.invalidate()
-        if hasattr(self.model, "_bg"):
-            self.model._bg = None
-        if full:
-            dev = self.optimizer._m.device
-            self.arena.from_canonical(sd["adam_m"].to(dev), self.optimizer._m)
-            self.arena.from_canonical(sd["adam_v"].to(dev), self.optimizer._v)
-            self.optimizer._t = int(sd["adam_t"])
-            for group in self.optimizer.param_groups:
-                group["lr"], group["betas"] = sd["lr"], tuple(sd["betas"])
-            if self.scheduler is not None:
-                self.scheduler.load_state_dict(sd["scheduler"])
