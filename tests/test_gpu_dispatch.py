@@ -1,6 +1,6 @@
 """Every conv dispatch branch against fp64, at its shape boundaries (csrc/vq2_conv.hip plan_conv with its conv_k4s2_c4,
 conv1x1_k64, Winograd (plan_wino) and sub-pixel gates and its fast-GEMM instantiation flags, use_convT_small; vq2_wgrad.hip
-plan_wgrad / launch_wgrad).  Kernel selection is a function of the layer's shape and strides alone, so the only way to reach a kernel is a
+plan_wgrad: role, kernel family, Winograd mode and the tile out of WGRAD_TILES).  Kernel selection is a function of the layer's shape and strides alone, so the only way to reach a kernel is a
 shape on the right side of every threshold: CASES is that list, written down as data, with the profiler label (tile and
 instantiation included) each case must produce under VQ2_FORMS = all / direct / general.
 
@@ -202,7 +202,7 @@ CASES = [
 #   K 448 | 512, Co % 64, Ci % 16);  use_convT_small (Cor 3 | 4, Co 4 | 8, Ci % 16; refusals: test_conv_transpose_small_refusals);
 #   plan_wino (rows64 | rows32 | neither, Ci 24 | 32 | 36, Co % 64, Co % 128 for k4s2 on 32-pixel rows, wide 399 | 400).
 # Branches that cannot be reached through the ABI, by the code (no case can exist):
-#   - launch_wgrad, `rows_per_split % 32 == 0`: plan_wgrad rounds rows_per_split up to a multiple of 32;
+#   - plan_wgrad's kernel family, `rows_per_split % 32 == 0`: it rounds rows_per_split up to a multiple of 32 just before;
 #   - plan_conv's `uni`, `K % BK == 0` once `Ci % BK == 0` holds: K = KH * KW * Ci;
 #   - the non-uniform instantiation of the four-per-CU 128x128x16 tile: its gate (Ci % 16 == 0, below 1 GiB) implies `small`,
 #     and `occ4` makes `uni` true then;

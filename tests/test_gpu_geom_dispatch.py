@@ -1,6 +1,6 @@
 """The second conv descriptor (vq2_conv_geom: rectangular kernels with top / left padding, output the size of the input) on
 every kernel the stage-2 prior trains with, against fp64 at the shape boundaries of plan_conv (csrc/vq2_conv.hip),
-plan_wgrad and wgrad_fast_ok (csrc/vq2_wgrad.hip).  tests/test_gpu_dispatch.py is that table for the first descriptor; this
+plan_wgrad with its kernel-family test (csrc/vq2_wgrad.hip).  tests/test_gpu_dispatch.py is that table for the first descriptor; this
 module is its counterpart and shares its helpers (counter-based inputs, launched / short_label / conv_labels, sliced /
 guarded / untouched, the label syntax "<family>|<variant>") unchanged.  The geometries (KH, KW, pad_top, pad_left) are
 KERNELS of tests/test_gpu_gated_resblock.py, whose own fp64 test stops at 144 rows and 8-pixel rows: every label here is

@@ -157,6 +157,37 @@ def test_forms_switch_plans_in_a_child_process(amd):
     assert r.returncode != 0 and "VQ2_FORMS" in r.stderr, r.stderr[-2000:]
 
 
+def test_wgrad_plans_match_the_recorded_ones(amd):
+    """tests/golden/wgrad_plans.json (scripts/record_wgrad_plans.py) holds what plan_wgrad decided for every layer of the
+    workloads, every weight-gradient row of the two dispatch tables and both sides of every plan condition, as far as the
+    library shows it without a launch: workspace size and the reduction job, with and without a bias gradient, under every
+    VQ2_FORMS.  Replayed here and compared exactly, this process's VQ2_FORMS in-process and the other values in a child each.
+    The file is a recording of the commit that wrote it, not a specification: a change that moves a plan on purpose records
+    it again and says which entries moved."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("record_wgrad_plans", os.path.join(ROOT, "scripts", "record_wgrad_plans.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    with open(rec.GOLDEN) as f:
+        golden = json.load(f)
+    entries = golden["entries"]
+    assert golden["fields"] == rec.FIELDS and len(entries) >= 300
+    here = os.environ.get("VQ2_FORMS", "all")
+    kids = {forms: rec.replay_in_child(forms, rec.GOLDEN) for forms in rec.FORMS if forms != here}
+    got = {here: rec.plans(entries, amd._lib)}
+    got.update({forms: rec.child_result(p) for forms, p in kids.items()})
+    for forms in rec.FORMS:
+        moved = [(e["src"], e["kind"], e["d"], e[forms], g) for e, g in zip(entries, got[forms]) if e[forms] != g]
+        assert not moved, (forms, len(moved), moved[:3])
+    # the recording reaches what it is there for: every role and Winograd mode, S = 1 and S > 32, both bias layouts
+    modes = set(e["all"][0][rec.FIELDS.index("swapped")] for e in entries)
+    assert modes == {0, 1, 2, 4, 7}, modes
+    S = [e["all"][0][rec.FIELDS.index("S")] for e in entries]
+    assert min(S) == 1 and max(S) > 32
+    assert any(e["all"][0][-1] > 0 for e in entries) and any(e["all"][1][-3] == 0 < e["all"][0][-3] for e in entries)
+
+
 def test_invalid_arguments_are_rejected_without_gpu(amd):
     lib = amd._lib.lib
     d = amd._lib.ConvDesc()
@@ -210,7 +241,7 @@ def test_invalid_arguments_are_rejected_without_gpu(amd):
 def _label_families_in_source():
     """Every kernel label the library can print, tile included, read from csrc/*.hip: the prof_label format strings, and for
     the templated launchers the template arguments in the tile tables (FAST_TILES / GEN_TILES of vq2_conv.hip, the three tables
-    of vq2_wino.hip) and at the call sites of launch_wgrad."""
+    of vq2_wino.hip, WGRAD_TILES of vq2_wgrad.hip)."""
     src = {f: open(os.path.join(ROOT, "vq-vae-2-pytorch_amd", "csrc", f)).read()
            for f in os.listdir(os.path.join(ROOT, "vq-vae-2-pytorch_amd", "csrc")) if f.endswith((".hip", ".cpp"))}
     fams = set(m.split("|")[0] for text in src.values() for m in re.findall(r'prof_label\("([^"]+)"', text))
@@ -220,10 +251,15 @@ def _label_families_in_source():
         tiles["fast"].add("conv_gemm<%dx%dx%s>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32, bk))
     for a, b, c, d_, bk in re.findall(r"\bgen_tile<(\d), (\d), (\d), (\d), (\d+)", conv):
         tiles["gen"].add("conv_gemm<%dx%dx%s>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32, bk))
-    for a, b, c, d_ in re.findall(r"launch_wgrad<(\d), (\d), (\d), (\d)>\(P", wgrad):
+    rows = re.findall(r"\bwgrad_tile<(\d), (\d), (\d), (\d)>\(\)", wgrad)
+    for a, b, c, d_ in rows:
         tiles["wgrad"].add("wgrad<%dx%d>" % (int(a) * int(c) * 32, int(b) * int(d_) * 32))
-    cand = re.search(r"cand\[6\]\[2\] = \{(.*?)\};", wgrad).group(1)
-    assert tiles["wgrad"] == set("wgrad<%sx%s>" % t for t in re.findall(r"\{(\d+), (\d+)\}", cand))   # launchers == candidates
+    # WGRAD_TILES is the only list: every row once and all of them inside the table, no kernel or launcher instantiated with
+    # literal tile arguments anywhere else, no second list of tile dimensions
+    table = re.search(r"WGRAD_TILES\[\] = \{(.*?)\n\};", wgrad, re.S).group(1)
+    assert len(rows) == len(set(rows)) == len(re.findall(r"\bwgrad_tile<\d", table))
+    assert not re.search(r"\b(launch_wgrad|wgrad_kernel|wgrad_fast_kernel)<\d", wgrad)
+    assert not re.search(r"\{\d+, \d+\}, \{\d+, \d+\}", wgrad)
     for tpw, nt in re.findall(r"\bwino3_tile<(\d+), (\d), \d+>", wino):
         tiles["wino"].add("conv_wino3<%dx%d,nt%s>" % (64 // int(tpw), 2 * int(tpw), nt))
     for tpw, nt in re.findall(r"\bk4s2_tile<(\d+), (\d), \d+>", wino):

@@ -238,14 +238,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams P) {
 // is "uniform chunk base + per-thread constant" -- one vector add per load, fetched with raw buffer loads
 // whose range check supplies the zeros (no exec branches, no 64-bit address math).  With two waves per
 // SIMD the partner's fp32 MFMAs starve the vector ALU, so the address work is what was limiting.
-typedef unsigned int u32x4w __attribute__((ext_vector_type(4)));
-constexpr int WOOB = 0x7FFFFFF0;
-constexpr unsigned WRSRC_FLAGS = 0x00020000;
-
-__device__ __forceinline__ float4 as_f4w(u32x4w v) {
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
+// (u32x4, OOB, RSRC_FLAGS, as_f4: vq2_conv.h)
 // WINO (3x3 stride-1 pad-1, 128 x 128 tiles, I % 128 == 0, Wo % 64 == 0): the same sum as F(2,3) Winograd along the image
 // rows (csrc/vq2_wino.hip has the forward form).  The reduction runs over column PAIRS (P.M, P.rows_per_split, P.Wo are
 // in pairs... P.Wo stays in pixels), the K axis is (kernel row kh, Winograd index v, channel): for pair t of a row with
@@ -286,9 +279,9 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
     const int m_end = min(P.M, m_begin + P.rows_per_split);
 
     const __amdgpu_buffer_rsrc_t rg =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.g), 0, (WINO ? 2 : 1) * P.M * P.ldg * 4, WRSRC_FLAGS);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.g), 0, (WINO ? 2 : 1) * P.M * P.ldg * 4, RSRC_FLAGS);
     const __amdgpu_buffer_rsrc_t rx =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.x), 0, P.N * P.H * P.W * P.ldx * 4, WRSRC_FLAGS);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.x), 0, P.N * P.H * P.W * P.ldx * 4, RSRC_FLAGS);
 
     // per-thread constants
     const int g_c = o0 + (tid % G_C4) * 4;
@@ -391,8 +384,8 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
         uwo = r - uho * row_len;
     }
 
-    u32x4w rgv[G_LD], rxv[X_LD];
-    u32x4w rgw[WINO ? G_LD : 1], rxw[WINO ? X_LD : 1];       // WINO: the second pixel of every staged element
+    u32x4 rgv[G_LD], rxv[X_LD];
+    u32x4 rgw[WINO ? G_LD : 1], rxw[WINO ? X_LD : 1];       // WINO: the second pixel of every staged element
     float4 bsum4 = make_float4(0.f, 0.f, 0.f, 0.f);          // WINO == 2, conv-transpose: bias partial of this thread's 4 channels
     auto load_chunk_wino = [&](int mbase) {
         const int rows_left = m_end - mbase;                  // uniform (pairs)
@@ -404,11 +397,11 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
                 const int col = 2 * (uwo + ((g_r + j * G_RSTEP) & (two_row ? 15 : 31)));
                 const bool va = v && (unsigned)(col + go_a) < (unsigned)P.Wo;
                 const bool vb = v && (unsigned)(col + go_b) < (unsigned)P.Wo;
-                rgv[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, va ? gbase + g_const[j] : WOOB, 0, 0);
-                rgw[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, vb ? gbase + g_const[j] + (go_b - go_a) * P.ldg * 4 : WOOB, 0, 0);
+                rgv[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, va ? gbase + g_const[j] : OOB, 0, 0);
+                rgw[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, vb ? gbase + g_const[j] + (go_b - go_a) * P.ldg * 4 : OOB, 0, 0);
             } else {
-            rgv[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, v ? gbase + g_const[j] : WOOB, 0, 0);
-            rgw[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, (v && g_two) ? gbase + g_const[j] + P.ldg * 4 : WOOB, 0, 0);
+            rgv[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, v ? gbase + g_const[j] : OOB, 0, 0);
+            rgw[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, (v && g_two) ? gbase + g_const[j] + P.ldg * 4 : OOB, 0, 0);
             }
         }
         constexpr int CS = WINO == 2 ? 4 : 2;
@@ -426,8 +419,8 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
             const bool v = ((x_r + j * X_RSTEP) >= 16 ? hv1 : hv0) && (x_r + j * X_RSTEP) < rows_left;
             const bool va = v && (unsigned)(iwu + x_iw[j] + xo_a) < (unsigned)P.W;
             const bool vb = v && want_b && (unsigned)(iwu + x_iw[j] + xo_b) < (unsigned)P.W;
-            rxv[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, va ? xbase + x_const[j] + xa : WOOB, 0, 0);
-            rxw[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, vb ? xbase + x_const[j] + xb : WOOB, 0, 0);
+            rxv[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, va ? xbase + x_const[j] + xa : OOB, 0, 0);
+            rxw[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, vb ? xbase + x_const[j] + xb : OOB, 0, 0);
         }
         uwo += WG_BKR;
         if (uwo >= row_len) {
@@ -443,7 +436,7 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
 #pragma unroll
         for (int j = 0; j < G_LD; ++j) {
             const bool v = g_cv && (g_r + j * G_RSTEP) < rows_left;
-            rgv[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, v ? gbase + g_const[j] : WOOB, 0, 0);
+            rgv[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, v ? gbase + g_const[j] : OOB, 0, 0);
         }
         const int ihu = uho * P.stride - P.pad_h;             // uniform
         const int xbase = ((un * P.H + ihu) * P.W + uwo * P.stride - P.pad_w) * P.ldx * 4;  // uniform
@@ -452,7 +445,7 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
 #pragma unroll
         for (int j = 0; j < X_LD; ++j) {
             const bool v = hv && (x_r + j * X_RSTEP) < rows_left && (unsigned)(iwu + x_iw[j]) < (unsigned)P.W;
-            rxv[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, v ? xbase + x_const[j] : WOOB, 0, 0);
+            rxv[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, v ? xbase + x_const[j] : OOB, 0, 0);
         }
         // next chunk: 32 rows further along the same output row, or the start of the next one
         uwo += WG_BKR;
@@ -466,11 +459,11 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
         float *xs = Xs + buf * WG_BKR * BNK;
 #pragma unroll
         for (int j = 0; j < G_LD; ++j) {
-            float4 v = as_f4w(rgv[j]);
+            float4 v = as_f4(rgv[j]);
             if (RELU_G) v = relu4(v);
             if constexpr (WINO) {
                 if (g_two) {                                   // workgroup-uniform
-                    float4 w = as_f4w(rgw[j]);
+                    float4 w = as_f4(rgw[j]);
                     if (RELU_G) w = relu4(w);
                     v = make_float4(fmaf(sg, w.x, v.x), fmaf(sg, w.y, v.y), fmaf(sg, w.z, v.z), fmaf(sg, w.w, v.w));
                 }
@@ -479,9 +472,9 @@ __global__ __launch_bounds__(256) void wgrad_fast_kernel(const WgradParams P) {
         }
 #pragma unroll
         for (int j = 0; j < X_LD; ++j) {
-            float4 v = as_f4w(rxv[j]);
+            float4 v = as_f4(rxv[j]);
             if constexpr (WINO) {
-                float4 w = as_f4w(rxw[j]);
+                float4 w = as_f4(rxw[j]);
                 if (RELU_X) { v = relu4(v); w = relu4(w); }
                 if (WINO == 2 && bias2u) {                     // (rows past the split and out-of-range pixels were read as 0)
                     bsum4.x += v.x + w.x; bsum4.y += v.y + w.y; bsum4.z += v.z + w.z; bsum4.w += v.w + w.w;
@@ -673,6 +666,9 @@ __device__ __forceinline__ void wino_reduce_unit(int mode, int t, int lane, int 
 // 256 threads = 32 outputs x 8 split-lanes: lane g adds splits g, g+8, ... (4 loads in flight), the 8
 // partial sums are combined through LDS in a fixed order -> bit-reproducible, and latency is paid
 // S/32 times instead of S times.  The last workgroup also folds the bias partials.
+// (This kernel and wgrad_reduce_batched_kernel take the same job -- wgrad_job_init_impl fills it for both -- and give the
+// same dw, but they are NOT one kernel: with more than 32 bias partials this one adds them into one accumulator per lane,
+// the batched one into four (its bias units run through the slab loop), so the db bits differ.  Merging them changes bits.)
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ ws, float *__restrict__ dw, int O,
                                                            int I, int Or, int Ir, int taps, int S,
                                                            const float *__restrict__ bias_ws, float *__restrict__ db,
@@ -743,6 +739,7 @@ static int colsum_impl(const float *dy, int64_t rows, int C, int ld, float *db, 
 // All layers' slab reductions in ONE launch (the per-layer reductions are latency-bound and tiny).
 // Index space = "units" of 32 consecutive outputs; a job owns [unit_offset, unit_offset + n_units_w +
 // n_units_b): first the weight units, then the bias units.  Same 32 x 8 fixed-order scheme as above.
+// (Bias units share the four-accumulator loop of the weight units: see the note at wgrad_reduce_kernel before merging.)
 __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const vq2_wgrad_job *__restrict__ jobs, int njobs,
                                                                    int64_t total_units) {
     __shared__ float part[8][33];
@@ -799,16 +796,95 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const vq2_wgr
     }
 }
 
+// ====================================================================== the plan: roles, kernel, tile, splits
+// plan_wgrad() decides everything about a launch from the layer (ConvGeo) alone; wgrad_params() and wgrad_job_init_impl()
+// fill the kernels' arguments from it, the tile's launcher launches what it says, wgrad_label() prints it (as on the
+// forward side: plan_conv / conv_tiles / conv_label / launch_conv).
+// Roles (see the head of this file): plain conv, the same conv with x and dy exchanged (plan_wgrad says when), conv-transpose
+enum WgradRole { WGRAD_PLAIN, WGRAD_EXCHANGED, WGRAD_CONVT };
+enum WgradFamily { WGRAD_GEN, WGRAD_FAST, WGRAD_WINO };   // wgrad_kernel, wgrad_fast_kernel direct, wgrad_fast_kernel<..., WINO = wino>
+
 struct WgradPlan {
-    int O, I, K, M, S, rows_per_split, bmo, bnk;
-    int tile;     // position of (bmo, bnk) in the candidate list
-    int swapped;  // roles of x and dy exchanged (see plan_wgrad)
-    int wino;     // F(2,3) Winograd along the rows: K = 12 * I (kh, v, i), M in column pairs (wgrad_fast_kernel<..., WINO>)
+    int role, family;   // WgradRole, WgradFamily
+    int wino;           // WGRAD_WINO: the mode, 1 F(2,3) along the rows, 2 F(2,2) by column parity, 3 F(2,3) with exchanged
+                        // roles (K and M are then the Winograd ones, M in column pairs: see wgrad_fast_kernel)
+    int tile;           // position in WGRAD_TILES
+    int O, I, K, M, S, rows_per_split;   // the GEMM [O x M] * [M x K] and its split
+    int Or, Ir;         // real channels of the rows and columns of a slab: the reduction writes dw for those only
+    int bias_taps, bias_nslots, bias_splits;   // see WgradParams; vq2_wgrad_job.bias_splits (S * nslots, or 0 for [S][O])
+    size_t bias_floats; // bias partials behind the S slabs: [S][nslots][I] from the gathered operand, or [S][O]
+    int mode;           // the reduction kernels' mode word (vq2_wgrad_job.swapped): bit 0 exchanged roles, bits 1-2 wino
+    long ext_x, ext_g;  // element counts of the two operands as the kernels index them
 };
 
+// The two operands as the kernels see them -- the exchange of x and dy, written once: X is gathered through the taps (an
+// H x W grid) and is dy unless the role is plain, G is streamed row by row (an Ho x Wo grid, M = N * Ho * Wo rows).
+static WgradParams wgrad_operands(const ConvGeo *d, int role) {
+    WgradParams P{};
+    P.N = d->N; P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = d->pad_h; P.pad_w = d->pad_w;
+    P.H = d->H; P.W = d->W; P.Ho = d->H; P.Wo = d->W;
+    P.ldx = role == WGRAD_PLAIN ? d->ldx : d->ldy;
+    P.ldg = role == WGRAD_PLAIN ? d->ldy : d->ldx;
+    if (role == WGRAD_PLAIN) { P.Ho = out_hw(d).h; P.Wo = out_hw(d).w; }
+    else if (role == WGRAD_CONVT) { P.H = 2 * d->H; P.W = 2 * d->W; }      // dy is the 2H x 2W tensor
+    else { P.stride = 1; P.pad_h = P.pad_w = d->KH - 1 - d->pad_h; }       // dy the size of x; flipped taps, pad' = K - 1 - p
+    return P;
+}
+
+// The launcher of a tile picks the instantiation the plan names: the family, and the operand the ReLU sits on (compile-time
+// in the fast kernel: every vector instruction competes with the MFMAs).  The Winograd modes exist on one tile each -- 1 and
+// 2 on 128 x 128, 3 on 128 x 96 -- and without a ReLU on the operand that is never x (mode 1: G, mode 3: X).
+template <int WM, int WN, int MT, int NT>
+static int launch_wgrad(const WgradPlan &pl, const WgradParams &P, hipStream_t s) {
+    constexpr int BMO = WM * MT * 32, BNK = WN * NT * 32;
+    const bool rx = P.relu_x, rg = P.relu_g;
+    void (*kern)(const WgradParams) = nullptr;
+    if (pl.family == WGRAD_GEN) kern = wgrad_kernel<WM, WN, MT, NT>;
+    else if (pl.family == WGRAD_FAST)
+        kern = rx ? wgrad_fast_kernel<WM, WN, MT, NT, true, false>
+                  : rg ? wgrad_fast_kernel<WM, WN, MT, NT, false, true> : wgrad_fast_kernel<WM, WN, MT, NT, false, false>;
+    else if constexpr (BMO == 128 && BNK == 128) {
+        if (pl.wino == 1) kern = rx ? wgrad_fast_kernel<WM, WN, MT, NT, true, false, 1> : wgrad_fast_kernel<WM, WN, MT, NT, false, false, 1>;
+        if (pl.wino == 2)
+            kern = rx ? wgrad_fast_kernel<WM, WN, MT, NT, true, false, 2>
+                      : rg ? wgrad_fast_kernel<WM, WN, MT, NT, false, true, 2> : wgrad_fast_kernel<WM, WN, MT, NT, false, false, 2>;
+    } else if constexpr (BMO == 128 && BNK == 96) {
+        if (pl.wino == 3) kern = rg ? wgrad_fast_kernel<WM, WN, MT, NT, false, true, 3> : wgrad_fast_kernel<WM, WN, MT, NT, false, false, 3>;
+    }
+    if (!kern) return set_error(VQ2_ERR_INVALID, "conv_wgrad: the %d x %d tile has no Winograd mode %d", BMO, BNK, pl.wino);
+    const size_t lds = (size_t)2 * WG_BKR * (BMO + BNK) * sizeof(float);
+    allow_big_lds(kern, lds);
+    // (Winograd modes: K is a whole number of tiles -- mode 3 has four, one per v -- and O a multiple of 128)
+    hipLaunchKernelGGL(kern, dim3(((P.K + BNK - 1) / BNK) * ((P.O + BMO - 1) / BMO) * pl.S), dim3(256), lds, s, P);
+    return check_launch(pl.wino == 3 ? "wgrad_fast_kernel<wino sw>" : pl.wino ? "wgrad_fast_kernel<wino>" : "wgrad_kernel");
+}
+
+// Every tile (o x k) once, with its launcher, in the order plan_wgrad tries them (a plan's `tile` is the position).
+struct WgradTile { int bmo, bnk; int (*launch)(const WgradPlan &, const WgradParams &, hipStream_t); };
+template <int WM, int WN, int MT, int NT>
+static constexpr WgradTile wgrad_tile() { return {WM * MT * 32, WN * NT * 32, launch_wgrad<WM, WN, MT, NT>}; }
+static constexpr WgradTile WGRAD_TILES[] = {
+    wgrad_tile<2, 2, 2, 2>(),     // 128 x 128
+    wgrad_tile<1, 4, 2, 1>(),     // 64 x 128
+    wgrad_tile<1, 4, 1, 2>(),     // 32 x 256
+    // 128 x 96 = one kernel row of a 3x3 conv with 32 gathered channels (the ResBlock weight gradient with
+    // exchanged roles, K = 288): 48 MFMAs per wave and chunk instead of 16 for the same staging
+    wgrad_tile<4, 1, 1, 3>(),
+    wgrad_tile<4, 1, 1, 1>(),     // 128 x 32 (1x1 convs with few inputs)
+    wgrad_tile<2, 2, 1, 1>(),     // 64 x 64
+};
+constexpr int WGRAD_NTILES = sizeof(WGRAD_TILES) / sizeof(WgradTile);
+
+// position of the tile with these dimensions (the two that plan_wgrad names exist: checked when this file is compiled)
+static constexpr int wgrad_tile_of(int bmo, int bnk) {
+    for (int i = 0; i < WGRAD_NTILES; ++i)
+        if (WGRAD_TILES[i].bmo == bmo && WGRAD_TILES[i].bnk == bnk) return i;
+    return -1;
+}
+static_assert(wgrad_tile_of(128, 128) >= 0 && wgrad_tile_of(128, 96) >= 0, "plan_wgrad names a tile that WGRAD_TILES lacks");
+
 static WgradPlan plan_wgrad(const ConvGeo *d) {
-    WgradPlan p;
-    p.swapped = 0;
+    WgradPlan p{};
     // A stride-1 "same" conv with few output channels (the ResBlock 3x3, 128 -> 32): gathering the im2col
     // of the WIDE tensor x re-reads it KH*KW times through L2.  The same sum with the roles exchanged,
     //   dw[co][ci][kh][kw] = sum_q relu(x)[q][ci] * dy[q - (kh-p, kw-p)][co],
@@ -820,22 +896,20 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
     // Winograd modes: tensors that the 32-bit byte offsets of wgrad_fast_kernel reach (x and dy counted over the INPUT grid)
     const long pix = (long)d->N * d->H * d->W;
     const bool wino = forms() == FORMS_ALL && pix * d->ldx < FAST_REACH && pix * d->ldy * (d->transposed ? 4 : 1) < FAST_REACH;
-    const ConvHW o = out_hw(d);
     if (fast && !d->transposed && d->stride == 1 && d->KH == d->KW && d->pad_h == d->pad_w && 2 * d->pad_h == d->KH - 1 &&
-        d->KH > 1 && d->Co <= 32 && d->Ci >= 64) {
-        p.swapped = 1;
-        p.O = d->Ci; p.I = d->Co;
-        p.M = d->N * d->H * d->W;
-    } else if (!d->transposed) {
-        p.O = d->Co; p.I = d->Ci;
-        p.M = d->N * o.h * o.w;
-    } else {
-        p.O = d->Ci; p.I = d->Co;
-        p.M = d->N * d->H * d->W;
-    }
+        d->KH > 1 && d->Co <= 32 && d->Ci >= 64)
+        p.role = WGRAD_EXCHANGED;
+    else
+        p.role = d->transposed ? WGRAD_CONVT : WGRAD_PLAIN;
+    const WgradParams v = wgrad_operands(d, p.role);
+    const bool plain = p.role == WGRAD_PLAIN;
+    p.O = plain ? d->Co : d->Ci;
+    p.I = plain ? d->Ci : d->Co;
+    p.Or = plain ? real_co(d) : real_ci(d);
+    p.Ir = plain ? real_ci(d) : real_co(d);
+    p.M = d->N * v.Ho * v.Wo;
     p.K = d->KH * d->KW * p.I;
-    p.wino = 0;
-    if (wino && !p.swapped && !d->transposed && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 &&
+    if (wino && plain && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 &&
         p.O % 128 == 0 && p.I % 128 == 0 && (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0))) {
         p.wino = 1;
         p.K = 12 * p.I;
@@ -843,7 +917,7 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
     }
     {   // 4x4 stride-2 conv / conv-transpose: F(2,2) by column parity over output column pairs
         const int wo = d->transposed ? d->W : d->W / 2;       // width of the G operand's grid
-        if (wino && !p.swapped && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_h == 1 && d->H % 2 == 0 &&
+        if (wino && p.role != WGRAD_EXCHANGED && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_h == 1 && d->H % 2 == 0 &&
             d->W % 2 == 0 && p.O % 128 == 0 && (p.I == 64 || p.I % 128 == 0) &&
             (wo % 64 == 0 || (wo == 32 && (d->transposed ? d->H : d->H / 2) % 2 == 0))) {
             p.wino = 2;
@@ -851,28 +925,31 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
             p.M = p.M / 2;
         }
     }
-    // output tile (o x k): the candidate that wastes the least padded work, larger tile on ties
-    // 128 x 96 = one kernel row of a 3x3 conv with 32 gathered channels (the ResBlock weight gradient with
-    // exchanged roles, K = 288): 48 MFMAs per wave and chunk instead of 16 for the same staging
-    static const int cand[6][2] = {{128, 128}, {64, 128}, {32, 256}, {128, 96}, {128, 32}, {64, 64}};
-    long best = -1;
-    for (int c = 0; c < (p.wino ? 1 : 6); ++c) {
-        if (cand[c][1] == 96 && p.M < 65536) continue;   // measured: +6 % at 131072 rows, -9 % at 32768
-        const long po = (p.O + cand[c][0] - 1) / cand[c][0] * cand[c][0];
-        const long pk = (p.K + cand[c][1] - 1) / cand[c][1] * cand[c][1];
-        const long work = po * pk;
-        if (best < 0 || work < best) { best = work; p.tile = c; }
+    // output tile (o x k): the one that wastes the least padded work, the earlier (larger) tile on ties; modes 1 and 2
+    // have the 128 x 128 tile only
+    if (p.wino) {
+        p.tile = wgrad_tile_of(128, 128);
+    } else {
+        long best = -1;
+        for (int c = 0; c < WGRAD_NTILES; ++c) {
+            const WgradTile &t = WGRAD_TILES[c];
+            if (t.bnk == 96 && p.M < 65536) continue;   // measured: +6 % at 131072 rows, -9 % at 32768
+            const long po = (p.O + t.bmo - 1) / t.bmo * t.bmo;
+            const long pk = (p.K + t.bnk - 1) / t.bnk * t.bnk;
+            const long work = po * pk;
+            if (best < 0 || work < best) { best = work; p.tile = c; }
+        }
     }
-    if (wino && p.swapped && d->KH == 3 && d->pad_h == 1 && p.I == 32 && p.O % 128 == 0 &&
+    if (wino && p.role == WGRAD_EXCHANGED && d->KH == 3 && d->pad_h == 1 && p.I == 32 && p.O % 128 == 0 &&
         (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0))) {
         p.wino = 3;                 // exchanged roles + F(2,3): four 128 x 96 tiles (v) of three kernel rows each
         p.K = 4 * 96;
         p.M = p.M / 2;
-        p.tile = 3;                 // 128 x 96
+        p.tile = wgrad_tile_of(128, 96);   // whatever the tile search said
     }
-    p.bmo = cand[p.tile][0]; p.bnk = cand[p.tile][1];
-    const int tiles = ((p.K + p.bnk - 1) / p.bnk) * ((p.O + p.bmo - 1) / p.bmo);
-    const int lds = 2 * WG_BKR * (p.bmo + p.bnk) * 4;
+    const int bmo = WGRAD_TILES[p.tile].bmo, bnk = WGRAD_TILES[p.tile].bnk;
+    const int tiles = ((p.K + bnk - 1) / bnk) * ((p.O + bmo - 1) / bmo);
+    const int lds = 2 * WG_BKR * (bmo + bnk) * 4;
     int per_cu = (160 * 1024) / lds;                 // resident workgroups per CU (LDS-bound), at most 4
     if (per_cu > 4) per_cu = 4;
     int S = (256 * per_cu) / tiles;                  // fill the resident slots without a tail round
@@ -883,51 +960,50 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
     rps = (rps + 31) / 32 * 32;
     p.S = (p.M + rps - 1) / rps;
     p.rows_per_split = rps;
+    // The kernel.  wgrad_fast_kernel in its direct forms: rows of whole 32-pixel chunks, tensors that 32-bit byte offsets
+    // reach.  This reach test is NOT the one of the Winograd modes above: it counts the operands as the kernels index them
+    // (X over its own grid, 2H x 2W for a conv-transpose; G over the M reduction rows), that one counts x and dy over the
+    // input grid.  (rows_per_split % 32 cannot fail after the rounding above: it is the kernel's own precondition, kept.)
+    p.ext_x = (long)d->N * v.H * v.W * v.ldx;
+    p.ext_g = (long)p.M * v.ldg;
+    const bool fast_ok = fast && v.Wo % WG_BKR == 0 && p.rows_per_split % WG_BKR == 0 && p.ext_x < FAST_REACH && p.ext_g < FAST_REACH;
+    p.family = p.wino ? WGRAD_WINO : fast_ok ? WGRAD_FAST : WGRAD_GEN;
+    // Bias partials.  Which taps of the gathered operand cover every dy pixel exactly once (bias gradient = their column
+    // sums): exchanged roles -> the centre tap (its own flip); conv-transpose k4 s2 p1 -> taps (1,1),(1,2),(2,1),(2,2), one
+    // per output phase, never out of bounds.  Plain conv: none, the bias gradient is the column sums of the G tile.
+    if (p.wino == 2 && d->transposed) { p.bias_taps = 1; p.bias_nslots = 4; }    // flag only: see wgrad_fast_kernel<..., 2>
+    else if (p.role == WGRAD_EXCHANGED) { p.bias_taps = 1 << ((d->KH / 2) * d->KW + d->KW / 2); p.bias_nslots = 1; }
+    else if (d->transposed) { p.bias_taps = (1 << 5) | (1 << 6) | (1 << 9) | (1 << 10); p.bias_nslots = 4; }
+    p.bias_floats = p.bias_taps ? (size_t)p.S * p.bias_nslots * p.I : (size_t)p.S * p.O;
+    p.bias_splits = p.bias_taps ? p.S * p.bias_nslots : 0;
+    p.mode = (p.role == WGRAD_EXCHANGED) | (p.wino << 1);
     return p;
 }
 
-// Which taps of the gathered operand cover every dy pixel exactly once (bias gradient = their column sums):
-// exchanged roles -> the centre tap (its own flip); conv-transpose k4 s2 p1 -> taps (1,1),(1,2),(2,1),(2,2),
-// one per output phase, never out of bounds.
-static void bias_taps_of(const ConvGeo *d, const WgradPlan &p, int &taps, int &nslots) {
-    taps = 0; nslots = 0;
-    if (p.wino == 2 && d->transposed) { taps = 1; nslots = 4; return; }    // flag only: see wgrad_fast_kernel<..., 2>
-    if (p.swapped) { taps = 1 << ((d->KH / 2) * d->KW + d->KW / 2); nslots = 1; }
-    else if (d->transposed) { taps = (1 << 5) | (1 << 6) | (1 << 9) | (1 << 10); nslots = 4; }
+static size_t wgrad_ws_bytes(const WgradPlan &p) { return ((size_t)p.S * p.O * p.K + p.bias_floats) * sizeof(float); }
+
+// The kernels' arguments of a planned launch; the slabs [S][O][K] come first in ws, the bias partials behind them.
+static int wgrad_params(const ConvGeo *d, const WgradPlan &p, int flags, const float *x, const float *dy, float *db, void *ws,
+                        WgradParams &P) {
+    VQ2_REQUIRE(p.ext_x < (1L << 31) && p.ext_g < (1L << 31), "conv_wgrad: tensor exceeds 2^31 elements");
+    const bool plain = p.role == WGRAD_PLAIN;
+    const int relu = (flags & VQ2_RELU_IN) != 0;       // of x, whichever operand that is
+    P = wgrad_operands(d, p.role);
+    P.x = plain ? x : dy; P.relu_x = plain ? relu : 0;
+    P.g = plain ? dy : x; P.relu_g = plain ? 0 : relu;
+    P.ws = static_cast<float *>(ws);
+    P.bias_ws = db ? P.ws + (size_t)p.S * p.O * p.K : nullptr;
+    P.bias_taps = p.bias_taps; P.bias_nslots = p.bias_nslots;
+    P.O = p.O; P.I = p.I; P.K = p.K; P.M = p.M; P.rows_per_split = p.rows_per_split;
+    return VQ2_OK;
 }
 
-static size_t bias_ws_floats(const ConvGeo *d, const WgradPlan &p) {
-    int taps, nslots;
-    bias_taps_of(d, p, taps, nslots);
-    return taps ? (size_t)p.S * nslots * p.I : (size_t)p.S * p.O;
-}
-
-// Element counts of the two operands of a launch as the kernels index them
-struct WgradExtents { long x, g; };
-static WgradExtents wgrad_extents(const WgradParams &P) { return {(long)P.N * P.H * P.W * P.ldx, (long)P.M * P.ldg}; }
-
-// wgrad_fast_kernel in its direct forms: rows of whole 32-pixel chunks, tensors that 32-bit byte offsets reach
-static bool wgrad_fast_ok(const WgradParams &P) {
-    const WgradExtents E = wgrad_extents(P);
-    return forms() > FORMS_GENERAL && P.Wo % WG_BKR == 0 && P.rows_per_split % WG_BKR == 0 && E.x < FAST_REACH && E.g < FAST_REACH;
-}
-
-template <int WAVES_M, int WAVES_N, int MT, int NT>
-static int launch_wgrad(const WgradParams &P, int S, hipStream_t s) {
-    constexpr int BMO = WAVES_M * MT * 32, BNK = WAVES_N * NT * 32;
-    const size_t lds = (size_t)2 * WG_BKR * (BMO + BNK) * sizeof(float);
-    void (*kern)(const WgradParams);
-    // ReLU flags are compile-time in the fast kernel: every vector instruction competes with the MFMAs
-    switch (!wgrad_fast_ok(P) ? 0 : P.relu_x ? 1 : P.relu_g ? 2 : 3) {
-        case 1:  kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, true, false>; break;
-        case 2:  kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, false, true>; break;
-        case 3:  kern = wgrad_fast_kernel<WAVES_M, WAVES_N, MT, NT, false, false>; break;
-        default: kern = wgrad_kernel<WAVES_M, WAVES_N, MT, NT>; break;
-    }
-    allow_big_lds(kern, lds);
-    dim3 grid(((P.K + BNK - 1) / BNK) * ((P.O + BMO - 1) / BMO) * S);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, P);
-    return check_launch("wgrad_kernel");
+// The profiler label of a planned launch, "wgrad<tile><form>|<shape>,fast|gen" (wgrad_fast_kernel or wgrad_kernel):
+// formatted here and nowhere else.
+static const char *wgrad_label(const WgradPlan &p, const WgradTile &t, const ConvGeo *d) {
+    const char *form = p.wino == 3 ? "swwino" : p.role == WGRAD_EXCHANGED ? "sw" : p.wino == 1 ? "wino" : p.wino == 2 ? "wino4" : "";
+    return prof_label("wgrad<%dx%d>%s|O=%d,K=%d,M=%d,S=%d,k%d,%s", t.bmo, t.bnk, form, p.O, p.K, p.M, p.S, d->KH,
+                      p.family == WGRAD_GEN ? "gen" : "fast");
 }
 
 // ------------------------------------------------------------------ column sums (bias gradient)
@@ -1006,28 +1082,54 @@ static int colsum_impl(const float *dy, int64_t rows, int C, int ld, float *db, 
 
 using namespace vq2;
 
-static size_t wgrad_ws_bytes(const ConvGeo *d) {
-    if (check_forms() || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Ci <= 0 || d->Co <= 0 || d->KH <= 0 || d->KW <= 0) return 0;
-    const WgradPlan p = plan_wgrad(d);
-    return ((size_t)p.S * p.O * p.K + bias_ws_floats(d, p)) * sizeof(float);
+// The preamble of the eight entry points, once per descriptor type: the checks that only that type has, then the common
+// ConvGeo.  `who` names the entry point in the first descriptor's null-pointer message.
+static int entry_geo(const vq2_conv_desc *d, const char *who, ConvGeo &g) {
+    VQ2_REQUIRE(d, "%s: null pointer", who);
+    g = geo_of(d);
+    return VQ2_OK;
+}
+static int entry_geo(const vq2_conv_geom *d, const char *, ConvGeo &g) {
+    if (int e = check_geom(d)) return e;
+    g = geo_of(d);
+    return VQ2_OK;
 }
 
-extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) {
-    if (!d) return 0;
-    const ConvGeo g = geo_of(d);
-    return wgrad_ws_bytes(&g);
+template <class Desc>
+static size_t wgrad_ws_entry(const Desc *d) {
+    ConvGeo g;
+    if (entry_geo(d, "conv_wgrad_workspace_bytes", g) || check_forms() || g.N <= 0 || g.H <= 0 || g.W <= 0 || g.Ci <= 0 ||
+        g.Co <= 0 || g.KH <= 0 || g.KW <= 0)
+        return 0;
+    return wgrad_ws_bytes(plan_wgrad(&g));
 }
 
-extern "C" size_t vq2_convg_wgrad_workspace_bytes(const vq2_conv_geom *d) {
-    if (check_geom(d)) return 0;
-    const ConvGeo g = geo_of(d);
-    return wgrad_ws_bytes(&g);
+extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) { return d ? wgrad_ws_entry(d) : 0; }   // (null: no message)
+extern "C" size_t vq2_convg_wgrad_workspace_bytes(const vq2_conv_geom *d) { return wgrad_ws_entry(d); }
+
+// The reduction job of a planned layer: what wgrad_reduce_batched_kernel reads, and the arguments of wgrad_reduce_kernel.
+static void wgrad_job_init_impl(const ConvGeo *d, const WgradPlan &p, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
+    const float *w = static_cast<const float *>(ws);
+    job->ws = w; job->dw = dw;
+    job->O = p.O; job->I = p.I; job->Or = p.Or; job->Ir = p.Ir;
+    job->swapped = p.mode;
+    job->taps = d->KH * d->KW; job->S = p.S;
+    job->n_units_w = p.wino ? (p.O * (p.wino == 2 ? 8 : 3) * p.I + 31) / 32 : (p.O * p.K + 31) / 32;
+    // without db no bias partials were asked for: nothing of the bias is described
+    job->db = db; job->bias_ws = db ? w + (size_t)p.S * p.O * p.K : nullptr;
+    job->bias_splits = db ? p.bias_splits : 0;
+    job->n_units_b = db ? ((p.bias_taps ? p.Ir : p.Or) + 31) / 32 : 0;
+    job->unit_offset = 0;
 }
 
 // slabs (+ bias partials); reduce == true also runs the per-layer reduction into dw/db
-static int wgrad_impl(const ConvGeo *d, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
+template <class Desc>
+static int wgrad_impl(const Desc *desc, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
                       size_t ws_bytes, vq2_stream_t stream, bool reduce) {
-    VQ2_REQUIRE(d && x && dy && ws && (dw || !reduce), "conv_wgrad: null pointer");
+    ConvGeo g;
+    if (int e = entry_geo(desc, "conv_wgrad", g)) return e;
+    const ConvGeo *d = &g;
+    VQ2_REQUIRE(x && dy && ws && (dw || !reduce), "conv_wgrad: null pointer");
     if (int e = check_forms()) return e;
     VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0 && d->Ci % 4 == 0 && d->Co % 4 == 0,
                 "conv_wgrad: bad dims");
@@ -1039,144 +1141,58 @@ static int wgrad_impl(const ConvGeo *d, int flags, const float *x, const float *
         VQ2_REQUIRE(d->KH == d->KW && d->KH >= 1 && d->KH <= 7 && (d->stride == 1 || d->stride == 2) && d->pad_h >= 0,
                     "conv_wgrad: unsupported conv geometry");
     const WgradPlan p = plan_wgrad(d);
-    VQ2_REQUIRE(ws_bytes >= wgrad_ws_bytes(d), "conv_wgrad: workspace too small");
-    WgradParams P{};
-    P.ws = static_cast<float *>(ws);
-    float *bias_ws = P.ws + (size_t)p.S * p.O * p.K;       // bias partials: [S][O], or [S][nslots][I] from the gathered operand
-    bias_taps_of(d, p, P.bias_taps, P.bias_nslots);
-    P.bias_ws = db ? bias_ws : nullptr;
-    P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = d->pad_h; P.pad_w = d->pad_w;
-    P.O = p.O; P.I = p.I; P.K = p.K; P.M = p.M; P.rows_per_split = p.rows_per_split;
-    P.N = d->N;
-    if (p.swapped) {
-        P.x = dy; P.ldx = d->ldy; P.H = d->H; P.W = d->W;       // gathered operand: dy (same spatial size as x)
-        P.g = x; P.ldg = d->ldx;
-        P.Ho = d->H; P.Wo = d->W;
-        P.stride = 1; P.pad_h = P.pad_w = d->KH - 1 - d->pad_h;
-        P.relu_x = 0; P.relu_g = (flags & VQ2_RELU_IN) != 0;
-    } else if (!d->transposed) {
-        P.x = x; P.ldx = d->ldx; P.H = d->H; P.W = d->W;
-        P.g = dy; P.ldg = d->ldy;
-        P.Ho = out_hw(d).h; P.Wo = out_hw(d).w;
-        P.relu_x = (flags & VQ2_RELU_IN) != 0; P.relu_g = 0;
-    } else {
-        P.x = dy; P.ldx = d->ldy; P.H = 2 * d->H; P.W = 2 * d->W;
-        P.g = x; P.ldg = d->ldx;
-        P.Ho = d->H; P.Wo = d->W;
-        P.relu_x = 0; P.relu_g = (flags & VQ2_RELU_IN) != 0;
-    }
-    VQ2_REQUIRE(wgrad_extents(P).x < (1L << 31) && wgrad_extents(P).g < (1L << 31), "conv_wgrad: tensor exceeds 2^31 elements");
+    VQ2_REQUIRE(ws_bytes >= wgrad_ws_bytes(p), "conv_wgrad: workspace too small");
+    WgradParams P;
+    if (int e = wgrad_params(d, p, flags, x, dy, db, ws, P)) return e;
     hipStream_t s = to_stream(stream);
-    int e;
+    const WgradTile &tile = WGRAD_TILES[p.tile];
     const ConvWork work = conv_work(d, 0, 0);
-    const char *pname = "wgrad";
-    if (prof_enabled()) pname = prof_label("wgrad<%dx%d>%s|O=%d,K=%d,M=%d,S=%d,k%d,%s", p.bmo, p.bnk, p.wino == 3 ? "swwino" : p.swapped ? "sw" : (p.wino == 1 ? "wino" : p.wino == 2 ? "wino4" : ""), p.O, p.K, p.M, p.S, d->KH,
-                                            p.wino || wgrad_fast_ok(P) ? "fast" : "gen");   // wgrad_fast_kernel or wgrad_kernel
-    ProfScope prof(pname, work.flops, work.bytes, s);
-    if (p.wino) {
-        // Winograd forms: one tile each (128 x 96 with exchanged roles, else 128 x 128); the ReLU sits on the operand that is x
-        void (*kern)(const WgradParams);
-        switch (p.wino * 4 + (P.relu_x ? 2 : P.relu_g ? 1 : 0)) {
-            case 1 * 4 + 2: kern = wgrad_fast_kernel<2, 2, 2, 2, true, false, 1>; break;
-            case 1 * 4 + 0:
-            case 1 * 4 + 1: kern = wgrad_fast_kernel<2, 2, 2, 2, false, false, 1>; break;
-            case 2 * 4 + 2: kern = wgrad_fast_kernel<2, 2, 2, 2, true, false, 2>; break;
-            case 2 * 4 + 1: kern = wgrad_fast_kernel<2, 2, 2, 2, false, true, 2>; break;
-            case 2 * 4 + 0: kern = wgrad_fast_kernel<2, 2, 2, 2, false, false, 2>; break;
-            case 3 * 4 + 1: kern = wgrad_fast_kernel<4, 1, 1, 3, false, true, 3>; break;
-            default:        kern = wgrad_fast_kernel<4, 1, 1, 3, false, false, 3>; break;
-        }
-        const size_t lds = (size_t)2 * WG_BKR * (p.bmo + p.bnk) * sizeof(float);
-        allow_big_lds(kern, lds);
-        const int ktiles = p.wino == 3 ? 4 : P.K / 128;
-        hipLaunchKernelGGL(kern, dim3(ktiles * ((P.O + 127) / 128) * p.S), dim3(256), lds, s, P);
-        e = check_launch(p.wino == 3 ? "wgrad_fast_kernel<wino sw>" : "wgrad_fast_kernel<wino>");
-    } else {
-        switch (p.tile) {   // the candidates of plan_wgrad, in their order
-            case 0:  e = launch_wgrad<2, 2, 2, 2>(P, p.S, s); break;     // 128 x 128
-            case 1:  e = launch_wgrad<1, 4, 2, 1>(P, p.S, s); break;     // 64 x 128
-            case 2:  e = launch_wgrad<1, 4, 1, 2>(P, p.S, s); break;     // 32 x 256
-            case 3:  e = launch_wgrad<4, 1, 1, 3>(P, p.S, s); break;     // 128 x 96
-            case 4:  e = launch_wgrad<4, 1, 1, 1>(P, p.S, s); break;     // 128 x 32 (1x1 convs with few inputs)
-            default: e = launch_wgrad<2, 2, 1, 1>(P, p.S, s); break;     // 64 x 64
-        }
-    }
-    if (e) return e;
+    ProfScope prof(prof_enabled() ? wgrad_label(p, tile, d) : "wgrad", work.flops, work.bytes, s);
+    if (int e = tile.launch(p, P, s)) return e;
     if (!reduce) return VQ2_OK;
+    vq2_wgrad_job j;   // what the deferred path hands to wgrad_reduce_batched_kernel, reduced at once
+    wgrad_job_init_impl(d, p, ws, dw, db, &j);
     const int total = p.O * p.K;
     const int blocks = (total + 31) / 32 < 4096 ? (total + 31) / 32 : 4096;
-    const bool sw = d->transposed || p.swapped;
-    const int Or = sw ? real_ci(d) : real_co(d), Ir = sw ? real_co(d) : real_ci(d);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, P.ws, dw, p.O, p.I, Or, Ir, d->KH * d->KW,
-                       p.S, P.bias_ws, db, p.swapped | (p.wino << 1), P.bias_taps ? p.S * P.bias_nslots : 0);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, j.ws, j.dw, j.O, j.I, j.Or, j.Ir, j.taps, j.S,
+                       j.bias_ws, j.db, j.swapped, j.bias_splits);
     return check_launch("wgrad_reduce_kernel");
 }
 
 extern "C" int vq2_conv_wgrad(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *dw, float *db,
                               void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    VQ2_REQUIRE(d, "conv_wgrad: null pointer");
-    const ConvGeo g = geo_of(d);
-    return wgrad_impl(&g, flags, x, dy, dw, db, ws, ws_bytes, stream, true);
+    return wgrad_impl(d, flags, x, dy, dw, db, ws, ws_bytes, stream, true);
 }
-
 extern "C" int vq2_conv_wgrad_partial(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *db,
                                       void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    VQ2_REQUIRE(d, "conv_wgrad: null pointer");
-    const ConvGeo g = geo_of(d);
-    return wgrad_impl(&g, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
+    return wgrad_impl(d, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
 }
-
 extern "C" int vq2_convg_wgrad(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *dw, float *db,
                                void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    if (int e = check_geom(d)) return e;
-    const ConvGeo g = geo_of(d);
-    return wgrad_impl(&g, flags, x, dy, dw, db, ws, ws_bytes, stream, true);
+    return wgrad_impl(d, flags, x, dy, dw, db, ws, ws_bytes, stream, true);
 }
-
 extern "C" int vq2_convg_wgrad_partial(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *db,
                                        void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    if (int e = check_geom(d)) return e;
-    const ConvGeo g = geo_of(d);
-    return wgrad_impl(&g, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
+    return wgrad_impl(d, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
 }
 
-static int wgrad_job_init_impl(const ConvGeo *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job);
+template <class Desc>
+static int wgrad_job_entry(const Desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
+    ConvGeo g;
+    if (int e = entry_geo(d, "wgrad_job_init", g)) return e;
+    VQ2_REQUIRE(ws && dw && job, "wgrad_job_init: null pointer");
+    // (the second descriptor's job_init checks the dims, the first one's never did)
+    VQ2_REQUIRE(!g.same || (g.N > 0 && g.H > 0 && g.W > 0 && g.Ci > 0 && g.Co > 0), "wgrad_job_init: non-positive dims");
+    if (int e = check_forms()) return e;
+    wgrad_job_init_impl(&g, plan_wgrad(&g), ws, dw, db, job);
+    return VQ2_OK;
+}
 
 extern "C" int vq2_wgrad_job_init(const vq2_conv_desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
-    VQ2_REQUIRE(d && ws && dw && job, "wgrad_job_init: null pointer");
-    const ConvGeo g = geo_of(d);
-    return wgrad_job_init_impl(&g, ws, dw, db, job);
+    return wgrad_job_entry(d, ws, dw, db, job);
 }
-
 extern "C" int vq2_convg_wgrad_job_init(const vq2_conv_geom *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
-    if (int e = check_geom(d)) return e;
-    VQ2_REQUIRE(ws && dw && job, "wgrad_job_init: null pointer");
-    VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0, "wgrad_job_init: non-positive dims");
-    const ConvGeo g = geo_of(d);
-    return wgrad_job_init_impl(&g, ws, dw, db, job);
-}
-
-static int wgrad_job_init_impl(const ConvGeo *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
-    if (int e = check_forms()) return e;
-    const WgradPlan p = plan_wgrad(d);
-    const int cir = real_ci(d), cor = real_co(d);
-    const float *w = static_cast<const float *>(ws);
-    job->ws = w; job->dw = dw; job->db = nullptr; job->bias_ws = nullptr;
-    const bool sw = d->transposed || p.swapped;
-    job->O = p.O; job->I = p.I; job->Or = sw ? cir : cor; job->Ir = sw ? cor : cir;
-    job->swapped = p.swapped | (p.wino << 1); job->bias_splits = 0;
-    job->taps = d->KH * d->KW; job->S = p.S;
-    job->n_units_w = p.wino ? (p.O * (p.wino == 2 ? 8 : 3) * p.I + 31) / 32 : (p.O * p.K + 31) / 32;
-    job->n_units_b = 0;
-    if (db) {
-        int taps, nslots;
-        bias_taps_of(d, p, taps, nslots);
-        job->db = db; job->bias_ws = w + (size_t)p.S * p.O * p.K;
-        job->bias_splits = taps ? p.S * nslots : 0;
-        job->n_units_b = ((taps ? job->Ir : job->Or) + 31) / 32;
-    }
-    job->unit_offset = 0;
-    return VQ2_OK;
+    return wgrad_job_entry(d, ws, dw, db, job);
 }
 
 extern "C" int vq2_wgrad_reduce_batched(const vq2_wgrad_job *jobs_dev, int32_t njobs, int64_t total_units,

@@ -7,6 +7,7 @@ every FLOP and every byte moved on this path is a libvq2 kernel.
 """
 from dataclasses import dataclass
 from types import SimpleNamespace
+import contextlib
 import ctypes as C
 import os
 
@@ -30,6 +31,11 @@ PACK_DGRAD = 1
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# `with (torch.cuda.stream(side) if ... else _THIS_STREAM):` -- one launch written once, on the side stream or on the
+# current one (nullcontext holds no state: one object serves every call and every thread)
+_THIS_STREAM = contextlib.nullcontext()
 
 
 def _p(t):
@@ -310,16 +316,15 @@ class WgradBatch:
             self.dirty = True
         # off the backward critical path: overlaps the next layers' data gradients.  A launch that fills the chip by
         # itself gains nothing from a second stream.
-        if n * h * w <= WGRAD_STREAM_MAX_PIXELS:
+        on_side = n * h * w <= WGRAD_STREAM_MAX_PIXELS
+        if on_side:
             side.wait_event(torch.cuda.current_stream().record_event())
-            with torch.cuda.stream(side):
-                check(_abi(spec).wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
-                                                 _p(ent["ws"]), ent["nbytes"], _stream()), "conv_wgrad_partial")
-            x.record_stream(side)
-            dy.record_stream(side)
-        else:
+        with (torch.cuda.stream(side) if on_side else _THIS_STREAM):
             check(_abi(spec).wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
                                              _p(ent["ws"]), ent["nbytes"], _stream()), "conv_wgrad_partial")
+        if on_side:
+            x.record_stream(side)
+            dy.record_stream(side)
         if not ent["used"]:
             ent["used"] = True
             self.order.append(key)
@@ -409,19 +414,17 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
         return (dw if want_dw else None), db
     dw = _grad_slot(weight)
     db = _grad_slot(bias) if (bias is not None and want_db) else None
+    side = None   # the side stream only for a gradient that lands in its arena slot (see StepContext)
     if sc is not None and getattr(weight, "_vq2_grad", None) is not None and dw.data_ptr() == weight._vq2_grad.data_ptr():
         side = sc.stream
         side.wait_event(torch.cuda.current_stream().record_event())
-        with torch.cuda.stream(side):
-            ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
-            check(_abi(spec).wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws),
-                                     nbytes, _stream()), "conv_wgrad")
+    with (torch.cuda.stream(side) if side is not None else _THIS_STREAM):
+        ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
+        check(_abi(spec).wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes,
+                                 _stream()), "conv_wgrad")
+    if side is not None:
         x.record_stream(side)   # keep the caching allocator from recycling these while the side stream reads
         dy.record_stream(side)
-        return (dw if want_dw else None), db
-    ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
-    check(_abi(spec).wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes,
-                             _stream()), "conv_wgrad")
     return (dw if want_dw else None), db
 
 
