@@ -51,12 +51,15 @@ typedef void *vq2_stream_t;
  * revision 10: additions only -- the one-hot convolution, cross-entropy and x2-upsample entry points of the stage-2 prior
  * (csrc/vq2_prior.hip); revision 11: additions only -- the row-incremental sampling entry points (vq2_convg_fwd_row with its
  * workspace query, vq2_causal_attn_fwd_rows, vq2_sample_categorical, vq2_sample_uniforms); revision 12: additions only -- the table-driven
- * weight-norm entry points vq2_wn_table_fwd and vq2_wn_table_bwd with their table entry vq2_wn_entry; see INTEGRATION.md
- * "ABI history").
+ * weight-norm entry points vq2_wn_table_fwd and vq2_wn_table_bwd with their table entry vq2_wn_entry; revision 13, BREAKING
+ * (the first since 4): vq2_conv_desc widened to 16 words that describe both conv forms (pad became pad_top / pad_left,
+ * same_size added); vq2_conv_geom and the eight vq2_convg_* twins removed, every layer goes through the vq2_conv_* entry
+ * points; vq2_conv_dgrad takes the flags argument and vq2_conv_dgrad_ex is gone; vq2_convg_fwd_row and its workspace query
+ * renamed vq2_conv_fwd_row / vq2_conv_fwd_row_workspace_bytes on vq2_conv_desc; see INTEGRATION.md "ABI history").
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 12
+#define VQ2_API_VERSION 13
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -71,17 +74,36 @@ int vq2_prof_report(char *buf, size_t cap);
 
 /* ------------------------------------------------------------------ conv
  * One descriptor describes the FORWARD op; fwd/dgrad/wgrad entry points all
- * take the same descriptor so callers never swap roles by hand.
+ * take the same descriptor so callers never swap roles by hand.  It has two forms:
+ *
+ * same_size == 0, the stage-1 layers: a square kernel (KH == KW) with the same padding on every side (pad_top == pad_left)
  *   conv  (transposed=0): y[N,Ho,Wo,Co] = conv2d(x[N,H,W,Ci], w[Co,Ci,KH,KW], stride, pad)
- *                         Ho = (H+2*pad-KH)/stride+1            (vqvae.py:87,89,105-116,137,184,189)
+ *                         Ho = (H+2*pad-KH)/stride+1; stride 1, or stride 2 with KH = 4, pad 1 on even H and W
+ *                                                               (vqvae.py:87,89,105-116,137,184,189)
  *   convT (transposed=1): y[N,2H,2W,Co] = conv_transpose2d(x, w[Ci,Co,4,4], stride 2, pad 1)
  *                                                               (vqvae.py:150-160,191-193)
+ * same_size == 1, the stage-2 layers: WNConv2d and CausalConv2d of the reference (pixelsnail.py:21-119, whose nn.ZeroPad2d +
+ *   unpadded conv is one op here).  A KH x KW kernel, stride 1, not transposed, output the size of the input:
+ *     y[n,h,w,co] = bias[co] + sum_{kh<KH, kw<KW, ci} w[co,ci,kh,kw] * x[n, h - pad_top + kh, w - pad_left + kw, ci]
+ *   with reads outside the image taken as 0.  KH * KW <= 32.  'downright' is (pad_top, pad_left) = (KH - 1, KW - 1); 'down'
+ *   and 'causal' are (KH - 1, KW / 2) with odd KW; a size-preserving WNConv2d is ((KH - 1) / 2, (KW - 1) / 2) with odd KH, KW.
+ *   Every tap enters the weight gradient, also those a 'causal' layer zeroes in its weight: the reference's gradient there
+ *   is the full correlation.  The data gradient is the correlation with the flipped kernel at (KH - 1 - pad_top,
+ *   KW - 1 - pad_left).
+ * Both forms: 1 <= KH, KW <= 7, 0 <= pad_top < KH, 0 <= pad_left < KW, every tensor below 2^31 elements.  A descriptor
+ * outside these rules is VQ2_ERR_INVALID, except more than 32 taps with same_size (VQ2_ERR_UNSUPPORTED), and reaches no
+ * kernel.  The kernel is chosen by one plan from the shape alone, so same_size changes nothing for a layer both forms can
+ * state (odd square kernel, stride 1, pad (KH - 1) / 2): bit for bit the same result; geometries the Winograd and fused
+ * forms do not name take the general GEMM tiles.
  */
 typedef struct vq2_conv_desc {
     int32_t N, H, W, Ci; /* input, NHWC                                         */
     int32_t Co;          /* output channels                                     */
-    int32_t KH, KW, stride, pad;
+    int32_t KH, KW;      /* kernel rows and columns                             */
+    int32_t stride;
+    int32_t pad_top, pad_left;
     int32_t transposed;  /* 0 conv, 1 conv-transpose (KH=KW=4, stride 2, pad 1) */
+    int32_t same_size;   /* 0 or 1: which of the two forms above                */
     int32_t ldx, ldy;    /* pixel strides of x and y buffers (elements)         */
     int32_t Cir, Cor;    /* channel counts of the reference weight/bias tensors (<= Ci, Co; 0 = same).
                             Ci/Co are rounded up to a multiple of 4 (the 3-channel image and
@@ -150,16 +172,13 @@ int vq2_resblock_bwd_data(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Cm
  * wp: VQ2_PACK_DGRAD packing of w.  mask (shape of x, pixel stride ldmask): the
  * pre-ReLU input when the forward op had VQ2_RELU_IN (ReLU backward fused);
  * residual (shape of x): the skip-path gradient of a ResBlock.  dx has pixel
- * stride lddx; dy has pixel stride d->ldy. */
-int vq2_conv_dgrad(const vq2_conv_desc *d, const float *dy, const float *wp, const float *mask, int32_t ldmask,
-                   const float *residual, int32_t ldres, float *dx, int32_t lddx, vq2_stream_t stream);
-/* Same with flags.  VQ2_MASK_AFTER_RESIDUAL: dx = (dgrad(dy) + residual) * (mask > 0) -- x is itself the
+ * stride lddx; dy has pixel stride d->ldy.
+ * flags: 0 or VQ2_MASK_AFTER_RESIDUAL: dx = (dgrad(dy) + residual) * (mask > 0) -- x is itself the
  * output of a fused trailing ReLU (vqvae.py:122,144) whose backward mask is applied to the COMPLETE
  * gradient here (residual = the gradient of x's other consumer), instead of by a vq2_relu_bwd pass. */
 #define VQ2_MASK_AFTER_RESIDUAL 4
-int vq2_conv_dgrad_ex(const vq2_conv_desc *d, int flags, const float *dy, const float *wp, const float *mask,
-                      int32_t ldmask, const float *residual, int32_t ldres, float *dx, int32_t lddx,
-                      vq2_stream_t stream);
+int vq2_conv_dgrad(const vq2_conv_desc *d, int flags, const float *dy, const float *wp, const float *mask, int32_t ldmask,
+                   const float *residual, int32_t ldres, float *dx, int32_t lddx, vq2_stream_t stream);
 
 /* dw (reference layout, OIHW or IOHW) = wgrad([relu]x, dy) and, if db != NULL, db[Cor] = sum over
  * pixels of dy (bias gradient, fused).  Deterministic split-K: partial slabs in `ws`, then an
@@ -440,44 +459,6 @@ int vq2_wn_table_fwd(const vq2_wn_entry *table, int32_t n_entries, float *params
 int vq2_wn_table_bwd(const vq2_wn_entry *table, int32_t first, int32_t last, const float *params, const float *dw,
                      float *grads, vq2_stream_t stream);
 
-/* ------------------------------------------------------------------ conv, second geometry (stage-2 prior)
- * Rectangular kernels with top / left padding: WNConv2d and CausalConv2d of the reference (pixelsnail.py:21-119, whose
- * nn.ZeroPad2d + unpadded conv is one op here).  Non-transposed, stride 1, output the size of the input:
- *     y[n,h,w,co] = bias[co] + sum_{kh<KH, kw<KW, ci} w[co,ci,kh,kw] * x[n, h - pad_top + kh, w - pad_left + kw, ci]
- * with reads outside the image taken as 0.  1 <= KH, KW <= 7, KH * KW <= 32, 0 <= pad_top < KH, 0 <= pad_left < KW;
- * anything else is VQ2_ERR_INVALID (a malformed descriptor) or VQ2_ERR_UNSUPPORTED (more than 32 taps) and reaches no kernel.
- * 'downright' is (pad_top, pad_left) = (KH - 1, KW - 1); 'down' and 'causal' are (KH - 1, KW / 2) with odd KW; a
- * size-preserving WNConv2d is ((KH - 1) / 2, (KW - 1) / 2) with odd KH and KW.
- * Everything else is as for vq2_conv_desc and each vq2_convg_* function is its vq2_conv_* namesake on this descriptor:
- * flags, bias, residual epilogue, Cir / Cor channel padding, pixel strides, the two weight panels packed from OIHW, the
- * mask / residual / VQ2_MASK_AFTER_RESIDUAL of the data gradient (vq2_convg_dgrad takes the flags of vq2_conv_dgrad_ex), the
- * immediate and the deferred weight gradient with their workspace and reduction job (every tap is computed, also those a
- * 'causal' layer zeroes in its weight: the reference's gradient there is the full correlation), and the 2^31-element checks.
- * The data gradient is the correlation with the flipped kernel at (KH - 1 - pad_top, KW - 1 - pad_left).  The kernel is
- * chosen by the same plan as for vq2_conv_desc, so a square kernel with pad_top == pad_left == (KH - 1) / 2 gives bit for
- * bit what the old descriptor gives; geometries the Winograd and fused forms do not name take the general GEMM tiles. */
-typedef struct vq2_conv_geom {
-    int32_t N, H, W, Ci; /* input, NHWC                                         */
-    int32_t Co;          /* output channels                                     */
-    int32_t KH, KW;      /* kernel rows and columns                             */
-    int32_t pad_top, pad_left;
-    int32_t ldx, ldy;    /* pixel strides of x and y buffers (elements)         */
-    int32_t Cir, Cor;    /* real channel counts, as in vq2_conv_desc            */
-    int32_t reserved;    /* must be 0                                           */
-} vq2_conv_geom;
-int vq2_convg_pack_weight(const vq2_conv_geom *d, int which, const float *w, float *packed, vq2_stream_t stream);
-int vq2_convg_pack_job_init(const vq2_conv_geom *d, int which, const float *w, float *packed, vq2_pack_job *job);
-int vq2_convg_fwd(const vq2_conv_geom *d, int flags, const float *x, const float *wp, const float *bias,
-                  const float *residual, int32_t ldres, float *y, vq2_stream_t stream);
-int vq2_convg_dgrad(const vq2_conv_geom *d, int flags, const float *dy, const float *wp, const float *mask, int32_t ldmask,
-                    const float *residual, int32_t ldres, float *dx, int32_t lddx, vq2_stream_t stream);
-size_t vq2_convg_wgrad_workspace_bytes(const vq2_conv_geom *d);
-int vq2_convg_wgrad(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
-                    size_t ws_bytes, vq2_stream_t stream);
-int vq2_convg_wgrad_partial(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *db, void *ws,
-                            size_t ws_bytes, vq2_stream_t stream);
-int vq2_convg_wgrad_job_init(const vq2_conv_geom *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job);
-
 /* ------------------------------------------------------------------ ELU, dropout and GLU of GatedResBlock (pixelsnail.py:122-179)
  * All over [pixels, C] NHWC rows with pixel strides (multiples of 4, >= ceil4(C); 16-byte aligned pointers), any C >= 1;
  * the pad lanes C .. ceil4(C) - 1 of every output are written as 0.  Deterministic: no reductions, no atomics.
@@ -513,7 +494,7 @@ int vq2_glu_res_bwd(const float *dout, int32_t lddo, const float *t, int32_t ldt
 /* ------------------------------------------------------------------ the two ends of PixelSNAIL (pixelsnail.py:397-431)
  * One-hot convolution (pixelsnail.py:401-406, :416-421): y = shift(conv(one_hot(idx), w) + bias) [+ acc] without a one-hot
  * tensor.  idx [N,H,W] int64 as torch holds it; w [Co, n_class, KH, KW]; the conv reads from (h - pad_top, w - pad_left) on
- * as in vq2_conv_geom; the result is moved shift_down rows down and shift_right columns right (each 0 or 1), the row / column
+ * as in a same_size vq2_conv_desc; the result is moved shift_down rows down and shift_right columns right (each 0 or 1), the row / column
  * that enters is 0 (bias included, as F.pad of the conv output makes it); `acc` (optional, NHWC, pixel stride ldacc) is added
  * everywhere.  y is NHWC [N,H,W,ldy >= ceil4(Co)], pad lanes 0.  An index outside [0, n_class) contributes nothing and no
  * address is formed from it (the reference's F.one_hot raises there; this does not).
@@ -560,16 +541,17 @@ int vq2_upsample2_bwd(const float *dy, int32_t lddy, float *dx, int32_t lddx, in
  * causal in raster order, so a sampler keeps what earlier rows produced and computes row i only; the two layer kinds that
  * look at earlier rows get entry points that read a history in place, and the draw is one launch.
  *
- * vq2_convg_fwd_row: output row `row` of what vq2_convg_fwd computes for the same descriptor (d->H is the number of rows
- *              the image has; 0 <= row < H; pad_top == KH - 1 is required, else VQ2_ERR_INVALID).  Input pixel (n, r, w) is at
+ * vq2_conv_fwd_row: output row `row` of what vq2_conv_fwd computes for the same descriptor (d->H is the number of rows
+ *              the image has; 0 <= row < H; same_size == 1 and pad_top == KH - 1 are required, else VQ2_ERR_INVALID;
+ *              a descriptor vq2_conv_fwd refuses is refused here too).  Input pixel (n, r, w) is at
  *              x + n * x_image_stride + r * x_row_stride + w * ldx (strides in elements, multiples of 4); rows r < 0 read as
  *              0, rows > row are never read.  y and residual are dense [N, W, ldy] / [N, W, ldres] single rows.  wp is the
  *              VQ2_PACK_FWD panel; bias, VQ2_RELU_IN / VQ2_RELU_OUT, the residual and the Cir / Cor padding are those of
- *              vq2_convg_fwd.  VQ2_ROW_CAUSAL_TAPS: the caller states that the weight is 0 at the taps a 'causal' layer
+ *              vq2_conv_fwd.  VQ2_ROW_CAUSAL_TAPS: the caller states that the weight is 0 at the taps a 'causal' layer
  *              zeroes (last kernel row, columns KW / 2 .. KW - 1) and those taps are skipped.  K is split over taps: one
- *              [N * W, Co] slab per split in `ws` (>= vq2_convg_fwd_row_workspace_bytes(d, flags), 16-byte aligned), then the
+ *              [N * W, Co] slab per split in `ws` (>= vq2_conv_fwd_row_workspace_bytes(d, flags), 16-byte aligned), then the
  *              slabs are added in ascending order with the epilogue.  fp32-input MFMA, fp32 accumulation, no atomics:
- *              bit-reproducible.  The sums run in another order than vq2_convg_fwd's, so the two agree to rounding only.
+ *              bit-reproducible.  The sums run in another order than vq2_conv_fwd's, so the two agree to rounding only.
  * vq2_causal_attn_fwd_rows: vq2_causal_attn_fwd for the queries at raster positions q0 .. q0 + nq - 1 (q0 + nq <= d->L).
  *              q and o are dense [B, nq, ldq / ldo]; the key or value at position p of image b is at
  *              base + b * kv_image_stride + (p / W) * kv_row_stride + (p % W) * ldk (ldv); positions < q0 + nq - 1 are read, the last
@@ -585,8 +567,8 @@ int vq2_upsample2_bwd(const float *dy, int32_t lddy, float *dx, int32_t lddx, in
  *              VQ2_ERR_INVALID.
  * vq2_sample_uniforms: those u values, u[r] for r < M -- the only way to check the draw against a reference. */
 #define VQ2_ROW_CAUSAL_TAPS 8
-size_t vq2_convg_fwd_row_workspace_bytes(const vq2_conv_geom *d, int flags);
-int vq2_convg_fwd_row(const vq2_conv_geom *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
+size_t vq2_conv_fwd_row_workspace_bytes(const vq2_conv_desc *d, int flags);
+int vq2_conv_fwd_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
                       const float *x, const float *wp, const float *bias, const float *residual, int32_t ldres, float *y,
                       void *ws, size_t ws_bytes, vq2_stream_t stream);
 int vq2_causal_attn_fwd_rows(const vq2_attn_desc *d, int32_t q0, int32_t nq, int32_t W, int64_t kv_image_stride,

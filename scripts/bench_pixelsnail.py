@@ -43,10 +43,10 @@ TINY = [
 
 class CallCounter:
     """Counts calls of libvq2 entry points on the host while active (the binding looks its functions up on `lib` at call
-    time; the conv entry points are also held by ops._ABI_DESC / ops._ABI_GEOM)."""
+    time)."""
 
     def __init__(self, amd):
-        self.lib, self.ops, self.names = amd._lib.lib, amd.ops, [n for n in amd._lib.EXPORTS if n != "vq2_last_error"]
+        self.lib, self.names = amd._lib.lib, [n for n in amd._lib.EXPORTS if n != "vq2_last_error"]
         self.counts = collections.Counter()
 
     def _wrap(self, name, fn):
@@ -57,23 +57,13 @@ class CallCounter:
 
     def __enter__(self):
         self.saved = {n: getattr(self.lib, n) for n in self.names}
-        wrapped = {n: self._wrap(n, f) for n, f in self.saved.items()}
-        by_fn = {id(f): wrapped[n] for n, f in self.saved.items()}
-        for n, w in wrapped.items():
-            setattr(self.lib, n, w)
-        self.saved_ns = []
-        for ns in (self.ops._ABI_DESC, self.ops._ABI_GEOM):
-            for k, f in list(vars(ns).items()):
-                if id(f) in by_fn:
-                    self.saved_ns.append((ns, k, f))
-                    setattr(ns, k, by_fn[id(f)])
+        for n, f in self.saved.items():
+            setattr(self.lib, n, self._wrap(n, f))
         return self
 
     def __exit__(self, *exc):
         for n, f in self.saved.items():
             setattr(self.lib, n, f)
-        for ns, k, f in self.saved_ns:
-            setattr(ns, k, f)
 
 
 def time_ms(fn, inner):

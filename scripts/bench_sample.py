@@ -15,7 +15,7 @@ Measured, with a host clock around work that ends in a device synchronise (no GP
               each), and integrated over the map by the trapezoid rule over rows: an ESTIMATE of the loop's time, which
               avoids running its 1,024 full-model passes
     launches  per sampler step, counted from the recorded program of a middle row plus the draw: library calls, and kernel
-              launches (a vq2_convg_fwd_row call is two kernels, every other call of the step one)
+              launches (a vq2_conv_fwd_row call is two kernels, every other call of the step one)
 Not measured: kernel times (no profiler run), the share of launch overhead, the full 64 x 64 bottom map."""
 import argparse
 import json
@@ -73,7 +73,7 @@ def bench(name, model, batch, rows, condition, repeats, baseline_steps):
     total += 0.5 * (per_step[picks[0]] + per_step[picks[-1]]) * width if len(picks) > 1 else per_step[picks[0]] * width
     med = statistics.median(times)
     calls = plan.programs[rows // 2].calls
-    two_kernels = sum(1 for _, _, what in calls if what == "convg_fwd_row")
+    two_kernels = sum(1 for _, _, what in calls if what == "conv_fwd_row")
     res = {
         "batch": batch, "rows": rows, "width": width, "steps": rows * width,
         "sampler_seconds_per_map": {"median": med, "min": min(times), "max": max(times), "repeats": repeats},

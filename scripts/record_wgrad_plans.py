@@ -2,9 +2,8 @@
 tests/golden/wgrad_plans.json.  tests/test_host_cpu.py::test_wgrad_plans_match_the_recorded_ones replays the file.
 
 What is recorded is what the library shows of a plan without launching anything (no GPU needed): the workspace size
-(vq2_conv_wgrad_workspace_bytes / vq2_convg_wgrad_workspace_bytes) and the fields of the reduction job
-(vq2_wgrad_job_init / vq2_convg_wgrad_job_init) -- O, I, Or, Ir, taps, S, n_units_w, n_units_b, swapped (bit 0 exchanged
-roles, bits 1-2 the Winograd mode), bias_splits -- each with and without a bias gradient, under VQ2_FORMS = all, direct and
+(vq2_conv_wgrad_workspace_bytes) and the fields of the reduction job (vq2_wgrad_job_init) -- O, I, Or, Ir, taps, S,
+n_units_w, n_units_b, swapped (bit 0 exchanged roles, bits 1-2 the Winograd mode), bias_splits -- each with and without a bias gradient, under VQ2_FORMS = all, direct and
 general.  The library reads VQ2_FORMS once per process: `all` is recorded in this process, the other two in a child each
 (`--replay FILE` is that child: it prints the plans of the shapes in FILE under the VQ2_FORMS it was started with).
 
@@ -31,8 +30,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "wgrad_plans.json")
 FIELDS = ["ws_bytes", "O", "I", "Or", "Ir", "taps", "S", "n_units_w", "n_units_b", "swapped", "bias_splits"]
 FORMS = ("all", "direct", "general")
+# The two layouts of an entry's integer list, by its "kind" (the file predates the one descriptor and keeps them): the
+# first form of vq2_conv_desc with its one `pad`, and the same_size form, which states neither stride nor transposed
 DESC = ("N", "H", "W", "Ci", "Co", "KH", "KW", "stride", "pad", "transposed", "ldx", "ldy", "Cir", "Cor")
 GEOM = ("N", "H", "W", "Ci", "Co", "KH", "KW", "pad_top", "pad_left", "ldx", "ldy", "Cir", "Cor")
+
+
+def descriptor(L, e):
+    """vq2_conv_desc of an entry."""
+    d = L.ConvDesc()
+    if e["kind"] == "geom":
+        v = dict(zip(GEOM, e["d"]), stride=1, transposed=0, same_size=1)
+    else:
+        v = dict(zip(DESC, e["d"]), same_size=0)
+        v["pad_top"] = v["pad_left"] = v.pop("pad")
+    for n, x in v.items():
+        setattr(d, n, x)
+    return d
 
 
 def load_binding():
@@ -50,21 +64,14 @@ def plans(entries, L):
     ptr = ctypes.c_void_p((ctypes.addressof(backing) + 15) & ~15)
     out = []
     for e in entries:
-        if e["kind"] == "geom":
-            d, names = L.ConvGeom(), GEOM
-            ws_bytes, job_init = L.lib.vq2_convg_wgrad_workspace_bytes, L.lib.vq2_convg_wgrad_job_init
-        else:
-            d, names = L.ConvDesc(), DESC
-            ws_bytes, job_init = L.lib.vq2_conv_wgrad_workspace_bytes, L.lib.vq2_wgrad_job_init
-        for n, v in zip(names, e["d"]):
-            setattr(d, n, v)
+        d = descriptor(L, e)
         both = []
         for db in (ptr, None):
             job = L.WgradJob()
-            rc = job_init(ctypes.byref(d), ptr, ptr, db, ctypes.byref(job))
+            rc = L.lib.vq2_wgrad_job_init(ctypes.byref(d), ptr, ptr, db, ctypes.byref(job))
             if rc != 0:
                 raise RuntimeError("%s: %s" % (e, L.lib.vq2_last_error().decode()))
-            both.append([int(ws_bytes(ctypes.byref(d)))] + [int(getattr(job, f)) for f in FIELDS[1:]])
+            both.append([int(L.lib.vq2_conv_wgrad_workspace_bytes(ctypes.byref(d)))] + [int(getattr(job, f)) for f in FIELDS[1:]])
         out.append(both)
     return out
 
@@ -84,7 +91,7 @@ def geom(src, cin, cout, g, n, h, w, wider=0):
 
 
 def of_spec(src, s, n, h, w):
-    if s.is_geom:
+    if s.same_size:
         return geom(src, s.cin, s.cout, (s.k, s.kw, s.pad_top, s.pad_left), n, h, w)
     return desc(src, s.transposed, s.cin, s.cout, s.k, s.stride, s.pad, n, h, w)
 

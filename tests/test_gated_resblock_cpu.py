@@ -130,13 +130,15 @@ def test_refusals_without_gpu():
 
 
 def test_new_descriptor_refusals_reach_no_kernel():
-    """Everything outside the contract of vq2_conv_geom is refused by every entry point before any device work."""
+    """Everything outside the contract of the same_size form of vq2_conv_desc is refused by every entry point before any
+    device work."""
     import ctypes
     import vqvae2_amd as A
     L = A._lib
     def geom(**kw):
-        d = L.ConvGeom()
+        d = L.ConvDesc()
         d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.pad_top, d.pad_left, d.ldx, d.ldy = 1, 4, 4, 8, 8, 3, 3, 1, 1, 8, 8
+        d.stride, d.same_size = 1, 1
         for k, v in kw.items():
             setattr(d, k, v)
         return d
@@ -144,33 +146,35 @@ def test_new_descriptor_refusals_reach_no_kernel():
     def every(d):
         """(every pointer is null: a call that got past the descriptor checks would still stop at its null check)"""
         job, pj = L.WgradJob(), L.PackJob()
-        return [L.lib.vq2_convg_fwd(ctypes.byref(d), 0, None, None, None, None, 0, None, None),
-                L.lib.vq2_convg_dgrad(ctypes.byref(d), 0, None, None, None, 0, None, 0, None, 8, None),
-                L.lib.vq2_convg_wgrad(ctypes.byref(d), 0, None, None, None, None, None, 1 << 30, None),
-                L.lib.vq2_convg_wgrad_partial(ctypes.byref(d), 0, None, None, None, None, 1 << 30, None),
-                L.lib.vq2_convg_wgrad_job_init(ctypes.byref(d), None, None, None, ctypes.byref(job)),
-                L.lib.vq2_convg_pack_weight(ctypes.byref(d), 0, None, None, None),
-                L.lib.vq2_convg_pack_job_init(ctypes.byref(d), 0, None, None, ctypes.byref(pj))]
+        return [L.lib.vq2_conv_fwd(ctypes.byref(d), 0, None, None, None, None, 0, None, None),
+                L.lib.vq2_conv_dgrad(ctypes.byref(d), 0, None, None, None, 0, None, 0, None, 8, None),
+                L.lib.vq2_conv_wgrad(ctypes.byref(d), 0, None, None, None, None, None, 1 << 30, None),
+                L.lib.vq2_conv_wgrad_partial(ctypes.byref(d), 0, None, None, None, None, 1 << 30, None),
+                L.lib.vq2_wgrad_job_init(ctypes.byref(d), None, None, None, ctypes.byref(job)),
+                L.lib.vq2_pack_weight(ctypes.byref(d), 0, None, None, None),
+                L.lib.vq2_pack_job_init(ctypes.byref(d), 0, None, None, ctypes.byref(pj))]
 
+    # (same_size is 0 or 1; a stride or a transposition cannot go with it)
     for bad, code, word in ((geom(KH=5, KW=7, pad_top=4, pad_left=3), 2, b"32 taps"), (geom(KH=8, pad_top=1), 1, b"1..7"),
                             (geom(KW=0), 1, b"1..7"), (geom(pad_top=3), 1, b"pad_top"), (geom(pad_left=-1), 1, b"pad_top"),
-                            (geom(reserved=1), 1, b"reserved")):
+                            (geom(same_size=2), 1, b"same_size"), (geom(stride=2), 1, b"same_size"),
+                            (geom(transposed=1), 1, b"same_size")):
         for rc in every(bad):
             assert rc == code, (rc, code, L.lib.vq2_last_error())
             assert word in L.lib.vq2_last_error()
-        assert L.lib.vq2_convg_wgrad_workspace_bytes(ctypes.byref(bad)) == 0
-    assert L.lib.vq2_convg_fwd(ctypes.byref(geom(Ci=6)), 0, None, None, None, None, 0, None, None) == 1
+        assert L.lib.vq2_conv_wgrad_workspace_bytes(ctypes.byref(bad)) == 0
+    assert L.lib.vq2_conv_fwd(ctypes.byref(geom(Ci=6)), 0, None, None, None, None, 0, None, None) == 1
     assert b"multiples of 4" in L.lib.vq2_last_error()
-    assert L.lib.vq2_convg_fwd(None, 0, None, None, None, None, 0, None, None) == 1
+    assert L.lib.vq2_conv_fwd(None, 0, None, None, None, None, 0, None, None) == 1
     ok = geom(KH=2, KW=5, pad_top=1, pad_left=2)
-    assert L.lib.vq2_convg_fwd(ctypes.byref(ok), 0, None, None, None, None, 0, None, None) == 1
+    assert L.lib.vq2_conv_fwd(ctypes.byref(ok), 0, None, None, None, None, 0, None, None) == 1
     assert b"null pointer" in L.lib.vq2_last_error()           # the descriptor itself is accepted
-    assert L.lib.vq2_convg_wgrad_workspace_bytes(ctypes.byref(ok)) > 0
+    assert L.lib.vq2_conv_wgrad_workspace_bytes(ctypes.byref(ok)) > 0
     job = L.WgradJob()
     host = (ctypes.c_float * 4)()                              # job_init only records the addresses
-    assert L.lib.vq2_convg_wgrad_job_init(ctypes.byref(ok), host, host, None, ctypes.byref(job)) == 0
+    assert L.lib.vq2_wgrad_job_init(ctypes.byref(ok), host, host, None, ctypes.byref(job)) == 0
     assert job.taps == 10 and (job.swapped & 1) == 0
-    assert L.lib.vq2_convg_fwd(ctypes.byref(geom(N=1 << 20, H=64, W=64)), 0, None, None, None, None, 0, None, None) == 1
+    assert L.lib.vq2_conv_fwd(ctypes.byref(geom(N=1 << 20, H=64, W=64)), 0, None, None, None, None, 0, None, None) == 1
     assert b"exceeds 2^31 elements" in L.lib.vq2_last_error()
     # the elementwise entry points refuse bad strides and probabilities
     assert L.lib.vq2_elu_fwd(None, 4, None, 8, 4, 5, None) == 1 and b"pixel stride" in L.lib.vq2_last_error()

@@ -207,8 +207,8 @@ CASES = [
 #   - the non-uniform instantiation of the four-per-CU 128x128x16 tile: its gate (Ci % 16 == 0, below 1 GiB) implies `small`,
 #     and `occ4` makes `uni` true then;
 #   - the conv_k4s2_c4 gate, `H % 2`, `W % 2`, `KH == 4`, `pad == 1` given stride 2, and the conv1x1_k64 gate, `stride == 1` given KH == 1:
-#     check_desc admits stride 2 only as k4 p1 on even sizes (phases == 1 with a 4x4 stride-2 kernel is that layer or the
-#     data gradient of a conv-transpose, which is k4 s2 p1 by check_desc as well).
+#     check_conv_desc admits stride 2 only as k4 p1 on even sizes (phases == 1 with a 4x4 stride-2 kernel is that layer or the
+#     data gradient of a conv-transpose, which is k4 s2 p1 by check_conv_desc as well).
 # Reachable only with a tensor of 1 GiB: `small == false` inside the 513..1024-tile window (an operand that is a channel slice
 # of a buffer 2048 floats wide) -- the first case of test_tensors_of_one_gib_and_more.
 # Not every (tile, instantiation) product is enumerated: each tile has a case, and each of tap / uni / var has cases on BK = 16

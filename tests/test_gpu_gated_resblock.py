@@ -1,5 +1,5 @@
-"""GPU checks of the stage-2 GatedResBlock work: the second conv geometry (vq2_conv_geom) against float64 torch, old
-versus new descriptor bit for bit, causality, the ELU / ELU+dropout / GLU kernels against float64, the dropout
+"""GPU checks of the stage-2 GatedResBlock work: the same_size form of vq2_conv_desc against float64 torch, the two
+forms of the descriptor bit for bit where both can state a layer, causality, the ELU / ELU+dropout / GLU kernels against float64, the dropout
 decisions, and the modules against the goldens captured from the reference."""
 import ctypes
 import glob

@@ -1,6 +1,6 @@
-"""The second conv descriptor (vq2_conv_geom: rectangular kernels with top / left padding, output the size of the input) on
+"""The same_size form of vq2_conv_desc (rectangular kernels with top / left padding, output the size of the input) on
 every kernel the stage-2 prior trains with, against fp64 at the shape boundaries of plan_conv (csrc/vq2_conv.hip),
-plan_wgrad with its kernel-family test (csrc/vq2_wgrad.hip).  tests/test_gpu_dispatch.py is that table for the first descriptor; this
+plan_wgrad with its kernel-family test (csrc/vq2_wgrad.hip).  tests/test_gpu_dispatch.py is that table for the other form; this
 module is its counterpart and shares its helpers (counter-based inputs, launched / short_label / conv_labels, sliced /
 guarded / untouched, the label syntax "<family>|<variant>") unchanged.  The geometries (KH, KW, pad_top, pad_left) are
 KERNELS of tests/test_gpu_gated_resblock.py, whose own fp64 test stops at 144 rows and 8-pixel rows: every label here is
@@ -31,15 +31,15 @@ What each section of GEOM_CASES straddles (8x16 images: wgs128 = N * ceil(Co / 1
 (tile, instantiation, geometry) products without a case, and why:
   - every product is not enumerated: each 128-row tile has a rectangular, asymmetrically padded case in each direction it
     trains in, and tap / uni / var each have one on a BK = 32 and (tap, uni) on a BK = 16 tile; 128x64x16 and 128x32x32 run
-    `tap` only here (their uni / var instantiations differ from the first descriptor's cases in the tap decomposition alone,
+    `tap` only here (their uni / var instantiations differ from the cases of tests/test_gpu_dispatch.py in the tap decomposition alone,
     which `tap` exercises with more taps);
   - 64x192x16 and 64x128x16 (K <= 64) need KH * KW * Ci <= 64 with Co > 128: no stage-2 layer has that shape;
   - the 64-row tiles other than 64x128x32 with these geometries are what tests/test_gpu_gated_resblock.py runs (M <= 144);
-  - conv1x1_k64, the Winograd, sub-pixel, k4s2 and conv-transpose families take square centred kernels only: the second
-    descriptor reaches the first three as (3,3,1,1) / (1,1,0,0), checked bit for bit against the first descriptor in
+  - conv1x1_k64, the Winograd, sub-pixel, k4s2 and conv-transpose families take square centred kernels only: the same_size
+    form reaches the first three as (3,3,1,1) / (1,1,0,0), checked bit for bit against the other form in
     test_old_and_new_descriptor_agree_bitwise_on_the_winograd_shapes;
   - the non-uniform instantiation of 128x128x16 cannot exist (see tests/test_gpu_dispatch.py);
-  - tensors of 1 GiB and more: the kernels are shared with the first descriptor, test_tensors_of_one_gib_and_more covers them.
+  - tensors of 1 GiB and more: the kernels are shared with the other form, test_tensors_of_one_gib_and_more covers them.
 
 Tolerances are the project's: rtol 0, atol 5e-6 * max|ref| for y and dx, 1e-5 * max|ref| for dw and db.  A case deeper than
 they were set for (y / dx depth above 4096, dw of more than 65,664 rows) would use max(project tolerance, 4 x the error of
@@ -232,7 +232,7 @@ def deep_tolerance(c, ref, ref32, what):
 def _bites(c):
     """CPU check that the tolerance of a case would catch a kernel that drops ONE product: plain fp32 torch with one tap of
     one (co, ci) pair of the weights zeroed (wgrad: one pixel of one channel of dy) must fail the comparison, and intact
-    fp32 must pass it (test_gpu_dispatch._bites for the second descriptor)."""
+    fp32 must pass it (test_gpu_dispatch._bites for the same_size form)."""
     op, cin, cout, (kh, kw, pt, pl), n, h, w, fl = c[:8]
     d = make_inputs(c)
     bad = dict(d)
@@ -369,7 +369,7 @@ def test_geom_census_of_labels_over_the_whole_table(amd):
     assert torch.cuda.max_memory_allocated() < (1 << 30)
 
 
-# --------------------------------------------------------------------------------------- old against new descriptor, bitwise
+# --------------------------------------------------------------------------------------- the two forms of one layer, bitwise
 # cin, cout, N, H, W, labels that must be among those seen under VQ2_FORMS=all (forward, data gradient, weight gradient):
 # conv_wino3 at both row widths, narrow and wide (`wide`: Co % 128 == 0 and N * H * W / 128 * (Co / 128) >= 400); Winograd
 # weight-gradient mode 1 (O % 128 == 0, I % 128 == 0; W % 64 == 0, or W == 32 with H even) and mode 3 (exchanged roles, I == 32)
@@ -386,9 +386,10 @@ WINO_SHAPES = [
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin,cout,n,h,w,want", WINO_SHAPES, ids=["%d-%d-%dx%dx%d" % s[:5] for s in WINO_SHAPES])
 def test_old_and_new_descriptor_agree_bitwise_on_the_winograd_shapes(amd, cin, cout, n, h, w, want):
-    """ConvSpec(False, cin, cout, 3, 1, 1) and ConvSpec.geom(cin, cout, 3, 3, 1, 1) give the same bits for y, dx, dw and db
-    on the shapes that reach conv_wino3 and the Winograd weight-gradient modes (tests/test_gpu_gated_resblock.py has the
-    same test up to 64 channels, which reaches neither)."""
+    """ConvSpec(False, cin, cout, 3, 1, 1) and ConvSpec.geom(cin, cout, 3, 3, 1, 1), one layer in the two forms of
+    vq2_conv_desc, give the same bits for y, dx, dw and db on the shapes that reach conv_wino3 and the Winograd
+    weight-gradient modes: same_size alone changes no plan (tests/test_gpu_gated_resblock.py has the same test up to 64
+    channels, which reaches neither)."""
     from vqvae2_amd import ops
     dev = torch.device("cuda:0")
     old, new = ops.ConvSpec(False, cin, cout, 3, 1, 1), ops.ConvSpec.geom(cin, cout, 3, 3, 1, 1)
@@ -424,7 +425,7 @@ DEFERRED = [c for c in GEOM_CASES if c[:7] in (('wgrad', 36, 132, C5, 4, 3, 32),
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", DEFERRED, ids=case_id)
 def test_deferred_weight_gradient_equals_the_immediate_one_bitwise(amd, c):
-    """vq2_convg_wgrad_partial + vq2_convg_wgrad_job_init + vq2_wgrad_reduce_batched through ops.WgradBatch, the collector
+    """vq2_conv_wgrad_partial + vq2_wgrad_job_init + vq2_wgrad_reduce_batched through ops.WgradBatch, the collector
     of the trainers, against the immediate conv_wgrad (itself compared with fp64 in the table): the same bits, on
     wgrad_fast_kernel and on wgrad_kernel."""
     from vqvae2_amd import ops

@@ -53,7 +53,7 @@ def _row_conv_case(amd, tag, n, h, w, cir, cor, kh, kw, mode, rows, relu=False):
     res = torch.randn(n, cor, h, w, generator=gen)
 
     def formula(dtype, with_res):
-        """[relu](conv([relu]x) + bias [+ residual]): relu = VQ2_RELU_IN | VQ2_RELU_OUT, as vq2_convg_fwd applies them"""
+        """[relu](conv([relu]x) + bias [+ residual]): relu = VQ2_RELU_IN | VQ2_RELU_OUT, as vq2_conv_fwd applies them"""
         xin = x.to(dtype).relu() if relu else x.to(dtype)
         y = R.conv_at(xin, wt.to(dtype), bias.to(dtype), pad_top, pad_left)
         if with_res:
@@ -76,10 +76,11 @@ def _row_conv_case(amd, tag, n, h, w, cir, cor, kh, kw, mode, rows, relu=False):
     layouts = {"batch-outer": (xn.cuda(), h * w * ci, w * ci),
                "row-outer": (xn.permute(1, 0, 2, 3).contiguous().cuda(), w * ci, n * w * ci)}
     full = ops.conv_forward(spec, xn.cuda(), wd, bias.cuda(), flags & 3).cpu().double()      # the existing kernel on the whole image
-    d = amd._lib.ConvGeom()
+    d = amd._lib.ConvDesc()
     d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.pad_top, d.pad_left = n, h, w, ci, co, kh, kw, pad_top, pad_left
+    d.stride, d.same_size = 1, 1
     d.ldx, d.ldy, d.Cir, d.Cor = ci, co, cir, cor
-    nbytes = lib.vq2_convg_fwd_row_workspace_bytes(C.byref(d), flags)
+    nbytes = lib.vq2_conv_fwd_row_workspace_bytes(C.byref(d), flags)
     ws = torch.empty(nbytes // 4, device="cuda")
     bad = []
     for row in rows:
@@ -91,9 +92,9 @@ def _row_conv_case(amd, tag, n, h, w, cir, cor, kh, kw, mode, rows, relu=False):
                 outs = []
                 for _ in range(2):
                     y = torch.full((n, w, co), float("nan"), device="cuda")
-                    amd._lib.check(lib.vq2_convg_fwd_row(C.byref(d), row, image_stride, row_stride, flags, ops._p(xd), ops._p(wp),
+                    amd._lib.check(lib.vq2_conv_fwd_row(C.byref(d), row, image_stride, row_stride, flags, ops._p(xd), ops._p(wp),
                                                          ops._p(bias.cuda()), ops._p(rrow), co if with_res else 0, ops._p(y),
-                                                         ops._p(ws), nbytes, ops._stream()), "convg_fwd_row")
+                                                         ops._p(ws), nbytes, ops._stream()), "conv_fwd_row")
                     outs.append(y.cpu())
                 assert torch.equal(outs[0], outs[1]), (tag, row, name)                           # bit-reproducible
                 assert torch.all(outs[0][..., cor:] == 0)                                        # pad lanes
@@ -114,7 +115,7 @@ def test_row_conv_against_float64(amd, tag, cir, cor, kh, kw, mode):
 
 
 def test_row_conv_relu_flags(amd):
-    # VQ2_RELU_IN | VQ2_RELU_OUT, the prologue and epilogue of vq2_convg_fwd, with and without a residual
+    # VQ2_RELU_IN | VQ2_RELU_OUT, the prologue and epilogue of vq2_conv_fwd, with and without a residual
     _row_conv_case(amd, "relu3x3", 2, 4, 5, 6, 10, 3, 3, "causal", [0, 3], relu=True)
 
 

@@ -29,6 +29,20 @@ def test_library_exports_every_declared_symbol(amd):
     assert lib.vq2_version() == amd._lib.API_VERSION == int(re.search(r"#define\s+VQ2_API_VERSION\s+(\d+)", hdr).group(1))
 
 
+def test_conv_desc_binding_matches_the_header(amd):
+    """The ctypes mirror of vq2_conv_desc: sixteen int32 words, 64 bytes without padding, in the header's order."""
+    hdr = open(os.path.join(ROOT, "include", "vq2.h")).read()
+    body = re.search(r"typedef struct vq2_conv_desc \{(.*?)\} vq2_conv_desc;", hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    decls = [s.strip() for s in body.split(";") if s.strip()]
+    assert all(s.startswith("int32_t ") for s in decls), decls
+    names = [n.strip() for s in decls for n in s[len("int32_t "):].split(",")]
+    D = amd._lib.ConvDesc
+    assert [n for n, _ in D._fields_] == names and len(names) == 16
+    assert all(t is ctypes.c_int32 for _, t in D._fields_)
+    assert ctypes.sizeof(D) == 64 and [getattr(D, n).offset for n in names] == list(range(0, 64, 4))
+
+
 def test_hot_kernels_do_not_spill():
     """The compiler's resource report written by csrc/build.sh: none of the kernels the train step runs may spill a
     register or use scratch memory (round 2: ONE spilled VGPR in the four-per-CU conv tile = 3 % of the whole step,
@@ -64,7 +78,7 @@ def test_weight_gradient_plans_and_slab_layouts_without_gpu(amd):
 
     def plan(cin, cout, k, stride, pad, transposed, n, h, w):
         d = amd._lib.ConvDesc()
-        d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad = n, h, w, cin, cout, k, k, stride, pad
+        d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad_top, d.pad_left = n, h, w, cin, cout, k, k, stride, pad, pad
         d.transposed, d.ldx, d.ldy, d.Cir, d.Cor = int(transposed), cin, cout, cin, cout
         job = amd._lib.WgradJob()
         dummy = ctypes.c_void_p(16)
@@ -113,7 +127,7 @@ L.lib.vq2_conv_wgrad_workspace_bytes.restype = ctypes.c_size_t
 out = {}
 for cout in (128, 32):
     d = L.ConvDesc()
-    d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad = 32, 64, 64, 128, cout, 3, 3, 1, 1
+    d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad_top, d.pad_left = 32, 64, 64, 128, cout, 3, 3, 1, 1, 1
     d.ldx, d.ldy, d.Cir, d.Cor = 128, cout, 128, cout
     job = L.WgradJob()
     dummy = ctypes.c_void_p(16)
@@ -193,7 +207,7 @@ def test_invalid_arguments_are_rejected_without_gpu(amd):
     d = amd._lib.ConvDesc()
     assert lib.vq2_conv_fwd(ctypes.byref(d), 0, None, None, None, None, 0, None, None) == 1
     assert b"non-positive" in lib.vq2_last_error()
-    d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad, d.ldx, d.ldy = 1, 8, 8, 6, 8, 3, 3, 1, 1, 8, 8
+    d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad_top, d.pad_left, d.ldx, d.ldy = 1, 8, 8, 6, 8, 3, 3, 1, 1, 1, 8, 8
     assert lib.vq2_conv_fwd(ctypes.byref(d), 0, None, None, None, None, 0, None, None) == 1
     assert b"multiples of 4" in lib.vq2_last_error()
     assert lib.vq2_vq_fwd(None, 0, None, None, None, 0, 0, 0, None, None, 0, None, None) == 1
@@ -202,22 +216,22 @@ def test_invalid_arguments_are_rejected_without_gpu(amd):
     assert lib.vq2_adam_step(None, None, None, None, 0, 1e-3, .9, .999, 1e-8, 1, 1.0, None) == 1
     with pytest.raises(RuntimeError):
         amd._lib.check(1, "x")
-    # tensors from 2^31 elements are refused by check_desc before any pointer is looked at (int32 indexing) ...
+    # tensors from 2^31 elements are refused by check_conv_desc before any pointer is looked at (int32 indexing) ...
     d = amd._lib.ConvDesc()
-    d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad, d.ldx, d.ldy = 2048, 64, 64, 128, 128, 3, 3, 1, 1, 256, 128
+    d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.stride, d.pad_top, d.pad_left, d.ldx, d.ldy = 2048, 64, 64, 128, 128, 3, 3, 1, 1, 1, 256, 128
     assert 2048 * 64 * 64 * 256 == 1 << 31
     assert lib.vq2_conv_fwd(ctypes.byref(d), 0, None, None, None, None, 0, None, None) == 1
     assert b"exceeds 2^31 elements" in lib.vq2_last_error()
     d.ldx, d.ldy = 128, 256                                    # ... on the output side as well
-    assert lib.vq2_conv_dgrad(ctypes.byref(d), None, None, None, 0, None, 0, None, 128, None) == 1
+    assert lib.vq2_conv_dgrad(ctypes.byref(d), 0, None, None, None, 0, None, 0, None, 128, None) == 1
     assert b"exceeds 2^31 elements" in lib.vq2_last_error()
-    d.N = 2047                                                 # one image fewer passes check_desc: the next check speaks
+    d.N = 2047                                                 # one image fewer passes check_conv_desc: the next check speaks
     assert lib.vq2_conv_fwd(ctypes.byref(d), 0, None, None, None, None, 0, None, None) == 1
     assert b"null pointer" in lib.vq2_last_error()
     # ... and a conv-transpose to <= 4 channels from 0x7F000000 bytes (its kernel's out-of-range offset) is unsupported:
     # 508 images of 128x128x64 are 0x7F000000 bytes exactly, 507 pass (tests/test_gpu_dispatch.py runs those)
     t = amd._lib.ConvDesc()
-    t.N, t.H, t.W, t.Ci, t.Co, t.KH, t.KW, t.stride, t.pad, t.ldx, t.ldy = 508, 128, 128, 64, 4, 4, 4, 2, 1, 64, 4
+    t.N, t.H, t.W, t.Ci, t.Co, t.KH, t.KW, t.stride, t.pad_top, t.pad_left, t.ldx, t.ldy = 508, 128, 128, 64, 4, 4, 4, 2, 1, 1, 64, 4
     t.transposed, t.Cir, t.Cor = 1, 64, 3
     assert 508 * 128 * 128 * 64 * 4 == 0x7F000000
     # (the refusals below come before any launch, but they need non-null, 16-byte aligned pointers: a real host allocation,
@@ -310,7 +324,7 @@ def test_dispatch_table_tolerances_bite_on_the_cpu():
 
 
 def test_geom_dispatch_table_tolerances_bite_on_the_cpu():
-    """The same for the table of the second descriptor (tests/test_gpu_geom_dispatch.py): the cheapest case of EVERY label
+    """The same for the table of the same_size form (tests/test_gpu_geom_dispatch.py): the cheapest case of EVERY label
     of EXPECTED_GEOM_LABELS["all"]; and the literal label sets are what the table says, for every value of VQ2_FORMS."""
     import test_gpu_geom_dispatch as G
     for forms, col in (("all", 8), ("direct", 9), ("general", 10)):

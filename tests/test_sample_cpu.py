@@ -55,10 +55,10 @@ def test_library_declares_the_sampling_entry_points():
     import vqvae2_amd as amd
     L = amd._lib
     P, I32, I64, F, U64, SZ = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
-    GP, AP = ctypes.POINTER(L.ConvGeom), ctypes.POINTER(L.AttnDesc)
+    GP, AP = ctypes.POINTER(L.ConvDesc), ctypes.POINTER(L.AttnDesc)
     want = {
-        "vq2_convg_fwd_row_workspace_bytes": (SZ, [GP, ctypes.c_int]),
-        "vq2_convg_fwd_row": (ctypes.c_int, [GP, I32, I64, I64, ctypes.c_int, P, P, P, P, I32, P, P, SZ, P]),
+        "vq2_conv_fwd_row_workspace_bytes": (SZ, [GP, ctypes.c_int]),
+        "vq2_conv_fwd_row": (ctypes.c_int, [GP, I32, I64, I64, ctypes.c_int, P, P, P, P, I32, P, P, SZ, P]),
         "vq2_causal_attn_fwd_rows": (ctypes.c_int, [AP, I32, I32, I32, I64, I64, P, P, P, P, P]),
         "vq2_sample_categorical": (ctypes.c_int, [P, I64, I32, I32, F, U64, U64, P, I64, P]),
         "vq2_sample_uniforms": (ctypes.c_int, [P, I32, U64, U64, P]),
@@ -67,17 +67,18 @@ def test_library_declares_the_sampling_entry_points():
         assert name in L.EXPORTS, name
         fn = getattr(L.lib, name)
         assert fn.restype == res and list(fn.argtypes) == args, name
-    assert L.API_VERSION >= 11
+    assert L.API_VERSION >= 13
     for name in ("PriorSampler", "sample_model", "load_model"):
         assert hasattr(amd, name)
     # argument checks that reach no kernel
-    d = L.ConvGeom()
+    d = L.ConvDesc()
     d.N, d.H, d.W, d.Ci, d.Co, d.KH, d.KW, d.pad_top, d.pad_left, d.ldx, d.ldy = 1, 4, 4, 4, 4, 3, 3, 1, 1, 4, 4
+    d.stride, d.same_size = 1, 1
     one = ctypes.c_void_p(16)
-    assert L.lib.vq2_convg_fwd_row(ctypes.byref(d), 0, 16, 64, 0, one, one, None, None, 0, one, one, 1 << 20, None) == 1   # pad_top != KH - 1
+    assert L.lib.vq2_conv_fwd_row(ctypes.byref(d), 0, 16, 64, 0, one, one, None, None, 0, one, one, 1 << 20, None) == 1   # pad_top != KH - 1
     assert b"pad_top" in L.lib.vq2_last_error()
     assert L.lib.vq2_sample_categorical(one, 8, 1, 8, 0.0, 1, 0, one, 1, None) == 1
     assert L.lib.vq2_sample_categorical(one, 16385, 1, 16385, 1.0, 1, 0, one, 1, None) == 1
     d.pad_top = 2
-    assert L.lib.vq2_convg_fwd_row_workspace_bytes(ctypes.byref(d), 0) == 9 * 4 * 4 * 4      # one slab per tap of [N * W, Co]
-    assert L.lib.vq2_convg_fwd_row_workspace_bytes(ctypes.byref(d), 8) == 7 * 4 * 4 * 4      # the two 'causal' taps skipped
+    assert L.lib.vq2_conv_fwd_row_workspace_bytes(ctypes.byref(d), 0) == 9 * 4 * 4 * 4      # one slab per tap of [N * W, Co]
+    assert L.lib.vq2_conv_fwd_row_workspace_bytes(ctypes.byref(d), 8) == 7 * 4 * 4 * 4      # the two 'causal' taps skipped

@@ -12,14 +12,10 @@ c_stream = C.c_void_p
 
 
 class ConvDesc(C.Structure):
+    """vq2_conv_desc: both conv forms (same_size 0: square kernel, pad_top == pad_left; 1: output the size of the input)."""
     _fields_ = [(n, C.c_int32) for n in
-                ("N", "H", "W", "Ci", "Co", "KH", "KW", "stride", "pad", "transposed", "ldx", "ldy", "Cir", "Cor")]
-
-
-class ConvGeom(C.Structure):
-    """vq2_conv_geom: rectangular kernels with top / left padding, output the size of the input."""
-    _fields_ = [(n, C.c_int32) for n in
-                ("N", "H", "W", "Ci", "Co", "KH", "KW", "pad_top", "pad_left", "ldx", "ldy", "Cir", "Cor", "reserved")]
+                ("N", "H", "W", "Ci", "Co", "KH", "KW", "stride", "pad_top", "pad_left", "transposed", "same_size",
+                 "ldx", "ldy", "Cir", "Cor")]
 
 
 class PackJob(C.Structure):
@@ -59,7 +55,6 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     P, I32, I64, SZ, F, D = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_double
     DP = C.POINTER(ConvDesc)
-    GP = C.POINTER(ConvGeom)
     U64 = C.c_uint64
     sig = {
         "vq2_version": (C.c_int, []),
@@ -70,8 +65,7 @@ def _load():
         "vq2_pack_job_init": (C.c_int, [DP, C.c_int, P, P, C.POINTER(PackJob)]),
         "vq2_pack_weights_batched": (C.c_int, [P, I32, I64, P]),
         "vq2_conv_fwd": (C.c_int, [DP, C.c_int, P, P, P, P, I32, P, P]),
-        "vq2_conv_dgrad": (C.c_int, [DP, P, P, P, I32, P, I32, P, I32, P]),
-        "vq2_conv_dgrad_ex": (C.c_int, [DP, C.c_int, P, P, P, I32, P, I32, P, I32, P]),
+        "vq2_conv_dgrad": (C.c_int, [DP, C.c_int, P, P, P, I32, P, I32, P, I32, P]),
         "vq2_conv_wgrad_workspace_bytes": (SZ, [DP]),
         "vq2_conv_wgrad": (C.c_int, [DP, C.c_int, P, P, P, P, P, SZ, P]),
         "vq2_conv_wgrad_partial": (C.c_int, [DP, C.c_int, P, P, P, P, SZ, P]),
@@ -124,14 +118,6 @@ def _load():
         "vq2_weight_norm_bwd": (C.c_int, [P, P, P, P, P, I32, I32, P]),
         "vq2_wn_table_fwd": (C.c_int, [P, I32, P, P, P]),
         "vq2_wn_table_bwd": (C.c_int, [P, I32, I32, P, P, P, P]),
-        "vq2_convg_pack_weight": (C.c_int, [GP, C.c_int, P, P, P]),
-        "vq2_convg_pack_job_init": (C.c_int, [GP, C.c_int, P, P, C.POINTER(PackJob)]),
-        "vq2_convg_fwd": (C.c_int, [GP, C.c_int, P, P, P, P, I32, P, P]),
-        "vq2_convg_dgrad": (C.c_int, [GP, C.c_int, P, P, P, I32, P, I32, P, I32, P]),
-        "vq2_convg_wgrad_workspace_bytes": (SZ, [GP]),
-        "vq2_convg_wgrad": (C.c_int, [GP, C.c_int, P, P, P, P, P, SZ, P]),
-        "vq2_convg_wgrad_partial": (C.c_int, [GP, C.c_int, P, P, P, P, SZ, P]),
-        "vq2_convg_wgrad_job_init": (C.c_int, [GP, P, P, P, C.POINTER(WgradJob)]),
         "vq2_elu_fwd": (C.c_int, [P, I32, P, I32, I64, I32, P]),
         "vq2_elu_bwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
         "vq2_elu_dropout_fwd": (C.c_int, [P, I32, P, I32, I64, I32, F, U64, P]),
@@ -147,8 +133,8 @@ def _load():
         "vq2_xent_bwd": (C.c_int, [P, I32, P, P, P, I64, I32, P, I32, P]),
         "vq2_upsample2_fwd": (C.c_int, [P, I32, P, I32, I32, I32, I32, I32, P]),
         "vq2_upsample2_bwd": (C.c_int, [P, I32, P, I32, I32, I32, I32, I32, P]),
-        "vq2_convg_fwd_row_workspace_bytes": (SZ, [GP, C.c_int]),
-        "vq2_convg_fwd_row": (C.c_int, [GP, I32, I64, I64, C.c_int, P, P, P, P, I32, P, P, SZ, P]),
+        "vq2_conv_fwd_row_workspace_bytes": (SZ, [DP, C.c_int]),
+        "vq2_conv_fwd_row": (C.c_int, [DP, I32, I64, I64, C.c_int, P, P, P, P, I32, P, P, SZ, P]),
         "vq2_causal_attn_fwd_rows": (C.c_int, [C.POINTER(AttnDesc), I32, I32, I32, I64, I64, P, P, P, P, P]),
         "vq2_sample_categorical": (C.c_int, [P, I64, I32, I32, F, U64, U64, P, I64, P]),
         "vq2_sample_uniforms": (C.c_int, [P, I32, U64, U64, P]),

@@ -48,52 +48,59 @@ __device__ __forceinline__ float4 as_f4(u32x4 v) {
 static inline int real_ci(const vq2_conv_desc *d) { return d->Cir ? d->Cir : d->Ci; }
 static inline int real_co(const vq2_conv_desc *d) { return d->Cor ? d->Cor : d->Co; }
 
-// What every conv entry point plans from: the layer as a vq2_conv_desc plus the top and left padding on their own.
-//   vq2_conv_desc:  pad_h = pad_w = pad, the output size follows from pad, kernel and stride
-//   vq2_conv_geom:  stride 1, not transposed, pad_h = pad_top, pad_w = pad_left, `same`: output the size of the input
-// (the `pad` member is not read past geo_of)
-struct ConvGeo : vq2_conv_desc {
-    int pad_h, pad_w;
-    bool same;
-};
-static inline ConvGeo geo_of(const vq2_conv_desc *d) {
-    ConvGeo g;
-    static_cast<vq2_conv_desc &>(g) = *d;
-    g.pad_h = g.pad_w = d->pad; g.same = false;
-    return g;
-}
-// The contract of the second descriptor (include/vq2.h), checked by every vq2_convg_* entry point before geo_of: the one
-// copy of it.  The checks shared with vq2_conv_desc (dims, multiples of 4, strides, Cir / Cor, 2^31) follow in the callers.
-static inline int check_geom(const vq2_conv_geom *d) {
-    VQ2_REQUIRE(d != nullptr, "conv geometry is null");
-    VQ2_REQUIRE(d->reserved == 0, "conv geometry: the reserved word must be 0");
-    VQ2_REQUIRE(d->KH >= 1 && d->KH <= 7 && d->KW >= 1 && d->KW <= 7, "conv geometry: KH=%d, KW=%d must lie in 1..7", d->KH, d->KW);
-    VQ2_REQUIRE(d->pad_top >= 0 && d->pad_top < d->KH && d->pad_left >= 0 && d->pad_left < d->KW,
-                "conv geometry: 0 <= pad_top < KH and 0 <= pad_left < KW required (got %d, %d)", d->pad_top, d->pad_left);
-    if (d->KH * d->KW > 32) return set_error(VQ2_ERR_UNSUPPORTED, "conv geometry: %d x %d has more than 32 taps", d->KH, d->KW);
-    VQ2_REQUIRE(d->Cir >= 0 && d->Cir <= d->Ci && d->Cor >= 0 && d->Cor <= d->Co, "conv geometry: Cir/Cor out of range");
-    return VQ2_OK;
-}
-static inline ConvGeo geo_of(const vq2_conv_geom *d) {
-    ConvGeo g;
-    g.N = d->N; g.H = d->H; g.W = d->W; g.Ci = d->Ci; g.Co = d->Co; g.KH = d->KH; g.KW = d->KW;
-    g.stride = 1; g.pad = d->pad_top; g.transposed = 0; g.ldx = d->ldx; g.ldy = d->ldy; g.Cir = d->Cir; g.Cor = d->Cor;
-    g.pad_h = d->pad_top; g.pad_w = d->pad_left; g.same = true;
-    return g;
+struct ConvHW { int h, w; };
+static inline ConvHW out_hw(const vq2_conv_desc *d) {
+    if (d->transposed) return {2 * d->H, 2 * d->W};
+    if (d->same_size) return {d->H, d->W};
+    return {(d->H + 2 * d->pad_top - d->KH) / d->stride + 1, (d->W + 2 * d->pad_left - d->KW) / d->stride + 1};
 }
 
-struct ConvHW { int h, w; };
-static inline ConvHW out_hw(const ConvGeo *d) {
-    if (d->transposed) return {2 * d->H, 2 * d->W};
-    if (d->same) return {d->H, d->W};
-    return {(d->H + 2 * d->pad_h - d->KH) / d->stride + 1, (d->W + 2 * d->pad_w - d->KW) / d->stride + 1};
+// The contract of vq2_conv_desc (include/vq2.h), checked by every conv entry point before anything is planned: the one copy
+// of it.  `who` names the entry point in the null-pointer message.  DESC_PLAN_ONLY: the two entry points that plan a weight
+// gradient without launching it (workspace size, reduction job) leave out the 2^31-element check, the one check that a
+// recorded plan of tests/golden/wgrad_plans.json fails; the launch itself is checked in full.
+enum { DESC_PLAN_ONLY = 1 };
+static inline int check_conv_desc(const vq2_conv_desc *d, const char *who, int how = 0) {
+    VQ2_REQUIRE(d != nullptr, "%s: the conv descriptor is null", who);
+    if (int e = check_forms()) return e;
+    VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0, "conv desc: non-positive dims");
+    VQ2_REQUIRE(d->Ci % 4 == 0 && d->Co % 4 == 0, "conv desc: Ci=%d, Co=%d must be multiples of 4", d->Ci, d->Co);
+    VQ2_REQUIRE(d->ldx >= d->Ci && d->ldx % 4 == 0, "conv desc: ldx=%d must be >= Ci and a multiple of 4", d->ldx);
+    VQ2_REQUIRE(d->ldy >= d->Co && d->ldy % 4 == 0, "conv desc: ldy=%d must be >= Co and a multiple of 4", d->ldy);
+    VQ2_REQUIRE(d->Cir >= 0 && d->Cir <= d->Ci && d->Cor >= 0 && d->Cor <= d->Co, "conv desc: Cir/Cor out of range");
+    VQ2_REQUIRE((d->same_size == 0 || d->same_size == 1) && (d->transposed == 0 || d->transposed == 1),
+                "conv desc: same_size=%d and transposed=%d must be 0 or 1", d->same_size, d->transposed);
+    VQ2_REQUIRE(d->KH >= 1 && d->KH <= 7 && d->KW >= 1 && d->KW <= 7, "conv desc: KH=%d, KW=%d must lie in 1..7", d->KH, d->KW);
+    VQ2_REQUIRE(d->pad_top >= 0 && d->pad_top < d->KH && d->pad_left >= 0 && d->pad_left < d->KW,
+                "conv desc: 0 <= pad_top < KH and 0 <= pad_left < KW required (got %d, %d)", d->pad_top, d->pad_left);
+    if (d->same_size) {
+        VQ2_REQUIRE(d->stride == 1 && !d->transposed, "conv desc: same_size needs stride 1 and no transposition");
+        if (d->KH * d->KW > 32) return set_error(VQ2_ERR_UNSUPPORTED, "conv desc: %d x %d has more than 32 taps", d->KH, d->KW);
+    } else {
+        VQ2_REQUIRE(d->KW == d->KH && d->pad_left == d->pad_top,
+                    "conv desc: a square kernel and pad_top == pad_left required without same_size");
+        if (d->transposed) {
+            VQ2_REQUIRE(d->KH == 4 && d->stride == 2 && d->pad_top == 1,
+                        "conv-transpose supports k4 s2 p1 only (vqvae.py:150-160,191-193)");
+        } else {
+            VQ2_REQUIRE(d->stride == 1 || d->stride == 2, "conv: stride 1 or 2");
+            VQ2_REQUIRE(d->H + 2 * d->pad_top >= d->KH && d->W + 2 * d->pad_left >= d->KW, "conv: kernel larger than padded input");
+            if (d->stride == 2) VQ2_REQUIRE(d->KH == 4 && d->pad_top == 1 && d->H % 2 == 0 && d->W % 2 == 0,
+                                            "stride-2 conv supports k4 p1 on even sizes (vqvae.py:105,107,114)");
+        }
+    }
+    const ConvHW o = out_hw(d);
+    const int64_t lim = (int64_t)1 << 31;
+    VQ2_REQUIRE((how & DESC_PLAN_ONLY) || ((int64_t)d->N * d->H * d->W * d->ldx < lim && (int64_t)d->N * o.h * o.w * d->ldy < lim),
+                "conv: tensor exceeds 2^31 elements (int32 indexing)");
+    return VQ2_OK;
 }
 
 // Algorithmic work of a layer, the same for its forward, data-gradient and weight-gradient launches (for the profiler only):
 // real channels, every tap once; the input-sized and the output-sized tensor cross memory once each, plus `more_in` /
 // `more_out` further tensors of those sizes (residual, mask), plus the weights.
 struct ConvWork { double flops, bytes; };
-static inline ConvWork conv_work(const ConvGeo *d, int more_in, int more_out) {
+static inline ConvWork conv_work(const vq2_conv_desc *d, int more_in, int more_out) {
     const double cir = real_ci(d), cor = real_co(d);
     const ConvHW o = out_hw(d);
     const double pix_in = (double)d->N * d->H * d->W, pix_out = (double)d->N * o.h * o.w;

@@ -1495,37 +1495,12 @@ static bool use_convT_small(const vq2_conv_desc *d) {
     return d->transposed && d->Co == 4 && d->Cor >= 1 && d->Cor <= 3 && d->Ci % 16 == 0;
 }
 
-static int check_desc(const ConvGeo *d) {
-    if (int e = check_forms()) return e;
-    VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0, "conv desc: non-positive dims");
-    VQ2_REQUIRE(d->Ci % 4 == 0 && d->Co % 4 == 0, "conv desc: Ci=%d, Co=%d must be multiples of 4", d->Ci, d->Co);
-    VQ2_REQUIRE(d->ldx >= d->Ci && d->ldx % 4 == 0, "conv desc: ldx=%d must be >= Ci and a multiple of 4", d->ldx);
-    VQ2_REQUIRE(d->ldy >= d->Co && d->ldy % 4 == 0, "conv desc: ldy=%d must be >= Co and a multiple of 4", d->ldy);
-    VQ2_REQUIRE(d->Cir >= 0 && d->Cir <= d->Ci && d->Cor >= 0 && d->Cor <= d->Co, "conv desc: Cir/Cor out of range");
-    if (d->transposed) {
-        VQ2_REQUIRE(d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_h == 1,
-                    "conv-transpose supports k4 s2 p1 only (vqvae.py:150-160,191-193)");
-    } else if (!d->same) {   // (the second descriptor's kernel and padding were checked by check_geom)
-        VQ2_REQUIRE(d->KH >= 1 && d->KH <= 7 && d->KW == d->KH, "conv: square kernel 1..7 required");
-        VQ2_REQUIRE(d->stride == 1 || d->stride == 2, "conv: stride 1 or 2");
-        VQ2_REQUIRE(d->pad_h >= 0 && d->pad_h < d->KH, "conv: 0 <= pad < KH");
-        VQ2_REQUIRE(d->H + 2 * d->pad_h >= d->KH && d->W + 2 * d->pad_w >= d->KW, "conv: kernel larger than padded input");
-        if (d->stride == 2) VQ2_REQUIRE(d->KH == 4 && d->pad_h == 1 && d->H % 2 == 0 && d->W % 2 == 0,
-                                        "stride-2 conv supports k4 p1 on even sizes (vqvae.py:105,107,114)");
-    }
-    const ConvHW o = out_hw(d);
-    const int64_t lim = (int64_t)1 << 31;
-    VQ2_REQUIRE((int64_t)d->N * d->H * d->W * d->ldx < lim && (int64_t)d->N * o.h * o.w * d->ldy < lim,
-                "conv: tensor exceeds 2^31 elements (int32 indexing)");
-    return VQ2_OK;
-}
-
 }  // namespace vq2
 
 using namespace vq2;
 
 // mode 3 = pack_convT_small layout
-static int pack_job_of(const ConvGeo *d, int which, vq2_pack_job *j) {
+static int pack_job_of(const vq2_conv_desc *d, int which, vq2_pack_job *j) {
     const int cir = real_ci(d), cor = real_co(d);
     j->KH = d->KH; j->KW = d->KW;
     if (which == VQ2_PACK_FWD && use_convT_small(d)) {
@@ -1575,24 +1550,12 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(const vq2_pack_job *_
     }
 }
 
-static int pack_job_init_impl(const ConvGeo *d, int which, const float *w, float *packed, vq2_pack_job *job) {
-    if (int e = check_desc(d)) return e;
+extern "C" int vq2_pack_job_init(const vq2_conv_desc *d, int which, const float *w, float *packed, vq2_pack_job *job) {
+    if (int e = check_conv_desc(d, "pack_job_init")) return e;
     VQ2_REQUIRE(w && packed && job, "pack_job_init: null pointer");
     VQ2_REQUIRE(which == VQ2_PACK_FWD || which == VQ2_PACK_DGRAD, "pack_job_init: bad `which`");
     job->w = w; job->packed = packed; job->offset = 0;
     return pack_job_of(d, which, job);
-}
-
-extern "C" int vq2_pack_job_init(const vq2_conv_desc *d, int which, const float *w, float *packed, vq2_pack_job *job) {
-    VQ2_REQUIRE(d != nullptr, "conv desc is null");
-    const ConvGeo g = geo_of(d);
-    return pack_job_init_impl(&g, which, w, packed, job);
-}
-
-extern "C" int vq2_convg_pack_job_init(const vq2_conv_geom *d, int which, const float *w, float *packed, vq2_pack_job *job) {
-    if (int e = check_geom(d)) return e;
-    const ConvGeo g = geo_of(d);
-    return pack_job_init_impl(&g, which, w, packed, job);
 }
 
 extern "C" int vq2_pack_weights_batched(const vq2_pack_job *jobs_dev, int32_t njobs, int64_t total, vq2_stream_t stream) {
@@ -1609,9 +1572,9 @@ __global__ void pack_single_kernel(const float *__restrict__ w, float *__restric
         p[t] = pack_elem(w, t, Or, Ir, Op, Ip, KH, KW, mode);
 }
 
-static int pack_weight_impl(const ConvGeo *d, int which, const float *w, float *packed, vq2_stream_t stream) {
+extern "C" int vq2_pack_weight(const vq2_conv_desc *d, int which, const float *w, float *packed, vq2_stream_t stream) {
     vq2_pack_job j;
-    if (int e = pack_job_init_impl(d, which, w, packed, &j)) return e;
+    if (int e = vq2_pack_job_init(d, which, w, packed, &j)) return e;
     const int total = (int)j.numel;
     const int blocks = (total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024;
     hipLaunchKernelGGL(pack_single_kernel, dim3(blocks), dim3(256), 0, to_stream(stream), w, packed, j.Or, j.Ir, j.Op, j.Ip,
@@ -1619,21 +1582,9 @@ static int pack_weight_impl(const ConvGeo *d, int which, const float *w, float *
     return check_launch("pack_single_kernel");
 }
 
-extern "C" int vq2_pack_weight(const vq2_conv_desc *d, int which, const float *w, float *packed, vq2_stream_t stream) {
-    VQ2_REQUIRE(d != nullptr, "conv desc is null");
-    const ConvGeo g = geo_of(d);
-    return pack_weight_impl(&g, which, w, packed, stream);
-}
-
-extern "C" int vq2_convg_pack_weight(const vq2_conv_geom *d, int which, const float *w, float *packed, vq2_stream_t stream) {
-    if (int e = check_geom(d)) return e;
-    const ConvGeo g = geo_of(d);
-    return pack_weight_impl(&g, which, w, packed, stream);
-}
-
-static int conv_fwd_impl(const ConvGeo *d, int flags, const float *x, const float *wp, const float *bias,
-                         const float *residual, int32_t ldres, float *y, vq2_stream_t stream) {
-    if (int e = check_desc(d)) return e;
+extern "C" int vq2_conv_fwd(const vq2_conv_desc *d, int flags, const float *x, const float *wp, const float *bias,
+                            const float *residual, int32_t ldres, float *y, vq2_stream_t stream) {
+    if (int e = check_conv_desc(d, "conv_fwd")) return e;
     VQ2_REQUIRE(x && wp && y, "conv_fwd: null pointer");
     VQ2_REQUIRE(aligned16(x) && aligned16(wp) && aligned16(y), "conv_fwd: pointers must be 16-byte aligned");
     VQ2_REQUIRE(!residual || (ldres >= d->Co), "conv_fwd: ldres < Co");
@@ -1647,7 +1598,7 @@ static int conv_fwd_impl(const ConvGeo *d, int flags, const float *x, const floa
     const ConvHW o = out_hw(d);
     P.Hy = o.h; P.Wy = o.w;
     if (!d->transposed) {
-        P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = d->pad_h; P.pad_w = d->pad_w;
+        P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = d->pad_top; P.pad_w = d->pad_left;
         P.Ho = P.Hy; P.Wo = P.Wy; P.phases = 1;
     } else {
         P.KH = 2; P.KW = 2; P.stride = 1; P.pad_h = P.pad_w = 1;
@@ -1681,30 +1632,10 @@ static int conv_fwd_impl(const ConvGeo *d, int flags, const float *x, const floa
     return launch_conv(plan_conv(P), P, s);
 }
 
-extern "C" int vq2_conv_fwd(const vq2_conv_desc *d, int flags, const float *x, const float *wp, const float *bias,
-                            const float *residual, int32_t ldres, float *y, vq2_stream_t stream) {
-    VQ2_REQUIRE(d != nullptr, "conv desc is null");
-    const ConvGeo g = geo_of(d);
-    return conv_fwd_impl(&g, flags, x, wp, bias, residual, ldres, y, stream);
-}
-
-extern "C" int vq2_convg_fwd(const vq2_conv_geom *d, int flags, const float *x, const float *wp, const float *bias,
-                             const float *residual, int32_t ldres, float *y, vq2_stream_t stream) {
-    if (int e = check_geom(d)) return e;
-    const ConvGeo g = geo_of(d);
-    return conv_fwd_impl(&g, flags, x, wp, bias, residual, ldres, y, stream);
-}
-
-extern "C" int vq2_conv_dgrad(const vq2_conv_desc *d, const float *dy, const float *wp, const float *mask,
+extern "C" int vq2_conv_dgrad(const vq2_conv_desc *d, int flags, const float *dy, const float *wp, const float *mask,
                               int32_t ldmask, const float *residual, int32_t ldres, float *dx, int32_t lddx,
                               vq2_stream_t stream) {
-    return vq2_conv_dgrad_ex(d, 0, dy, wp, mask, ldmask, residual, ldres, dx, lddx, stream);
-}
-
-static int conv_dgrad_impl(const ConvGeo *d, int flags, const float *dy, const float *wp, const float *mask,
-                           int32_t ldmask, const float *residual, int32_t ldres, float *dx, int32_t lddx,
-                           vq2_stream_t stream) {
-    if (int e = check_desc(d)) return e;
+    if (int e = check_conv_desc(d, "conv_dgrad")) return e;
     VQ2_REQUIRE((flags & ~VQ2_MASK_AFTER_RESIDUAL) == 0, "conv_dgrad: unknown flag");
     VQ2_REQUIRE(dy && wp && dx, "conv_dgrad: null pointer");
     VQ2_REQUIRE(aligned16(dy) && aligned16(wp) && aligned16(dx), "conv_dgrad: pointers must be 16-byte aligned");
@@ -1722,7 +1653,7 @@ static int conv_dgrad_impl(const ConvGeo *d, int flags, const float *dy, const f
     P.Hy = d->H; P.Wy = d->W;
     if (!d->transposed && d->stride == 1) {
         // full correlation with the flipped kernel: pad' = K-1-pad per axis
-        P.KH = d->KH; P.KW = d->KW; P.stride = 1; P.pad_h = d->KH - 1 - d->pad_h; P.pad_w = d->KW - 1 - d->pad_w;
+        P.KH = d->KH; P.KW = d->KW; P.stride = 1; P.pad_h = d->KH - 1 - d->pad_top; P.pad_w = d->KW - 1 - d->pad_left;
         P.Ho = d->H; P.Wo = d->W; P.phases = 1;
     } else if (!d->transposed) {
         // stride-2 k4 p1: dx = conv_transpose(dy): sub-pixel phases over the dy grid
@@ -1737,20 +1668,4 @@ static int conv_dgrad_impl(const ConvGeo *d, int flags, const float *dy, const f
     const ConvWork work = conv_work(d, (mask ? 1 : 0) + (residual ? 1 : 0), 0);   // dy read once, dx written once (+ mask, residual)
     P.flops = work.flops; P.bytes = work.bytes;
     return launch_conv(plan_conv(P), P, to_stream(stream));
-}
-
-extern "C" int vq2_conv_dgrad_ex(const vq2_conv_desc *d, int flags, const float *dy, const float *wp, const float *mask,
-                                 int32_t ldmask, const float *residual, int32_t ldres, float *dx, int32_t lddx,
-                                 vq2_stream_t stream) {
-    VQ2_REQUIRE(d != nullptr, "conv desc is null");
-    const ConvGeo g = geo_of(d);
-    return conv_dgrad_impl(&g, flags, dy, wp, mask, ldmask, residual, ldres, dx, lddx, stream);
-}
-
-extern "C" int vq2_convg_dgrad(const vq2_conv_geom *d, int flags, const float *dy, const float *wp, const float *mask,
-                               int32_t ldmask, const float *residual, int32_t ldres, float *dx, int32_t lddx,
-                               vq2_stream_t stream) {
-    if (int e = check_geom(d)) return e;
-    const ConvGeo g = geo_of(d);
-    return conv_dgrad_impl(&g, flags, dy, wp, mask, ldmask, residual, ldres, dx, lddx, stream);
 }

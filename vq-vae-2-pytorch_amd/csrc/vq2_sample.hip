@@ -4,7 +4,7 @@
 //   row convolution    output row `row` of a causal conv (pad_top == KH - 1) from input rows kept in a history with its own
 //                      image and row strides.  The GEMM is small in M (N * W pixels) and long in K (KH * KW * Ci), so K is
 //                      split over taps: convg_row_partial_kernel writes one [M][Co] slab per split, convg_row_reduce_kernel
-//                      adds the slabs in ascending order and applies the epilogue of vq2_convg_fwd.  No atomics: two runs
+//                      adds the slabs in ascending order and applies the epilogue of vq2_conv_fwd.  No atomics: two runs
 //                      give the same bits.  v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation) with the
 //                      weight panel rows on the A side and the pixels on the B side: a lane then holds 4 consecutive output
 //                      channels of one pixel and stores 16 bytes.  Both operands come straight from global memory as float4
@@ -38,7 +38,7 @@ struct RowConv {
 
 // which taps are computed and how they are cut into splits: a function of the shape and the flags alone
 struct RowPlan { unsigned mask; int ntaps, tps, splits; };
-static RowPlan row_plan(const vq2_conv_geom *d, int flags) {
+static RowPlan row_plan(const vq2_conv_desc *d, int flags) {
     RowPlan p{0u, 0, 1, 1};
     for (int kh = 0; kh < d->KH; ++kh)
         for (int kw = 0; kw < d->KW; ++kw) {
@@ -211,44 +211,40 @@ __global__ __launch_bounds__(256) void sample_uniforms_kernel(float *__restrict_
     if (row < M) u[row] = uniform_of(seed_lo, seed_hi, pos_lo, pos_hi, (uint32_t)row);
 }
 
-int check_row_geom(const vq2_conv_geom *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags) {
-    if (int e = vq2::check_geom(d)) return e;
-    VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0, "convg_fwd_row: non-positive dims");
-    VQ2_REQUIRE(d->Ci % 4 == 0 && d->Co % 4 == 0, "convg_fwd_row: Ci=%d, Co=%d must be multiples of 4", d->Ci, d->Co);
-    VQ2_REQUIRE(d->ldx >= d->Ci && d->ldx % 4 == 0, "convg_fwd_row: ldx=%d must be >= Ci and a multiple of 4", d->ldx);
-    VQ2_REQUIRE(d->ldy >= d->Co && d->ldy % 4 == 0, "convg_fwd_row: ldy=%d must be >= Co and a multiple of 4", d->ldy);
-    VQ2_REQUIRE(d->pad_top == d->KH - 1, "convg_fwd_row: pad_top == KH - 1 required (the kernel must end at the output row)");
-    VQ2_REQUIRE(row >= 0 && row < d->H, "convg_fwd_row: row %d outside the %d rows", row, d->H);
+// what the row form asks beyond vq2::check_conv_desc
+int check_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags) {
+    if (int e = vq2::check_conv_desc(d, "conv_fwd_row")) return e;
+    VQ2_REQUIRE(d->same_size == 1 && d->pad_top == d->KH - 1,
+                "conv_fwd_row: same_size and pad_top == KH - 1 required (the kernel must end at the output row)");
+    VQ2_REQUIRE(row >= 0 && row < d->H, "conv_fwd_row: row %d outside the %d rows", row, d->H);
     VQ2_REQUIRE(x_image_stride >= 0 && x_row_stride >= 0 && x_image_stride % 4 == 0 && x_row_stride % 4 == 0,
-                "convg_fwd_row: input strides must be non-negative multiples of 4");
-    VQ2_REQUIRE((flags & ~(VQ2_RELU_IN | VQ2_RELU_OUT | VQ2_ROW_CAUSAL_TAPS)) == 0, "convg_fwd_row: unknown flag");
-    VQ2_REQUIRE((int64_t)d->N * d->W * (d->ldy > d->Co ? d->ldy : d->Co) < ((int64_t)1 << 31) &&
-                    (int64_t)d->Co * d->KH * d->KW * d->Ci < ((int64_t)1 << 31),
-                "convg_fwd_row: tensor exceeds 2^31 elements");
+                "conv_fwd_row: input strides must be non-negative multiples of 4");
+    VQ2_REQUIRE((flags & ~(VQ2_RELU_IN | VQ2_RELU_OUT | VQ2_ROW_CAUSAL_TAPS)) == 0, "conv_fwd_row: unknown flag");
+    VQ2_REQUIRE((int64_t)d->Co * d->KH * d->KW * d->Ci < ((int64_t)1 << 31), "conv_fwd_row: tensor exceeds 2^31 elements");
     return VQ2_OK;
 }
 
 }  // namespace
 
-extern "C" size_t vq2_convg_fwd_row_workspace_bytes(const vq2_conv_geom *d, int flags) {
+extern "C" size_t vq2_conv_fwd_row_workspace_bytes(const vq2_conv_desc *d, int flags) {
     if (!d || d->N <= 0 || d->W <= 0 || d->Co <= 0 || d->KH < 1 || d->KW < 1 || d->KH * d->KW > 32) return 0;
     const RowPlan p = row_plan(d, flags);
     return (size_t)p.splits * d->N * d->W * d->Co * sizeof(float);
 }
 
-extern "C" int vq2_convg_fwd_row(const vq2_conv_geom *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
-                                 const float *x, const float *wp, const float *bias, const float *residual, int32_t ldres,
-                                 float *y, void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    if (int e = check_row_geom(d, row, x_image_stride, x_row_stride, flags)) return e;
-    VQ2_REQUIRE(x && wp && y && ws, "convg_fwd_row: null pointer");
+extern "C" int vq2_conv_fwd_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
+                                const float *x, const float *wp, const float *bias, const float *residual, int32_t ldres,
+                                float *y, void *ws, size_t ws_bytes, vq2_stream_t stream) {
+    if (int e = check_row(d, row, x_image_stride, x_row_stride, flags)) return e;
+    VQ2_REQUIRE(x && wp && y && ws, "conv_fwd_row: null pointer");
     VQ2_REQUIRE(vq2::aligned16(x) && vq2::aligned16(wp) && vq2::aligned16(y) && vq2::aligned16(ws) &&
                     (!residual || vq2::aligned16(residual)),
-                "convg_fwd_row: pointers must be 16-byte aligned");
-    VQ2_REQUIRE(!residual || (ldres >= d->Co && ldres % 4 == 0), "convg_fwd_row: ldres must be >= Co and a multiple of 4");
+                "conv_fwd_row: pointers must be 16-byte aligned");
+    VQ2_REQUIRE(!residual || (ldres >= d->Co && ldres % 4 == 0), "conv_fwd_row: ldres must be >= Co and a multiple of 4");
     const RowPlan pl = row_plan(d, flags);
-    if (ws_bytes < vq2_convg_fwd_row_workspace_bytes(d, flags))
-        return vq2::set_error(VQ2_ERR_WORKSPACE, "convg_fwd_row: workspace of %zu bytes, %zu needed", ws_bytes,
-                              vq2_convg_fwd_row_workspace_bytes(d, flags));
+    if (ws_bytes < vq2_conv_fwd_row_workspace_bytes(d, flags))
+        return vq2::set_error(VQ2_ERR_WORKSPACE, "conv_fwd_row: workspace of %zu bytes, %zu needed", ws_bytes,
+                              vq2_conv_fwd_row_workspace_bytes(d, flags));
     hipStream_t s = vq2::to_stream(stream);
     RowConv P{};
     P.x = x; P.w = wp; P.ws = static_cast<float *>(ws);

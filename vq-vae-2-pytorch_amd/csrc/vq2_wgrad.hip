@@ -797,7 +797,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const vq2_wgr
 }
 
 // ====================================================================== the plan: roles, kernel, tile, splits
-// plan_wgrad() decides everything about a launch from the layer (ConvGeo) alone; wgrad_params() and wgrad_job_init_impl()
+// plan_wgrad() decides everything about a launch from the layer (vq2_conv_desc) alone; wgrad_params() and wgrad_job_init_impl()
 // fill the kernels' arguments from it, the tile's launcher launches what it says, wgrad_label() prints it (as on the
 // forward side: plan_conv / conv_tiles / conv_label / launch_conv).
 // Roles (see the head of this file): plain conv, the same conv with x and dy exchanged (plan_wgrad says when), conv-transpose
@@ -819,15 +819,15 @@ struct WgradPlan {
 
 // The two operands as the kernels see them -- the exchange of x and dy, written once: X is gathered through the taps (an
 // H x W grid) and is dy unless the role is plain, G is streamed row by row (an Ho x Wo grid, M = N * Ho * Wo rows).
-static WgradParams wgrad_operands(const ConvGeo *d, int role) {
+static WgradParams wgrad_operands(const vq2_conv_desc *d, int role) {
     WgradParams P{};
-    P.N = d->N; P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = d->pad_h; P.pad_w = d->pad_w;
+    P.N = d->N; P.KH = d->KH; P.KW = d->KW; P.stride = d->stride; P.pad_h = d->pad_top; P.pad_w = d->pad_left;
     P.H = d->H; P.W = d->W; P.Ho = d->H; P.Wo = d->W;
     P.ldx = role == WGRAD_PLAIN ? d->ldx : d->ldy;
     P.ldg = role == WGRAD_PLAIN ? d->ldy : d->ldx;
     if (role == WGRAD_PLAIN) { P.Ho = out_hw(d).h; P.Wo = out_hw(d).w; }
     else if (role == WGRAD_CONVT) { P.H = 2 * d->H; P.W = 2 * d->W; }      // dy is the 2H x 2W tensor
-    else { P.stride = 1; P.pad_h = P.pad_w = d->KH - 1 - d->pad_h; }       // dy the size of x; flipped taps, pad' = K - 1 - p
+    else { P.stride = 1; P.pad_h = P.pad_w = d->KH - 1 - d->pad_top; }       // dy the size of x; flipped taps, pad' = K - 1 - p
     return P;
 }
 
@@ -883,7 +883,7 @@ static constexpr int wgrad_tile_of(int bmo, int bnk) {
 }
 static_assert(wgrad_tile_of(128, 128) >= 0 && wgrad_tile_of(128, 96) >= 0, "plan_wgrad names a tile that WGRAD_TILES lacks");
 
-static WgradPlan plan_wgrad(const ConvGeo *d) {
+static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     WgradPlan p{};
     // A stride-1 "same" conv with few output channels (the ResBlock 3x3, 128 -> 32): gathering the im2col
     // of the WIDE tensor x re-reads it KH*KW times through L2.  The same sum with the roles exchanged,
@@ -896,7 +896,7 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
     // Winograd modes: tensors that the 32-bit byte offsets of wgrad_fast_kernel reach (x and dy counted over the INPUT grid)
     const long pix = (long)d->N * d->H * d->W;
     const bool wino = forms() == FORMS_ALL && pix * d->ldx < FAST_REACH && pix * d->ldy * (d->transposed ? 4 : 1) < FAST_REACH;
-    if (fast && !d->transposed && d->stride == 1 && d->KH == d->KW && d->pad_h == d->pad_w && 2 * d->pad_h == d->KH - 1 &&
+    if (fast && !d->transposed && d->stride == 1 && d->KH == d->KW && d->pad_top == d->pad_left && 2 * d->pad_top == d->KH - 1 &&
         d->KH > 1 && d->Co <= 32 && d->Ci >= 64)
         p.role = WGRAD_EXCHANGED;
     else
@@ -909,7 +909,7 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
     p.Ir = plain ? real_ci(d) : real_co(d);
     p.M = d->N * v.Ho * v.Wo;
     p.K = d->KH * d->KW * p.I;
-    if (wino && plain && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 &&
+    if (wino && plain && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_top == 1 && d->pad_left == 1 &&
         p.O % 128 == 0 && p.I % 128 == 0 && (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0))) {
         p.wino = 1;
         p.K = 12 * p.I;
@@ -917,7 +917,7 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
     }
     {   // 4x4 stride-2 conv / conv-transpose: F(2,2) by column parity over output column pairs
         const int wo = d->transposed ? d->W : d->W / 2;       // width of the G operand's grid
-        if (wino && p.role != WGRAD_EXCHANGED && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_h == 1 && d->H % 2 == 0 &&
+        if (wino && p.role != WGRAD_EXCHANGED && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_top == 1 && d->H % 2 == 0 &&
             d->W % 2 == 0 && p.O % 128 == 0 && (p.I == 64 || p.I % 128 == 0) &&
             (wo % 64 == 0 || (wo == 32 && (d->transposed ? d->H : d->H / 2) % 2 == 0))) {
             p.wino = 2;
@@ -940,7 +940,7 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
             if (best < 0 || work < best) { best = work; p.tile = c; }
         }
     }
-    if (wino && p.role == WGRAD_EXCHANGED && d->KH == 3 && d->pad_h == 1 && p.I == 32 && p.O % 128 == 0 &&
+    if (wino && p.role == WGRAD_EXCHANGED && d->KH == 3 && d->pad_top == 1 && p.I == 32 && p.O % 128 == 0 &&
         (d->W % 64 == 0 || (d->W == 32 && d->H % 2 == 0))) {
         p.wino = 3;                 // exchanged roles + F(2,3): four 128 x 96 tiles (v) of three kernel rows each
         p.K = 4 * 96;
@@ -983,7 +983,7 @@ static WgradPlan plan_wgrad(const ConvGeo *d) {
 static size_t wgrad_ws_bytes(const WgradPlan &p) { return ((size_t)p.S * p.O * p.K + p.bias_floats) * sizeof(float); }
 
 // The kernels' arguments of a planned launch; the slabs [S][O][K] come first in ws, the bias partials behind them.
-static int wgrad_params(const ConvGeo *d, const WgradPlan &p, int flags, const float *x, const float *dy, float *db, void *ws,
+static int wgrad_params(const vq2_conv_desc *d, const WgradPlan &p, int flags, const float *x, const float *dy, float *db, void *ws,
                         WgradParams &P) {
     VQ2_REQUIRE(p.ext_x < (1L << 31) && p.ext_g < (1L << 31), "conv_wgrad: tensor exceeds 2^31 elements");
     const bool plain = p.role == WGRAD_PLAIN;
@@ -1000,7 +1000,7 @@ static int wgrad_params(const ConvGeo *d, const WgradPlan &p, int flags, const f
 
 // The profiler label of a planned launch, "wgrad<tile><form>|<shape>,fast|gen" (wgrad_fast_kernel or wgrad_kernel):
 // formatted here and nowhere else.
-static const char *wgrad_label(const WgradPlan &p, const WgradTile &t, const ConvGeo *d) {
+static const char *wgrad_label(const WgradPlan &p, const WgradTile &t, const vq2_conv_desc *d) {
     const char *form = p.wino == 3 ? "swwino" : p.role == WGRAD_EXCHANGED ? "sw" : p.wino == 1 ? "wino" : p.wino == 2 ? "wino4" : "";
     return prof_label("wgrad<%dx%d>%s|O=%d,K=%d,M=%d,S=%d,k%d,%s", t.bmo, t.bnk, form, p.O, p.K, p.M, p.S, d->KH,
                       p.family == WGRAD_GEN ? "gen" : "fast");
@@ -1082,33 +1082,14 @@ static int colsum_impl(const float *dy, int64_t rows, int C, int ld, float *db, 
 
 using namespace vq2;
 
-// The preamble of the eight entry points, once per descriptor type: the checks that only that type has, then the common
-// ConvGeo.  `who` names the entry point in the first descriptor's null-pointer message.
-static int entry_geo(const vq2_conv_desc *d, const char *who, ConvGeo &g) {
-    VQ2_REQUIRE(d, "%s: null pointer", who);
-    g = geo_of(d);
-    return VQ2_OK;
+// 0 for anything check_conv_desc refuses
+extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) {
+    if (!d || check_conv_desc(d, "conv_wgrad_workspace_bytes", DESC_PLAN_ONLY)) return 0;   // (null: no message)
+    return wgrad_ws_bytes(plan_wgrad(d));
 }
-static int entry_geo(const vq2_conv_geom *d, const char *, ConvGeo &g) {
-    if (int e = check_geom(d)) return e;
-    g = geo_of(d);
-    return VQ2_OK;
-}
-
-template <class Desc>
-static size_t wgrad_ws_entry(const Desc *d) {
-    ConvGeo g;
-    if (entry_geo(d, "conv_wgrad_workspace_bytes", g) || check_forms() || g.N <= 0 || g.H <= 0 || g.W <= 0 || g.Ci <= 0 ||
-        g.Co <= 0 || g.KH <= 0 || g.KW <= 0)
-        return 0;
-    return wgrad_ws_bytes(plan_wgrad(&g));
-}
-
-extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) { return d ? wgrad_ws_entry(d) : 0; }   // (null: no message)
-extern "C" size_t vq2_convg_wgrad_workspace_bytes(const vq2_conv_geom *d) { return wgrad_ws_entry(d); }
 
 // The reduction job of a planned layer: what wgrad_reduce_batched_kernel reads, and the arguments of wgrad_reduce_kernel.
-static void wgrad_job_init_impl(const ConvGeo *d, const WgradPlan &p, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
+static void wgrad_job_init_impl(const vq2_conv_desc *d, const WgradPlan &p, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
     const float *w = static_cast<const float *>(ws);
     job->ws = w; job->dw = dw;
     job->O = p.O; job->I = p.I; job->Or = p.Or; job->Ir = p.Ir;
@@ -1123,23 +1104,11 @@ static void wgrad_job_init_impl(const ConvGeo *d, const WgradPlan &p, const void
 }
 
 // slabs (+ bias partials); reduce == true also runs the per-layer reduction into dw/db
-template <class Desc>
-static int wgrad_impl(const Desc *desc, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
+static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
                       size_t ws_bytes, vq2_stream_t stream, bool reduce) {
-    ConvGeo g;
-    if (int e = entry_geo(desc, "conv_wgrad", g)) return e;
-    const ConvGeo *d = &g;
+    if (int e = check_conv_desc(d, "conv_wgrad")) return e;
     VQ2_REQUIRE(x && dy && ws && (dw || !reduce), "conv_wgrad: null pointer");
-    if (int e = check_forms()) return e;
-    VQ2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ci > 0 && d->Co > 0 && d->Ci % 4 == 0 && d->Co % 4 == 0,
-                "conv_wgrad: bad dims");
-    VQ2_REQUIRE(d->ldx >= d->Ci && d->ldy >= d->Co && d->ldx % 4 == 0 && d->ldy % 4 == 0, "conv_wgrad: bad strides");
     VQ2_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(ws), "conv_wgrad: pointers must be 16-byte aligned");
-    if (d->transposed)
-        VQ2_REQUIRE(d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_h == 1, "conv_wgrad: convT must be k4 s2 p1");
-    else if (!d->same)   // (the second descriptor was checked by check_geom)
-        VQ2_REQUIRE(d->KH == d->KW && d->KH >= 1 && d->KH <= 7 && (d->stride == 1 || d->stride == 2) && d->pad_h >= 0,
-                    "conv_wgrad: unsupported conv geometry");
     const WgradPlan p = plan_wgrad(d);
     VQ2_REQUIRE(ws_bytes >= wgrad_ws_bytes(p), "conv_wgrad: workspace too small");
     WgradParams P;
@@ -1167,32 +1136,12 @@ extern "C" int vq2_conv_wgrad_partial(const vq2_conv_desc *d, int flags, const f
                                       void *ws, size_t ws_bytes, vq2_stream_t stream) {
     return wgrad_impl(d, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
 }
-extern "C" int vq2_convg_wgrad(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *dw, float *db,
-                               void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    return wgrad_impl(d, flags, x, dy, dw, db, ws, ws_bytes, stream, true);
-}
-extern "C" int vq2_convg_wgrad_partial(const vq2_conv_geom *d, int flags, const float *x, const float *dy, float *db,
-                                       void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    return wgrad_impl(d, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
-}
-
-template <class Desc>
-static int wgrad_job_entry(const Desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
-    ConvGeo g;
-    if (int e = entry_geo(d, "wgrad_job_init", g)) return e;
-    VQ2_REQUIRE(ws && dw && job, "wgrad_job_init: null pointer");
-    // (the second descriptor's job_init checks the dims, the first one's never did)
-    VQ2_REQUIRE(!g.same || (g.N > 0 && g.H > 0 && g.W > 0 && g.Ci > 0 && g.Co > 0), "wgrad_job_init: non-positive dims");
-    if (int e = check_forms()) return e;
-    wgrad_job_init_impl(&g, plan_wgrad(&g), ws, dw, db, job);
-    return VQ2_OK;
-}
 
 extern "C" int vq2_wgrad_job_init(const vq2_conv_desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
-    return wgrad_job_entry(d, ws, dw, db, job);
-}
-extern "C" int vq2_convg_wgrad_job_init(const vq2_conv_geom *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
-    return wgrad_job_entry(d, ws, dw, db, job);
+    if (int e = check_conv_desc(d, "wgrad_job_init", DESC_PLAN_ONLY)) return e;
+    VQ2_REQUIRE(ws && dw && job, "wgrad_job_init: null pointer");
+    wgrad_job_init_impl(d, plan_wgrad(d), ws, dw, db, job);
+    return VQ2_OK;
 }
 
 extern "C" int vq2_wgrad_reduce_batched(const vq2_wgrad_job *jobs_dev, int32_t njobs, int64_t total_units,

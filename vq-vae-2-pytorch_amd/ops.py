@@ -6,7 +6,6 @@ wider buffer).  PyTorch is used for device memory, streams and autograd bookkeep
 every FLOP and every byte moved on this path is a libvq2 kernel.
 """
 from dataclasses import dataclass
-from types import SimpleNamespace
 import contextlib
 import ctypes as C
 import os
@@ -14,7 +13,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from ._lib import lib, check, AttnDesc, ConvDesc, ConvGeom, OneHotDesc, PackJob, WgradJob, WnEntry
+from ._lib import lib, check, AttnDesc, ConvDesc, OneHotDesc, PackJob, WgradJob, WnEntry
 
 VQ2_RELU_IN = 1
 VQ2_RELU_OUT = 2
@@ -100,31 +99,36 @@ def packed(t):
 # ----------------------------------------------------------------------------- conv plumbing
 @dataclass(frozen=True)
 class ConvSpec:
+    """A conv layer as vq2_conv_desc (include/vq2.h) states it, without the batch.  ConvSpec(transposed, cin, cout, k, stride,
+    pad) is the square kernel with the same padding on every side of the stage-1 layers; ConvSpec.geom() the stride-1
+    kh x kw kernel with top / left padding and an output the size of the input (WNConv2d / CausalConv2d of the stage-2 prior)."""
     transposed: bool
     cin: int
     cout: int
-    k: int
+    k: int                    # kernel rows
     stride: int
-    pad: int
-    # The second geometry (vq2_conv_geom of include/vq2.h; WNConv2d / CausalConv2d of the stage-2 prior): kernel columns
-    # and top / left padding on their own, output the size of the input.  All None (the default): the square, symmetric
-    # layer that `k` and `pad` describe, through vq2_conv_desc as before.  Set together by ConvSpec.geom().
-    kw: int = None
-    pad_top: int = None
-    pad_left: int = None
+    pad: int                  # top padding
+    kw: int = 0               # kernel columns and left padding; without same_size always k and pad (__post_init__)
+    pad_left: int = 0
+    same_size: bool = False   # vq2_conv_desc.same_size
+
+    def __post_init__(self):
+        if not self.same_size:
+            object.__setattr__(self, "kw", self.k)
+            object.__setattr__(self, "pad_left", self.pad)
 
     @classmethod
     def geom(cls, cin, cout, kh, kw, pad_top, pad_left):
         """A stride-1 conv with a kh x kw kernel that reads from row h - pad_top and column w - pad_left on."""
-        return cls(False, cin, cout, kh, 1, pad_top, kw, pad_top, pad_left)
+        return cls(False, cin, cout, kh, 1, pad_top, kw, pad_left, True)
 
     @property
-    def is_geom(self):
-        return self.kw is not None
+    def pad_top(self):
+        return self.pad
 
     @property
     def taps(self):
-        return self.k * (self.kw if self.is_geom else self.k)
+        return self.k * self.kw
 
     @property
     def ci(self):
@@ -137,23 +141,16 @@ class ConvSpec:
     def out_hw(self, h, w):
         if self.transposed:
             return 2 * h, 2 * w
-        if self.is_geom:
+        if self.same_size:
             return h, w
         return (h + 2 * self.pad - self.k) // self.stride + 1, (w + 2 * self.pad - self.k) // self.stride + 1
 
 
 def _desc(spec, n, h, w, ldx, ldy):
-    if spec.is_geom:
-        d = ConvGeom()
-        d.N, d.H, d.W, d.Ci, d.Co = n, h, w, spec.ci, spec.co
-        d.KH, d.KW, d.pad_top, d.pad_left = spec.k, spec.kw, spec.pad_top, spec.pad_left
-        d.ldx, d.ldy = ldx, ldy
-        d.Cir, d.Cor = spec.cin, spec.cout
-        return d
     d = ConvDesc()
     d.N, d.H, d.W, d.Ci, d.Co = n, h, w, spec.ci, spec.co
-    d.KH = d.KW = spec.k
-    d.stride, d.pad, d.transposed = spec.stride, spec.pad, int(spec.transposed)
+    d.KH, d.KW, d.stride, d.pad_top, d.pad_left = spec.k, spec.kw, spec.stride, spec.pad, spec.pad_left
+    d.transposed, d.same_size = int(spec.transposed), int(spec.same_size)
     d.ldx, d.ldy = ldx, ldy
     d.Cir, d.Cor = spec.cin, spec.cout
     return d
@@ -164,21 +161,6 @@ def touch_weights(params):
     does not bump tensor._version."""
     for p in params:
         p._vq2_epoch = getattr(p, "_vq2_epoch", 0) + 1
-
-
-# The entry points of the two descriptor types (vq2_conv_desc, vq2_conv_geom) under one set of names
-_ABI_DESC = SimpleNamespace(
-    pack_weight=lib.vq2_pack_weight, pack_job_init=lib.vq2_pack_job_init, fwd=lib.vq2_conv_fwd, dgrad=lib.vq2_conv_dgrad_ex,
-    wgrad_workspace_bytes=lib.vq2_conv_wgrad_workspace_bytes, wgrad=lib.vq2_conv_wgrad,
-    wgrad_partial=lib.vq2_conv_wgrad_partial, wgrad_job_init=lib.vq2_wgrad_job_init)
-_ABI_GEOM = SimpleNamespace(
-    pack_weight=lib.vq2_convg_pack_weight, pack_job_init=lib.vq2_convg_pack_job_init, fwd=lib.vq2_convg_fwd,
-    dgrad=lib.vq2_convg_dgrad, wgrad_workspace_bytes=lib.vq2_convg_wgrad_workspace_bytes, wgrad=lib.vq2_convg_wgrad,
-    wgrad_partial=lib.vq2_convg_wgrad_partial, wgrad_job_init=lib.vq2_convg_wgrad_job_init)
-
-
-def _abi(spec):
-    return _ABI_GEOM if spec.is_geom else _ABI_DESC
 
 
 def _pack_version(spec, weight):
@@ -200,7 +182,7 @@ def packed_weight(spec, weight, which):
     buf = hit[1] if (hit is not None and hit[1].numel() == n and hit[1].device == weight.device) else \
         torch.empty(n, device=weight.device, dtype=torch.float32)
     d = _desc(spec, 1, max(spec.k, 2), max(spec.k, 2), spec.ci, spec.co)
-    check(_abi(spec).pack_weight(C.byref(d), which, _p(wsrc), _p(buf), _stream()), "pack_weight")
+    check(lib.vq2_pack_weight(C.byref(d), which, _p(wsrc), _p(buf), _stream()), "pack_weight")
     packs[which] = (ver, buf)
     return buf
 
@@ -229,7 +211,7 @@ class PackPlan:
             d = _desc(spec, 1, max(spec.k, 2), max(spec.k, 2), spec.ci, spec.co)
             if not weight.is_contiguous():
                 raise RuntimeError("PackPlan: weights must be contiguous")
-            check(_abi(spec).pack_job_init(C.byref(d), which, _p(weight), _p(buf), C.byref(arr[i])), "pack_job_init")
+            check(lib.vq2_pack_job_init(C.byref(d), which, _p(weight), _p(buf), C.byref(arr[i])), "pack_job_init")
             arr[i].offset = off
             assert arr[i].numel == numel
             self.entries.append((spec, weight, which, buf))
@@ -260,7 +242,7 @@ def conv_forward(spec, x, weight, bias, flags=0, residual=None, out=None):
     d = _desc(spec, n, h, w, ld_of(x), ld_of(out))
     wp = packed_weight(spec, weight, PACK_FWD)
     ldres = ld_of(residual) if residual is not None else 0
-    check(_abi(spec).fwd(C.byref(d), flags, _p(x), _p(wp), _p(bias), _p(residual), ldres, _p(out), _stream()),
+    check(lib.vq2_conv_fwd(C.byref(d), flags, _p(x), _p(wp), _p(bias), _p(residual), ldres, _p(out), _stream()),
           "conv_fwd")
     return out
 
@@ -271,9 +253,9 @@ def conv_dgrad(spec, xshape, dy, weight, mask=None, residual=None, out=None, mas
         out = torch.empty((n, h, w, spec.ci), device=dy.device, dtype=torch.float32)
     d = _desc(spec, n, h, w, spec.ci, ld_of(dy))
     wp = packed_weight(spec, weight, PACK_DGRAD)
-    check(_abi(spec).dgrad(C.byref(d), VQ2_MASK_AFTER_RESIDUAL if mask_after else 0, _p(dy), _p(wp), _p(mask),
-                                ld_of(mask) if mask is not None else 0, _p(residual),
-                                ld_of(residual) if residual is not None else 0, _p(out), ld_of(out), _stream()),
+    check(lib.vq2_conv_dgrad(C.byref(d), VQ2_MASK_AFTER_RESIDUAL if mask_after else 0, _p(dy), _p(wp), _p(mask),
+                             ld_of(mask) if mask is not None else 0, _p(residual),
+                             ld_of(residual) if residual is not None else 0, _p(out), ld_of(out), _stream()),
           "conv_dgrad")
     return out
 
@@ -305,12 +287,12 @@ class WgradBatch:
         d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
         ent = self.entries.get(key)
         if ent is None:
-            nbytes = _abi(spec).wgrad_workspace_bytes(C.byref(d))
+            nbytes = lib.vq2_conv_wgrad_workspace_bytes(C.byref(d))
             ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
             dw = weight._vq2_grad
             db = bias._vq2_grad if (bias is not None and want_db) else None
             job = WgradJob()
-            check(_abi(spec).wgrad_job_init(C.byref(d), _p(ws), _p(dw), _p(db), C.byref(job)), "wgrad_job_init")
+            check(lib.vq2_wgrad_job_init(C.byref(d), _p(ws), _p(dw), _p(db), C.byref(job)), "wgrad_job_init")
             ent = {"ws": ws, "nbytes": nbytes, "job": job, "dw": dw, "db": db, "used": False}
             self.entries[key] = ent
             self.dirty = True
@@ -320,7 +302,7 @@ class WgradBatch:
         if on_side:
             side.wait_event(torch.cuda.current_stream().record_event())
         with (torch.cuda.stream(side) if on_side else _THIS_STREAM):
-            check(_abi(spec).wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
+            check(lib.vq2_conv_wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
                                              _p(ent["ws"]), ent["nbytes"], _stream()), "conv_wgrad_partial")
         if on_side:
             x.record_stream(side)
@@ -405,7 +387,7 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
     """(dw, db) in the reference layouts; the bias gradient is fused into the same launches."""
     n, h, w, _ = x.shape
     d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
-    nbytes = _abi(spec).wgrad_workspace_bytes(C.byref(d))
+    nbytes = lib.vq2_conv_wgrad_workspace_bytes(C.byref(d))
     sc = _step_ctx(weight)
     if sc is not None and getattr(weight, "_vq2_grad", None) is not None and weight.grad is None and \
             (bias is None or (getattr(bias, "_vq2_grad", None) is not None and bias.grad is None)) and \
@@ -420,7 +402,7 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
         side.wait_event(torch.cuda.current_stream().record_event())
     with (torch.cuda.stream(side) if side is not None else _THIS_STREAM):
         ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
-        check(_abi(spec).wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes,
+        check(lib.vq2_conv_wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes,
                                  _stream()), "conv_wgrad")
     if side is not None:
         x.record_stream(side)   # keep the caching allocator from recycling these while the side stream reads

@@ -5,7 +5,7 @@ of the model is causal in raster order, so rows < i never change.  PriorSampler 
 
     row-local layers     (ELU, GLU, 1x1 convs, the concatenations with the coordinate planes, the condition) run the
                          library's kernels on a dense [B, 1, W, C] row
-    'causal' convs       keep their input rows in a history [H, B, W, C] and compute output row i with vq2_convg_fwd_row
+    'causal' convs       keep their input rows in a history [H, B, W, C] and compute output row i with vq2_conv_fwd_row
     CausalAttention      keeps the projected keys and values [H, B, W, C / 2]; row i's W queries go through
                          vq2_causal_attn_fwd_rows
     the input convs      run vq2_onehot_conv_fwd on the band of code rows that ends at row i (-1 above the image: such a code
@@ -25,7 +25,7 @@ import weakref
 import torch
 
 from . import ops
-from ._lib import lib, check, AttnDesc, ConvGeom
+from ._lib import lib, check, AttnDesc
 from .evaluate import eval_mode
 from .pixelsnail import CausalConv2d, GatedResBlock, PixelSNAIL, WNConv2d, _WNLinear
 
@@ -78,28 +78,22 @@ class _Conv:
         g = par.weight_g.detach().contiguous()
         w = torch.empty_like(v)
         check(lib.vq2_weight_norm_fwd(ops._p(v), ops._p(g), ops._p(w), s.cout, v.numel() // s.cout, ops._stream()), "weight_norm_fwd")
-        self.kh = s.k
-        self.kw = s.kw if s.is_geom else s.k
+        self.kh, self.kw = s.k, s.kw
         self.weight = w.view(s.cout, s.cin, self.kh, self.kw)
         self.bias = None if par.bias is None else par.bias.detach()
         self.row_flags = VQ2_ROW_CAUSAL_TAPS if causal_cols is not None else 0
-        if self.kh > 1 and not (s.is_geom and s.pad_top == self.kh - 1):
+        if self.kh > 1 and not (s.same_size and s.pad_top == self.kh - 1):
             raise NotImplementedError("vqvae2_amd.PriorSampler: a conv over several rows must end at its output row")
         self.wp = ops.packed_weight(s, self.weight, ops.PACK_FWD) if pack else None
         self.hist = None
 
     def row_desc(self, batch, rows, width):
-        s = self.spec
-        d = ConvGeom()
-        d.N, d.H, d.W, d.Ci, d.Co = batch, rows, width, s.ci, s.co
-        d.KH, d.KW, d.pad_top, d.pad_left = s.k, s.kw, s.pad_top, s.pad_left
-        d.ldx, d.ldy, d.Cir, d.Cor = s.ci, s.co, s.cin, s.cout
-        return d
+        return ops._desc(self.spec, batch, rows, width, self.spec.ci, self.spec.co)
 
     def workspace_bytes(self, batch, rows, width):
         if self.kh == 1:
             return 0
-        return lib.vq2_convg_fwd_row_workspace_bytes(C.byref(self.row_desc(batch, rows, width)), self.row_flags)
+        return lib.vq2_conv_fwd_row_workspace_bytes(C.byref(self.row_desc(batch, rows, width)), self.row_flags)
 
 
 class _Plan:
@@ -199,12 +193,12 @@ class _Plan:
         ldres = residual.shape[3] if residual is not None else 0
         if conv.kh == 1:
             d = ops._desc(sp, self.B, 1, self.W, x.shape[3], out.shape[3])
-            self.add("conv_fwd", ops._abi(sp).fwd, d, 0, _ptr(x), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres, _ptr(out))
+            self.add("conv_fwd", lib.vq2_conv_fwd, d, 0, _ptr(x), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres, _ptr(out))
             return
         hist = self.hist(name + ".hist", sp.ci)
         assert x.data_ptr() == hist[self.row].data_ptr() and out.shape[3] == sp.co
         d = conv.row_desc(self.B, self.H, self.W)
-        self.add("convg_fwd_row", lib.vq2_convg_fwd_row, d, self.row, self.W * sp.ci, self.B * self.W * sp.ci, conv.row_flags,
+        self.add("conv_fwd_row", lib.vq2_conv_fwd_row, d, self.row, self.W * sp.ci, self.B * self.W * sp.ci, conv.row_flags,
                  _ptr(hist), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres, _ptr(out), _ptr(self.ws), self.ws_bytes)
 
     def input_stage(self):
