@@ -10,7 +10,14 @@ under --ckpt_dir (the reference's fixed 'checkpoint').  The priors are rebuilt f
 
 Extra arguments of this script: --ckpt_dir; --seed (torch.manual_seed, which fixes every draw); --vqvae_arg NAME=INT (repeatable)
 for a VQVAE that was not built with the defaults (channel, n_res_block, n_res_channel, embed_dim, n_embed), since
-examples/train_stage1.py saves a bare state_dict.  A PNG needs PIL; without it the same canvas is written as .npy."""
+examples/train_stage1.py saves a bare state_dict.  A PNG needs PIL; without it the same canvas is written as .npy.
+
+Truncated sampling, for both priors: --top_k INT draws from the INT most likely codes only, --top_p FLOAT from the smallest set
+of most likely codes that holds FLOAT of the probability (0 and 1.0: off).
+
+Completing images: --from_images FILE.npy --keep_rows R.  FILE.npy holds uint8 [B, H, W, 3]; the images are normalised to
+[-1, 1], encoded with the VQ-VAE, and the first R rows of their top codes and 2 R rows of their bottom codes are kept; the priors
+draw the rest.  The batch size is that of the file."""
 import argparse
 import os
 import sys
@@ -32,7 +39,46 @@ def parse_args(argv=None):
     parser.add_argument('--ckpt_dir', type=str, default='checkpoint')
     parser.add_argument('--seed', type=int)
     parser.add_argument('--vqvae_arg', action='append', default=[], metavar='NAME=INT')
+    parser.add_argument('--top_k', type=int, default=0)
+    parser.add_argument('--top_p', type=float, default=1.0)
+    parser.add_argument('--from_images', type=str, metavar='FILE.npy')
+    parser.add_argument('--keep_rows', type=int, default=0)
     return parser.parse_args(argv)
+
+
+def encode_images(model_vqvae, path, device):
+    """The top and bottom codes (int64 [B, Ht, Wt], [B, Hb, Wb]) of the uint8 images [B, H, W, 3] stored at `path`."""
+    import numpy as np
+    import vqvae2_amd
+    images = np.load(path)
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
+        raise SystemExit(f"--from_images: uint8 [B, H, W, 3] expected, {path} holds {images.dtype} {images.shape}")
+    norm = vqvae2_amd.ImageNormalizer([0.5] * 3, [0.5] * 3)
+    with torch.no_grad():
+        _, _, _, id_t, id_b = model_vqvae.encode(norm.nchw(torch.from_numpy(images).to(device).contiguous()))
+    return id_t, id_b
+
+
+def draw_codes(args, model_vqvae, model_top, model_bottom, device):
+    """(top codes, bottom codes) as the command line asks for them: drawn freely, or completed from encoded images."""
+    import vqvae2_amd
+    top_size = list(model_top.background.shape[2:])
+    bottom_size = list(model_bottom.background.shape[2:])
+    batch, top_prefix, bottom_prefix = args.batch, None, None
+    if args.from_images:
+        id_t, id_b = encode_images(model_vqvae, args.from_images, device)
+        if list(id_t.shape[1:]) != top_size or list(id_b.shape[1:]) != bottom_size:
+            raise SystemExit(f"--from_images: the images encode to {list(id_t.shape[1:])} / {list(id_b.shape[1:])} codes, "
+                             f"the priors draw {top_size} / {bottom_size}")
+        if not 0 <= args.keep_rows <= top_size[0]:
+            raise SystemExit(f"--keep_rows must be in 0..{top_size[0]}")
+        batch = id_t.shape[0]
+        top_prefix, bottom_prefix = id_t[:, :args.keep_rows].contiguous(), id_b[:, :2 * args.keep_rows].contiguous()
+    kw = dict(top_k=args.top_k, top_p=args.top_p)
+    top_sample = vqvae2_amd.sample_model(model_top, device, batch, top_size, args.temp, prefix=top_prefix, **kw)
+    bottom_sample = vqvae2_amd.sample_model(model_bottom, device, batch, bottom_size, args.temp, condition=top_sample,
+                                            prefix=bottom_prefix, **kw)
+    return top_sample, bottom_sample
 
 
 def main(argv=None):
@@ -45,16 +91,13 @@ def main(argv=None):
     model_vqvae = vqvae2_amd.load_model('vqvae', args.vqvae, device, ckpt_dir=args.ckpt_dir, **vqvae_kw)
     model_top = vqvae2_amd.load_model('pixelsnail_top', args.top, device, ckpt_dir=args.ckpt_dir)
     model_bottom = vqvae2_amd.load_model('pixelsnail_bottom', args.bottom, device, ckpt_dir=args.ckpt_dir)
-    top_size = list(model_top.background.shape[2:])
-    bottom_size = list(model_bottom.background.shape[2:])
-    top_sample = vqvae2_amd.sample_model(model_top, device, args.batch, top_size, args.temp)
-    bottom_sample = vqvae2_amd.sample_model(model_bottom, device, args.batch, bottom_size, args.temp, condition=top_sample)
+    top_sample, bottom_sample = draw_codes(args, model_vqvae, model_top, model_bottom, device)
     with torch.no_grad():
         decoded = model_vqvae.decode_code(top_sample, bottom_sample).clamp(-1, 1)
     # the reference's save_image(normalize=True, range=(-1, 1)): (x + 1) / 2 is the inverse of Normalize(0.5, 0.5)
     denorm = vqvae2_amd.ImageDenormalizer([0.5] * decoded.shape[1], [0.5] * decoded.shape[1])
     path = vqvae2_amd.save_u8_image(denorm.grid(decoded, nhwc=False), args.filename)
-    print(f"wrote {path}: {args.batch} images of {decoded.shape[2]} x {decoded.shape[3]}")
+    print(f"wrote {path}: {decoded.shape[0]} images of {decoded.shape[2]} x {decoded.shape[3]}")
 
 
 if __name__ == '__main__':

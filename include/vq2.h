@@ -55,11 +55,12 @@ typedef void *vq2_stream_t;
  * (the first since 4): vq2_conv_desc widened to 16 words that describe both conv forms (pad became pad_top / pad_left,
  * same_size added); vq2_conv_geom and the eight vq2_convg_* twins removed, every layer goes through the vq2_conv_* entry
  * points; vq2_conv_dgrad takes the flags argument and vq2_conv_dgrad_ex is gone; vq2_convg_fwd_row and its workspace query
- * renamed vq2_conv_fwd_row / vq2_conv_fwd_row_workspace_bytes on vq2_conv_desc; see INTEGRATION.md "ABI history").
+ * renamed vq2_conv_fwd_row / vq2_conv_fwd_row_workspace_bytes on vq2_conv_desc; see INTEGRATION.md "ABI history");
+ * revision 14: an addition only -- vq2_sample_filtered, the draw from a top-k / nucleus truncated support with its log-probability.
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 13
+#define VQ2_API_VERSION 14
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -565,6 +566,31 @@ int vq2_upsample2_bwd(const float *dy, int32_t lddy, float *dx, int32_t lddx, in
  *              e_0 + .. + e_c exceeds u * sum (the rule cumsum(softmax) > u, scaled by the sum), or n_class - 1 if rounding
  *              leaves none.  Written as int64 to out[r * out_stride].  temperature <= 0 or n_class outside 1..16384:
  *              VQ2_ERR_INVALID.
+ * vq2_sample_filtered: vq2_sample_categorical on a truncated support.  For one row, with z_c = l_c / temperature (float32),
+ *              mx = max z, e_c = expf(z_c - mx) and the same u (same Philox call, same seed / position / row):
+ *                top-k   top_k == 0: off, K = all classes.  Otherwise 1 <= top_k <= n_class: v_k is the k-th largest z
+ *                        counting multiplicity and K = {c : z_c >= v_k} -- ties at the k-th value are all kept.  An exact
+ *                        function of the float32 z.
+ *                top-p   0 < top_p <= 1, 1: off.  Applied after top-k, on the distribution over K: with S_K the sum of e_c
+ *                        over K and mass(v) the sum of e_c over {c in K : z_c >= v}, t* is the largest value among
+ *                        {z_c : c in K} with mass(t*) >= top_p * S_K (the product in float32), and the kept set is
+ *                        {c in K : z_c >= t*}: tie-closed, and the arg-max is always in it.
+ *                sums    S_K, every mass(v) and the sum of the draw are float32 sums in the order of
+ *                        vq2_sample_categorical: lane i of 64 adds the classes i * chunk .. (i + 1) * chunk - 1
+ *                        (chunk = ceil(n_class / 64)) in ascending order starting from 0.f, a class outside the set adding
+ *                        0.f in its place; the 64 lane sums go through one fixed scan tree.  Two runs give the same bits.
+ *                        Such a sum is monotone under replacing terms by 0, so mass is monotone in v and both v_k and t*
+ *                        are found by bisection over the order-preserving 32-bit key of z (32 passes each, no sort).
+ *                draw    the smallest kept c, in ascending class order, whose running sum of kept e exceeds u * S_kept;
+ *                        the last kept class if rounding leaves none.  int64 to out[r * out_stride].
+ *                logp    (may be null, dense [M]) logp[r] = (z_cls - mx) - logf(S_kept): the log-probability of the drawn
+ *                        class under the tempered, truncated distribution.
+ *                kept    (may be null, dense int32 [M]) kept[r] = the number of kept classes.
+ *              With both filters off the drawn code is vq2_sample_categorical's bit for bit (the same sums, a removed
+ *              class being the only source of a 0.f term).  -inf logits are legal and carry mass 0; NaN is unspecified.
+ *              top_k < 0 or > n_class, top_p outside (0, 1] (NaN included) and whatever vq2_sample_categorical refuses:
+ *              VQ2_ERR_INVALID before any launch.  Rows of up to 512 classes keep z and e in registers over the passes;
+ *              longer rows stage z in LDS (64 KB at 16,384 classes) and form e again from it.
  * vq2_sample_uniforms: those u values, u[r] for r < M -- the only way to check the draw against a reference. */
 #define VQ2_ROW_CAUSAL_TAPS 8
 size_t vq2_conv_fwd_row_workspace_bytes(const vq2_conv_desc *d, int flags);
@@ -576,6 +602,9 @@ int vq2_causal_attn_fwd_rows(const vq2_attn_desc *d, int32_t q0, int32_t nq, int
                              vq2_stream_t stream);
 int vq2_sample_categorical(const float *logits, int64_t row_stride, int32_t M, int32_t n_class, float temperature,
                            uint64_t seed, uint64_t position, int64_t *out, int64_t out_stride, vq2_stream_t stream);
+int vq2_sample_filtered(const float *logits, int64_t row_stride, int32_t M, int32_t n_class, float temperature,
+                        int32_t top_k, float top_p, uint64_t seed, uint64_t position, int64_t *out, int64_t out_stride,
+                        float *logp, int32_t *kept, vq2_stream_t stream);
 int vq2_sample_uniforms(float *u, int32_t M, uint64_t seed, uint64_t position, vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ data-parallel exchange (RCCL over xGMI)

@@ -1,7 +1,10 @@
 """Sampling from the PixelSNAIL prior on one MI355X: PriorSampler (row-incremental) against the reference's loop on this
 package's modules, at the top prior's real size and at the bottom prior's with a reduced row count.
 
-    python scripts/bench_sample.py [--batch 8] [--bottom_rows 8] [--out profiles/sample.json]
+    python scripts/bench_sample.py [--batch 8] [--bottom_rows 8] [--top_k K] [--top_p P] [--out profiles/sample.json]
+
+--top_k / --top_p time the sampler with the truncated draw (vq2_sample_filtered in place of vq2_sample_categorical, one launch per
+step either way); the baseline loop is the reference's and has no such filter.
 
 Priors (random weights; the time does not depend on them):
     top     PixelSNAIL([32, 32], 512, 256, 5, 4, 4, 256), no condition
@@ -53,11 +56,11 @@ def baseline_step_seconds(model, batch, rows, width, row_index, condition, steps
         return sync_time(lambda: [step(j % width) for j in range(steps)]) / steps
 
 
-def bench(name, model, batch, rows, condition, repeats, baseline_steps):
+def bench(name, model, batch, rows, condition, repeats, baseline_steps, top_k=0, top_p=1.0):
     import vqvae2_amd
     width = model.background.shape[3]
     sampler = vqvae2_amd.PriorSampler(model)
-    run = lambda: sampler.sample(batch, 1.0, condition, seed=1, rows=rows)
+    run = lambda: sampler.sample(batch, 1.0, condition, seed=1, rows=rows, top_k=top_k, top_p=top_p)
     sync_time(run)
     times = [sync_time(run) for _ in range(repeats)]
     plan = sampler._plan[1]
@@ -75,7 +78,7 @@ def bench(name, model, batch, rows, condition, repeats, baseline_steps):
     calls = plan.programs[rows // 2].calls
     two_kernels = sum(1 for _, _, what in calls if what == "conv_fwd_row")
     res = {
-        "batch": batch, "rows": rows, "width": width, "steps": rows * width,
+        "batch": batch, "rows": rows, "width": width, "steps": rows * width, "top_k": top_k, "top_p": top_p,
         "sampler_seconds_per_map": {"median": med, "min": min(times), "max": max(times), "repeats": repeats},
         "sampler_ms_per_step": 1e3 * med / (rows * width),
         "sampler_library_calls_per_step": len(calls) + 1,
@@ -97,6 +100,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline_steps", type=int, default=40)
     ap.add_argument("--skip_bottom", action="store_true")
+    ap.add_argument("--top_k", type=int, default=0)
+    ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sample.json"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -106,13 +111,14 @@ def main():
     doc = {"device": torch.cuda.get_device_name(0), "method": "host clock around device-synchronised work; baseline integrated "
            "from per-step times at the first, middle and last row (an estimate)"}
     top = vqvae2_amd.PixelSNAIL([32, 32], 512, 256, 5, 4, 4, 256).cuda().eval()
-    doc["top"] = bench("top", top, args.batch, 32, None, args.repeats, args.baseline_steps)
+    doc["top"] = bench("top", top, args.batch, 32, None, args.repeats, args.baseline_steps, args.top_k, args.top_p)
     del top
     if not args.skip_bottom:
         bottom = vqvae2_amd.PixelSNAIL([64, 64], 512, 256, 5, 4, 4, 256, attention=False, n_cond_res_block=3,
                                        cond_res_channel=256).cuda().eval()
         cond = torch.randint(0, 512, (args.batch, 32, 32), device="cuda")
-        doc["bottom_first_rows"] = bench("bottom", bottom, args.batch, args.bottom_rows, cond, args.repeats, args.baseline_steps)
+        doc["bottom_first_rows"] = bench("bottom", bottom, args.batch, args.bottom_rows, cond, args.repeats, args.baseline_steps,
+                                         args.top_k, args.top_p)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)

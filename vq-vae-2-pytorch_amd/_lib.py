@@ -137,6 +137,7 @@ def _load():
         "vq2_conv_fwd_row": (C.c_int, [DP, I32, I64, I64, C.c_int, P, P, P, P, I32, P, P, SZ, P]),
         "vq2_causal_attn_fwd_rows": (C.c_int, [C.POINTER(AttnDesc), I32, I32, I32, I64, I64, P, P, P, P, P]),
         "vq2_sample_categorical": (C.c_int, [P, I64, I32, I32, F, U64, U64, P, I64, P]),
+        "vq2_sample_filtered": (C.c_int, [P, I64, I32, I32, F, I32, F, U64, U64, P, I64, P, P, P]),
         "vq2_sample_uniforms": (C.c_int, [P, I32, U64, U64, P]),
         "vq2_comm_unique_id": (C.c_int, [P]),
         "vq2_comm_init": (C.c_int, [P, I32, I32]),

@@ -14,6 +14,10 @@
 //   categorical draw   one wave per row of logits: maximum, sum of exponentials over lane-contiguous chunks, a fixed-order
 //                      scan over the lanes, then every lane walks its chunk for the first class whose running sum passes
 //                      u * sum; the lowest such lane wins.  u comes from Philox4x32-7 keyed by (seed, position, row).
+//   filtered draw      the same draw over a top-k / nucleus truncated support (semantics: include/vq2.h).  Both cuts are
+//                      thresholds on z, found by bisection over the order-preserving 32-bit key of z: a pass counts, or sums
+//                      in the draw's own order, the classes at or above a candidate key.  A removed class adds 0.f, so with
+//                      the filters off the sums, and the code, are the plain draw's bit for bit.
 #include "vq2_conv.h"
 #include "vq2_philox.h"
 
@@ -167,6 +171,33 @@ __device__ __forceinline__ float uniform_of(uint32_t seed_lo, uint32_t seed_hi, 
     return (float)(w.x >> 8) * 5.9604644775390625e-08f;   // 2^-24: u in [0, 1), exact
 }
 
+// -- the pieces both draw kernels are made of (one wave per row; lane `lane` owns classes c0 .. c1 - 1)
+__device__ __forceinline__ float wave_max(float mx) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    return mx;
+}
+
+// inclusive scan of the lanes' chunk sums in one fixed tree; excl is the sum of the lanes below, the return value the total
+__device__ __forceinline__ float lane_scan(float s, int lane, float &excl) {
+    float incl = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.f;
+    return __shfl(incl, 63, 64);
+}
+
+// the class of the lowest lane that found one, else `fallback`
+__device__ __forceinline__ int lowest_hit(int found, int fallback, int &winner) {
+    const unsigned long long hit = __ballot(found >= 0);
+    winner = hit ? __ffsll((long long)hit) - 1 : 0;
+    return hit ? __shfl(found, winner, 64) : fallback;
+}
+
 __global__ __launch_bounds__(256) void sample_categorical_kernel(const float *__restrict__ logits, long long row_stride, int M,
                                                                  int n_class, float temperature, uint32_t seed_lo,
                                                                  uint32_t seed_hi, uint32_t pos_lo, uint32_t pos_hi,
@@ -178,19 +209,11 @@ __global__ __launch_bounds__(256) void sample_categorical_kernel(const float *__
     const int c0 = min(lane * chunk, n_class), c1 = min(c0 + chunk, n_class);
     float mx = -INFINITY;
     for (int c = c0; c < c1; ++c) mx = fmaxf(mx, l[c] / temperature);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mx = wave_max(mx);
     float s = 0.f;
     for (int c = c0; c < c1; ++c) s += expf(l[c] / temperature - mx);
-    float incl = s;                                            // inclusive scan over the lanes, one fixed tree
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    float excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 0.f;
-    const float total = __shfl(incl, 63, 64);
+    float excl;
+    const float total = lane_scan(s, lane, excl);
     const float thr = uniform_of(seed_lo, seed_hi, pos_lo, pos_hi, (uint32_t)row) * total;
     // running sum at class c of this lane: excl + (own exponentials up to c, in order); first class that passes thr
     int found = -1;
@@ -199,10 +222,150 @@ __global__ __launch_bounds__(256) void sample_categorical_kernel(const float *__
         run += expf(l[c] / temperature - mx);
         if (excl + run > thr) { found = c; break; }
     }
-    const unsigned long long hit = __ballot(found >= 0);
-    int cls = n_class - 1;                                     // rounding left no class above thr: the last one
-    if (hit) cls = __shfl(found, __ffsll((long long)hit) - 1, 64);
+    int winner;
+    const int cls = lowest_hit(found, n_class - 1, winner);    // rounding left no class above thr: the last one
     if (lane == 0) out[(long long)row * out_stride] = (long long)cls;
+}
+
+// -- the draw from a truncated support (top-k, then nucleus)
+// z in an unsigned key of the same order (z >= v  <=>  key(z) >= key(v) for non-NaN values; -0 counts as +0)
+__device__ __forceinline__ uint32_t order_key(float z) {
+    const uint32_t b = z == 0.f ? 0u : __float_as_uint(z);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+constexpr int SF_REG = 8;            // a lane's chunk for n_class <= 512: z and e stay in registers
+constexpr int SF_LDS_FLOATS = 16384; // larger rows: z staged in LDS, 64 KB at the most
+
+// a lane's chunk of z = l / temperature and e = exp(z - max).  REG: both in registers, every loop unrolled over SF_REG
+// guarded slots.  Otherwise z sits in the wave's LDS slab at [k][lane] (a lane reads back only what it wrote: no barrier,
+// no bank conflict) and e is formed again where it is needed -- expf of the same arguments, so the same bits.
+template <bool REG> struct Chunk {
+    float z[REG ? SF_REG : 1], e[REG ? SF_REG : 1];
+    float *slab;
+    float mx;
+    int cnt;
+    template <class F> __device__ __forceinline__ void each(F f) const {
+        if constexpr (REG) {
+#pragma unroll
+            for (int k = 0; k < SF_REG; ++k)
+                if (k < cnt) f(k, z[k], e[k]);
+        } else {
+            for (int k = 0; k < cnt; ++k) {
+                const float zk = slab[k * 64];
+                f(k, zk, expf(zk - mx));
+            }
+        }
+    }
+    template <class F> __device__ __forceinline__ void each_z(F f) const {
+        if constexpr (REG) {
+#pragma unroll
+            for (int k = 0; k < SF_REG; ++k)
+                if (k < cnt) f(z[k]);
+        } else {
+            for (int k = 0; k < cnt; ++k) f(slab[k * 64]);
+        }
+    }
+};
+
+template <bool REG>
+__global__ __launch_bounds__(256) void sample_filtered_kernel(const float *__restrict__ logits, long long row_stride, int M,
+                                                              int n_class, float temperature, int top_k, float top_p,
+                                                              uint32_t seed_lo, uint32_t seed_hi, uint32_t pos_lo, uint32_t pos_hi,
+                                                              long long *__restrict__ out, long long out_stride,
+                                                              float *__restrict__ logp, int *__restrict__ kept) {
+    extern __shared__ float sf_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (row >= M) return;                                      // whole waves leave; the kernel has no barrier
+    const float *l = logits + (long long)row * row_stride;
+    const int chunk = (n_class + 63) / 64;
+    const int c0 = min(lane * chunk, n_class), c1 = min(c0 + chunk, n_class);
+    Chunk<REG> ch;
+    ch.cnt = c1 - c0;
+    ch.slab = sf_lds + (size_t)wave * chunk * 64 + lane;
+    float mx = -INFINITY;
+    if constexpr (REG) {
+#pragma unroll
+        for (int k = 0; k < SF_REG; ++k) {
+            ch.z[k] = k < ch.cnt ? l[c0 + k] / temperature : -INFINITY;
+            mx = fmaxf(mx, ch.z[k]);
+        }
+    } else {
+        for (int k = 0; k < ch.cnt; ++k) {
+            const float zk = l[c0 + k] / temperature;
+            ch.slab[k * 64] = zk;
+            mx = fmaxf(mx, zk);
+        }
+    }
+    ch.mx = mx = wave_max(mx);
+    if constexpr (REG) {
+#pragma unroll
+        for (int k = 0; k < SF_REG; ++k) ch.e[k] = expf(ch.z[k] - mx);
+    }
+    // Both cuts are the largest 32-bit key t for which a predicate that is true at t = 0 and monotone in t still holds, built
+    // bit by bit from the top: 32 passes each, the same for every lane (the predicate is a wave-wide reduction).
+    uint32_t cut = 0u;                                         // kept: order_key(z) >= cut
+    if (top_k > 0 && top_k < n_class) {                        // v_k: the largest t with |{z >= t}| >= k
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t t = cut | (1u << bit);
+            int n = 0;
+            ch.each_z([&](float zk) { n += order_key(zk) >= t ? 1 : 0; });
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+            if (n >= top_k) cut = t;
+        }
+    }
+    float excl;
+    if (top_p < 1.f) {                                         // t*: the largest t >= v_k with mass(t) >= top_p * S_K
+        float s = 0.f;
+        ch.each([&](int, float zk, float ek) { s += order_key(zk) >= cut ? ek : 0.f; });
+        const float target = top_p * lane_scan(s, lane, excl);
+        const uint32_t floor_key = cut;
+        cut = 0u;
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t t = cut | (1u << bit);
+            const uint32_t both = t > floor_key ? t : floor_key;
+            float m = 0.f;
+            ch.each([&](int, float zk, float ek) { m += order_key(zk) >= both ? ek : 0.f; });
+            const float mass = lane_scan(m, lane, excl);
+            if (mass >= target && mass > 0.f) cut = t;         // mass > 0: the arg-max stays whatever top_p * S_K rounds to
+        }
+        if (cut < floor_key) cut = floor_key;
+    }
+    // the draw over the kept classes: the sums of sample_categorical_kernel with 0.f in place of a removed class
+    float s = 0.f;
+    int n = 0;
+    ch.each([&](int, float zk, float ek) {
+        const bool keep = order_key(zk) >= cut;
+        s += keep ? ek : 0.f;
+        n += keep ? 1 : 0;
+    });
+    const float total = lane_scan(s, lane, excl);
+    const float thr = uniform_of(seed_lo, seed_hi, pos_lo, pos_hi, (uint32_t)row) * total;
+    int found = -1, last = -1;
+    float zfound = 0.f, zlast = 0.f, run = 0.f;
+    ch.each([&](int k, float zk, float ek) {
+        const bool keep = order_key(zk) >= cut;
+        run += keep ? ek : 0.f;
+        if (keep) { last = c0 + k; zlast = zk; }
+        if (keep && found < 0 && excl + run > thr) { found = c0 + k; zfound = zk; }
+    });
+    // rounding left no kept class above thr: the last kept one (the highest lane that kept any)
+    const unsigned long long any = __ballot(last >= 0);
+    const int top_lane = any ? 63 - __clzll((long long)any) : 0;
+    const int fallback = any ? __shfl(last, top_lane, 64) : n_class - 1;
+    const float zfallback = __shfl(zlast, top_lane, 64);
+    int winner;
+    const int cls = lowest_hit(found, fallback, winner);
+    const float zw = __shfl(zfound, winner, 64);
+    const float zcls = __ballot(found >= 0) ? zw : zfallback;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if (lane == 0) {
+        out[(long long)row * out_stride] = (long long)cls;
+        if (logp) logp[row] = (zcls - mx) - logf(total);
+        if (kept) kept[row] = n;
+    }
 }
 
 __global__ __launch_bounds__(256) void sample_uniforms_kernel(float *__restrict__ u, int M, uint32_t seed_lo, uint32_t seed_hi,
@@ -273,6 +436,34 @@ extern "C" int vq2_sample_categorical(const float *logits, int64_t row_stride, i
                        (uint32_t)(position & 0xFFFFFFFFu), (uint32_t)(position >> 32), reinterpret_cast<long long *>(out),
                        (long long)out_stride);
     return vq2::check_launch("sample_categorical_kernel");
+}
+
+extern "C" int vq2_sample_filtered(const float *logits, int64_t row_stride, int32_t M, int32_t n_class, float temperature,
+                                   int32_t top_k, float top_p, uint64_t seed, uint64_t position, int64_t *out, int64_t out_stride,
+                                   float *logp, int32_t *kept, vq2_stream_t stream) {
+    VQ2_REQUIRE(logits && out, "sample_filtered: null pointer");
+    VQ2_REQUIRE(M >= 1 && row_stride >= n_class && out_stride >= 1, "sample_filtered: M >= 1, row_stride >= n_class and out_stride >= 1 required");
+    VQ2_REQUIRE(temperature > 0.f, "sample_filtered: temperature must be positive");
+    VQ2_REQUIRE(n_class >= 1 && n_class <= 16384, "sample_filtered: n_class must be in 1..16384 (got %d)", n_class);
+    VQ2_REQUIRE(top_k >= 0 && top_k <= n_class, "sample_filtered: top_k must be 0 (off) or in 1..n_class (got %d)", top_k);
+    VQ2_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_filtered: top_p must be in (0, 1]");      // false for NaN
+    hipStream_t s = vq2::to_stream(stream);
+    const uint32_t seed_lo = (uint32_t)(seed & 0xFFFFFFFFu), seed_hi = (uint32_t)(seed >> 32);
+    const uint32_t pos_lo = (uint32_t)(position & 0xFFFFFFFFu), pos_hi = (uint32_t)(position >> 32);
+    const int chunk = (n_class + 63) / 64;
+    if (chunk <= SF_REG) {
+        hipLaunchKernelGGL(sample_filtered_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, s, logits, (long long)row_stride, M, n_class,
+                           temperature, top_k, top_p, seed_lo, seed_hi, pos_lo, pos_hi, reinterpret_cast<long long *>(out),
+                           (long long)out_stride, logp, kept);
+        return vq2::check_launch("sample_filtered_kernel<registers>");
+    }
+    // one LDS slab of chunk * 64 floats per wave: as many waves per workgroup, up to 4, as 64 KB hold
+    const int slab = chunk * 64;
+    const int waves = SF_LDS_FLOATS / slab >= 4 ? 4 : SF_LDS_FLOATS / slab;
+    hipLaunchKernelGGL(sample_filtered_kernel<false>, dim3((M + waves - 1) / waves), dim3(64 * waves),
+                       (size_t)waves * slab * sizeof(float), s, logits, (long long)row_stride, M, n_class, temperature, top_k, top_p,
+                       seed_lo, seed_hi, pos_lo, pos_hi, reinterpret_cast<long long *>(out), (long long)out_stride, logp, kept);
+    return vq2::check_launch("sample_filtered_kernel<lds>");
 }
 
 extern "C" int vq2_sample_uniforms(float *u, int32_t M, uint64_t seed, uint64_t position, vq2_stream_t stream) {

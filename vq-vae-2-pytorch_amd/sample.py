@@ -287,10 +287,20 @@ class _Plan:
 class PriorSampler:
     """PriorSampler(model): a row-incremental sampler over a vqvae2_amd.PixelSNAIL on the GPU.
 
-    sample(batch, temperature=1.0, condition=None, seed=None, rows=None) -> int64 [B, rows, W] on the device.  condition: the
+    sample(batch, temperature=1.0, condition=None, seed=None, rows=None, *, top_k=0, top_p=1.0, prefix=None,
+        return_logp=False) -> int64 [B, rows, W] on the device.  condition: the
         int64 top codes [B, H / 2, W / 2] for a model built with a condition network.  seed None takes one integer from torch's
         default CPU generator (as the dropout layers do), so torch.manual_seed makes a run repeatable.  The code of pixel (i, j)
-        of image b is drawn by vq2_sample_categorical at position i * W + j, row b.
+        of image b is drawn by vq2_sample_categorical at position i * W + j, row b.  Keyword only:
+        top_k, top_p   draw from the top_k most likely codes (0: off; above n_class: n_class) and, of those, from the smallest
+                       set of most likely codes that holds top_p of the mass (1.0: off); ties at a cut are kept.  The draw is
+                       then vq2_sample_filtered (include/vq2.h has the exact rule), still one launch per step.
+        prefix         int64 [B, r0, W] on the device, 0 <= r0 <= rows: the first r0 rows of the result are these codes and
+                       drawing starts at (r0, 0).  A given row costs one run of its row program, not W.  Draws keep their
+                       position i * W + j, so a prefix taken from sample(seed=s) is completed to that very map.
+        return_logp    returns (codes, logp): logp float32 [B, rows, W], the log-probability of each drawn code under the
+                       tempered, truncated distribution it was drawn from; 0 at prefix positions.
+        With these at their defaults the calls and their arguments are what they were without them.
     logits_given(codes, condition=None) -> [B, n_class, H, W]: the same stepping with `codes` written where sample() draws;
         entry (i, j) is what step (i, j) saw, which by causality is the model's own output for those codes.
     The weights are those of the moment of construction: a model whose parameters changed since is refused until refresh().
@@ -382,25 +392,57 @@ class PriorSampler:
         return plan
 
     @torch.no_grad()
-    def sample(self, batch, temperature=1.0, condition=None, seed=None, rows=None):
+    def sample(self, batch, temperature=1.0, condition=None, seed=None, rows=None, *, top_k=0, top_p=1.0, prefix=None,
+               return_logp=False):
         rows = self.model.background.shape[2] if rows is None else int(rows)
         if not temperature > 0:
             raise ValueError(f"PriorSampler: temperature must be positive, got {temperature}")
+        n_class, ld = self.model.n_class, ops.ceil4(self.model.n_class)
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError(f"PriorSampler: top_k must be 0 (off) or a positive integer, got {top_k}")
+        if not 0 < top_p <= 1:
+            raise ValueError(f"PriorSampler: top_p must be in (0, 1], got {top_p}")
+        top_k, top_p = min(int(top_k), n_class), float(top_p)
+        batch = int(batch)
+        r0 = 0
+        if prefix is not None:
+            prefix = ops._require_codes(prefix, "prefix")
+            if prefix.device != self.device or prefix.dim() != 3 or prefix.shape[0] != batch or prefix.shape[2] != self.width \
+                    or prefix.shape[1] > rows:
+                raise RuntimeError(f"PriorSampler: prefix [B, r0 <= rows, W] = [{batch}, <= {rows}, {self.width}] of int64 codes on "
+                                   f"{self.device} expected, got {tuple(prefix.shape)} on {prefix.device}")
+            r0 = prefix.shape[1]
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         seed = int(seed) & _MASK64
-        plan = self._plan_for(int(batch), rows, condition)
+        plan = self._plan_for(batch, rows, condition)
         b, w, r = plan.B, plan.W, plan.R
-        n_class, ld = self.model.n_class, ops.ceil4(self.model.n_class)
-        draw, t = lib.vq2_sample_categorical, float(temperature)
+        t = float(temperature)
+        filtered = top_k > 0 or top_p < 1.0 or return_logp
+        # step-outer [rows, W, B]: the draw of step (i, j) writes its B values densely
+        logp = torch.zeros((rows, w, b), device=self.device, dtype=torch.float32) if return_logp else None
         for i in range(rows):
             prog = plan.programs[i]
             band = plan.bands[i]
+            if i < r0:
+                # a given row: with all its codes in place one run of the row's program is exact in every column
+                band[:, r - 1].copy_(prefix[:, i])
+                prog.run()
+                plan.end_row(i)
+                continue
             for j in range(w):
                 prog.run()
-                check(draw(_ptr(plan.logits, j * ld), w * ld, b, n_class, t, seed, i * w + j, _ptr(band, (r - 1) * w + j), r * w,
-                           plan.stream), "sample_categorical")
+                if filtered:
+                    check(lib.vq2_sample_filtered(_ptr(plan.logits, j * ld), w * ld, b, n_class, t, top_k, top_p, seed, i * w + j,
+                                                  _ptr(band, (r - 1) * w + j), r * w,
+                                                  _ptr(logp, (i * w + j) * b) if return_logp else None, None, plan.stream),
+                          "sample_filtered")
+                else:
+                    check(lib.vq2_sample_categorical(_ptr(plan.logits, j * ld), w * ld, b, n_class, t, seed, i * w + j,
+                                                     _ptr(band, (r - 1) * w + j), r * w, plan.stream), "sample_categorical")
             plan.end_row(i)
+        if return_logp:
+            return plan.codes(), logp.permute(2, 0, 1).contiguous()
         return plan.codes()
 
     @torch.no_grad()
@@ -426,18 +468,18 @@ class PriorSampler:
 _SAMPLERS = weakref.WeakKeyDictionary()      # model -> its PriorSampler (which refers to the model weakly)
 
 
-def sample_model(model, device, batch, size, temperature, condition=None):
+def sample_model(model, device, batch, size, temperature, condition=None, *, top_k=0, top_p=1.0, prefix=None):
     """The reference's sample_model (sample.py:12-24): int64 codes [batch, size[0], size[1]] on `device`, drawn from `model`
     pixel by pixel in raster order.  One PriorSampler per model is kept in this module, keyed weakly by the model (it goes
     when the model goes, and the model itself carries nothing: it still pickles and deep-copies), and is rebuilt when the
-    model's parameters change."""
+    model's parameters change.  top_k, top_p and prefix (keyword only, not in the reference) are PriorSampler.sample's."""
     if tuple(size)[1] != model.background.shape[3]:
         raise RuntimeError(f"sample_model: width {size[1]} does not fit the model's {model.background.shape[3]}")
     model = model.to(device)
     sampler = _SAMPLERS.get(model)
     if sampler is None or sampler._snapshot() != sampler._versions:
         sampler = _SAMPLERS[model] = PriorSampler(model, _weak=True)
-    return sampler.sample(batch, temperature, condition, rows=int(size[0]))
+    return sampler.sample(batch, temperature, condition, rows=int(size[0]), top_k=top_k, top_p=top_p, prefix=prefix)
 
 
 def _arg(args, name, default):
