@@ -29,7 +29,6 @@ import subprocess
 import sys
 import time
 
-import numpy as np
 import pytest
 import torch
 
@@ -223,8 +222,7 @@ def w2_job(ops, n, h, w, ws, dw, db):
     job.unit_offset = 0
     arr = (WgradJob * 1)()
     arr[0] = job
-    raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
-    return torch.from_numpy(raw).to(_dev()), job.n_units_w + job.n_units_b
+    return ops._upload_structs(arr, _dev()), job.n_units_w + job.n_units_b
 
 
 def run_bwd(amd, c, kind, layout, with_ws):

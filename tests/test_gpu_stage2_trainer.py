@@ -65,7 +65,7 @@ def table(amd):
         params[e.g_off:e.g_off + e.rows] = torch.randn(e.rows, generator=gen)
         params[e.v_off:e.v_off + n] = torch.randn(n, generator=gen)
         dw[e.w_off:e.w_off + n] = torch.randn(n, generator=gen)
-    dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).cuda()
+    dev = amd.ops._upload_structs(arr, "cuda")
     return dict(entries=list(arr)[:-1], dev=dev, params=params.cuda(), dw=dw.cuda(), n_p=off, n_w=w_off)
 
 

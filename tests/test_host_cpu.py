@@ -508,6 +508,86 @@ def test_stage2_trainer_runs_the_same_unsent_slices(amd):
     assert amd.Stage2Trainer._unsent_slices is amd.Stage1Trainer._unsent_slices
 
 
+SLOT_SHAPE = (4, 6)
+SLOT_KINDS = {"absent": lambda: None, "present": lambda: torch.full(SLOT_SHAPE, 7.0),
+              "wrong shape": lambda: torch.full((6, 4), 7.0), "non-contiguous": lambda: torch.full((6, 4), 7.0).t()}
+
+
+def _slot_case(leaf, grad_set, kind):
+    """A CPU tensor in one row of the table: a leaf parameter or the output of an operation on one, with or without .grad,
+    `_vq2_grad` attached by hand as ParamArena / planned_weight attach it."""
+    p = torch.zeros(SLOT_SHAPE, requires_grad=True)
+    if not leaf:
+        p = p * 1.0
+        if grad_set:
+            p.retain_grad()
+            p.sum().backward()
+    elif grad_set:
+        p.grad = torch.ones(SLOT_SHAPE)
+    slot = SLOT_KINDS[kind]()
+    if slot is not None:
+        p._vq2_grad = slot
+    assert p.is_leaf == leaf
+    if leaf or grad_set:                                # (asking a non-leaf that retains none for .grad warns)
+        assert (p.grad is not None) == grad_set
+    return p, slot
+
+
+@pytest.mark.parametrize("kind", list(SLOT_KINDS))
+@pytest.mark.parametrize("grad_set", (False, True), ids=("no grad", "grad set"))
+@pytest.mark.parametrize("leaf", (True, False), ids=("leaf", "non-leaf"))
+def test_gradient_slot_rule_truth_table(amd, leaf, grad_set, kind):
+    """ops.slot_of / _grad_slot / landed over (leaf, .grad set, slot): the slot is writable when it is there with the
+    parameter's shape and contiguous, and the tensor is no leaf or a leaf without a gradient yet; _grad_slot then hands out
+    a NEW tensor on the slot's storage, otherwise a fresh contiguous one; landed() is the pointer comparison of .grad."""
+    ops = amd.ops
+    p, slot = _slot_case(leaf, grad_set, kind)
+    writable = kind == "present" and (not leaf or not grad_set)
+    assert (ops.slot_of(p) is slot) if writable else (ops.slot_of(p) is None)
+    out = ops._grad_slot(p)
+    assert out is not slot and out.shape == p.shape and out.is_contiguous() and out.dtype == p.dtype
+    if writable:
+        assert out.data_ptr() == slot.data_ptr() and out.untyped_storage().data_ptr() == slot.untyped_storage().data_ptr()
+        out.fill_(3.0)
+        assert bool((slot == 3.0).all())
+    else:
+        assert slot is None or out.untyped_storage().data_ptr() != slot.untyped_storage().data_ptr()
+        out.fill_(3.0)
+        assert slot is None or bool((slot == 7.0).all())
+    # landed: whatever .grad holds now is not the slot (a tensor of its own, or nothing)
+    if leaf or grad_set:
+        assert ops.landed(p) is False
+    if leaf and slot is not None:
+        p.grad = None
+        assert ops.landed(p) is False
+        if kind == "present":
+            p.grad = slot.view_as(slot)
+            assert ops.landed(p) is True
+            assert ops.slot_of(p) is None               # ...and a second backward would no longer write there
+            p.grad = torch.ones(SLOT_SHAPE)
+            assert ops.landed(p) is False
+
+
+def test_gradient_slot_of_no_parameter(amd):
+    assert amd.ops.slot_of(None) is None and amd.ops._grad_slot(None) is None
+
+
+def test_upload_structs_is_the_arrays_bytes(amd):
+    """ops._upload_structs: the device table is the ctypes array byte for byte (here on the CPU)."""
+    W = amd._lib.WgradJob
+    arr = (W * 2)()
+    for i, job in enumerate(arr):
+        for j, (name, _) in enumerate(W._fields_):
+            if isinstance(getattr(job, name), int):
+                setattr(job, name, 1000 * (i + 1) + j)
+    raw = bytes(arr)
+    assert len(raw) == 2 * ctypes.sizeof(W) and any(raw)
+    t = amd.ops._upload_structs(arr, "cpu")
+    assert t.dtype == torch.uint8 and t.device.type == "cpu" and t.dim() == 1 and bytes(t.numpy()) == raw
+    arr[0].unit_offset = 77                             # a copy, not a window on the ctypes memory
+    assert bytes(t.numpy()) == raw
+
+
 def test_split_checkpoint_recognises_every_accepted_file(amd):
     """What load_state_dict makes of a checkpoint before it touches anything: the model's state_dict without the
     "module." prefix of DDP / DataParallel, and whether optimizer state comes with it."""

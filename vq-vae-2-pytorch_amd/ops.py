@@ -21,11 +21,15 @@ VQ2_MASK_AFTER_RESIDUAL = 4
 PACK_FWD = 0
 PACK_DGRAD = 1
 
-# There is NO process-global mutable state on the autograd path (SURVEY 8b threading row): the packed-weight
-# cache lives on each weight tensor (`_vq2_packs`), raw-pointer weight updates are tracked per parameter
-# (`_vq2_epoch`, see touch_weights), and the deferred weight-gradient reduction / side stream of a training step
-# belong to the StepContext its Stage1Trainer hangs on its own parameters (`_vq2_ctx`), so two trainers or
-# models can coexist in one process and back-propagate on different autograd threads.
+# There is NO process-global mutable state on the autograd path (SURVEY 8b threading row): what a step shares hangs on the
+# tensors, so two trainers or models can coexist in one process and back-propagate on different autograd threads:
+#   _vq2_packs  packed-weight cache {which: (version, buffer)}: set by packed_weight / PackPlan.run, read by packed_weight
+#   _vq2_epoch  count of raw-pointer weight updates (no _version bump): set by touch_weights, read through weight_epoch
+#               (_pack_version, the sampler's snapshot)
+#   _vq2_ctx    the owning trainer's StepContext (deferred reduction, side stream): set by the trainer, read by _step_ctx
+#   _vq2_grad   slot in a flat gradient buffer: set by ParamArena (parameters) and planned_weight (a WeightNormPlan's
+#               effective weight), read by slot_of / landed alone
+#   _vq2_wn     the WeightNormPlan that forms this weight_v's effective weight: set by the plan, read by plan_ready
 
 
 def _stream():
@@ -160,11 +164,22 @@ def touch_weights(params):
     """Tell the packed-weight caches that `params` were updated through raw pointers (vq2_adam_step), which
     does not bump tensor._version."""
     for p in params:
-        p._vq2_epoch = getattr(p, "_vq2_epoch", 0) + 1
+        p._vq2_epoch = weight_epoch(p) + 1
+
+
+def weight_epoch(param):
+    """How often touch_weights reported a raw-pointer update of `param` (a cache of its values compares this too)."""
+    return getattr(param, "_vq2_epoch", 0)
 
 
 def _pack_version(spec, weight):
-    return (weight.data_ptr(), weight._version, getattr(weight, "_vq2_epoch", 0), spec)
+    return (weight.data_ptr(), weight._version, weight_epoch(weight), spec)
+
+
+def _upload_structs(arr, device):
+    """A ctypes array of job structs as a uint8 tensor on `device`, byte for byte."""
+    import numpy as np
+    return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(device)
 
 
 def packed_weight(spec, weight, which):
@@ -194,7 +209,6 @@ class PackPlan:
 
     def __init__(self, layers):
         """layers: iterable of (ConvSpec, weight Parameter, needs_dgrad)."""
-        import numpy as np
         jobs = []
         for spec, weight, needs_dgrad in layers:
             for which in ((PACK_FWD, PACK_DGRAD) if needs_dgrad else (PACK_FWD,)):
@@ -217,8 +231,7 @@ class PackPlan:
             self.entries.append((spec, weight, which, buf))
             off += numel
         self.total = off
-        raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
-        self.jobs_dev = torch.from_numpy(raw).to(dev)
+        self.jobs_dev = _upload_structs(arr, dev)
         self.njobs = len(jobs)
         self._ptrs = [w.data_ptr() for _, w, _, _ in self.entries]
 
@@ -260,14 +273,36 @@ def conv_dgrad(spec, xshape, dy, weight, mask=None, residual=None, out=None, mas
     return out
 
 
-def _grad_slot(param):
-    """ParamArena: the gradient of `param` lands directly in the flat gradient buffer."""
+def slot_of(param):
+    """THE SLOT RULE (truth tables: DESIGN §3).  The slot `_vq2_grad` that a weight-gradient launch may write for `param`
+    now, or None: it exists with param's shape, contiguous (the kernels write numel() floats through its pointer), and
+    param is a leaf whose .grad is None -- a second backward (accumulation) must not overwrite the first, it gets a fresh
+    tensor that autograd adds -- or no leaf: a WeightNormPlan's effective weight, which has no .grad to ask and whose slot,
+    the plan's dW buffer, is written once per step (PlannedWeightFn.backward refuses a second backward itself).
+    The deferred branch of conv_wgrad and ResBlockFn's w2 job need both slots, weight and bias.  The deferred branch keeps
+    bias.numel() == spec.cout too: its job writes spec.cout floats through the raw slot pointer at flush(), after autograd
+    has checked what it was handed, so a bias of another length would have the reduction end in the neighbouring slot or
+    short of its own.  One site differs: OneHotConvFn keeps no weight and decides in forward, where a leaf's .grad says
+    nothing about the time of backward, so it takes the slot of a non-leaf weight only (a leaf's goes to a fresh tensor)."""
     slot = getattr(param, "_vq2_grad", None) if param is not None else None
-    # a second backward (accumulation) must not overwrite the first; an effective weight handed out by a WeightNormPlan
-    # is no leaf (it has no .grad): its slot is that plan's dW buffer, written once per step
-    if slot is not None and (not param.is_leaf or param.grad is None):
-        return slot.view_as(slot)  # fresh tensor object so autograd can adopt it as .grad without a copy
+    ok = slot is not None and (not param.is_leaf or param.grad is None) and slot.shape == param.shape and slot.is_contiguous()
+    return slot if ok else None
+
+
+def _grad_slot(param):
+    """Where the gradient of `param` is written: a view of slot_of(param), a fresh tensor object so that autograd can adopt
+    it as .grad without a copy, else a fresh contiguous tensor."""
+    slot = slot_of(param)
+    if slot is not None:
+        return slot.view_as(slot)
     return None if param is None else torch.empty_like(param, memory_format=torch.contiguous_format)
+
+
+def landed(param):
+    """True when `param.grad` is its slot (starts where `_vq2_grad` does): what ParamArena.grads_ready, FusedAdam.step and
+    the trainers' early buckets ask before they read the flat gradient buffer."""
+    slot, grad = getattr(param, "_vq2_grad", None), param.grad
+    return slot is not None and grad is not None and grad.data_ptr() == slot.data_ptr()
 
 
 class WgradBatch:
@@ -281,21 +316,30 @@ class WgradBatch:
         self.tables = {}
         self.dirty = True
 
+    def _entry(self, key, device, create):
+        """The entry of `key`; made on first use from create() -> (workspace bytes, dw slot, db slot, job_init(ws, dw, db, job))"""
+        ent = self.entries.get(key)
+        if ent is None:
+            nbytes, dw, db, job_init = create()
+            ws = torch.empty(max(nbytes // 4, 4), device=device, dtype=torch.float32)
+            job = WgradJob()
+            job_init(_p(ws), _p(dw), _p(db), C.byref(job))
+            ent = self.entries[key] = {"ws": ws, "nbytes": nbytes, "job": job, "dw": dw, "db": db, "used": False}
+            self.dirty = True
+        return ent
+
+    def _mark_used(self, key, ent):
+        if not ent["used"]:
+            ent["used"] = True
+            self.order.append(key)
+
     def launch(self, spec, x, dy, relu_in, weight, bias, want_db, side):
         n, h, w, _ = x.shape
         key = (id(weight), n, h, w, ld_of(x), ld_of(dy), relu_in)
         d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
-        ent = self.entries.get(key)
-        if ent is None:
-            nbytes = lib.vq2_conv_wgrad_workspace_bytes(C.byref(d))
-            ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
-            dw = weight._vq2_grad
-            db = bias._vq2_grad if (bias is not None and want_db) else None
-            job = WgradJob()
-            check(lib.vq2_wgrad_job_init(C.byref(d), _p(ws), _p(dw), _p(db), C.byref(job)), "wgrad_job_init")
-            ent = {"ws": ws, "nbytes": nbytes, "job": job, "dw": dw, "db": db, "used": False}
-            self.entries[key] = ent
-            self.dirty = True
+        ent = self._entry(key, x.device, lambda: (
+            lib.vq2_conv_wgrad_workspace_bytes(C.byref(d)), slot_of(weight), slot_of(bias) if want_db else None,
+            lambda *a: check(lib.vq2_wgrad_job_init(C.byref(d), *a), "wgrad_job_init")))
         # off the backward critical path: overlaps the next layers' data gradients.  A launch that fills the chip by
         # itself gains nothing from a second stream.
         on_side = n * h * w <= WGRAD_STREAM_MAX_PIXELS
@@ -307,9 +351,7 @@ class WgradBatch:
         if on_side:
             x.record_stream(side)
             dy.record_stream(side)
-        if not ent["used"]:
-            ent["used"] = True
-            self.order.append(key)
+        self._mark_used(key, ent)
         dw, db = ent["dw"], ent["db"]
         return dw.view_as(dw), (None if db is None else db.view_as(db))
 
@@ -317,19 +359,10 @@ class WgradBatch:
         """Workspace for the 1x1 weight/bias gradient that vq2_resblock_bwd_data leaves per workgroup; its job
         joins the batched reduction like any other layer's slabs.  Returns (workspace tensor, dw view, db view)."""
         key = (id(weight), n, h, w, "rbw2")
-        ent = self.entries.get(key)
-        if ent is None:
-            nbytes = lib.vq2_resblock_w2_workspace_bytes(n, h, w, c, cm)
-            ws = torch.empty(max(nbytes // 4, 4), device=weight.device, dtype=torch.float32)
-            dw, db = weight._vq2_grad, bias._vq2_grad
-            job = WgradJob()
-            check(lib.vq2_resblock_w2_job_init(n, h, w, c, cm, _p(ws), _p(dw), _p(db), C.byref(job)), "resblock_w2_job_init")
-            ent = {"ws": ws, "nbytes": nbytes, "job": job, "dw": dw, "db": db, "used": False}
-            self.entries[key] = ent
-            self.dirty = True
-        if not ent["used"]:
-            ent["used"] = True
-            self.order.append(key)
+        ent = self._entry(key, weight.device, lambda: (
+            lib.vq2_resblock_w2_workspace_bytes(n, h, w, c, cm), slot_of(weight), slot_of(bias),
+            lambda *a: check(lib.vq2_resblock_w2_job_init(n, h, w, c, cm, *a), "resblock_w2_job_init")))
+        self._mark_used(key, ent)
         return ent["ws"], ent["dw"].view_as(ent["dw"]), ent["db"].view_as(ent["db"])
 
     def flush(self):
@@ -341,7 +374,6 @@ class WgradBatch:
             self.dirty = False
         tab = self.tables.get(sig)
         if tab is None:   # job table of this subset of layers: built and uploaded once, then reused every step
-            import numpy as np
             arr = (WgradJob * len(self.order))()
             off = 0
             for i, key in enumerate(self.order):
@@ -349,8 +381,7 @@ class WgradBatch:
                 job.unit_offset = off
                 arr[i] = job
                 off += job.n_units_w + job.n_units_b
-            raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
-            tab = (torch.from_numpy(raw).to(self.entries[self.order[0]]["ws"].device), off)
+            tab = (_upload_structs(arr, self.entries[self.order[0]]["ws"].device), off)
             self.tables[sig] = tab
         check(lib.vq2_wgrad_reduce_batched(_p(tab[0]), len(self.order), tab[1], _stream()), "wgrad_reduce_batched")
         for key in self.order:
@@ -389,15 +420,15 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
     d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
     nbytes = lib.vq2_conv_wgrad_workspace_bytes(C.byref(d))
     sc = _step_ctx(weight)
-    if sc is not None and getattr(weight, "_vq2_grad", None) is not None and weight.grad is None and \
-            (bias is None or (getattr(bias, "_vq2_grad", None) is not None and bias.grad is None)) and \
-            (bias is None or bias.numel() == spec.cout):
+    in_slot = sc is not None and slot_of(weight) is not None
+    # deferred: both slots writable (slot_of), and the bias exactly as long as the job's reduction writes
+    if in_slot and (bias is None or (slot_of(bias) is not None and bias.numel() == spec.cout)):
         dw, db = sc.batch.launch(spec, x, dy, relu_in, weight, bias, want_db, sc.stream)
         return (dw if want_dw else None), db
     dw = _grad_slot(weight)
     db = _grad_slot(bias) if (bias is not None and want_db) else None
     side = None   # the side stream only for a gradient that lands in its arena slot (see StepContext)
-    if sc is not None and getattr(weight, "_vq2_grad", None) is not None and dw.data_ptr() == weight._vq2_grad.data_ptr():
+    if in_slot:
         side = sc.stream
         side.wait_event(torch.cuda.current_stream().record_event())
     with (torch.cuda.stream(side) if side is not None else _THIS_STREAM):
@@ -768,8 +799,7 @@ class ResBlockFn(Function):
             sc = _step_ctx(w2)
             w2_ws = None
             if (sc is not None and ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and
-                    getattr(w2, "_vq2_grad", None) is not None and getattr(b2, "_vq2_grad", None) is not None and
-                    w2.grad is None and b2.grad is None):
+                    slot_of(w2) is not None and slot_of(b2) is not None):
                 w2_ws, dw2, db2 = sc.batch.resblock_w2(n, h, w, c, s1.co, w2, b2)
             check(lib.vq2_resblock_bwd_data(n, h, w, c, s1.co, _p(g), ld_of(g), _p(r), ld_of(r), _p(x), ld_of(x),
                                             _p(packed_weight(s2, w2, PACK_DGRAD)), _p(packed_weight(s1, w1, PACK_DGRAD)),
@@ -1057,7 +1087,6 @@ class WeightNormPlan:
         return rows_of, skipped
 
     def __init__(self, model, arena):
-        import numpy as np
         self.arena = arena
         self.table, self.skipped = self.entries(model, arena.offset)
         if not self.table:
@@ -1081,8 +1110,7 @@ class WeightNormPlan:
             self.dw_views.append(self.dw[e["w_off"]:e["w_off"] + numel].view(shape))
             mod.weight_v._vq2_wn = self
         arr[n].row_start = self.table[-1]["row_start"] + self.table[-1]["rows"]      # the terminator: total rows
-        raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
-        self.table_dev = torch.from_numpy(raw).to(dev)
+        self.table_dev = _upload_structs(arr, dev)
         self._ptrs = [(v.data_ptr(), g.data_ptr()) for v, g in self.vg]
         self.active = False
         self.current = False
@@ -1130,7 +1158,7 @@ class PlannedWeightFn(Function):
         v, g = plan.vg[i]
         if v.grad is not None or g.grad is not None:
             raise RuntimeError("WeightNormPlan: a second backward inside one trainer step (arena.zero_grad() first)")
-        return v._vq2_grad.view_as(v._vq2_grad), g._vq2_grad.view_as(g._vq2_grad), None, None
+        return _grad_slot(v), _grad_slot(g), None, None
 
 
 def plan_ready(weight_v):
@@ -1311,8 +1339,9 @@ class OneHotConvFn(Function):
                                       _p(y), _stream()), "onehot_conv_fwd")
         ctx.save_for_backward(idx)
         ctx.geom, ctx.shift, ctx.wshape, ctx.has_bias = tuple(geom), tuple(shift), tuple(weight.shape), bias is not None
-        # where the gradients go: a plan's dW slot for the weight, the arena slot for the bias (None: fresh tensors)
-        ctx.dw_slot, ctx.bias = (None if weight.is_leaf else getattr(weight, "_vq2_grad", None)), bias
+        # where the gradients go: a plan's dW slot for the weight (decided here, the weight is not kept: non-leaf only, see
+        # slot_of), the arena slot for the bias (None: fresh tensors)
+        ctx.dw_slot, ctx.bias = (None if weight.is_leaf else slot_of(weight)), bias
         return y
 
     @staticmethod
@@ -1325,8 +1354,7 @@ class OneHotConvFn(Function):
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             d = _onehot_desc(n, h, w, cout, n_class, ctx.geom, ctx.shift, ld_of(dy))
             slot = ctx.dw_slot
-            dw = slot.view_as(slot) if slot is not None and tuple(slot.shape) == ctx.wshape and slot.is_contiguous() else \
-                torch.empty(ctx.wshape, device=dy.device, dtype=torch.float32)
+            dw = slot.view_as(slot) if slot is not None else torch.empty(ctx.wshape, device=dy.device, dtype=torch.float32)
             ws = nbytes = None
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 db = _grad_slot(ctx.bias)

@@ -77,7 +77,7 @@ class ParamArena:
             raise RuntimeError("ParamArena: state vector belongs to a different model")
 
     def grads_ready(self):
-        return all(p.grad is not None and p.grad.data_ptr() == p._vq2_grad.data_ptr() for p in self.params)
+        return all(ops.landed(p) for p in self.params)
 
     def zero_grad(self):
         for p in self.params:
@@ -107,8 +107,7 @@ class FusedAdam(torch.optim.Optimizer):
                 raise RuntimeError("FusedAdam: a ParamArena supports a single param group")
             if not self.arena.grads_ready():
                 # falling back to the per-tensor path here would silently fork the optimizer state (fresh m/v)
-                missing = [i for i, p in enumerate(self.arena.params)
-                           if p.grad is None or p.grad.data_ptr() != p._vq2_grad.data_ptr()]
+                missing = [i for i, p in enumerate(self.arena.params) if not ops.landed(p)]
                 raise RuntimeError(f"FusedAdam: {len(missing)} gradient(s) did not land in the flat arena (first: "
                                    f"parameter #{missing[0]}); every arena parameter must receive exactly one "
                                    "gradient per step (zero_grad() before each backward)")

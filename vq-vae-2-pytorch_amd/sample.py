@@ -366,7 +366,7 @@ class PriorSampler:
         return wp
 
     def _snapshot(self):
-        return [(p.data_ptr(), p._version, getattr(p, "_vq2_epoch", 0)) for p in self.model.parameters()]
+        return [(p.data_ptr(), p._version, ops.weight_epoch(p)) for p in self.model.parameters()]
 
     def _plan_for(self, batch, rows, condition):
         if self._snapshot() != self._versions:

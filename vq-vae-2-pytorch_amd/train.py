@@ -104,7 +104,7 @@ class _ArenaTrainer:
         seen = self._hooks_seen[bucket.name] = self._hooks_seen.get(bucket.name, 0) + 1
         if seen != need:
             return
-        if not all(p.grad is not None and p.grad.data_ptr() == p._vq2_grad.data_ptr() for p in bucket.params):
+        if not all(ops.landed(p) for p in bucket.params):
             # a gradient is not in its slot (autograd ordered the graph differently, or it missed the arena, which
             # _reduce_unsent / FusedAdam report): keep the slice for the collective after backward
             return
