@@ -14,7 +14,9 @@ continues from exactly (model, Adam moments, schedule position).
 
 Extra arguments of this script (all default to the reference's fixed values): --size H W of the top codes (the bottom codes
 are twice that), --n_class, --n_block, --kernel_size, --max_steps to stop early, --ckpt_dir, --workers, --seed (the torch
-generator is seeded with seed + rank: it draws the shuffle and the dropout seeds), --resume FILE."""
+generator is seeded with seed + rank: it draws the shuffle and the dropout seeds), --resume FILE, and --val_path CODES with
+--eval_every N: every N steps each rank scores its share of the held-out codes (Stage2Trainer.evaluate: eval mode, no
+dropout seed drawn, the training run itself unchanged) and the primary rank prints the totals.  N = 0, the default, is off."""
 import argparse
 import os
 import sys
@@ -51,6 +53,8 @@ def parse_args(argv=None):
     parser.add_argument('--workers', type=int, default=4)
     parser.add_argument('--seed', type=int, default=None)
     parser.add_argument('--resume', type=str, default=None)
+    parser.add_argument('--val_path', type=str, default=None)
+    parser.add_argument('--eval_every', type=int, default=0)
     return parser.parse_args(argv)
 
 
@@ -82,6 +86,12 @@ def main(argv=None):
     # (the DistributedSampler pads every shard to the same length and drop_last cuts whole batches: every rank takes the
     # same number of steps)
     loader = DataLoader(dataset, batch_size=args.batch, sampler=sampler, num_workers=args.workers, drop_last=True)
+    val_loader, eval_every = None, args.eval_every
+    if args.val_path is not None and eval_every > 0:
+        # every image once: rank r takes the rows r, r + world, ... (a DistributedSampler would repeat rows to pad the shards)
+        held_out = vqvae2_amd.codes.CodeDataset(args.val_path)
+        share = torch.utils.data.Subset(held_out, range(rank, len(held_out), max(world, 1)))
+        val_loader = DataLoader(share, batch_size=args.batch, shuffle=False, num_workers=0)
     # (--resume keeps this command line: give the run's own arguments again)
     resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume is not None else None
     ckpt = {}
@@ -108,6 +118,10 @@ def main(argv=None):
             steps += 1
             if primary:
                 print(f"epoch: {i + 1}; loss: {r['loss'].item():.5f}; acc: {r['accuracy'].item():.5f}; lr: {r['lr']:.5f}")
+            if val_loader is not None and steps % eval_every == 0:
+                held = trainer.evaluate(val_loader)
+                if primary:
+                    print(f"step: {steps}; held-out {vqvae2_amd.PriorEvaluator.summary(held)}")
             if args.max_steps and steps >= args.max_steps:
                 break
         done = bool(args.max_steps and steps >= args.max_steps)

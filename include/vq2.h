@@ -56,11 +56,12 @@ typedef void *vq2_stream_t;
  * same_size added); vq2_conv_geom and the eight vq2_convg_* twins removed, every layer goes through the vq2_conv_* entry
  * points; vq2_conv_dgrad takes the flags argument and vq2_conv_dgrad_ex is gone; vq2_convg_fwd_row and its workspace query
  * renamed vq2_conv_fwd_row / vq2_conv_fwd_row_workspace_bytes on vq2_conv_desc; see INTEGRATION.md "ABI history");
- * revision 14: an addition only -- vq2_sample_filtered, the draw from a top-k / nucleus truncated support with its log-probability.
+ * revision 14: an addition only -- vq2_sample_filtered, the draw from a top-k / nucleus truncated support with its log-probability;
+ * revision 15: additions only -- vq2_prior_eval_rows and vq2_prior_eval_accumulate, the held-out evaluation of the stage-2 prior.
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 14
+#define VQ2_API_VERSION 15
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -394,6 +395,32 @@ int vq2_image_metrics(const float *a, int32_t lda, const float *b, int32_t ldb, 
                       vq2_stream_t stream);
 int vq2_image_metrics_accumulate(const int64_t *sse_u8, const double *ssim, int32_t N, int64_t *acc_i, double *acc_d,
                                  vq2_stream_t stream);
+
+/* ------------------------------------------------------------------ held-out evaluation of the stage-2 prior
+ * A second head on the logits vq2_xent_fwd reads (fp32 rows of n_class real values, row stride ld floats, ld % 4 == 0,
+ * ld >= ceil4(n_class), 16-byte aligned; lanes beyond n_class are never read as data): what a likelihood evaluation
+ * reports beside the train step's mean.  1 <= n_class <= 16384, 1 <= M < 2^31.
+ * vq2_prior_eval_rows: one wavefront per row, two passes over it.  With m the row maximum, d = l - m and s = sum exp(d)
+ *   (exp in fp32, the sums carried in fp64, one rounding to fp32 at the end):
+ *     row_nll[r]     = log s - (l[t] - m)                    the cross-entropy term of vq2_xent_fwd, nats
+ *     row_entropy[r] = log s - (sum exp(d) * d) / s          entropy of the predicted distribution, nats
+ *     row_rank[r]    = #{c : l[c] > l[t]} + #{c < t : l[c] == l[t]}      integer, exact; 0 is the hit of vq2_xent_fwd
+ *                                                                        (the lowest index wins a tie)
+ *   A target outside [0, n_class): row_nll = 0, row_entropy as computed, row_rank = -1; nothing is read through it.
+ * vq2_prior_eval_accumulate: rows ordered [N, L] (L = H * W positions).  No atomics, one fixed order: position p belongs
+ *   to one thread, which adds row_nll[n * L + p] for n = 0 .. N - 1 in that order to pos_nll[p] in fp64 (pos_entropy the
+ *   same way), pos_hit1[p] += #{n : rank == 0}, pos_hitk[p] += #{n : 0 <= rank < top_k}; counters[0] += N,
+ *   counters[1] += #{rows : rank == -1}.  Each position is a running sum in batch order: batches of 5, 3 and 1 leave
+ *   bit for bit the state one batch of 9 leaves.  image_nll (device fp32 [N], or NULL): image_nll[n] = the sum over p
+ *   ascending of row_nll[n * L + p], in fp64, rounded once.  N, L, top_k >= 1, N * L < 2^31; the caller zeroes the
+ *   state once.  No synchronisation; the caller owns all memory. */
+int vq2_prior_eval_rows(const float *logits, int32_t ld, const int64_t *target, int64_t M, int32_t n_class,
+                        float *row_nll, float *row_entropy, int32_t *row_rank, vq2_stream_t stream);
+int vq2_prior_eval_accumulate(const float *row_nll, const float *row_entropy, const int32_t *row_rank,
+                              int32_t N, int32_t L, int32_t top_k,
+                              double *pos_nll, double *pos_entropy, int64_t *pos_hit1, int64_t *pos_hitk,
+                              int64_t *counters /* [images, bad targets] */, float *image_nll /* [N] or NULL */,
+                              vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ causal self-attention (stage-2 prior)
  * CausalAttention of the reference (pixelsnail.py:195-234) after its three projections: q, k, v, o are [B, L, n_head *

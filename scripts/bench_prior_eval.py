@@ -1,0 +1,109 @@
+"""Rate of the held-out evaluation of the PixelSNAIL prior, the reference's two configurations (train_pixelsnail.py:99-126,
+512 classes): the top prior on 32x32 codes at batch 32 and the bottom prior on 64x64 codes (conditioned on 32x32) at batch
+8, freshly initialised weights, codes resident in HBM.  HIP events around `steps` calls after `warmup` calls, REPEATS times
+in one session; every figure is reported as the mean of the repeats with their minimum and maximum.
+
+  update          PriorEvaluator.update: eval forward + vq2_prior_eval_rows + vq2_prior_eval_accumulate + vq2_index_hist
+  forward         the eval-mode forward under no_grad alone
+  added launches  the three launches on logits that are already there
+  rows kernel     vq2_prior_eval_rows alone, against the bytes it must read, M * ld * 4
+
+    python scripts/bench_prior_eval.py            (REPEATS=3 STEPS=20 WARMUP=5 by default; writes profiles/prior_eval.json)
+"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+import vqvae2_amd  # noqa: E402
+from vqvae2_amd import ops  # noqa: E402
+from vqvae2_amd.evaluate import eval_mode  # noqa: E402
+
+REPEATS = int(os.environ.get("REPEATS", "3"))
+STEPS = int(os.environ.get("STEPS", "20"))
+WARMUP = int(os.environ.get("WARMUP", "5"))
+N_CLASS = 512
+dev = torch.device("cuda:0")
+
+
+def by_events(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps * 1e-3
+
+
+def spread(values, scale=1.0, digits=3):
+    return {"mean": round(sum(values) / len(values) * scale, digits), "min": round(min(values) * scale, digits),
+            "max": round(max(values) * scale, digits)}
+
+
+def measure(hier, batch):
+    torch.manual_seed(0)
+    if hier == "top":
+        model = vqvae2_amd.PixelSNAIL([32, 32], N_CLASS, 256, 5, 4, 4, 256, dropout=0.1, n_out_res_block=0)
+        size = (32, 32)
+    else:
+        model = vqvae2_amd.PixelSNAIL([64, 64], N_CLASS, 256, 5, 4, 4, 256, attention=False, dropout=0.1, n_cond_res_block=3,
+                                      cond_res_channel=256)
+        size = (64, 64)
+    model = model.to(dev).train()
+    g = torch.Generator().manual_seed(1)
+    top = torch.randint(0, N_CLASS, (batch, 32, 32), generator=g).to(dev)
+    bottom = torch.randint(0, N_CLASS, (batch, 64, 64), generator=g).to(dev)
+    target = top if hier == "top" else bottom
+    ev = vqvae2_amd.PriorEvaluator(model, hier)
+
+    def forward():
+        with eval_mode(model), torch.no_grad():
+            return model(top)[0] if hier == "top" else model(bottom, condition=top)[0]
+
+    x = ops.to_nhwc(forward())
+    rows = target.numel()
+    ld = ops.ld_of(x)
+    pos_nll, pos_entropy, hit1, hitk, counters, counts, flag = ev._buffers(dev, size)
+
+    def added():
+        nll, entropy, rank = ops.prior_eval_rows(x, target, N_CLASS)
+        ops.prior_eval_accumulate(nll, entropy, rank, batch, ev.top_k, pos_nll, pos_entropy, hit1, hitk, counters)
+        ops.index_hist(target, counts, flag)
+
+    t = {"update": [], "forward": [], "added": [], "rows": []}
+    for _ in range(REPEATS):
+        t["update"].append(by_events(lambda: ev.update(top, bottom if hier == "bottom" else None), STEPS, WARMUP))
+        t["forward"].append(by_events(forward, STEPS, WARMUP))
+        t["added"].append(by_events(added, 10 * STEPS, 10 * WARMUP))
+        t["rows"].append(by_events(lambda: ops.prior_eval_rows(x, target, N_CLASS), 10 * STEPS, 10 * WARMUP))
+    ev.reset()
+    ev.update(top, bottom if hier == "bottom" else None)
+    r = ev.result()
+    nbytes = rows * ld * 4
+    return {"hier": hier, "batch": batch, "codes_per_batch": rows, "n_class": N_CLASS, "row_stride": ld,
+            "update_ms": spread(t["update"], 1e3), "update_codes_per_s": spread([rows / v for v in t["update"]], 1.0, 0),
+            "forward_ms": spread(t["forward"], 1e3), "added_launches_us": spread(t["added"], 1e6, 2),
+            "rows_kernel_us": spread(t["rows"], 1e6, 2), "rows_kernel_bytes": nbytes,
+            "rows_kernel_TB_per_s": spread([nbytes / v / 1e12 for v in t["rows"]]),
+            "nll_of_the_untrained_model": round(r["nll"], 4), "ln_n_class": round(float(torch.tensor(float(N_CLASS)).log()), 4)}
+
+
+def main():
+    out = {"method": f"HIP events around {STEPS} calls after {WARMUP} warm-up calls (10x both for the launches alone), "
+                     f"{REPEATS} repeats in one session; mean with min and max of the repeats",
+           "device": torch.cuda.get_device_name(0), "results": [measure("top", 32), measure("bottom", 8)]}
+    for r in out["results"]:
+        print(json.dumps(r), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "prior_eval.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

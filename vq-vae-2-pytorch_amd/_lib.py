@@ -85,6 +85,8 @@ def _load():
         "vq2_image_metrics_workspace_bytes": (SZ, [I32, I32, I32, I32]),
         "vq2_image_metrics": (C.c_int, [P, I32, P, I32, I32, I32, I32, I32, C.POINTER(F), C.POINTER(F), P, P, P, SZ, P]),
         "vq2_image_metrics_accumulate": (C.c_int, [P, P, I32, P, P, P]),
+        "vq2_prior_eval_rows": (C.c_int, [P, I32, P, I64, I32, P, P, P, P]),
+        "vq2_prior_eval_accumulate": (C.c_int, [P, P, P, I32, I32, I32, P, P, P, P, P, P, P]),
         "vq2_relu_bwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
         "vq2_resblock_supported": (C.c_int, [I32, I32]),
         "vq2_resblock_bwd_data": (C.c_int, [I32, I32, I32, I32, I32, P, I32, P, I32, P, I32, P, P, P, I32, P, I32, P, P]),

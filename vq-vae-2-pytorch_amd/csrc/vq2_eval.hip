@@ -4,6 +4,8 @@
 //   index_hist       code-usage histogram of a quantizer's indices (integer atomics only)
 //   eval_accumulate  folds a batch into a device accumulator of doubles, so that an evaluation loop never syncs
 //   image_metrics    per image: integer squared error and Gaussian-window SSIM of the two 8-bit images nhwc_to_u8 writes
+//   prior_eval_rows        per logits row of the stage-2 prior: cross-entropy term, predictive entropy, rank of the target
+//   prior_eval_accumulate  folds those rows into per-position running totals, one thread per position, in batch order
 #include <math.h>
 #include "vq2_common.h"
 
@@ -405,6 +407,130 @@ __global__ __launch_bounds__(256) void image_metrics_accumulate_kernel(const lon
     }
 }
 
+// ------------------------------------------------------------------ stage-2 prior: per-row likelihood terms
+// One wave per row, as xent_rows_kernel (vq2_prior.hip): lane c takes the float4 groups c, c + 64, ... of the row; the
+// guards keep the pad lanes of the last group out of every result.  Pass 1: the row maximum.  Pass 2: with d = l - m and
+// e = expf(d) in fp32, the sums of e and of e * d in fp64 (a 16,384-class row is 64 groups per lane: the row is looped
+// over, never held), and the integer count of the classes that beat the target -- a larger logit, or an equal one at a
+// lower index, which is the tie rule of xent_rows_kernel's arg-max: rank 0 there is a hit here.  An out-of-range target
+// is compared with nothing and read through nowhere.
+struct RowSums { double s, u; int above; };
+
+__device__ __forceinline__ void row_term(RowSums &a, float v, float m, float lt, int c, int t) {
+    const float d = v - m, e = expf(d);
+    a.s += (double)e;
+    a.u += (double)e * (double)d;
+    a.above += (v > lt || (v == lt && c < t)) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void prior_eval_rows_kernel(const float *__restrict__ logits, int ld,
+                                                              const int64_t *__restrict__ target, int64_t M, int ncls,
+                                                              float *__restrict__ nll, float *__restrict__ entropy,
+                                                              int32_t *__restrict__ rank) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += (int64_t)gridDim.x * 4) {
+        const float *x = logits + row * ld;
+        const int64_t t64 = target[row];
+        const bool valid = (uint64_t)t64 < (uint64_t)ncls;
+        const int t = valid ? (int)t64 : 0;
+        const float lt = valid ? x[t] : INFINITY;      // out of range: the count below is not used
+        float m = -INFINITY;
+        for (int c = lane * 4; c < ncls; c += 256) {
+            const float4 v = *reinterpret_cast<const float4 *>(x + c);
+            m = fmaxf(m, v.x);
+            if (c + 1 < ncls) m = fmaxf(m, v.y);
+            if (c + 2 < ncls) m = fmaxf(m, v.z);
+            if (c + 3 < ncls) m = fmaxf(m, v.w);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        RowSums a = {0.0, 0.0, 0};
+        for (int c = lane * 4; c < ncls; c += 256) {
+            const float4 v = *reinterpret_cast<const float4 *>(x + c);
+            row_term(a, v.x, m, lt, c, t);
+            if (c + 1 < ncls) row_term(a, v.y, m, lt, c + 1, t);
+            if (c + 2 < ncls) row_term(a, v.z, m, lt, c + 2, t);
+            if (c + 3 < ncls) row_term(a, v.w, m, lt, c + 3, t);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            a.s += __shfl_xor(a.s, o, 64);
+            a.u += __shfl_xor(a.u, o, 64);
+            a.above += __shfl_xor(a.above, o, 64);
+        }
+        if (lane == 0) {
+            const double ls = log(a.s);                // s >= 1: the maximum's own term is exp(0)
+            nll[row] = valid ? (float)(ls - (double)(lt - m)) : 0.f;
+            entropy[row] = (float)(ls - a.u / a.s);
+            rank[row] = valid ? a.above : -1;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ stage-2 prior: rows -> running totals
+// Rows are [N, L].  Three kinds of workgroup in one launch, none of which shares an output with another:
+//   blockIdx.x <  PB            positions: thread p owns pos_*[p] and adds the batch's N rows to it in image order
+//   blockIdx.x == PB            counters: images += N; bad += rows of rank -1 (integers: any order gives the same sum)
+//   blockIdx.x >  PB            image blockIdx.x - PB - 1: its L rows through LDS, thread 0 adds them in position order
+__global__ __launch_bounds__(256) void prior_eval_accumulate_kernel(const float *__restrict__ row_nll,
+                                                                    const float *__restrict__ row_entropy,
+                                                                    const int32_t *__restrict__ row_rank, int N, int L, int top_k,
+                                                                    int PB, double *__restrict__ pos_nll,
+                                                                    double *__restrict__ pos_entropy,
+                                                                    long long *__restrict__ pos_hit1,
+                                                                    long long *__restrict__ pos_hitk,
+                                                                    long long *__restrict__ counters, float *__restrict__ image_nll) {
+    __shared__ float buf[256];
+    __shared__ int bad_of[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b < PB) {
+        const int p = b * 256 + tid;
+        if (p >= L) return;
+        double sn = pos_nll[p], se = pos_entropy[p];
+        int h1 = 0, hk = 0;
+        for (int n = 0; n < N; ++n) {
+            const int64_t r = (int64_t)n * L + p;
+            const int rk = row_rank[r];
+            sn += (double)row_nll[r];
+            se += (double)row_entropy[r];
+            h1 += rk == 0;
+            hk += rk >= 0 && rk < top_k;
+        }
+        pos_nll[p] = sn;
+        pos_entropy[p] = se;
+        pos_hit1[p] += h1;
+        pos_hitk[p] += hk;
+    } else if (b == PB) {
+        const int64_t rows = (int64_t)N * L;
+        int bad = 0;
+        for (int64_t r = tid; r < rows; r += 256) bad += row_rank[r] == -1;
+        bad_of[tid] = bad;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (tid < o) bad_of[tid] += bad_of[tid + o];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            counters[0] += N;
+            counters[1] += bad_of[0];
+        }
+    } else {
+        const int n = b - PB - 1;
+        const float *src = row_nll + (int64_t)n * L;
+        double s = 0.0;
+        for (int base = 0; base < L; base += 256) {
+            if (base + tid < L) buf[tid] = src[base + tid];
+            __syncthreads();
+            if (tid == 0) {
+                const int m = L - base < 256 ? L - base : 256;
+                for (int i = 0; i < m; ++i) s += (double)buf[i];
+            }
+            __syncthreads();
+        }
+        if (tid == 0) image_nll[n] = (float)s;
+    }
+}
+
 }  // namespace vq2
 
 using namespace vq2;
@@ -551,4 +677,35 @@ extern "C" int vq2_image_metrics_accumulate(const int64_t *sse_u8, const double 
     hipLaunchKernelGGL(image_metrics_accumulate_kernel, dim3(1), dim3(256), 0, to_stream(stream),
                        reinterpret_cast<const long long *>(sse_u8), ssim, N, reinterpret_cast<long long *>(acc_i), acc_d);
     return check_launch("image_metrics_accumulate_kernel");
+}
+
+extern "C" int vq2_prior_eval_rows(const float *logits, int32_t ld, const int64_t *target, int64_t M, int32_t n_class,
+                                   float *row_nll, float *row_entropy, int32_t *row_rank, vq2_stream_t stream) {
+    VQ2_REQUIRE(logits && target && row_nll && row_entropy && row_rank, "prior_eval_rows: null pointer");
+    VQ2_REQUIRE(M >= 1 && M < ((int64_t)1 << 31), "prior_eval_rows: need 1 <= M < 2^31 rows");
+    VQ2_REQUIRE(n_class >= 1 && n_class <= 16384, "prior_eval_rows: n_class must be in 1..16384, got %d", n_class);
+    VQ2_REQUIRE(ld % 4 == 0 && ld >= (n_class + 3) / 4 * 4, "prior_eval_rows: row stride %d must be a multiple of 4 and >= ceil4(%d)",
+                ld, n_class);
+    VQ2_REQUIRE(aligned16(logits), "prior_eval_rows: the logits must be 16-byte aligned");
+    const int64_t blocks = (M + 3) / 4;
+    hipLaunchKernelGGL(prior_eval_rows_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, to_stream(stream),
+                       logits, ld, target, M, n_class, row_nll, row_entropy, row_rank);
+    return check_launch("prior_eval_rows_kernel");
+}
+
+extern "C" int vq2_prior_eval_accumulate(const float *row_nll, const float *row_entropy, const int32_t *row_rank, int32_t N,
+                                         int32_t L, int32_t top_k, double *pos_nll, double *pos_entropy, int64_t *pos_hit1,
+                                         int64_t *pos_hitk, int64_t *counters, float *image_nll, vq2_stream_t stream) {
+    VQ2_REQUIRE(row_nll && row_entropy && row_rank && pos_nll && pos_entropy && pos_hit1 && pos_hitk && counters,
+                "prior_eval_accumulate: null pointer");
+    VQ2_REQUIRE(N >= 1 && L >= 1 && top_k >= 1, "prior_eval_accumulate: need N >= 1, L >= 1 and top_k >= 1");
+    VQ2_REQUIRE((int64_t)N * L < ((int64_t)1 << 31), "prior_eval_accumulate: 2^31 rows and more are not supported");
+    VQ2_REQUIRE(((reinterpret_cast<uintptr_t>(pos_nll) | reinterpret_cast<uintptr_t>(pos_entropy) | reinterpret_cast<uintptr_t>(pos_hit1) |
+                  reinterpret_cast<uintptr_t>(pos_hitk) | reinterpret_cast<uintptr_t>(counters)) & 7u) == 0,
+                "prior_eval_accumulate: the state must be 8-byte aligned");
+    const int PB = (L + 255) / 256;
+    hipLaunchKernelGGL(prior_eval_accumulate_kernel, dim3((unsigned)(PB + 1 + (image_nll ? N : 0))), dim3(256), 0, to_stream(stream),
+                       row_nll, row_entropy, row_rank, N, L, top_k, PB, pos_nll, pos_entropy, reinterpret_cast<long long *>(pos_hit1),
+                       reinterpret_cast<long long *>(pos_hitk), reinterpret_cast<long long *>(counters), image_nll);
+    return check_launch("prior_eval_accumulate_kernel");
 }

@@ -645,6 +645,57 @@ def image_metrics_accumulate(sse_u8, ssim, acc_i, acc_d):
           "image_metrics_accumulate")
 
 
+def prior_eval_rows(out_nhwc, target, n_class):
+    """Per pixel of the prior's NHWC logits [N,H,W,ceil4(n_class)] (any dense pixel stride, read in place) against int64
+    targets [N,H,W] (vq2_prior_eval_rows) -> (nll float32 [N*H*W], entropy float32 [N*H*W], rank int32 [N*H*W]): the
+    cross-entropy term, the entropy of the predicted distribution (both in nats) and the number of classes that beat the
+    target (0: the hit of prior_loss, the lowest index winning a tie).  A target outside [0, n_class) gives nll 0 and
+    rank -1.  Not an autograd function."""
+    x = _rows(out_nhwc.detach(), n_class)
+    target = _require_codes(target, "target")
+    n, h, w, _ = x.shape
+    m = n * h * w
+    if target.numel() != m or target.device != x.device:
+        raise RuntimeError("prior_eval_rows: one target per pixel, on the logits' GPU, expected")
+    if not 1 <= n_class <= ONEHOT_MAX_CLASSES:
+        raise NotImplementedError(f"vqvae2_amd: n_class must be in 1..{ONEHOT_MAX_CLASSES}, got {n_class}")
+    nll = torch.empty(m, device=x.device, dtype=torch.float32)
+    entropy = torch.empty(m, device=x.device, dtype=torch.float32)
+    rank = torch.empty(m, device=x.device, dtype=torch.int32)
+    check(lib.vq2_prior_eval_rows(_p(x), ld_of(x), _p(target), m, n_class, _p(nll), _p(entropy), _p(rank), _stream()),
+          "prior_eval_rows")
+    return nll, entropy, rank
+
+
+def prior_eval_accumulate(nll, entropy, rank, n_images, top_k, pos_nll, pos_entropy, pos_hit1, pos_hitk, counters,
+                          return_image_nll=False):
+    """Fold the rows of one batch ([n_images, L] in image order, from prior_eval_rows) into the running state on the
+    device (vq2_prior_eval_accumulate): pos_nll / pos_entropy float64 [L] += the rows of each position in image order,
+    pos_hit1 / pos_hitk int64 [L] += the rows of rank 0 / of rank in [0, top_k), counters int64 [2] += (n_images, rows of
+    rank -1).  No atomics: the state after batches of 5, 3 and 1 is bit for bit that after one batch of 9.
+    return_image_nll: also the float32 [n_images] sums of nll over each image's positions."""
+    m = nll.numel()
+    if not (nll.is_cuda and nll.dtype == torch.float32 and entropy.dtype == torch.float32 and rank.dtype == torch.int32
+            and entropy.numel() == m and rank.numel() == m and entropy.device == nll.device and rank.device == nll.device
+            and nll.is_contiguous() and entropy.is_contiguous() and rank.is_contiguous()):
+        raise RuntimeError("prior_eval_accumulate: float32 nll and entropy and int32 rank of one length on one GPU expected; "
+                           "no CPU path")
+    n_images, top_k = int(n_images), int(top_k)
+    if n_images < 1 or m % n_images or top_k < 1:
+        raise RuntimeError(f"prior_eval_accumulate: {m} rows are not {n_images} images, or top_k {top_k} < 1")
+    length = m // n_images
+    for t, dtype, size, what in ((pos_nll, torch.float64, length, "pos_nll"), (pos_entropy, torch.float64, length, "pos_entropy"),
+                                 (pos_hit1, torch.int64, length, "pos_hit1"), (pos_hitk, torch.int64, length, "pos_hitk"),
+                                 (counters, torch.int64, 2, "counters")):
+        if not (t.dtype == dtype and t.numel() == size and t.is_contiguous() and t.device == nll.device):
+            raise RuntimeError(f"prior_eval_accumulate: {what} must be a contiguous {dtype} [{size}] tensor on {nll.device}")
+    image_nll = torch.empty(n_images, device=nll.device, dtype=torch.float32) if return_image_nll else None
+    check(lib.vq2_prior_eval_accumulate(_p(nll), _p(entropy), _p(rank), n_images, length, top_k, _p(pos_nll), _p(pos_entropy),
+                                        _p(pos_hit1), _p(pos_hitk), _p(counters),
+                                        _p(image_nll) if image_nll is not None else None, _stream()), "prior_eval_accumulate")
+    return image_nll
+
+
 def from_nhwc(y, c):
     """Internal NHWC -> NCHW-shaped result (zero-copy channels-last view when C % 4 == 0)."""
     if y.shape[3] == c:

@@ -500,3 +500,18 @@ class Stage2Trainer(_ArenaTrainer):
             self.scheduler.step()
         self.optimizer.step()
         return {"loss": loss.detach(), "accuracy": accuracy, "lr": self.optimizer.param_groups[0]["lr"]}
+
+    # ------------------------------------------------------------------ held-out evaluation
+    def evaluate(self, batches, top_k=5):
+        """PriorEvaluator.result() over an iterable of (top, bottom) or (top, bottom, filename) code batches, between two
+        steps: eval-mode forwards under no_grad that draw no dropout seed and write no arena slot; the plan is not active,
+        so every layer forms its weight from the parameters as they are, and the steps that follow are bit for bit those of
+        a run that never evaluated.  Every module's train / eval flag is restored.  Data parallel: every rank calls it
+        (result() sums over the group)."""
+        from .evaluate import PriorEvaluator
+        ev = PriorEvaluator(self.model, self.hier, top_k=top_k)
+        device = next(self.model.parameters()).device
+        for batch in batches:
+            top, bottom = batch[0], batch[1]
+            ev.update(top.to(device), bottom.to(device) if self.hier == "bottom" else None)
+        return ev.result()
