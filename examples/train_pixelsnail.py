@@ -16,7 +16,11 @@ Extra arguments of this script (all default to the reference's fixed values): --
 are twice that), --n_class, --n_block, --kernel_size, --max_steps to stop early, --ckpt_dir, --workers, --seed (the torch
 generator is seeded with seed + rank: it draws the shuffle and the dropout seeds), --resume FILE, and --val_path CODES with
 --eval_every N: every N steps each rank scores its share of the held-out codes (Stage2Trainer.evaluate: eval mode, no
-dropout seed drawn, the training run itself unchanged) and the primary rank prints the totals.  N = 0, the default, is off."""
+dropout seed drawn, the training run itself unchanged) and the primary rank prints the totals.  N = 0, the default, is off.
+--clip_grad_norm X clips the global gradient norm to X on the device (the printed line gains gnorm:, the norm before
+clipping; a step whose norm is not finite is skipped and counted, the count is printed at the end).  --ema_decay D keeps
+Polyak-averaged weights: every save also writes pixelsnail_<hier>_<NNN>_ema.pt, the same file with the averaged weights
+(sample.py and eval_pixelsnail.py load it like any checkpoint), and the held-out line is printed for both sets of weights."""
 import argparse
 import os
 import sys
@@ -55,6 +59,8 @@ def parse_args(argv=None):
     parser.add_argument('--resume', type=str, default=None)
     parser.add_argument('--val_path', type=str, default=None)
     parser.add_argument('--eval_every', type=int, default=0)
+    parser.add_argument('--clip_grad_norm', type=float, default=None)
+    parser.add_argument('--ema_decay', type=float, default=None)
     return parser.parse_args(argv)
 
 
@@ -93,6 +99,7 @@ def main(argv=None):
         share = torch.utils.data.Subset(held_out, range(rank, len(held_out), max(world, 1)))
         val_loader = DataLoader(share, batch_size=args.batch, shuffle=False, num_workers=0)
     # (--resume keeps this command line: give the run's own arguments again)
+    clip_grad_norm, ema_decay = args.clip_grad_norm, args.ema_decay     # of THIS command line, like --resume
     resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume is not None else None
     ckpt = {}
     if args.ckpt is not None:
@@ -102,7 +109,8 @@ def main(argv=None):
     if 'model' in ckpt:
         model.load_state_dict(ckpt['model'])
     model = model.to(device).train()
-    trainer = vqvae2_amd.Stage2Trainer(model, args.hier, lr=args.lr, sched=args.sched, n_iter=len(loader) * args.epoch)
+    trainer = vqvae2_amd.Stage2Trainer(model, args.hier, lr=args.lr, sched=args.sched, n_iter=len(loader) * args.epoch,
+                                       clip_grad_norm=clip_grad_norm, ema_decay=ema_decay)
     first_epoch = 0
     if resume is not None:
         trainer.load_state_dict(resume['trainer'] if 'trainer' in resume else resume)
@@ -117,21 +125,32 @@ def main(argv=None):
             r = trainer.step(top.to(device), bottom.to(device) if args.hier == 'bottom' else None)
             steps += 1
             if primary:
-                print(f"epoch: {i + 1}; loss: {r['loss'].item():.5f}; acc: {r['accuracy'].item():.5f}; lr: {r['lr']:.5f}")
+                gnorm = f"; gnorm: {r['grad_norm'].item():.5f}" if 'grad_norm' in r else ''
+                print(f"epoch: {i + 1}; loss: {r['loss'].item():.5f}; acc: {r['accuracy'].item():.5f}; lr: {r['lr']:.5f}{gnorm}")
             if val_loader is not None and steps % eval_every == 0:
                 held = trainer.evaluate(val_loader)
                 if primary:
                     print(f"step: {steps}; held-out {vqvae2_amd.PriorEvaluator.summary(held)}")
+                if ema_decay is not None:
+                    with trainer.averaged_weights():
+                        held = trainer.evaluate(val_loader)
+                    if primary:
+                        print(f"step: {steps}; held-out (averaged weights) {vqvae2_amd.PriorEvaluator.summary(held)}")
             if args.max_steps and steps >= args.max_steps:
                 break
         done = bool(args.max_steps and steps >= args.max_steps)
         if primary and (i % 10 == 0 or i >= args.epoch - 1 or done):
             tag = f'{args.hier}_{str(i + 1).zfill(3)}.pt'
             torch.save({'model': model.state_dict(), 'args': args}, os.path.join(args.ckpt_dir, 'pixelsnail_' + tag))
+            if ema_decay is not None:
+                torch.save({'model': trainer.averaged_state_dict(), 'args': args},
+                           os.path.join(args.ckpt_dir, 'pixelsnail_' + tag[:-3] + '_ema.pt'))
             torch.save({'trainer': trainer.state_dict(), 'args': args, 'epoch': i + 1},
                        os.path.join(args.ckpt_dir, 'trainer_' + tag))
         if done:
             break
+    if primary and clip_grad_norm is not None:
+        print(f"skipped steps (non-finite gradient norm): {trainer.skipped_steps()}")
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         dist_fn.synchronize()
         torch.distributed.destroy_process_group()

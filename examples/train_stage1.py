@@ -23,6 +23,11 @@ Stage1Trainer.evaluate -- its batches dealt over the ranks, totals summed -- and
 and used codes of both levels.  --sample_every N: rank 0 writes the reference's sample grid (train_vqvae.py:120-139:
 the first min(batch, 25) inputs over their reconstructions, nrow = len(sample)) to sample/{epoch+1:05d}_{i:05d}.png.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_stage1.py ...
+
+--clip_grad_norm X clips the global gradient norm to X on the device (the printed line gains gnorm:, the norm before
+clipping; a step whose norm is not finite is skipped and counted, the count is printed at the end).  --ema_decay D keeps
+Polyak-averaged weights: every save also writes vqvae_<NNN>_ema.pt, the reference's file with the averaged weights (and the
+codebooks as they are), and the held-out line is printed for both sets of weights.
 """
 import argparse
 import glob
@@ -105,7 +110,7 @@ def print_validation(epoch, i, r):
           + (f"; psnr: {r['psnr']:.2f} dB; ssim: {r['ssim']:.4f}" if "psnr" in r else ""), flush=True)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n_gpu", type=int, default=1)            # kept for CLI parity; world size comes from the launcher
     ap.add_argument("--dist_url", default="env://")
@@ -125,9 +130,16 @@ def main():
     ap.add_argument("--sample_every", type=int, default=0, help="steps between sample grids under sample/ (0 = never)")
     ap.add_argument("--image_metrics", action="store_true",
                     help="with --val_path: also PSNR and SSIM of the 8-bit reconstructions of the held-out set")
-    args = ap.parse_args()
+    ap.add_argument("--clip_grad_norm", type=float, default=None, help="clip the global gradient norm to this value")
+    ap.add_argument("--ema_decay", type=float, default=None, help="decay of the Polyak-averaged weights")
+    args = ap.parse_args(argv)
     if args.eval_every and not args.val_path:
         raise SystemExit("--eval_every needs --val_path")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     rank, local_rank, world = dist.bringup("nccl")             # launch.py:52-92 (RCCL group + device binding)
     device = torch.device("cuda", local_rank)
@@ -141,7 +153,7 @@ def main():
         if (u8 or args.sample_every or args.eval_every) else None
     val_plan = plan_val_batches(args, rank, world) if args.eval_every else None
     trainer = vqvae2_amd.Stage1Trainer(model, lr=args.lr, sched=args.sched, n_iter=len(plan) * args.epoch,
-                                       normalizer=normalizer)
+                                       normalizer=normalizer, clip_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay)
     first_epoch = 0
     if args.resume:                                            # train_vqvae.py:173-182
         sd = torch.load(args.resume, map_location=device, weights_only=True)
@@ -164,6 +176,12 @@ def main():
                 r = evaluate(val_batches(args, val_plan, device))
                 if dist.is_primary():
                     print_validation(epoch, i, r)
+                if args.ema_decay is not None:
+                    with trainer.averaged_weights():
+                        r = evaluate(val_batches(args, val_plan, device))
+                    if dist.is_primary():
+                        print("averaged weights -- ", end="")
+                        print_validation(epoch, i, r)
             if args.sample_every and i % args.sample_every == 0 and dist.is_primary():   # train_vqvae.py:120-139
                 grid = trainer.sample_grid(img[:min(img.shape[0], 25)].contiguous())
                 os.makedirs("sample", exist_ok=True)
@@ -174,15 +192,19 @@ def main():
                 if dist.is_primary():
                     lr = trainer.optimizer.param_groups[0]["lr"]
                     print(f"epoch: {epoch + 1}; it {i}; mse: {float(out['recon']):.5f}; "
-                          f"latent: {float(out['latent']):.3f}; avg mse: {float(agg[0] / agg[1]):.5f}; lr: {lr:.5f}",
-                          flush=True)
+                          f"latent: {float(out['latent']):.3f}; avg mse: {float(agg[0] / agg[1]):.5f}; lr: {lr:.5f}"
+                          + (f"; gnorm: {float(out['grad_norm']):.5f}" if "grad_norm" in out else ""), flush=True)
         if dist.is_primary() and (epoch % 10 == 0 or epoch == args.epoch - 1):   # train_vqvae.py:205-206
             os.makedirs(args.out, exist_ok=True)
             tag = str(epoch + 1).zfill(3)
             torch.save(model.state_dict(), os.path.join(args.out, f"vqvae_{tag}.pt"))       # the reference's file
+            if args.ema_decay is not None:
+                torch.save(trainer.averaged_state_dict(), os.path.join(args.out, f"vqvae_{tag}_ema.pt"))
             full = trainer.state_dict()
             full["epoch"] = epoch + 1
             torch.save(full, os.path.join(args.out, f"trainer_{tag}.pt"))                   # exact-resume extras
+    if dist.is_primary() and args.clip_grad_norm is not None:
+        print(f"skipped steps (non-finite gradient norm): {trainer.skipped_steps()}")
     if feed is not None:
         feed.close()
     dist.synchronize()

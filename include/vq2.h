@@ -57,11 +57,13 @@ typedef void *vq2_stream_t;
  * points; vq2_conv_dgrad takes the flags argument and vq2_conv_dgrad_ex is gone; vq2_convg_fwd_row and its workspace query
  * renamed vq2_conv_fwd_row / vq2_conv_fwd_row_workspace_bytes on vq2_conv_desc; see INTEGRATION.md "ABI history");
  * revision 14: an addition only -- vq2_sample_filtered, the draw from a top-k / nucleus truncated support with its log-probability;
- * revision 15: additions only -- vq2_prior_eval_rows and vq2_prior_eval_accumulate, the held-out evaluation of the stage-2 prior.
+ * revision 15: additions only -- vq2_prior_eval_rows and vq2_prior_eval_accumulate, the held-out evaluation of the stage-2 prior;
+ * revision 16: additions only -- vq2_grad_norm with its workspace query and vq2_adam_step_ex (global-norm clipping, skipped
+ * steps, averaged weights).
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 15
+#define VQ2_API_VERSION 16
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -345,6 +347,28 @@ int vq2_stage1_loss(const float *a, const float *b, int64_t numel, int64_t denom
                     float *recon, float *total, float *grad, void *ws, size_t ws_bytes, vq2_stream_t stream);
 int vq2_adam_step(float *p, const float *g, float *m, float *v, int64_t n, double lr, double beta1, double beta2,
                   double eps, int32_t step, double grad_scale, vq2_stream_t stream);
+/* Global-norm clipping, skipped steps and averaged weights: a second step tail next to vq2_adam_step, over the same flat
+ * arenas.  ctl (device, 4 floats, 16-byte aligned) = [norm, coef, skip, skipped_total]; nothing comes back to the host.
+ * Both entry points use 16-byte accesses: n % 4 == 0 and 16-byte aligned pointers.  That, n <= 0, a null pointer (where
+ * none is allowed), max_norm <= 0 or NaN and avg_decay outside [0, 1) are VQ2_ERR_INVALID before any launch.
+ * vq2_grad_norm: norm = sqrt(sum_i (g[i] * grad_scale)^2): the product in fp32 exactly as vq2_adam_step forms it, squares
+ *              and sums in fp64.  One fixed summation order (a block count that depends on n alone, per-block partials in
+ *              ws, folded in index order by one wave; no atomics): two calls on the same buffer agree bit for bit.
+ *              coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), evaluated in fp64, stored as fp32:
+ *              exactly 1 for max_norm = +inf.  A non-finite norm gives coef = 0, skip = 1 and skipped_total += 1 (read,
+ *              modified and written by one thread); otherwise skip = 0 and skipped_total is left alone.  Two launches.
+ *              ws >= vq2_grad_norm_workspace_bytes(n), 16-byte aligned.
+ * vq2_adam_step_ex: vq2_adam_step's arithmetic, operation for operation, on (g[i] * grad_scale) * coef with
+ *              coef = ctl ? ctl[1] : 1.  Multiplying by 1.0f is exact: with ctl == NULL or coef == 1, and p_avg == NULL, p, m
+ *              and v come out bit for bit as from vq2_adam_step.  p_avg (may be NULL): p_avg[i] += w * (p_new - p_avg[i])
+ *              in the same pass, w = (float)(1 - avg_decay) rounded once on the host.  ctl[2] != 0: nothing is written.
+ *              One launch. */
+size_t vq2_grad_norm_workspace_bytes(int64_t n);
+int vq2_grad_norm(const float *g, int64_t n, double grad_scale, double max_norm, float *ctl, void *ws, size_t ws_bytes,
+                  vq2_stream_t stream);
+int vq2_adam_step_ex(float *p, const float *g, float *m, float *v, float *p_avg, int64_t n, double lr, double beta1,
+                     double beta2, double eps, int32_t step, double grad_scale, const float *ctl, double avg_decay,
+                     vq2_stream_t stream);
 /* dst = a + alpha * b (flat): the 0.25 * latent_loss accumulation and small host-free scalar math */
 int vq2_axpby(const float *a, const float *b, float alpha, float *dst, int64_t n, vq2_stream_t stream);
 /* dst = src * scalar[0] * alpha, scalar read on the device (upstream gradient of a loss) */

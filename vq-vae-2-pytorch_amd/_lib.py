@@ -111,6 +111,9 @@ def _load():
         "vq2_mse_fwd_bwd": (C.c_int, [P, P, I64, I64, P, P, P, P, SZ, P]),
         "vq2_stage1_loss": (C.c_int, [P, P, I64, I64, P, F, P, P, P, P, SZ, P]),
         "vq2_adam_step": (C.c_int, [P, P, P, P, I64, D, D, D, D, I32, D, P]),
+        "vq2_grad_norm_workspace_bytes": (SZ, [I64]),
+        "vq2_grad_norm": (C.c_int, [P, I64, D, D, P, P, SZ, P]),
+        "vq2_adam_step_ex": (C.c_int, [P, P, P, P, P, I64, D, D, D, D, I32, D, P, D, P]),
         "vq2_axpby": (C.c_int, [P, P, F, P, I64, P]),
         "vq2_scale": (C.c_int, [P, P, F, P, I64, P]),
         "vq2_causal_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P, P]),

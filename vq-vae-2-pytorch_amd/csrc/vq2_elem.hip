@@ -162,6 +162,96 @@ __global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, 
     }
 }
 
+// ------------------------------------------------------------------ global gradient norm, clipped / averaged Adam
+// The second path of the step tail, taken only on request (FusedAdam(clip_grad_norm=, ema_decay=)); adam_kernel above
+// stays the default.  ctl (device, 4 floats) = [norm, coef, skip, skipped_total].
+//   grad_norm_partial_kernel  part[b] = sum over block b's float4s of (g[i] * gscale)^2: the product in fp32 exactly as
+//                             adam_kernel forms gi, squares and sums in fp64.  GN_BLOCKS caps the grid, so the block count
+//                             is a function of n alone; a thread adds its elements in index order, a wave folds by xor
+//                             shuffles, the four waves in wave order: no atomics, one order.
+//   grad_norm_final_kernel    one wave: lane l adds its contiguous run of partials in index order, lane 0 adds the 64 lane
+//                             sums in lane order; the same lane writes all of ctl.
+//   adam_ex_kernel            adam_kernel's operations on gi = (g[i] * gscale) * coef, four elements per 16-byte access;
+//                             AVG: p_avg += wavg * (p_new - p_avg) in the same pass.  ctl[2] != 0: every thread returns
+//                             before its first store.
+constexpr int GN_BLOCKS = 1024;
+constexpr int ADAM_EX_BLOCKS = 2048;     // 8 waves on every SIMD of 256 CUs: one resident round
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float4 *__restrict__ g, int64_t n4, float gscale,
+                                                                double *__restrict__ part) {
+    __shared__ double wsum[4];
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 x = g[i];
+        const float a = x.x * gscale, b = x.y * gscale, c = x.z * gscale, d = x.w * gscale;
+        s += (double)a * (double)a; s += (double)b * (double)b; s += (double)c * (double)c; s += (double)d * (double)d;
+    }
+    s = wave_sum_f64(s);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+__global__ __launch_bounds__(64) void grad_norm_final_kernel(const double *__restrict__ part, int nparts, double max_norm,
+                                                             float *__restrict__ ctl) {
+    __shared__ double lane_sum[64];
+    const int run = (nparts + 63) / 64, lo = threadIdx.x * run, hi = min(lo + run, nparts);
+    double s = 0.0;
+    for (int i = lo; i < hi; ++i) s += part[i];
+    lane_sum[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double total = 0.0;
+    for (int l = 0; l < 64; ++l) total += lane_sum[l];
+    const double norm = sqrt(total);
+    const bool finite = norm - norm == 0.0;             // false for inf and NaN
+    // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
+    const double coef = finite ? fmin(1.0, max_norm / (norm + 1e-6)) : 0.0;
+    ctl[0] = (float)norm;
+    ctl[1] = (float)coef;
+    ctl[2] = finite ? 0.f : 1.f;
+    if (!finite) ctl[3] = ctl[3] + 1.f;
+}
+
+template <bool AVG>
+__global__ __launch_bounds__(256) void adam_ex_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
+                                                      float4 *__restrict__ m, float4 *__restrict__ v,
+                                                      float4 *__restrict__ p_avg, int64_t n4, float w1, float b2, float w2,
+                                                      float bc2_sqrt, float eps, float neg_step, float gscale,
+                                                      const float *__restrict__ ctl, float wavg) {
+    float coef = 1.f;
+    if (ctl) {
+        if (ctl[2] != 0.f) return;                      // a non-finite gradient norm: the step is skipped whole
+        coef = ctl[1];
+    }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 g4 = g[i];
+        float4 p4 = p[i], m4 = m[i], v4 = v[i], a4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (AVG) a4 = p_avg[i];
+        const float gs[4] = {g4.x, g4.y, g4.z, g4.w};
+        float *ps = &p4.x, *ms = &m4.x, *vs = &v4.x, *as = &a4.x;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float gi = (gs[k] * gscale) * coef;
+            float mi = ms[k], vi = vs[k];
+            mi = mi + w1 * (gi - mi);
+            vi = vi * b2 + (w2 * gi) * gi;
+            const float denom = sqrtf(vi) / bc2_sqrt + eps;
+            const float pi = ps[k] + neg_step * (mi / denom);
+            ps[k] = pi; ms[k] = mi; vs[k] = vi;
+            if (AVG) as[k] = as[k] + wavg * (pi - as[k]);
+        }
+        p[i] = p4; m[i] = m4; v[i] = v4;
+        if (AVG) p_avg[i] = a4;
+    }
+}
+
 __global__ void axpby_kernel(const float *__restrict__ a, const float *__restrict__ b, float alpha,
                              float *__restrict__ dst, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -401,6 +491,50 @@ extern "C" int vq2_adam_step(float *p, const float *g, float *m, float *v, int64
                        (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)bc2_sqrt, (float)eps,
                        (float)(-step_size), (float)grad_scale);
     return check_launch("adam_kernel");
+}
+
+extern "C" size_t vq2_grad_norm_workspace_bytes(int64_t n) { return n > 0 ? GN_BLOCKS * sizeof(double) : 0; }
+
+extern "C" int vq2_grad_norm(const float *g, int64_t n, double grad_scale, double max_norm, float *ctl, void *ws,
+                             size_t ws_bytes, vq2_stream_t stream) {
+    VQ2_REQUIRE(g && ctl && ws, "grad_norm: null pointer");
+    VQ2_REQUIRE(n > 0 && n % 4 == 0, "grad_norm: n = %lld must be a positive multiple of 4", (long long)n);
+    VQ2_REQUIRE(aligned16(g) && aligned16(ctl) && aligned16(ws), "grad_norm: pointers must be 16-byte aligned");
+    VQ2_REQUIRE(max_norm > 0.0, "grad_norm: max_norm must be positive (+inf: measure only), got %g", max_norm);  // NaN fails too
+    VQ2_REQUIRE(ws_bytes >= GN_BLOCKS * sizeof(double), "grad_norm: workspace too small");
+    const int blocks = grid_for(n / 4, GN_BLOCKS);
+    hipStream_t s = to_stream(stream);
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4 *>(g), n / 4,
+                       (float)grad_scale, static_cast<double *>(ws));
+    if (int e = check_launch("grad_norm_partial_kernel")) return e;
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(64), 0, s, static_cast<const double *>(ws), blocks, max_norm, ctl);
+    return check_launch("grad_norm_final_kernel");
+}
+
+extern "C" int vq2_adam_step_ex(float *p, const float *g, float *m, float *v, float *p_avg, int64_t n, double lr,
+                                double beta1, double beta2, double eps, int32_t step, double grad_scale, const float *ctl,
+                                double avg_decay, vq2_stream_t stream) {
+    VQ2_REQUIRE(p && g && m && v && step >= 1, "adam_ex: bad arguments");
+    VQ2_REQUIRE(n > 0 && n % 4 == 0, "adam_ex: n = %lld must be a positive multiple of 4", (long long)n);
+    VQ2_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(p_avg),
+                "adam_ex: pointers must be 16-byte aligned");
+    VQ2_REQUIRE(avg_decay >= 0.0 && avg_decay < 1.0, "adam_ex: avg_decay must lie in [0, 1), got %g", avg_decay);  // NaN fails too
+    // scalar prep as in vq2_adam_step
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    const double step_size = lr / bc1;
+    const double bc2_sqrt = sqrt(bc2);
+    hipStream_t s = to_stream(stream);
+    const dim3 grid(grid_for(n / 4, ADAM_EX_BLOCKS)), block(256);
+#define VQ2_ADAM_EX(AVG)                                                                                                  \
+    hipLaunchKernelGGL(adam_ex_kernel<AVG>, grid, block, 0, s, reinterpret_cast<float4 *>(p),                             \
+                       reinterpret_cast<const float4 *>(g), reinterpret_cast<float4 *>(m), reinterpret_cast<float4 *>(v), \
+                       reinterpret_cast<float4 *>(p_avg), n / 4, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),  \
+                       (float)bc2_sqrt, (float)eps, (float)(-step_size), (float)grad_scale, ctl, (float)(1.0 - avg_decay))
+    if (p_avg) VQ2_ADAM_EX(true);
+    else VQ2_ADAM_EX(false);
+#undef VQ2_ADAM_EX
+    return check_launch("adam_ex_kernel");
 }
 
 extern "C" int vq2_axpby(const float *a, const float *b, float alpha, float *dst, int64_t n, vq2_stream_t stream) {

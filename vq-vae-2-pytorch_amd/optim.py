@@ -86,16 +86,51 @@ class ParamArena:
 
 class FusedAdam(torch.optim.Optimizer):
     """Adam over libvq2's vq2_adam_step.  With a ParamArena whose gradients all landed in the flat
-    buffer the whole update is one launch; otherwise one launch per parameter tensor."""
+    buffer the whole update is one launch; otherwise one launch per parameter tensor.
 
-    def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, arena=None):
+    clip_grad_norm / ema_decay (arena path only; both None: exactly the launch above and no further buffer):
+      clip_grad_norm  max_norm of torch.nn.utils.clip_grad_norm_ over the arena's parameter gradients times grad_scale
+                      (float('inf'): measure, never clip).  vq2_grad_norm leaves [norm, coef, skip, skipped_total] in
+                      self.ctl (device, float32 [4]) and vq2_adam_step_ex applies coef.  A non-finite norm skips the step:
+                      parameters, moments and average stay as they were and skipped_total goes up by one.  The host step
+                      count _t (the bias correction's exponent) advances on every ATTEMPTED step, as a scheduler does, so
+                      a skipped step leaves the state untouched but still counts.
+      ema_decay       d in [0, 1): self._avg (a flat buffer laid out like the arena) follows the parameters,
+                      avg += (1 - d) * (p_new - avg), in the Adam launch.  It starts as a copy of the parameters, taken
+                      by init_average() (a trainer calls it once its construction, initial broadcast included, is done)
+                      or else at the first step.  Alone it runs no norm launch."""
+
+    def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, arena=None, clip_grad_norm=None, ema_decay=None):
+        if arena is None and (clip_grad_norm is not None or ema_decay is not None):
+            raise ValueError("FusedAdam: clip_grad_norm and ema_decay need the arena path (arena=ParamArena(...))")
+        if clip_grad_norm is not None and not float(clip_grad_norm) > 0:        # NaN fails too
+            raise ValueError(f"FusedAdam: clip_grad_norm must be positive, got {clip_grad_norm!r}")
+        if ema_decay is not None and not 0 <= float(ema_decay) < 1:
+            raise ValueError(f"FusedAdam: ema_decay must lie in [0, 1), got {ema_decay!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self.arena = arena
         self.grad_scale = 1.0  # 1/world_size when gradients were SUM-all-reduced
         self._t = 0
+        self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self._avg = None
         if arena is not None:
-            self._m = torch.zeros(arena.n, device=arena.flat_p.device)
-            self._v = torch.zeros(arena.n, device=arena.flat_p.device)
+            dev = arena.flat_p.device
+            self._m = torch.zeros(arena.n, device=dev)
+            self._v = torch.zeros(arena.n, device=dev)
+            if self.clip_grad_norm is not None or self.ema_decay is not None:
+                self.ctl = torch.zeros(4, device=dev, dtype=torch.float32)
+            if self.clip_grad_norm is not None:
+                self._norm_ws_bytes = int(lib.vq2_grad_norm_workspace_bytes(arena.n))
+                self._norm_ws = torch.empty(self._norm_ws_bytes // 8, device=dev, dtype=torch.float64)
+
+    @torch.no_grad()
+    def init_average(self):
+        """Start the average from the parameters as they are now."""
+        if self.ema_decay is not None:
+            if self._avg is None:
+                self._avg = torch.empty_like(self.arena.flat_p)
+            self._avg.copy_(self.arena.flat_p)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -113,8 +148,20 @@ class FusedAdam(torch.optim.Optimizer):
                                    "gradient per step (zero_grad() before each backward)")
             self._t += 1
             a = self.arena
-            check(lib.vq2_adam_step(ops._p(a.flat_p), ops._p(a.gp), ops._p(self._m), ops._p(self._v), a.n,
-                                    lr, b1, b2, eps, self._t, self.grad_scale, s), "adam_step")
+            clip, ema = self.clip_grad_norm, self.ema_decay
+            if clip is None and ema is None:
+                check(lib.vq2_adam_step(ops._p(a.flat_p), ops._p(a.gp), ops._p(self._m), ops._p(self._v), a.n,
+                                        lr, b1, b2, eps, self._t, self.grad_scale, s), "adam_step")
+            else:
+                if ema is not None and self._avg is None:
+                    self.init_average()
+                if clip is not None:
+                    check(lib.vq2_grad_norm(ops._p(a.gp), a.n, self.grad_scale, clip, ops._p(self.ctl),
+                                            ops._p(self._norm_ws), self._norm_ws_bytes, s), "grad_norm")
+                check(lib.vq2_adam_step_ex(ops._p(a.flat_p), ops._p(a.gp), ops._p(self._m), ops._p(self._v),
+                                           None if ema is None else ops._p(self._avg), a.n, lr, b1, b2, eps, self._t,
+                                           self.grad_scale, None if clip is None else ops._p(self.ctl),
+                                           0.0 if ema is None else ema, s), "adam_step_ex")
         else:
             for group in self.param_groups:
                 lr, (b1, b2), eps = group["lr"], group["betas"], group["eps"]

@@ -10,6 +10,7 @@ to the communicator from backward hooks, the all-reduce of whatever did not go o
 trainer adds its own step, what "finish this slice of the gradient buffer" means, and which derived state to drop when
 the parameters are overwritten behind autograd's back.
 """
+import contextlib
 import os
 from collections import namedtuple
 
@@ -142,30 +143,108 @@ class _ArenaTrainer:
                 self.comm.all_reduce(self.arena.flat_g[lo:hi])
         torch.cuda.current_stream().wait_stream(self.comm_stream)
 
+    # ------------------------------------------------------------------ clipping, skipped steps, averaged weights
+    def _finish_construction(self):
+        """Last line of a constructor: the average starts from the parameters every rank now holds."""
+        self.optimizer.init_average()
+
+    def _clip_result(self, out):
+        """step()'s result gains the pre-clip norm and the coefficient (0-dim device views of optimizer.ctl) when clipping
+        is on; otherwise it keeps the keys it has."""
+        if self.optimizer.clip_grad_norm is not None:
+            out["grad_norm"], out["clip_coef"] = self.optimizer.ctl[0], self.optimizer.ctl[1]
+        return out
+
+    def skipped_steps(self):
+        """How many steps a non-finite gradient norm has skipped so far: the one host read of optimizer.ctl."""
+        ctl = getattr(self.optimizer, "ctl", None)
+        return 0 if ctl is None else int(ctl[3].item())
+
+    def _need_average(self, what):
+        self._need_arena(what)
+        if self.optimizer.ema_decay is None:
+            raise RuntimeError(f"{type(self).__name__}.{what} needs averaged weights (ema_decay=...)")
+
+    def _weights_replaced(self):
+        """The whole parameter arena was rewritten in place."""
+        ops.touch_weights(self.arena.params)
+        self._params_overwritten()
+
+    def averaged_state_dict(self):
+        """model.state_dict() with every arena parameter replaced by its averaged value; buffers (stage 1's codebooks among
+        them) and parameters outside the arena as they are.  Loads wherever the reference's checkpoints load."""
+        self._need_average("averaged_state_dict")
+        a, avg = self.arena, self.optimizer._avg
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for name, p in self.model.named_parameters():
+            if id(p) in a.offset and name in sd:
+                off = a.offset[id(p)]
+                sd[name] = avg[off:off + p.numel()].view(p.shape).clone()
+        return sd
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """`with trainer.averaged_weights(): trainer.evaluate(...)`: inside, the model's parameters are the averaged ones.
+        The contents of the parameter arena and of the average are exchanged on entry and back on exit (also when the body
+        raises); no generator is drawn from, and the steps after the block are bit for bit those of a run that never
+        entered.  A forward pass may write the arena (a 'causal' convolution zeroes the masked taps of its weight_v in
+        place), so the average goes back from a copy kept aside for the block, not from the arena.  Do not call step()
+        inside."""
+        self._need_average("averaged_weights")
+        p, avg = self.arena.flat_p, self.optimizer._avg
+        with torch.no_grad():
+            kept = avg.clone()
+            avg.copy_(p)
+            p.copy_(kept)
+        self._weights_replaced()
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                p.copy_(avg)
+                avg.copy_(kept)
+            self._weights_replaced()
+
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self):
         """"model" is exactly what the reference saves (train_vqvae.py:205-206, train_pixelsnail.py:150-153:
         model.state_dict(), loadable by extract_code.py / sample.py); the rest is what the reference lacks for an exact
-        resume: Adam moments and step count, learning rate / betas, the schedule position."""
+        resume: Adam moments and step count, learning rate / betas, the schedule position.  With ema_decay also "avg" (laid
+        out as the moments are) and "ema_decay"; with clip_grad_norm also "clip_grad_norm" and "skipped"."""
         self._need_arena("state_dict")
-        group = self.optimizer.param_groups[0]
-        return {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-                # Adam moments in REGISTRATION order (the arena's internal order is an implementation detail)
-                "adam_m": self.arena.canonical(self.optimizer._m), "adam_v": self.arena.canonical(self.optimizer._v),
-                "adam_t": self.optimizer._t,
-                "lr": group["lr"], "betas": tuple(group["betas"]),
-                "scheduler": None if self.scheduler is None else self.scheduler.state_dict()}
+        opt = self.optimizer
+        group = opt.param_groups[0]
+        sd = {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+              # Adam moments in REGISTRATION order (the arena's internal order is an implementation detail)
+              "adam_m": self.arena.canonical(opt._m), "adam_v": self.arena.canonical(opt._v),
+              "adam_t": opt._t,
+              "lr": group["lr"], "betas": tuple(group["betas"]),
+              "scheduler": None if self.scheduler is None else self.scheduler.state_dict()}
+        if opt.ema_decay is not None:
+            sd["avg"], sd["ema_decay"] = self.arena.canonical(opt._avg), opt.ema_decay
+        if opt.clip_grad_norm is not None:
+            sd["clip_grad_norm"], sd["skipped"] = opt.clip_grad_norm, self.skipped_steps()
+        return sd
 
     def load_state_dict(self, sd):
         """Inverse of state_dict(); also accepts what split_checkpoint() calls not full (the reference's files):
-        optimizer state then starts fresh.  Raises before it changes anything."""
+        optimizer state then starts fresh.  Averaged weights: a checkpoint's "avg" goes into a trainer with ema_decay; a
+        checkpoint without one starts the average from the loaded weights; a checkpoint with one and a trainer without
+        ema_decay disagree.  Raises before it changes anything."""
         self._need_arena("load_state_dict")
         who = f"{type(self).__name__}.load_state_dict"
         model_sd, full = split_checkpoint(sd)
+        opt = self.optimizer
+        n_real = sum(p.numel() for p in self.arena.params)
         if full:
             if (self.scheduler is None) != (sd.get("scheduler") is None):
                 raise RuntimeError(f"{who}: checkpoint and trainer disagree about --sched")
-            n, n_real = sd["adam_m"].numel(), sum(p.numel() for p in self.arena.params)
+            if "avg" in sd and opt.ema_decay is None:
+                raise RuntimeError(f"{who}: the checkpoint carries averaged weights and the trainer was built without "
+                                   "--ema_decay")
+            if "avg" in sd and sd["avg"].numel() != n_real:
+                raise RuntimeError(f"{who}: averaged weights belong to a different model")
+            n = sd["adam_m"].numel()
             if n != n_real and n == self.optimizer._m.numel():
                 # a round-2 checkpoint: moments in that arena's padded registration order
                 raise RuntimeError(f"{who}: optimizer state uses the pre-round-3 padded layout; "
@@ -183,6 +262,13 @@ class _ArenaTrainer:
                 group["lr"], group["betas"] = sd["lr"], tuple(sd["betas"])
             if self.scheduler is not None:
                 self.scheduler.load_state_dict(sd["scheduler"])
+            if opt.clip_grad_norm is not None:
+                opt.ctl[3] = float(sd.get("skipped", 0))
+        if opt.ema_decay is not None:
+            if full and "avg" in sd:
+                self.arena.from_canonical(sd["avg"].to(opt._avg.device), opt._avg)
+            else:
+                opt.init_average()
         self._params_overwritten()
 
 
@@ -197,7 +283,8 @@ class Stage1Trainer(_ArenaTrainer):
     normalizer: a data.ImageNormalizer; step() then also takes uint8 image batches on the device (the loader's
     ToTensor + Normalize + CenterCrop run as one kernel inside the step, train_vqvae.py:149-155)."""
 
-    def __init__(self, model, lr=3e-4, sched=None, n_iter=None, betas=(0.9, 0.999), eps=1e-8, normalizer=None):
+    def __init__(self, model, lr=3e-4, sched=None, n_iter=None, betas=(0.9, 0.999), eps=1e-8, normalizer=None,
+                 clip_grad_norm=None, ema_decay=None):
         self.model = model
         self.normalizer = normalizer
         live = model.live_parameters() if hasattr(model, "live_parameters") else list(model.parameters())
@@ -213,7 +300,8 @@ class Stage1Trainer(_ArenaTrainer):
             n = ops.vq_stats_numel(q.n_embed, q.dim)   # a multiple of 4: every quantizer's slice stays 16-byte aligned
             q.deferred_stats = self.arena.extra[off:off + n]
             off += n
-        self.optimizer = FusedAdam(live, lr=lr, betas=betas, eps=eps, arena=self.arena)
+        self.optimizer = FusedAdam(live, lr=lr, betas=betas, eps=eps, arena=self.arena, clip_grad_norm=clip_grad_norm,
+                                   ema_decay=ema_decay)
         self.scheduler = None
         if sched == "cycle":  # train_vqvae.py:188-195
             self.scheduler = CycleScheduler(self.optimizer, lr, n_iter=n_iter, momentum=None, warmup_proportion=0.05)
@@ -266,10 +354,15 @@ class Stage1Trainer(_ArenaTrainer):
             if self.dp:
                 first = enc_t.blocks[0]
                 self._send_when_reported(middle, (first.weight, first.bias), self._flush_slabs)
+        self._finish_construction()
 
     def _params_overwritten(self):
         for q in self.quantizers:       # anything a Quantize derived from its OLD codebook is stale now
             q.invalidate_prepared()
+
+    def _weights_replaced(self):
+        super()._weights_replaced()
+        self.pack_plan.run()            # the packed panels are made from the weights as they were
 
     def _flush_slabs(self):
         """Finish a slice: reduce the split-K slabs produced so far into the arena, on the side stream."""
@@ -330,7 +423,7 @@ class Stage1Trainer(_ArenaTrainer):
             self.scheduler.step()
         self.optimizer.step()
         self.pack_plan.run()
-        out = {"loss": loss.detach(), "recon": recon, "latent": latent}
+        out = self._clip_result({"loss": loss.detach(), "recon": recon, "latent": latent})
         if return_dec:
             d = dec.detach()
             out["dec"] = ops.from_nhwc(d, channels) if hasattr(model, "forward_nhwc") else d
@@ -399,7 +492,7 @@ class Stage2Trainer(_ArenaTrainer):
     back-propagates.  VQ2_DP_FORCE=1 takes this path whenever a process group exists, also at world size 1.  Dropout seeds
     come from each rank's own torch generator; the trainer does not touch them."""
 
-    def __init__(self, model, hier="top", lr=3e-4, sched=None, n_iter=None, arena=True):
+    def __init__(self, model, hier="top", lr=3e-4, sched=None, n_iter=None, arena=True, clip_grad_norm=None, ema_decay=None):
         if hier not in ("top", "bottom"):
             raise ValueError(f"Stage2Trainer: hier must be 'top' or 'bottom', got {hier!r}")
         if sched not in (None, "cycle"):
@@ -408,13 +501,14 @@ class Stage2Trainer(_ArenaTrainer):
         self.arena = self.plan = None
         self.plan_info = {"entries": 0, "per_layer": len(ops.WeightNormPlan.layers(model)), "per_layer_names": []}
         if arena:
-            self._init_arena(lr)
+            self._init_arena(lr, clip_grad_norm, ema_decay)
         else:
             if dist_fn.get_world_size() > 1:
                 raise RuntimeError("Stage2Trainer: data-parallel training needs the arena path (arena=True)")
             self.world, self.dp = 1, False
             self.buckets, self.bucket_bytes, self.early_buckets = [], {}, 0
-            self.optimizer = FusedAdam(model.parameters(), lr=lr)
+            # (FusedAdam refuses clip_grad_norm / ema_decay without an arena)
+            self.optimizer = FusedAdam(model.parameters(), lr=lr, clip_grad_norm=clip_grad_norm, ema_decay=ema_decay)
         self.scheduler = None
         if sched == "cycle":
             self.scheduler = CycleScheduler(self.optimizer, lr, n_iter=n_iter, momentum=None)
@@ -430,7 +524,7 @@ class Stage2Trainer(_ArenaTrainer):
             early.append(model.out)
         return early
 
-    def _init_arena(self, lr):
+    def _init_arena(self, lr, clip_grad_norm=None, ema_decay=None):
         model = self.model
         live = [p for p in model.parameters() if p.requires_grad]
         # registration order is horizontal vertical blocks[...] cond_resnet out; with the early modules at the end the
@@ -439,7 +533,7 @@ class Stage2Trainer(_ArenaTrainer):
         if len(early) == len(live):
             early = []
         self.arena = a = ParamArena(live, last=early)
-        self.optimizer = FusedAdam(live, lr=lr, arena=a)
+        self.optimizer = FusedAdam(live, lr=lr, arena=a, clip_grad_norm=clip_grad_norm, ema_decay=ema_decay)
         self.plan = ops.WeightNormPlan(model, a)
         self.plan_info = {"entries": self.plan.n, "per_layer": len(self.plan.skipped), "per_layer_names": list(self.plan.skipped),
                           "w_floats": self.plan.w.numel()}
@@ -451,6 +545,7 @@ class Stage2Trainer(_ArenaTrainer):
         self._early_entries = (self.plan.first_entry_at(lo), self.plan.first_entry_at(total))
         if self.dp and len(self.buckets) == 2:
             self._send_when_reported(self.buckets[0], self.buckets[0].params, self._finish_early)
+        self._finish_construction()
 
     def _params_overwritten(self):
         self.plan.invalidate()
@@ -499,7 +594,7 @@ class Stage2Trainer(_ArenaTrainer):
         if self.scheduler is not None:
             self.scheduler.step()
         self.optimizer.step()
-        return {"loss": loss.detach(), "accuracy": accuracy, "lr": self.optimizer.param_groups[0]["lr"]}
+        return self._clip_result({"loss": loss.detach(), "accuracy": accuracy, "lr": self.optimizer.param_groups[0]["lr"]})
 
     # ------------------------------------------------------------------ held-out evaluation
     def evaluate(self, batches, top_k=5):
