@@ -5,7 +5,7 @@
     python -m torch.distributed.run --nproc-per-node N examples/train_pixelsnail.py [...] CODES
 
 CODES is what examples/extract_code.py wrote (vqvae2_amd.codes.CodeDataset reads it).  The command line is the
-reference's; `--amp` is accepted only as O0 (this path is fp32).  The reference wraps the model in nn.DataParallel; here
+reference's; `--amp` is accepted only as O0; `--precision bf16` is this path's reduced precision (bf16 conv operands, see --help).  The reference wraps the model in nn.DataParallel; here
 data parallelism is one process per GPU under torch.distributed.run: every rank takes its shard of each epoch (--batch is
 per rank), Stage2Trainer all-reduces the gradients, and only the primary rank prints and saves.  Every epoch whose number
 is 1 modulo 10, and the last, saves {'model': state_dict, 'args': args} as <ckpt_dir>/pixelsnail_<hier>_<NNN>.pt, the
@@ -61,6 +61,8 @@ def parse_args(argv=None):
     parser.add_argument('--eval_every', type=int, default=0)
     parser.add_argument('--clip_grad_norm', type=float, default=None)
     parser.add_argument('--ema_decay', type=float, default=None)
+    parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16'],
+                        help='fp32 (default), or bf16: the eligible conv forwards and data gradients multiply bf16-rounded operands and accumulate in fp32; weight gradients, weights, optimizer state and every stored tensor stay fp32 (no loss scaling); the counterpart of --amp O1 of the reference')
     return parser.parse_args(argv)
 
 
@@ -100,6 +102,7 @@ def main(argv=None):
         val_loader = DataLoader(share, batch_size=args.batch, shuffle=False, num_workers=0)
     # (--resume keeps this command line: give the run's own arguments again)
     clip_grad_norm, ema_decay = args.clip_grad_norm, args.ema_decay     # of THIS command line, like --resume
+    precision = args.precision
     resume = torch.load(args.resume, map_location='cpu', weights_only=False) if args.resume is not None else None
     ckpt = {}
     if args.ckpt is not None:
@@ -111,6 +114,8 @@ def main(argv=None):
     model = model.to(device).train()
     trainer = vqvae2_amd.Stage2Trainer(model, args.hier, lr=args.lr, sched=args.sched, n_iter=len(loader) * args.epoch,
                                        clip_grad_norm=clip_grad_norm, ema_decay=ema_decay)
+    if precision == 'bf16':
+        trainer.set_precision('bf16')
     first_epoch = 0
     if resume is not None:
         trainer.load_state_dict(resume['trainer'] if 'trainer' in resume else resume)

@@ -59,11 +59,12 @@ typedef void *vq2_stream_t;
  * revision 14: an addition only -- vq2_sample_filtered, the draw from a top-k / nucleus truncated support with its log-probability;
  * revision 15: additions only -- vq2_prior_eval_rows and vq2_prior_eval_accumulate, the held-out evaluation of the stage-2 prior;
  * revision 16: additions only -- vq2_grad_norm with its workspace query and vq2_adam_step_ex (global-norm clipping, skipped
- * steps, averaged weights).
+ * steps, averaged weights); revision 17: additions only -- the bf16-operand conv forward / data gradient: the flag
+ * VQ2_ALLOW_BF16, the panels VQ2_PACK_FWD_BF16 / VQ2_PACK_DGRAD_BF16 and vq2_conv_bf16_eligible.
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 16
+#define VQ2_API_VERSION 17
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -124,6 +125,26 @@ typedef struct vq2_conv_desc {
  * buffer has exactly w.numel() floats. */
 #define VQ2_PACK_FWD 0   /* operand of vq2_conv_fwd   */
 #define VQ2_PACK_DGRAD 1 /* operand of vq2_conv_dgrad */
+
+/* bf16 operands (same_size layers): a PERMISSION in `flags` of vq2_conv_fwd and vq2_conv_dgrad, free in both flag sets.
+ * With it, a launch for which vq2_conv_bf16_eligible() holds computes
+ *     y = sum_k bf16(a_k) * bf16(w_k)      accumulated in fp32 by the matrix instruction,
+ * followed by the unchanged fp32 epilogue (bias, mask, residual, ReLU-out).  bf16() is round-to-nearest-even of the fp32
+ * value (tensor.to(torch.bfloat16)); a = the input activation (after VQ2_RELU_IN) and w the weight for the forward, a = dy
+ * and w the flipped weight for the data gradient.  Every tensor in memory keeps its fp32 format and layout; the weight
+ * gradient is not affected (it reads the unrounded x and dy).  No atomics and no split-K: bit-reproducible, and an image's
+ * result does not depend on the batch it is in.
+ * Eligibility, vq2_conv_bf16_eligible(d, dgrad): same_size == 1 and the depth-side channel count -- Ci for the forward
+ * (dgrad = 0), Co for the data gradient (dgrad = 1) -- a multiple of 16.  An eligible launch with the flag reads `wp` as
+ * the VQ2_PACK_FWD_BF16 / VQ2_PACK_DGRAD_BF16 panel; every other launch plans exactly as without the flag and reads the
+ * fp32 panel.  The caller asks the same function which panel to pack.
+ * The bf16 panels hold w.numel() (padded: Co * Ci * KH * KW) bf16 values = half that many floats at the start of `packed`,
+ * rows of KH * KW * depth values per GEMM column; vq2_pack_weight alone packs them (not the batched form), and refuses a
+ * layer that is not eligible (VQ2_ERR_UNSUPPORTED). */
+#define VQ2_ALLOW_BF16 16
+#define VQ2_PACK_FWD_BF16 2   /* operand of vq2_conv_fwd   with VQ2_ALLOW_BF16, eligible layers */
+#define VQ2_PACK_DGRAD_BF16 3 /* operand of vq2_conv_dgrad with VQ2_ALLOW_BF16, eligible layers */
+int vq2_conv_bf16_eligible(const vq2_conv_desc *d, int dgrad);
 int vq2_pack_weight(const vq2_conv_desc *d, int which, const float *w, float *packed, vq2_stream_t stream);
 
 /* Re-packing every layer after an optimizer step in ONE launch: fill one job per (layer, which) on

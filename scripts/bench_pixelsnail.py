@@ -15,7 +15,11 @@ same number of pixels per step), dropout 0.1, random codes from a seed.  Per mod
   * peak device memory: torch.cuda.max_memory_allocated over steps of ONE path with only that trainer alive.
 
 Writes one JSON document (default profiles/pixelsnail.json).  No GPU: fails.  Not measured here: kernel times (no
-profiler run), anything on more than one GPU."""
+profiler run), anything on more than one GPU.
+
+--amp O1: instead, per model, the arena trainer with bf16 conv operands (Stage2Trainer.set_precision('bf16')) against the
+arena trainer in fp32, from the same weights, alternating in the same way; the first losses must agree to 1e-2 relative
+(they cannot be bit-equal).  Default output profiles/pixelsnail_bf16.json."""
 import argparse
 import collections
 import gc
@@ -148,19 +152,69 @@ def bench_model(amd, spec, repeats, inner):
     return row
 
 
+def bench_amp(amd, spec, repeats, inner):
+    """One model: the fp32 arena trainer against the bf16 one, alternated."""
+    dev = torch.device("cuda:0")
+    h, w = spec["shape"]
+    gen = torch.Generator().manual_seed(1)
+    n_class = spec["args"][0]
+    codes = torch.randint(0, n_class, (spec["batch"], h, w), generator=gen).to(dev)
+    top = torch.randint(0, n_class, (spec["batch"], h // 2, w // 2), generator=gen).to(dev)
+    step_args = (codes,) if spec["hier"] == "top" else (top, codes)
+    torch.manual_seed(0)
+    state = amd.PixelSNAIL(spec["shape"], *spec["args"], dropout=0.1, **spec["kw"]).state_dict()
+    row = {"name": spec["name"], "shape": spec["shape"], "batch": spec["batch"], "args": spec["args"], "kw": spec["kw"]}
+    trainers, first = {}, {}
+    for prec in ("fp32", "bf16"):
+        m = amd.PixelSNAIL(spec["shape"], *spec["args"], dropout=0.1, **spec["kw"])
+        m.load_state_dict(state)
+        tr = amd.Stage2Trainer(m.to(dev).train(), spec["hier"], lr=3e-4, sched="cycle", n_iter=1000)
+        if prec == "bf16":
+            row["eligible_layers"], row["conv_layers"] = tr.set_precision("bf16")
+        torch.manual_seed(7)
+        first[prec] = float(tr.step(*step_args)["loss"])
+        tr.step(*step_args)
+        trainers[prec] = tr
+    row["first_loss"] = first
+    if not abs(first["bf16"] - first["fp32"]) <= 1e-2 * abs(first["fp32"]):
+        raise SystemExit(f"{spec['name']}: first losses {first} are further apart than 1e-2 relative; not timed")
+    fns = {p: (lambda t=t: t.step(*step_args)) for p, t in trainers.items()}
+    torch.cuda.synchronize()
+    ms = {p: [] for p in fns}
+    for _ in range(repeats + 1):
+        for p, fn in fns.items():
+            ms[p].append(time_ms(fn, inner))
+    for p in ms:
+        v = ms[p][1:]
+        med = statistics.median(v)
+        row[p + "_ms"], row[p + "_median_ms"], row[p + "_spread"] = v, med, (max(v) - min(v)) / med
+    row["fp32_over_bf16"] = row["fp32_median_ms"] / row["bf16_median_ms"]
+    print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()
+                      if k in ("name", "batch", "fp32_median_ms", "bf16_median_ms", "fp32_spread", "bf16_spread", "fp32_over_bf16",
+                               "eligible_layers", "conv_layers", "first_loss")}), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pixelsnail.json"))
+    ap.add_argument("--out", default=None, help="default profiles/pixelsnail.json, pixelsnail_bf16.json with --amp O1")
+    ap.add_argument("--amp", default="O0", choices=["O0", "O1"],
+                    help="O1: time the arena trainer with bf16 conv operands against the fp32 one (not arena against per-layer)")
     ap.add_argument("--repeats", type=int, default=4, help="timed repeats per path (one more is run first and discarded)")
     ap.add_argument("--inner", type=int, default=3, help="steps per timed window")
     ap.add_argument("--tiny", action="store_true", help="toy models: a rehearsal of the script, not a measurement")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pixelsnail_bf16.json" if args.amp == "O1" else "pixelsnail.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_pixelsnail.py needs the MI355X")
     import vqvae2_amd
     results = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "inner": args.inner, "tiny": args.tiny,
                "not_measured": ["kernel times (no profiler run)", "more than one GPU"],
-               "models": [bench_model(vqvae2_amd, spec, args.repeats, args.inner) for spec in (TINY if args.tiny else MODELS)]}
+               "models": [(bench_amp if args.amp == "O1" else bench_model)(vqvae2_amd, spec, args.repeats, args.inner)
+                          for spec in (TINY if args.tiny else MODELS)]}
+    if args.amp == "O1":
+        results["amp"] = "O1"
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(results, f, indent=1)

@@ -8,7 +8,7 @@ from . import vqvae_deep  # noqa: F401
 from .vqvae_deep import VQVAE_Deep  # noqa: F401
 from . import pixelsnail  # noqa: F401
 from .pixelsnail import (CausalAttention, WNConv2d, CausalConv2d, GatedResBlock, PixelBlock, CondResNet,  # noqa: F401
-                         PixelSNAIL)
+                         PixelSNAIL, set_conv_precision, conv_precision)
 from .ops import prior_loss  # noqa: F401
 from . import distributed  # noqa: F401
 from . import ops  # noqa: F401

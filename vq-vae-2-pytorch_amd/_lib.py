@@ -62,6 +62,7 @@ def _load():
         "vq2_prof_enable": (C.c_int, [C.c_int]),
         "vq2_prof_report": (C.c_int, [C.c_char_p, SZ]),
         "vq2_pack_weight": (C.c_int, [DP, C.c_int, P, P, P]),
+        "vq2_conv_bf16_eligible": (C.c_int, [DP, C.c_int]),
         "vq2_pack_job_init": (C.c_int, [DP, C.c_int, P, P, C.POINTER(PackJob)]),
         "vq2_pack_weights_batched": (C.c_int, [P, I32, I64, P]),
         "vq2_conv_fwd": (C.c_int, [DP, C.c_int, P, P, P, P, I32, P, P]),

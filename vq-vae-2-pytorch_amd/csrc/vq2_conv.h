@@ -24,6 +24,7 @@ struct ConvGemmParams {
     int nbias;            // bias has nbias entries (real output channels)
     int c4_tpw;           // conv_k4s2_c4_kernel: tiles per workgroup
     int ci_real;          // real input channels (<= Ci; the rest are zero padding), 0 = Ci
+    int allow_bf16;       // the caller set VQ2_ALLOW_BF16 on a same_size layer: P.w is the bf16 panel if conv_bf16_shape(Ci)
     double flops, bytes;  // algorithmic work of this launch (for the profiler only)
 };
 
@@ -127,6 +128,7 @@ static inline ConvExtents conv_extents(const ConvGemmParams &P) {
 // launch_conv() launches what the plan says.
 enum ConvFamily {
     CONV_GEMM_GEN, CONV_GEMM_FAST, CONV_K4S2_C4, CONV_1X1_K64, CONV_SUBPIXEL, CONV_WINO3, CONV_WINO_K4S2, CONV_WINO_SUBPIXEL,
+    CONV_GEMM_BF16,
     CONV_FAMILIES
 };
 
@@ -153,6 +155,13 @@ struct ConvTile {
 struct ConvTiles { const ConvTile *tile; int n; };
 ConvTiles conv_tiles(int family);                 // vq2_conv.hip; the Winograd families from wino_tiles
 ConvTiles wino_tiles(int family);                 // vq2_wino.hip
+ConvTiles bf16_tiles();                           // vq2_conv_bf16.hip
+
+// The eligibility rule of the bf16-operand kernel (vq2_conv_bf16.hip), the one copy of it: a same_size layer whose
+// depth-side channel count (Ci for the forward, Co for the data gradient) is a multiple of 16, so that a 16-deep MFMA step
+// stays inside one tap.  vq2_conv_bf16_eligible() exports it; the host packs the bf16 panel exactly when it holds.
+static inline bool conv_bf16_shape(int same_size, int depth_channels) { return same_size == 1 && depth_channels % 16 == 0; }
+int pack_weight_bf16(const vq2_conv_desc *d, int flip, const float *w, float *packed, hipStream_t s);   // vq2_conv_bf16.hip
 
 namespace wino {
 constexpr int BK = 8;   // input channels per staged block of the Winograd kernels (vq2_wino.hip)

@@ -1185,6 +1185,7 @@ ConvTiles conv_tiles(int family) {
         case CONV_K4S2_C4:   return {C4_TILES, 1};
         case CONV_1X1_K64:   return {K64_TILES, sizeof(K64_TILES) / sizeof(ConvTile)};
         case CONV_SUBPIXEL:  return {SUBPIXEL_TILES, 1};
+        case CONV_GEMM_BF16: return bf16_tiles();
         default:             return wino_tiles(family);
     }
 }
@@ -1241,6 +1242,13 @@ static bool plan_wino(const ConvGemmParams &P, const ConvExtents &E, ConvPlan &p
 ConvPlan plan_conv(const ConvGemmParams &P) {
     ConvPlan pl{};
     const ConvExtents E = conv_extents(P);
+    // bf16 operands: a permission of the caller (VQ2_ALLOW_BF16), taken whenever the shape is eligible -- the caller packed
+    // the bf16 panel by the same rule, so no other kernel could read P.w.  128 x 128 tiles, 128 x 64 up to 64 channels.
+    if (P.allow_bf16 && conv_bf16_shape(1, P.Ci)) {
+        pl.family = CONV_GEMM_BF16;
+        pl.tile = P.Co > 64 ? tile_of(pl.family, 128, 128, 32) : tile_of(pl.family, 128, 64, 32);
+        return pl;
+    }
     // Tile by output-channel count (GEMM N).  Chunk depth per tile measured on MI355X: the 128x128 tile is
     // register-bound at 2 waves/SIMD and prefers BK=32; the narrower tiles run 4+ waves/SIMD with BK=16.
     // few row tiles (the 32x32-resolution layers): halve the tile height so every CU still holds >= 2
@@ -1323,6 +1331,9 @@ static const char *conv_label(const ConvPlan &pl, const int *d, const ConvGemmPa
             return prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%d,s%d,ph%d,%s", d[0], d[1], d[2], P.M, P.Co, P.K, P.KH,
                               P.stride, P.phases,
                               pl.family == CONV_GEMM_GEN ? "gen" : pl.tap_inner ? "tap" : pl.uni ? "uni" : "var");
+        case CONV_GEMM_BF16:
+            // (a tile of the conv_gemm family; the last field names the instantiation, as tap / uni / var / gen do)
+            return prof_label("conv_gemm<%dx%dx%d>|M=%d,N=%d,K=%d,k%dx%d,bf16", d[0], d[1], d[2], P.M, P.Co, P.K, P.KH, P.KW);
         case CONV_K4S2_C4:  return prof_label("conv_k4s2_c4|M=%d,N=%d,K=%d%s", P.M, P.Co, P.K, P.mask ? ",mask" : "");
         case CONV_1X1_K64:  return prof_label("conv1x1_k64|M=%d,N=%d,K=64", P.M, P.Co);
         case CONV_SUBPIXEL: return prof_label("subpixel_conv|M=%d,N=%d,K=%d,ph4", P.M, P.Co, P.K);
@@ -1335,7 +1346,8 @@ static const char *conv_label(const ConvPlan &pl, const int *d, const ConvGemmPa
 
 int launch_conv(const ConvPlan &pl, const ConvGemmParams &P, hipStream_t s) {
     static const char *const family_name[CONV_FAMILIES] = {"conv_gemm", "conv_gemm", "conv_k4s2_c4", "conv1x1_k64",
-                                                           "subpixel_conv", "conv_wino", "conv_wino_k4s2", "conv_wino_subpixel"};
+                                                           "subpixel_conv", "conv_wino", "conv_wino_k4s2", "conv_wino_subpixel",
+                                                           "conv_gemm"};
     const ConvTiles t = conv_tiles(pl.family);
     if (pl.tile < 0 || pl.tile >= t.n) return set_error(VQ2_ERR_INVALID, "conv: the plan names no tile of family %d", pl.family);
     const ConvTile &tile = t.tile[pl.tile];
@@ -1553,7 +1565,8 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(const vq2_pack_job *_
 extern "C" int vq2_pack_job_init(const vq2_conv_desc *d, int which, const float *w, float *packed, vq2_pack_job *job) {
     if (int e = check_conv_desc(d, "pack_job_init")) return e;
     VQ2_REQUIRE(w && packed && job, "pack_job_init: null pointer");
-    VQ2_REQUIRE(which == VQ2_PACK_FWD || which == VQ2_PACK_DGRAD, "pack_job_init: bad `which`");
+    VQ2_REQUIRE(which == VQ2_PACK_FWD || which == VQ2_PACK_DGRAD, "pack_job_init: bad `which` (the bf16 panels are packed by "
+                "vq2_pack_weight only)");
     job->w = w; job->packed = packed; job->offset = 0;
     return pack_job_of(d, which, job);
 }
@@ -1572,7 +1585,20 @@ __global__ void pack_single_kernel(const float *__restrict__ w, float *__restric
         p[t] = pack_elem(w, t, Or, Ir, Op, Ip, KH, KW, mode);
 }
 
+extern "C" int vq2_conv_bf16_eligible(const vq2_conv_desc *d, int dgrad) {
+    return d != nullptr && conv_bf16_shape(d->same_size, dgrad ? d->Co : d->Ci);
+}
+
 extern "C" int vq2_pack_weight(const vq2_conv_desc *d, int which, const float *w, float *packed, vq2_stream_t stream) {
+    if (which == VQ2_PACK_FWD_BF16 || which == VQ2_PACK_DGRAD_BF16) {
+        if (int e = check_conv_desc(d, "pack_weight")) return e;
+        VQ2_REQUIRE(w && packed && aligned16(packed), "pack_weight: null or misaligned pointer");
+        const int dgrad = which == VQ2_PACK_DGRAD_BF16;
+        if (!vq2_conv_bf16_eligible(d, dgrad))
+            return set_error(VQ2_ERR_UNSUPPORTED, "pack_weight: no bf16 panel for this layer (same_size and %s %% 16 == 0 "
+                             "required: vq2_conv_bf16_eligible)", dgrad ? "Co" : "Ci");
+        return pack_weight_bf16(d, dgrad, w, packed, to_stream(stream));
+    }
     vq2_pack_job j;
     if (int e = vq2_pack_job_init(d, which, w, packed, &j)) return e;
     const int total = (int)j.numel;
@@ -1595,6 +1621,7 @@ extern "C" int vq2_conv_fwd(const vq2_conv_desc *d, int flags, const float *x, c
     P.relu_in = (flags & VQ2_RELU_IN) != 0; P.relu_out = (flags & VQ2_RELU_OUT) != 0;
     P.nbias = real_co(d);
     P.ci_real = real_ci(d);
+    P.allow_bf16 = (flags & VQ2_ALLOW_BF16) != 0 && d->same_size == 1;
     const ConvHW o = out_hw(d);
     P.Hy = o.h; P.Wy = o.w;
     if (!d->transposed) {
@@ -1636,7 +1663,7 @@ extern "C" int vq2_conv_dgrad(const vq2_conv_desc *d, int flags, const float *dy
                               int32_t ldmask, const float *residual, int32_t ldres, float *dx, int32_t lddx,
                               vq2_stream_t stream) {
     if (int e = check_conv_desc(d, "conv_dgrad")) return e;
-    VQ2_REQUIRE((flags & ~VQ2_MASK_AFTER_RESIDUAL) == 0, "conv_dgrad: unknown flag");
+    VQ2_REQUIRE((flags & ~(VQ2_MASK_AFTER_RESIDUAL | VQ2_ALLOW_BF16)) == 0, "conv_dgrad: unknown flag");
     VQ2_REQUIRE(dy && wp && dx, "conv_dgrad: null pointer");
     VQ2_REQUIRE(aligned16(dy) && aligned16(wp) && aligned16(dx), "conv_dgrad: pointers must be 16-byte aligned");
     VQ2_REQUIRE(lddx >= d->Ci && lddx % 4 == 0, "conv_dgrad: lddx=%d must be >= Ci and a multiple of 4", lddx);
@@ -1650,6 +1677,7 @@ extern "C" int vq2_conv_dgrad(const vq2_conv_desc *d, int flags, const float *dy
     P.relu_in = 0; P.relu_out = 0;
     P.ci_real = real_co(d);   // the gradient GEMM's input channels are the forward op's output channels
     P.mask_after = (flags & VQ2_MASK_AFTER_RESIDUAL) != 0;
+    P.allow_bf16 = (flags & VQ2_ALLOW_BF16) != 0 && d->same_size == 1;
     P.Hy = d->H; P.Wy = d->W;
     if (!d->transposed && d->stride == 1) {
         // full correlation with the flipped kernel: pad' = K-1-pad per axis

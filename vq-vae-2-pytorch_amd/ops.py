@@ -18,8 +18,11 @@ from ._lib import lib, check, AttnDesc, ConvDesc, OneHotDesc, PackJob, WgradJob,
 VQ2_RELU_IN = 1
 VQ2_RELU_OUT = 2
 VQ2_MASK_AFTER_RESIDUAL = 4
+VQ2_ALLOW_BF16 = 16
 PACK_FWD = 0
 PACK_DGRAD = 1
+PACK_FWD_BF16 = 2
+PACK_DGRAD_BF16 = 3
 
 # There is NO process-global mutable state on the autograd path (SURVEY 8b threading row): what a step shares hangs on the
 # tensors, so two trainers or models can coexist in one process and back-propagate on different autograd threads:
@@ -115,6 +118,7 @@ class ConvSpec:
     kw: int = 0               # kernel columns and left padding; without same_size always k and pad (__post_init__)
     pad_left: int = 0
     same_size: bool = False   # vq2_conv_desc.same_size
+    bf16: bool = False        # permission: forward and data gradient round their operands to bf16 where conv_bf16_eligible
 
     def __post_init__(self):
         if not self.same_size:
@@ -148,6 +152,13 @@ class ConvSpec:
         if self.same_size:
             return h, w
         return (h + 2 * self.pad - self.k) // self.stride + 1, (w + 2 * self.pad - self.k) // self.stride + 1
+
+
+def conv_bf16_eligible(spec, dgrad=False):
+    """The host mirror of vq2_conv_bf16_eligible (include/vq2.h): a same_size layer whose depth-side channel count (the
+    padded input channels for the forward, output channels for the data gradient) is a multiple of 16.  A spec with
+    `bf16` set takes the bf16-operand kernel, and packs the bf16 panel, exactly where this holds."""
+    return bool(spec.same_size) and (spec.co if dgrad else spec.ci) % 16 == 0
 
 
 def _desc(spec, n, h, w, ldx, ldy):
@@ -253,7 +264,11 @@ def conv_forward(spec, x, weight, bias, flags=0, residual=None, out=None):
     elif tuple(out.shape) != (n, ho, wo, spec.co) or not is_nhwc_dense(out):
         raise RuntimeError("conv_forward: bad `out` buffer")
     d = _desc(spec, n, h, w, ld_of(x), ld_of(out))
-    wp = packed_weight(spec, weight, PACK_FWD)
+    if spec.bf16 and conv_bf16_eligible(spec):
+        flags |= VQ2_ALLOW_BF16
+        wp = packed_weight(spec, weight, PACK_FWD_BF16)
+    else:
+        wp = packed_weight(spec, weight, PACK_FWD)
     ldres = ld_of(residual) if residual is not None else 0
     check(lib.vq2_conv_fwd(C.byref(d), flags, _p(x), _p(wp), _p(bias), _p(residual), ldres, _p(out), _stream()),
           "conv_fwd")
@@ -265,8 +280,13 @@ def conv_dgrad(spec, xshape, dy, weight, mask=None, residual=None, out=None, mas
     if out is None:
         out = torch.empty((n, h, w, spec.ci), device=dy.device, dtype=torch.float32)
     d = _desc(spec, n, h, w, spec.ci, ld_of(dy))
-    wp = packed_weight(spec, weight, PACK_DGRAD)
-    check(lib.vq2_conv_dgrad(C.byref(d), VQ2_MASK_AFTER_RESIDUAL if mask_after else 0, _p(dy), _p(wp), _p(mask),
+    flags = VQ2_MASK_AFTER_RESIDUAL if mask_after else 0
+    if spec.bf16 and conv_bf16_eligible(spec, dgrad=True):
+        flags |= VQ2_ALLOW_BF16
+        wp = packed_weight(spec, weight, PACK_DGRAD_BF16)
+    else:
+        wp = packed_weight(spec, weight, PACK_DGRAD)
+    check(lib.vq2_conv_dgrad(C.byref(d), flags, _p(dy), _p(wp), _p(mask),
                              ld_of(mask) if mask is not None else 0, _p(residual),
                              ld_of(residual) if residual is not None else 0, _p(out), ld_of(out), _stream()),
           "conv_dgrad")

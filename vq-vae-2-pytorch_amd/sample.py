@@ -19,6 +19,7 @@ list of library calls with their arguments and replayed W times, without autogra
 (i, j) recomputes the whole row: columns <= j are exact, later ones are placeholders nothing reads.  The integer code map
 is moved by torch copies once per row (band of row i + 1 from band of row i); everything else is a libvq2 kernel."""
 import ctypes as C
+import dataclasses
 import os
 import weakref
 
@@ -71,6 +72,8 @@ class _Conv:
             par, self.spec = mod, mod.spec
         else:
             raise NotImplementedError(f"vqvae2_amd.PriorSampler: cannot step through {type(mod).__name__}")
+        if self.spec.bf16:       # the row kernels are fp32: the sampler's copy of a spec drops the bf16 permission
+            self.spec = dataclasses.replace(self.spec, bf16=False)
         s = self.spec
         v = par.weight_v.detach().clone().contiguous()
         if causal_cols is not None:

@@ -498,6 +498,7 @@ class Stage2Trainer(_ArenaTrainer):
         if sched not in (None, "cycle"):
             raise ValueError(f"Stage2Trainer: sched must be None or 'cycle', got {sched!r}")
         self.model, self.hier = model, hier
+        self.precision = None           # set_precision()
         self.arena = self.plan = None
         self.plan_info = {"entries": 0, "per_layer": len(ops.WeightNormPlan.layers(model)), "per_layer_names": []}
         if arena:
@@ -546,6 +547,33 @@ class Stage2Trainer(_ArenaTrainer):
         if self.dp and len(self.buckets) == 2:
             self._send_when_reported(self.buckets[0], self.buckets[0].params, self._finish_early)
         self._finish_construction()
+
+    def set_precision(self, precision):
+        """The conv precision of the run, 'bf16' or 'fp32': pixelsnail.set_conv_precision on the model (bf16 operands in the
+        eligible conv forwards and data gradients; weight gradients, parameters and optimizer state stay fp32), remembered
+        for the checkpoint.  Returns (eligible_layers, total_layers).  A trainer that was never told keeps the model's convs
+        as they are and saves no "precision"."""
+        from .pixelsnail import set_conv_precision
+        counts = set_conv_precision(self.model, precision)      # (refuses anything else)
+        self.precision = precision
+        return counts
+
+    def state_dict(self):
+        """_ArenaTrainer.state_dict(), with "precision" when set_precision() was called."""
+        sd = super().state_dict()
+        if self.precision is not None:
+            sd["precision"] = self.precision
+        return sd
+
+    def load_state_dict(self, sd):
+        """_ArenaTrainer.load_state_dict(); a full checkpoint whose conv precision (absent = 'fp32') differs from this
+        trainer's (None = 'fp32') is refused before anything changes: the steps that follow would not be the run's."""
+        if split_checkpoint(sd)[1]:
+            mine, theirs = self.precision or "fp32", sd.get("precision") or "fp32"
+            if mine != theirs:
+                raise RuntimeError(f"Stage2Trainer.load_state_dict: the checkpoint was trained with precision {theirs!r}, "
+                                   f"the trainer runs {mine!r} (set_precision)")
+        super().load_state_dict(sd)
 
     def _params_overwritten(self):
         self.plan.invalidate()
