@@ -168,6 +168,7 @@ CASES = [
     ('dgrad', F, 96, 64, 1, 1, 0, 1, 128, 128, 'mra',        'conv1x1_k64|', 'conv1x1_k64|', 'conv_gemm<64x128x16>|gen'),
     ('dgrad', T, 128, 64, 4, 2, 1, 3, 2, 64, 'mra',          'conv_wino_k4s2<2x64,nt1>|', 'conv_gemm<64x128x32>|tap', 'conv_gemm<64x128x16>|gen'),
     ('dgrad', F, 64, 32, 4, 2, 1, 2, 8, 128, 'mra',          'conv_wino_subpixel<4x64>|', 'conv_gemm<64x64x32>|uni', 'conv_gemm<64x64x16>|gen'),
+    ('dgrad', F, 32, 48, 3, 1, 1, 3, 9, 7, 'mra',            'conv_gemm<128x32x32>|var', 'conv_gemm<128x32x32>|var', 'conv_gemm<128x32x16>|gen'),
     ('fwd', T, 128, 64, 4, 2, 1, 2, 10, 20, 'ibro',          'subpixel_conv|', 'subpixel_conv|', 'conv_gemm<64x64x16>|gen'),
     ('fwd', F, 32, 64, 4, 2, 1, 3, 4, 128, 'ibro',           'conv_wino_k4s2<2x64,nt1>|', 'conv_gemm<64x64x32>|uni', 'conv_gemm<64x64x16>|gen'),
     ('fwd', T, 32, 64, 4, 2, 1, 2, 4, 64, 'ibro',            'conv_wino_subpixel<4x64>|', 'conv_gemm<64x64x32>|uni', 'conv_gemm<64x64x16>|gen'),

@@ -1,5 +1,5 @@
-// Launch parameters, kernel plan and host helpers shared by the conv kernels of libvq2 (vq2_conv.hip, vq2_wino.hip,
-// vq2_wgrad.hip).
+// Launch parameters, kernel plan, host helpers and the device-side GEMM skeleton shared by the conv kernels of libvq2
+// (vq2_conv.hip, vq2_conv_bf16.hip, vq2_wino.hip, vq2_wgrad.hip); the epilogue contract is vq2_conv_epilogue.h, included below.
 #pragma once
 #include "vq2_common.h"
 
@@ -44,6 +44,7 @@ constexpr long PENALTY_REACH = (1L << 30) / 4;
 __device__ __forceinline__ float4 as_f4(u32x4 v) {
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
+__device__ __forceinline__ float f4_at(const float4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 
 // ---------------------------------------------------------------------------------------------- descriptor helpers
 static inline int real_ci(const vq2_conv_desc *d) { return d->Cir ? d->Cir : d->Ci; }
@@ -170,4 +171,110 @@ constexpr int BK = 8;   // input channels per staged block of the Winograd kerne
 ConvPlan plan_conv(const ConvGemmParams &P);
 int launch_conv(const ConvPlan &plan, const ConvGemmParams &P, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------- device: GEMM skeleton
+template <int A, int B>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[A][B]) {
+#pragma unroll
+    for (int i = 0; i < A; ++i)
+#pragma unroll
+        for (int j = 0; j < B; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+template <int A>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[A]) {
+#pragma unroll
+    for (int i = 0; i < A; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
+// The pixels a staging thread of the pointer GEMM kernels (conv_gemm_kernel, conv_gemm_bf16_kernel) gathers for: GEMM rows
+// m_first + m_step * j of the Ho x Wo output grid, as the input pixel of tap (0, 0) and its coordinates.
+template <int A_LD>
+struct GatherRows {
+    int pix[A_LD], h[A_LD], w[A_LD];
+    __device__ __forceinline__ GatherRows(const ConvGemmParams &P, int m_first, int m_step, int Ho, int Wo, int stride, int pad_h,
+                                          int pad_w) {
+        const int HoWo = Ho * Wo;
+#pragma unroll
+        for (int j = 0; j < A_LD; ++j) {
+            const int m = m_first + m_step * j;
+            if (m < P.M) {
+                const int n = m / HoWo;
+                const int r = m - n * HoWo;
+                const int ho = r / Wo;
+                const int wo = r - ho * Wo;
+                h[j] = ho * stride - pad_h;
+                w[j] = wo * stride - pad_w;
+                pix[j] = (n * P.H + h[j]) * P.W + w[j];
+            } else {
+                h[j] = -(1 << 24); w[j] = 0; pix[j] = 0;  // every bounds test fails
+            }
+        }
+    }
+    // is tap (kh, kw) of row j inside the image, and where (in elements of x, 64-bit)
+    __device__ __forceinline__ bool inside(const ConvGemmParams &P, int j, int kh, int kw) const {
+        return (unsigned)(h[j] + kh) < (unsigned)P.H && (unsigned)(w[j] + kw) < (unsigned)P.W;
+    }
+    __device__ __forceinline__ size_t at(const ConvGemmParams &P, int j, int kh, int kw, int ci) const {
+        return (size_t)(pix[j] + kh * P.W + kw) * P.ldx + ci;
+    }
+};
+
+// k -> (kh, kw, ci) of a staging thread's run of consecutive k (4 floats, or 8 in the bf16 kernel), advanced by one chunk
+struct KWalker {
+    int k, ci, kh, kw;
+    __device__ __forceinline__ KWalker(const ConvGemmParams &P, int k0) : k(k0) {
+        const int tap = k0 / P.Ci;
+        ci = k0 - tap * P.Ci;
+        kh = tap / P.KW;
+        kw = tap - kh * P.KW;
+    }
+    __device__ __forceinline__ void advance(const ConvGemmParams &P, int bk) {
+        k += bk;
+        ci += bk;
+        while (ci >= P.Ci) {
+            ci -= P.Ci;
+            if (++kw == P.KW) { kw = 0; ++kh; }
+        }
+    }
+};
+
+// One staged chunk of the fp32 GEMM kernels: a / b = this lane's fragment rows in the LDS tiles (rows LDK floats apart, 32
+// rows per MFMA tile).  The fragment registers are double-buffered: the ds_reads of k-group g+1 are issued before the MFMAs
+// of group g, so LDS latency never sits between two MFMA groups; the MT * NT independent accumulators take turns, so
+// consecutive MFMAs never depend on each other.  PRIO raises the wave's priority around the MFMAs; after_group0() runs
+// behind the MFMAs of k-group 0.
+template <int MT, int NT, int BK, int LDK, bool PRIO, class F>
+__device__ __forceinline__ void mfma_chunk_f32(f32x16 (&acc)[MT][NT], const float *a, const float *b, F after_group0) {
+    float4 fa[2][MT], fb[2][NT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) fa[0][i] = *reinterpret_cast<const float4 *>(a + i * 32 * LDK);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) fb[0][j] = *reinterpret_cast<const float4 *>(b + j * 32 * LDK);
+#pragma unroll
+    for (int k8 = 0; k8 < BK / 8; ++k8) {
+        const int cur = k8 & 1, nxt = cur ^ 1;
+        if (k8 + 1 < BK / 8) {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) fa[nxt][i] = *reinterpret_cast<const float4 *>(a + i * 32 * LDK + (k8 + 1) * 8);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) fb[nxt][j] = *reinterpret_cast<const float4 *>(b + j * 32 * LDK + (k8 + 1) * 8);
+        }
+        if (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)   // x, y, z, w
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f4_at(fa[cur][i], c), f4_at(fb[cur][j], c), acc[i][j], 0, 0, 0);
+        if (PRIO) __builtin_amdgcn_s_setprio(0);
+        if (k8 == 0) after_group0();
+    }
+}
+
 }  // namespace vq2
+
+#include "vq2_conv_epilogue.h"

@@ -9,7 +9,8 @@
 //   GEMM cols  co
 //   GEMM depth k = (kh, kw, ci), ci fastest  -> 16-byte coalesced loads along ci
 //
-// Everything the reference does around a conv on this path is fused:
+// Everything the reference does around a conv on this path is fused (the epilogue of every kernel of this file but
+// convT_small_mfma_kernel is the one definition of vq2_conv_epilogue.h):
 //   - ReLU on the input (vqvae.py:86,88,107,109,...)      -> applied while staging A into LDS
 //   - bias                                                 -> epilogue
 //   - `out += input` of ResBlock (vqvae.py:94)             -> residual in the epilogue
@@ -65,57 +66,24 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
     // ---- per-thread staging coordinates (fixed over the K loop)
     const int lrow = tid / KQ;        // 0..RPP-1
     const int lk = (tid % KQ) * 4;    // float4 column inside a chunk
-    int a_pix[A_LD], a_h[A_LD], a_w[A_LD];
-    const int HoWo = P.Ho * P.Wo;
-#pragma unroll
-    for (int j = 0; j < A_LD; ++j) {
-        const int m = m0 + lrow + RPP * j;
-        if (m < P.M) {
-            const int n = m / HoWo;
-            const int r = m - n * HoWo;
-            const int ho = r / P.Wo;
-            const int wo = r - ho * P.Wo;
-            a_h[j] = ho * P.stride - pad_h;
-            a_w[j] = wo * P.stride - pad_w;
-            a_pix[j] = (n * P.H + a_h[j]) * P.W + a_w[j];
-        } else {
-            a_h[j] = -(1 << 24); a_w[j] = 0; a_pix[j] = 0;  // every bounds test fails
-        }
-    }
-    // k -> (kh, kw, ci) of this thread's float4, advanced incrementally
-    int kglob = lk;
-    int ci, kh, kw;
-    {
-        const int tap = kglob / P.Ci;
-        ci = kglob - tap * P.Ci;
-        kh = tap / P.KW;
-        kw = tap - kh * P.KW;
-    }
+    const GatherRows<A_LD> rows(P, m0 + lrow, RPP, P.Ho, P.Wo, P.stride, pad_h, pad_w);
+    KWalker kk(P, lk);                // k -> (kh, kw, ci) of this thread's float4, advanced incrementally
 
     float4 ra0[A_LD], rb0[B_LD];
     auto load_chunk = [&](float4 (&ra)[A_LD], float4 (&rb)[B_LD]) {
-        const bool kv = kglob < P.K;
+        const bool kv = kk.k < P.K;
 #pragma unroll
         for (int j = 0; j < A_LD; ++j) {
-            const bool v = kv && (unsigned)(a_h[j] + kh) < (unsigned)P.H && (unsigned)(a_w[j] + kw) < (unsigned)P.W;
             float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (v) val = *reinterpret_cast<const float4 *>(P.x + (size_t)(a_pix[j] + kh * P.W + kw) * P.ldx + ci);
+            if (kv && rows.inside(P, j, kk.kh, kk.kw)) val = *reinterpret_cast<const float4 *>(P.x + rows.at(P, j, kk.kh, kk.kw, kk.ci));
             ra[j] = val;  // ReLU is applied when the registers are written to LDS (no wait on the load here)
         }
 #pragma unroll
         for (int j = 0; j < B_LD; ++j) {
             const int co = n0 + lrow + RPP * j;
             float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (kv && co < P.Co && lrow + RPP * j < BN) val = *reinterpret_cast<const float4 *>(wp + (size_t)co * P.K + kglob);
+            if (kv && co < P.Co && lrow + RPP * j < BN) val = *reinterpret_cast<const float4 *>(wp + (size_t)co * P.K + kk.k);
             rb[j] = val;
-        }
-    };
-    auto advance_k = [&]() {
-        kglob += BK;
-        ci += BK;
-        while (ci >= P.Ci) {
-            ci -= P.Ci;
-            if (++kw == P.KW) { kw = 0; ++kh; }
         }
     };
     auto store_chunk = [&](int buf, const float4 (&ra)[A_LD], const float4 (&rb)[B_LD]) {
@@ -130,43 +98,14 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
     };
 
     f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int frag_row = lane & 31;
     const int frag_k = 4 * (lane >> 5);
     auto compute = [&](int buf) {
         const float *a = As + buf * BM * LDK + (wm * MT * 32 + frag_row) * LDK + frag_k;
         const float *b = Bs + buf * BN * LDK + (wn * NT * 32 + frag_row) * LDK + frag_k;
-        // fragment registers are double-buffered: the ds_reads of k-group g+1 are issued before the MFMAs
-        // of group g, so LDS latency never sits between two MFMA groups
-        float4 fa[2][MT], fb[2][NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) fa[0][i] = *reinterpret_cast<const float4 *>(a + i * 32 * LDK);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) fb[0][j] = *reinterpret_cast<const float4 *>(b + j * 32 * LDK);
-#pragma unroll
-        for (int k8 = 0; k8 < BK / 8; ++k8) {
-            const int cur = k8 & 1, nxt = cur ^ 1;
-            if (k8 + 1 < BK / 8) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i) fa[nxt][i] = *reinterpret_cast<const float4 *>(a + i * 32 * LDK + (k8 + 1) * 8);
-#pragma unroll
-                for (int j = 0; j < NT; ++j) fb[nxt][j] = *reinterpret_cast<const float4 *>(b + j * 32 * LDK + (k8 + 1) * 8);
-            }
-            // round-robin over the MT*NT independent accumulators: consecutive MFMAs never depend on each other
-#define VQ2_MFMA_STEP(C)                                                                                         \
-    _Pragma("unroll") for (int i = 0; i < MT; ++i) _Pragma("unroll") for (int j = 0; j < NT; ++j)                 \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][i].C, fb[cur][j].C, acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(1);
-            VQ2_MFMA_STEP(x) VQ2_MFMA_STEP(y) VQ2_MFMA_STEP(z) VQ2_MFMA_STEP(w)
-            __builtin_amdgcn_s_setprio(0);
-#undef VQ2_MFMA_STEP
-        }
+        mfma_chunk_f32<MT, NT, BK, LDK, true>(acc, a, b, [] {});
     };
 
     const int nchunks = (P.K + BK - 1) / BK;
@@ -176,7 +115,7 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
     for (int c = 0; c < nchunks; ++c) {
         const int buf = c & 1;
         if (c + 1 < nchunks) {
-            advance_k();
+            kk.advance(P, BK);
             load_chunk(ra0, rb0);  // global loads in flight while the matrix pipe works on chunk c
         }
         compute(buf);
@@ -184,62 +123,7 @@ __global__ __launch_bounds__(256, (MT * NT == 4) ? (BK == 16 ? 3 : 2) : 1) void 
         __syncthreads();
     }
 
-    // ---- epilogue: lane holds column (lane&31) of 16 rows per 32x32 tile.
-    // All mask/residual loads of a tile are issued BEFORE its stores: y may alias neither, but the
-    // compiler cannot know that, and a load->store->load chain would serialise on HBM latency.
-    const float *__restrict__ maskp = P.mask;
-    const float *__restrict__ resp = P.res;
-    float *__restrict__ yp = P.y;
-    const int colq = lane & 31;
-    const int rowq = 4 * (lane >> 5);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int co = n0 + (wn * NT + j) * 32 + colq;
-        const bool cv = co < P.Co;
-        const float bv = (P.bias && co < P.nbias) ? P.bias[co] : 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int mb = m0 + (wm * MT + i) * 32 + rowq;
-#pragma unroll
-            for (int rb = 0; rb < 16; rb += 8) {     // 8 rows at a time keeps the register footprint small
-                int pix[8];
-                bool ok[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int r = rb + q;
-                    const int m = mb + (r & 3) + 8 * (r >> 2);
-                    ok[q] = cv && m < P.M;
-                    if (os == 1) {
-                        pix[q] = m;
-                    } else {
-                        const int n = m / HoWo;
-                        const int rr = m - n * HoWo;
-                        const int ho = rr / P.Wo;
-                        const int wo = rr - ho * P.Wo;
-                        pix[q] = (n * P.Hy + (ho * os + oh)) * P.Wy + (wo * os + ow);
-                    }
-                }
-                float mk[8], rs[8];
-                if (maskp) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) mk[q] = ok[q] ? maskp[(size_t)pix[q] * P.ldm + co] : 0.f;
-                }
-                if (resp) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) rs[q] = ok[q] ? resp[(size_t)pix[q] * P.ldr + co] : 0.f;
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    float v = acc[i][j][rb + q] + bv;
-                    if (maskp && !P.mask_after) v = (mk[q] > 0.f) ? v : 0.f;
-                    if (resp) v += rs[q];
-                    if (maskp && P.mask_after) v = (mk[q] > 0.f) ? v : 0.f;
-                    v = relu_floor(v, P.relu_out ? 0 : (int)0x80000000);
-                    if (ok[q]) yp[(size_t)pix[q] * P.ldy + co] = v;
-                }
-            }
-        }
-    }
+    conv_epilogue_pointers<MT, NT>(P, acc, m0, n0, wm, wn, lane, os, oh, ow);
 }
 
 
@@ -441,39 +325,16 @@ __global__ __launch_bounds__(256, OCC4 ? 4 : ((MT * NT == 4) ? (BK == 16 ? 3 : 2
     };
 
     f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int frag_row = lane & 31;
     const int frag_k = 4 * (lane >> 5);
     auto compute = [&](int buf, bool prep_next) {
         const float *a = As + buf * BM * LDK + (wm * MT * 32 + frag_row) * LDK + frag_k;
         const float *b = Bs + buf * BN * LDK + (wn * NT * 32 + frag_row) * LDK + frag_k;
-        float4 fa[2][MT], fb[2][NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) fa[0][i] = *reinterpret_cast<const float4 *>(a + i * 32 * LDK);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) fb[0][j] = *reinterpret_cast<const float4 *>(b + j * 32 * LDK);
-#pragma unroll
-        for (int k8 = 0; k8 < BK / 8; ++k8) {
-            const int cur = k8 & 1, nxt = cur ^ 1;
-            if (k8 + 1 < BK / 8) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i) fa[nxt][i] = *reinterpret_cast<const float4 *>(a + i * 32 * LDK + (k8 + 1) * 8);
-#pragma unroll
-                for (int j = 0; j < NT; ++j) fb[nxt][j] = *reinterpret_cast<const float4 *>(b + j * 32 * LDK + (k8 + 1) * 8);
-            }
-#define VQ2_MFMA_STEP(C)                                                                                         \
-    _Pragma("unroll") for (int i = 0; i < MT; ++i) _Pragma("unroll") for (int j = 0; j < NT; ++j)                 \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][i].C, fb[cur][j].C, acc[i][j], 0, 0, 0);
-            VQ2_MFMA_STEP(x) VQ2_MFMA_STEP(y) VQ2_MFMA_STEP(z) VQ2_MFMA_STEP(w)
-#undef VQ2_MFMA_STEP
-            if (PIPE && k8 == 0 && prep_next) { advance_k(); prep_offsets(); }   // offsets of chunk c+2, in the MFMA shadow
-        }
+        mfma_chunk_f32<MT, NT, BK, LDK, false>(acc, a, b, [&] {
+            if (PIPE && prep_next) { advance_k(); prep_offsets(); }   // offsets of chunk c+2, in the MFMA shadow
+        });
     };
 
     const int nchunks = (P.K + BK - 1) / BK;
@@ -502,18 +363,10 @@ __global__ __launch_bounds__(256, OCC4 ? 4 : ((MT * NT == 4) ? (BK == 16 ? 3 : 2
         }
     }
 
-    // ---- epilogue with 32-bit offsets through buffer descriptors
-    const int ybytes = P.N * P.Hy * P.Wy * 4;  // per unit of pixel stride
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(P.y, 0, ybytes * P.ldy, RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rmk =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.mask ? P.mask : P.y), 0, P.mask ? ybytes * P.ldm : 0, RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rrs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.res ? P.res : P.y), 0, P.res ? ybytes * P.ldr : 0, RSRC_FLAGS);
-    const bool has_mask = P.mask != nullptr, has_res = P.res != nullptr;
-    const bool mask_first = has_mask && !P.mask_after, mask_last = has_mask && P.mask_after;
+    // ---- epilogue (vq2_conv_epilogue.h) with 32-bit offsets through buffer descriptors
+    const ConvEpilogue ep(P);
     const int colq = lane & 31;
     const int rowq = 4 * (lane >> 5);
-    const int ldy4 = P.ldy * 4, ldm4 = P.ldm * 4, ldr4 = P.ldr * 4;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         const int mt0 = m0 + (wm * MT + i) * 32;   // first GEMM row of this 32-row tile
@@ -537,38 +390,19 @@ __global__ __launch_bounds__(256, OCC4 ? 4 : ((MT * NT == 4) ? (BK == 16 ? 3 : 2
         for (int j = 0; j < NT; ++j) {
             const int co = n0 + (wn * NT + j) * 32 + colq;
             const bool cv = co < P.Co;
-            const float bv = (P.bias && co < P.nbias) ? P.bias[co] : 0.f;
-            const int co4 = co * 4;
+            const float bv = conv_bias_value(P, co);
 #pragma unroll
             for (int rb8 = 0; rb8 < 16; rb8 += 8) {
                 int pix[8];
-                float mk[8], rs[8];
+                float val[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    const int r = rb8 + q;
-                    const int rr = rowq + (r & 3) + 8 * (r >> 2);
+                    const int rr = acc_row(rowq, rb8 + q);
                     pix[q] = (os == 1) ? ((mt0 + rr < P.M) ? mt0 + rr : -1) : __shfl(pix_lane, rr, 64);
                     if (!cv) pix[q] = -1;
+                    val[q] = acc[i][j][rb8 + q];
                 }
-                if (has_mask) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        mk[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmk, pix[q] >= 0 ? pix[q] * ldm4 + co4 : OOB, 0, 0));
-                }
-                if (has_res) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        rs[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrs, pix[q] >= 0 ? pix[q] * ldr4 + co4 : OOB, 0, 0));
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    float v = acc[i][j][rb8 + q] + bv;
-                    if (mask_first) v = (mk[q] > 0.f) ? v : 0.f;
-                    if (has_res) v += rs[q];
-                    if (mask_last) v = (mk[q] > 0.f) ? v : 0.f;
-                    v = relu_floor(v, P.relu_out ? 0 : (int)0x80000000);
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, pix[q] >= 0 ? pix[q] * ldy4 + co4 : OOB, 0, 0);
-                }
+                ep.store8<OOB>(val, pix, co * 4, bv);
             }
         }
     }
@@ -696,12 +530,7 @@ __global__ __launch_bounds__(256, 2) void subpixel_conv_kernel(const ConvGemmPar
     };
 
     f32x16 acc[4][2];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[p][j][r] = 0.f;
+    zero_acc(acc);
 
     // GEMM row l31 of this wave = tile pixel (2*wq + l31/16, tx): second row rotated by 14 columns so that every
     // tap's ds_read_b128 hits the LDS slots like 32 consecutive rows (see vq2_resblock.hip)
@@ -750,57 +579,28 @@ __global__ __launch_bounds__(256, 2) void subpixel_conv_kernel(const ConvGemmPar
         }
     }
 
-    // ---- epilogue: output pixel (2*gy + ph, 2*gx + pw) of phase p = 2*ph + pw
-    const int ybytes = P.N * P.Hy * P.Wy * 4;
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(P.y, 0, ybytes * P.ldy, RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rmk =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.mask ? P.mask : P.y), 0, P.mask ? ybytes * P.ldm : 0, RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rrs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.res ? P.res : P.y), 0, P.res ? ybytes * P.ldr : 0, RSRC_FLAGS);
-    const bool has_mask = P.mask != nullptr, has_res = P.res != nullptr;
-    const bool mask_first = has_mask && !P.mask_after, mask_last = has_mask && P.mask_after;
+    // ---- epilogue (vq2_conv_epilogue.h): output pixel (2*gy + ph, 2*gx + pw) of phase p = 2*ph + pw
+    const ConvEpilogue ep(P);
     int pb_lane;   // output pixel of phase (0,0) for GEMM row l31, or -1
     {
         const int gy = y0 + 2 * wq + (l31 >> 4), gx = x0 + txr;
         pb_lane = (gy < P.H && gx < P.W) ? (n * P.Hy + 2 * gy) * P.Wy + 2 * gx : -1;
     }
-    const int ldy4 = P.ldy * 4, ldm4 = P.ldm * 4, ldr4 = P.ldr * 4;
 #pragma unroll
     for (int rb8 = 0; rb8 < 16; rb8 += 8) {
         int pb[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int r = rb8 + q;
-            pb[q] = __shfl(pb_lane, rowq + (r & 3) + 8 * (r >> 2), 64);
-        }
+        for (int q = 0; q < 8; ++q) pb[q] = __shfl(pb_lane, acc_row(rowq, rb8 + q), 64);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const int poff = (p >> 1) * P.Wy + (p & 1);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int co = cg * 64 + j * 32 + l31;
-                const float bv = (P.bias && co < P.nbias) ? P.bias[co] : 0.f;
-                const int co4 = co * 4;
-                float mk[8], rs[8];
-                if (has_mask) {
+                float val[8];
 #pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        mk[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmk, pb[q] >= 0 ? (pb[q] + poff) * ldm4 + co4 : SOOB, 0, 0));
-                }
-                if (has_res) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        rs[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrs, pb[q] >= 0 ? (pb[q] + poff) * ldr4 + co4 : SOOB, 0, 0));
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    float v = acc[p][j][rb8 + q] + bv;
-                    if (mask_first) v = (mk[q] > 0.f) ? v : 0.f;
-                    if (has_res) v += rs[q];
-                    if (mask_last) v = (mk[q] > 0.f) ? v : 0.f;
-                    v = relu_floor(v, P.relu_out ? 0 : (int)0x80000000);
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, pb[q] >= 0 ? (pb[q] + poff) * ldy4 + co4 : SOOB, 0, 0);
-                }
+                for (int q = 0; q < 8; ++q) val[q] = acc[p][j][rb8 + q];
+                ep.store8<SOOB>(val, pb, co * 4, conv_bias_value(P, co), poff);
             }
         }
     }
@@ -899,10 +699,7 @@ __global__ __launch_bounds__(256, 3) void conv_k4s2_c4_kernel(const ConvGemmPara
         int n, y0, x0;
         tile_of(v, n, y0, x0);
         f32x16 acc[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+        zero_acc(acc);
         u32x4 mk[2][4];
         if (HAS_MASK) {    // the mask of this lane's 16 outputs, requested BEHIND the MFMAs instead of after them
             const int oy = y0 + ty, ox = x0 + tx;
@@ -948,35 +745,27 @@ __global__ __launch_bounds__(256, 3) void conv_k4s2_c4_kernel(const ConvGemmPara
                 for (int g = 0; g < 4; ++g) {
                     const int co4 = (32 * j + 8 * g + 4 * h) * 4;
                     const float4 bv = *reinterpret_cast<const float4 *>(bias_s + 32 * j + 8 * g + 4 * h);
-                    float4 o = make_float4(acc[j][4 * g] + bv.x, acc[j][4 * g + 1] + bv.y, acc[j][4 * g + 2] + bv.z,
-                                           acc[j][4 * g + 3] + bv.w);
-                    if (HAS_MASK) {
-                        const float4 m = as_f4(mk[j][g]);
-                        o.x = m.x > 0.f ? o.x : 0.f; o.y = m.y > 0.f ? o.y : 0.f; o.z = m.z > 0.f ? o.z : 0.f; o.w = m.w > 0.f ? o.w : 0.f;
-                    }
-                    o.x = relu_floor(o.x, relu_floor_bits); o.y = relu_floor(o.y, relu_floor_bits);
-                    o.z = relu_floor(o.z, relu_floor_bits); o.w = relu_floor(o.w, relu_floor_bits);
+                    const float4 m = as_f4(mk[j][g]);
+                    // the shared rule (vq2_conv_epilogue.h) on four channels: a mask, never a residual (the plan's rule)
                     u32x4 u;
-                    u.x = __float_as_uint(o.x); u.y = __float_as_uint(o.y); u.z = __float_as_uint(o.z); u.w = __float_as_uint(o.w);
+                    u.x = __float_as_uint(conv_epilogue_value(acc[j][4 * g], bv.x, m.x, 0.f, true, false, false, relu_floor_bits));
+                    u.y = __float_as_uint(conv_epilogue_value(acc[j][4 * g + 1], bv.y, m.y, 0.f, true, false, false, relu_floor_bits));
+                    u.z = __float_as_uint(conv_epilogue_value(acc[j][4 * g + 2], bv.z, m.z, 0.f, true, false, false, relu_floor_bits));
+                    u.w = __float_as_uint(conv_epilogue_value(acc[j][4 * g + 3], bv.w, m.w, 0.f, true, false, false, relu_floor_bits));
                     __builtin_amdgcn_raw_buffer_store_b128(u, ry, pv ? pix * P.ldy * 4 + co4 : COOB, 0, 0);
                 }
         } else {
             // lane = channel l31 (+32 j); register r = pixel 4*h + (r&3) + 8*(r>>2) of this wave's 32
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int pp = 4 * h + (r & 3) + 8 * (r >> 2);
+                const int pp = acc_row(4 * h, r);
                 const int oy = y0 + 2 * wq + (pp >> 4), ox = x0 + (pp & 15);
                 const bool pv = oy < P.Ho && ox < P.Wo;
                 const int pix = (n * P.Ho + oy) * P.Wo + ox;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int co4 = (32 * j + l31) * 4;
-                    float v = acc[j][r] + bias_s[32 * j + l31];
-                    if (HAS_MASK) {
-                        const float m = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmk, pv ? pix * P.ldm * 4 + co4 : COOB, 0, 0));
-                        v = m > 0.f ? v : 0.f;
-                    }
-                    v = relu_floor(v, relu_floor_bits);
+                    const float v = conv_epilogue_value(acc[j][r], bias_s[32 * j + l31], 0.f, 0.f, false, false, false, relu_floor_bits);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, pv ? pix * P.ldy * 4 + co4 : COOB, 0, 0);
                 }
             }
@@ -993,7 +782,7 @@ __global__ __launch_bounds__(256, 3) void conv_k4s2_c4_kernel(const ConvGemmPara
 // workgroup of eight waves (one per CU: 52 KB of panel + 8 x 8.7 KB of row tiles), every wave streams 32-pixel row blocks of
 // its own through a private LDS tile (no workgroup barrier in the loop; LDS operations of one wave execute in order, so the
 // tile needs no second buffer: the next block's loads are in flight while this block's MFMAs and stores run) and walks a
-// strided range of blocks.  Epilogue = the generic one (bias, ReLU mask, residual, ReLU).
+// strided range of blocks.  Epilogue = the one of vq2_conv_epilogue.h (bias, ReLU mask, residual, ReLU).
 namespace k64 {
 constexpr int KC = 64, LDW = KC + 4;               // 272-byte LDS rows: conflict-free ds_read_b128
 constexpr int X_FLOATS = 32 * LDW;                 // one wave's row block
@@ -1037,20 +826,11 @@ __global__ __launch_bounds__(512, 2) void conv1x1_k64_kernel(const ConvGemmParam
             *reinterpret_cast<float4 *>(xs + (srow + 4 * j) * LDW + 4 * sq) = RELU_IN ? relu4(v) : v;
         }
     };
-    const int ybytes = P.M * 4;
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(P.y, 0, ybytes * P.ldy, RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rmk =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.mask ? P.mask : P.y), 0, P.mask ? ybytes * P.ldm : 0, RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rrs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.res ? P.res : P.y), 0, P.res ? ybytes * P.ldr : 0, RSRC_FLAGS);
-    const bool has_mask = P.mask != nullptr, has_res = P.res != nullptr;
-    const bool mask_first = has_mask && !P.mask_after, mask_last = has_mask && P.mask_after;
+    const ConvEpilogue ep(P);   // (a 1x1 layer: M = N * Hy * Wy output pixels)
     const int colq = lane & 31, rowq = 4 * (lane >> 5), fk = 4 * (lane >> 5);
-    const int ldy4 = P.ldy * 4, ldm4 = P.ldm * 4, ldr4 = P.ldr * 4;
-    const int relu_bits = P.relu_out ? 0 : (int)0x80000000;
     float bv[NB];
 #pragma unroll
-    for (int j = 0; j < NB; ++j) bv[j] = (P.bias && j * 32 + colq < P.nbias) ? P.bias[j * 32 + colq] : 0.f;
+    for (int j = 0; j < NB; ++j) bv[j] = conv_bias_value(P, j * 32 + colq);
 
     load_block(gw);
     __syncthreads();                       // the panel (the only workgroup-wide dependency)
@@ -1059,10 +839,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_k64_kernel(const ConvGemmParam
         store_block(xs);                   // wave-private tile: program order + the LDS counter are the only sync needed
         load_block(b + nwaves);            // next block of this wave, in flight behind the MFMAs and stores below
         f32x16 acc[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+        zero_acc(acc);
         const float *a = xs + colq * LDW + fk;
         const float *w = Ws + colq * LDW + fk;
 #pragma unroll
@@ -1080,36 +857,17 @@ __global__ __launch_bounds__(512, 2) void conv1x1_k64_kernel(const ConvGemmParam
         const int m0 = b * 32;
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-            const int co4 = (j * 32 + colq) * 4;
 #pragma unroll
             for (int rb8 = 0; rb8 < 16; rb8 += 8) {
                 int pix[8];
-                float mk[8], rs[8];
+                float val[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    const int r = rb8 + q;
-                    const int m = m0 + rowq + (r & 3) + 8 * (r >> 2);
+                    const int m = m0 + acc_row(rowq, rb8 + q);
                     pix[q] = m < P.M ? m : -1;
+                    val[q] = acc[j][rb8 + q];
                 }
-                if (has_mask) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        mk[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmk, pix[q] >= 0 ? pix[q] * ldm4 + co4 : OOB, 0, 0));
-                }
-                if (has_res) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        rs[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrs, pix[q] >= 0 ? pix[q] * ldr4 + co4 : OOB, 0, 0));
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    float v = acc[j][rb8 + q] + bv[j];
-                    if (mask_first) v = (mk[q] > 0.f) ? v : 0.f;
-                    if (has_res) v += rs[q];
-                    if (mask_last) v = (mk[q] > 0.f) ? v : 0.f;
-                    v = relu_floor(v, relu_bits);
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, pix[q] >= 0 ? pix[q] * ldy4 + co4 : OOB, 0, 0);
-                }
+                ep.store8<OOB>(val, pix, (j * 32 + colq) * 4, bv[j]);
             }
         }
     }

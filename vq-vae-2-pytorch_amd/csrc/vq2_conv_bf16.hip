@@ -1,7 +1,7 @@
 // bf16-operand implicit-GEMM conv forward / data gradient for gfx950 (MI355X): the stage-2 layers (same_size == 1).
 //
-//   y = sum_k bf16(a_k) * bf16(w_k), accumulated in fp32 by v_mfma_f32_32x32x16_bf16, then the fp32 epilogue of
-//   conv_gemm_kernel (bias, mask, residual, ReLU-out).  bf16() is round-to-nearest-even of the fp32 value.
+//   y = sum_k bf16(a_k) * bf16(w_k), accumulated in fp32 by v_mfma_f32_32x32x16_bf16, then the one fp32 conv
+//   epilogue (vq2_conv_epilogue.h: bias, mask, residual, ReLU-out).  bf16() is round-to-nearest-even of the fp32 value.
 //
 //   GEMM rows  m = (n, h, w) output pixels        GEMM cols  co        GEMM depth  k = (kh, kw, ci), ci fastest
 //
@@ -59,40 +59,18 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf16_kernel(const ConvGemmPa
     // ---- per-thread staging coordinates (fixed over the K loop)
     const int lrow = tid >> 2;          // 0..63
     const int lk = (tid & 3) * 8;       // first of this thread's 8 k inside a chunk
-    int a_pix[A_LD], a_h[A_LD], a_w[A_LD];
-    const int HW = P.H * P.W;
-#pragma unroll
-    for (int j = 0; j < A_LD; ++j) {
-        const int m = m0 + lrow + RPP * j;
-        if (m < P.M) {
-            const int n = m / HW;
-            const int r = m - n * HW;
-            const int ho = r / P.W;
-            a_h[j] = ho - P.pad_h;
-            a_w[j] = r - ho * P.W - P.pad_w;
-            a_pix[j] = (n * P.H + a_h[j]) * P.W + a_w[j];
-        } else {
-            a_h[j] = -(1 << 24); a_w[j] = 0; a_pix[j] = 0;   // every bounds test fails
-        }
-    }
-    int kglob = lk, ci, kh, kw;
-    {
-        const int tap = kglob / P.Ci;
-        ci = kglob - tap * P.Ci;
-        kh = tap / P.KW;
-        kw = tap - kh * P.KW;
-    }
+    const GatherRows<A_LD> rows(P, m0 + lrow, RPP, P.H, P.W, 1, P.pad_h, P.pad_w);   // same_size: the output grid is the input's
+    KWalker kk(P, lk);
 
     float4 ra[A_LD][2];
     uint4 rb[B_LD];
     auto load_chunk = [&]() {
-        const bool kv = kglob < P.K;
+        const bool kv = kk.k < P.K;
 #pragma unroll
         for (int j = 0; j < A_LD; ++j) {
-            const bool v = kv && (unsigned)(a_h[j] + kh) < (unsigned)P.H && (unsigned)(a_w[j] + kw) < (unsigned)P.W;
             ra[j][0] = ra[j][1] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (v) {
-                const float4 *src = reinterpret_cast<const float4 *>(xp + (size_t)(a_pix[j] + kh * P.W + kw) * P.ldx + ci);
+            if (kv && rows.inside(P, j, kk.kh, kk.kw)) {
+                const float4 *src = reinterpret_cast<const float4 *>(xp + rows.at(P, j, kk.kh, kk.kw, kk.ci));
                 ra[j][0] = src[0];
                 ra[j][1] = src[1];
             }
@@ -101,15 +79,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf16_kernel(const ConvGemmPa
         for (int j = 0; j < B_LD; ++j) {
             const int co = n0 + lrow + RPP * j;
             rb[j] = make_uint4(0u, 0u, 0u, 0u);
-            if (kv && co < P.Co) rb[j] = *reinterpret_cast<const uint4 *>(wp + (size_t)co * P.K + kglob);
-        }
-    };
-    auto advance_k = [&]() {
-        kglob += BK;
-        ci += BK;
-        while (ci >= P.Ci) {
-            ci -= P.Ci;
-            if (++kw == P.KW) { kw = 0; ++kh; }
+            if (kv && co < P.Co) rb[j] = *reinterpret_cast<const uint4 *>(wp + (size_t)co * P.K + kk.k);
         }
     };
     auto store_chunk = [&](int buf) {
@@ -123,12 +93,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf16_kernel(const ConvGemmPa
     };
 
     f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // operand maps of v_mfma_f32_32x32x16_bf16: lane l holds A[row l & 31][k = 8 (l >> 5) + j] and B[k][col l & 31], j < 8
     const int frag_row = lane & 31, frag_k = 8 * (lane >> 5);
@@ -161,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf16_kernel(const ConvGemmPa
     for (int c = 0; c < nchunks; ++c) {
         const int buf = c & 1;
         if (c + 1 < nchunks) {
-            advance_k();
+            kk.advance(P, BK);
             load_chunk();   // global loads in flight while the matrix pipe works on chunk c
         }
         compute(buf);
@@ -169,52 +134,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf16_kernel(const ConvGemmPa
         __syncthreads();
     }
 
-    // ---- epilogue (conv_gemm_kernel's, one output pixel per GEMM row): lane holds column (lane & 31) of 16 rows per
-    // 32x32 tile, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  Mask / residual loads are issued before the stores.
-    const float *__restrict__ maskp = P.mask;
-    const float *__restrict__ resp = P.res;
-    float *__restrict__ yp = P.y;
-    const int colq = lane & 31, rowq = 4 * (lane >> 5);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int co = n0 + (wn * NT + j) * 32 + colq;
-        const bool cv = co < P.Co;
-        const float bv = (P.bias && co < P.nbias) ? P.bias[co] : 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int mb = m0 + (wm * MT + i) * 32 + rowq;
-#pragma unroll
-            for (int rb8 = 0; rb8 < 16; rb8 += 8) {
-                bool ok[8];
-                size_t pix[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int r = rb8 + q;
-                    const int m = mb + (r & 3) + 8 * (r >> 2);
-                    ok[q] = cv && m < P.M;
-                    pix[q] = (size_t)m;
-                }
-                float mk[8], rs[8];
-                if (maskp) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) mk[q] = ok[q] ? maskp[pix[q] * P.ldm + co] : 0.f;
-                }
-                if (resp) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) rs[q] = ok[q] ? resp[pix[q] * P.ldr + co] : 0.f;
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    float v = acc[i][j][rb8 + q] + bv;
-                    if (maskp && !P.mask_after) v = (mk[q] > 0.f) ? v : 0.f;
-                    if (resp) v += rs[q];
-                    if (maskp && P.mask_after) v = (mk[q] > 0.f) ? v : 0.f;
-                    v = relu_floor(v, P.relu_out ? 0 : (int)0x80000000);
-                    if (ok[q]) yp[pix[q] * P.ldy + co] = v;
-                }
-            }
-        }
-    }
+    // ---- epilogue: the pointer form of the one conv epilogue (vq2_conv_epilogue.h), one output pixel per GEMM row
+    conv_epilogue_pointers<MT, NT>(P, acc, m0, n0, wm, wn, lane, 1, 0, 0);
 }
 
 template <int MT, int NT>

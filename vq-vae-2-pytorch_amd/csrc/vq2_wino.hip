@@ -48,57 +48,27 @@ __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(
 // Epilogue shared by the kernels of this file: lane (lane & 31) of a wave holds the first output pixel of its pair in
 // pix_lane (shared through ds_bpermute), the second one is dpix further; vals(j, r, y0, y1) yields the two outputs of
 // accumulator row r of column block j.
-// Then exactly the direct kernel's epilogue (vq2_conv.hip): bias, ReLU mask, residual, ReLU, strided store.
+// Then the one conv epilogue (vq2_conv_epilogue.h) on four pairs at a time; every pixel of a tile lies inside the image.
 template <int NT, class F>
 __device__ __forceinline__ void store_pairs(const ConvGemmParams &P, int co0, int lane, int pix_lane, F vals, int dpix = 1) {
-    const int ybytes = P.N * P.Hy * P.Wy * 4;
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(P.y, 0, ybytes * P.ldy, RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rmk =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.mask ? P.mask : P.y), 0, P.mask ? ybytes * P.ldm : 0, RSRC_FLAGS);
-    const __amdgpu_buffer_rsrc_t rrs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.res ? P.res : P.y), 0, P.res ? ybytes * P.ldr : 0, RSRC_FLAGS);
-    const bool has_mask = P.mask != nullptr, has_res = P.res != nullptr;
-    const bool mask_first = has_mask && !P.mask_after, mask_last = has_mask && P.mask_after;
+    const ConvEpilogue ep(P);
     const int colq = lane & 31, rowq = 4 * (lane >> 5);
-    const int ldy4 = P.ldy * 4, ldm4 = P.ldm * 4, ldr4 = P.ldr * 4;
-    const int relu_bits = P.relu_out ? 0 : (int)0x80000000;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int co = co0 + j * 32 + colq;
-        const float bv = (P.bias && co < P.nbias) ? P.bias[co] : 0.f;
-        const int co4 = co * 4;
+        const float bv = conv_bias_value(P, co);
 #pragma unroll
         for (int rb4 = 0; rb4 < 16; rb4 += 4) {
             int pix[8];
-            float mk[8], rs[8], val[8];
+            float val[8];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int r = rb4 + q;
-                const int rr = rowq + (r & 3) + 8 * (r >> 2);
-                const int p0 = __shfl(pix_lane, rr, 64);
+                const int p0 = __shfl(pix_lane, acc_row(rowq, rb4 + q), 64);
                 pix[2 * q] = p0;
                 pix[2 * q + 1] = p0 + dpix;
-                vals(j, r, val[2 * q], val[2 * q + 1]);
+                vals(j, rb4 + q, val[2 * q], val[2 * q + 1]);
             }
-            if (has_mask) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    mk[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmk, pix[q] * ldm4 + co4, 0, 0));
-            }
-            if (has_res) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    rs[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrs, pix[q] * ldr4 + co4, 0, 0));
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                float v = val[q] + bv;
-                if (mask_first) v = (mk[q] > 0.f) ? v : 0.f;
-                if (has_res) v += rs[q];
-                if (mask_last) v = (mk[q] > 0.f) ? v : 0.f;
-                v = relu_floor(v, relu_bits);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, pix[q] * ldy4 + co4, 0, 0);
-            }
+            ep.store8<ALL_VALID>(val, pix, co * 4, bv);
         }
     }
 }
@@ -167,12 +137,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void wino3_kernel(const ConvG
     };
 
     f32x16 acc[4][NT];
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[v][j][r] = 0.f;
+    zero_acc(acc);
 
     const int frag_row = lane & 31, frag_k = 4 * (lane >> 5);
     const int pi = wm * 32 + frag_row;                 // this lane's column pair of the tile
@@ -356,12 +321,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void wino_k4s2_kernel(const C
     };
 
     f32x16 acc[3][NT];
-#pragma unroll
-    for (int v = 0; v < 3; ++v)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[v][j][r] = 0.f;
+    zero_acc(acc);
 
     const int frag_row = lane & 31, frag_k = 4 * (lane >> 5);
     const int pi = wm * 32 + frag_row;                                   // this lane's pair of the tile
@@ -543,12 +503,7 @@ __global__ __launch_bounds__(256, 2) void wino_subpixel_kernel(const ConvGemmPar
     };
 
     f32x16 acc[3][NT];
-#pragma unroll
-    for (int v = 0; v < 3; ++v)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[v][j][r] = 0.f;
+    zero_acc(acc);
 
     const int frag_row = lane & 31, frag_k = 4 * (lane >> 5);
     const int pi = wave * 32 + frag_row;                                 // this lane's pair of the tile
