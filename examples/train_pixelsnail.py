@@ -61,8 +61,8 @@ def parse_args(argv=None):
     parser.add_argument('--eval_every', type=int, default=0)
     parser.add_argument('--clip_grad_norm', type=float, default=None)
     parser.add_argument('--ema_decay', type=float, default=None)
-    parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16'],
-                        help='fp32 (default), or bf16: the eligible conv forwards and data gradients multiply bf16-rounded operands and accumulate in fp32; weight gradients, weights, optimizer state and every stored tensor stay fp32 (no loss scaling); the counterpart of --amp O1 of the reference')
+    parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16', 'bf16_wgrad'],
+                        help='fp32 (default), or bf16: the eligible conv forwards and data gradients multiply bf16-rounded operands and accumulate in fp32; weight gradients, weights, optimizer state and every stored tensor stay fp32 (no loss scaling); the counterpart of --amp O1 of the reference; bf16_wgrad: as bf16, and the eligible weight gradients (input and output channels both multiples of 16) multiply bf16-rounded x and dy as well, bias gradients stay fp32 sums')
     return parser.parse_args(argv)
 
 
@@ -114,8 +114,8 @@ def main(argv=None):
     model = model.to(device).train()
     trainer = vqvae2_amd.Stage2Trainer(model, args.hier, lr=args.lr, sched=args.sched, n_iter=len(loader) * args.epoch,
                                        clip_grad_norm=clip_grad_norm, ema_decay=ema_decay)
-    if precision == 'bf16':
-        trainer.set_precision('bf16')
+    if precision in ('bf16', 'bf16_wgrad'):
+        trainer.set_precision(precision)
     first_epoch = 0
     if resume is not None:
         trainer.load_state_dict(resume['trainer'] if 'trainer' in resume else resume)

@@ -60,11 +60,13 @@ typedef void *vq2_stream_t;
  * revision 15: additions only -- vq2_prior_eval_rows and vq2_prior_eval_accumulate, the held-out evaluation of the stage-2 prior;
  * revision 16: additions only -- vq2_grad_norm with its workspace query and vq2_adam_step_ex (global-norm clipping, skipped
  * steps, averaged weights); revision 17: additions only -- the bf16-operand conv forward / data gradient: the flag
- * VQ2_ALLOW_BF16, the panels VQ2_PACK_FWD_BF16 / VQ2_PACK_DGRAD_BF16 and vq2_conv_bf16_eligible.
+ * VQ2_ALLOW_BF16, the panels VQ2_PACK_FWD_BF16 / VQ2_PACK_DGRAD_BF16 and vq2_conv_bf16_eligible; revision 18: additions
+ * only -- the bf16-operand weight gradient: VQ2_ALLOW_BF16 in the flags of vq2_conv_wgrad / vq2_conv_wgrad_partial (ignored
+ * before), vq2_conv_wgrad_bf16_eligible, vq2_conv_wgrad_workspace_bytes_ex and vq2_wgrad_job_init_ex.
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 17
+#define VQ2_API_VERSION 18
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -132,8 +134,8 @@ typedef struct vq2_conv_desc {
  * followed by the unchanged fp32 epilogue (bias, mask, residual, ReLU-out).  bf16() is round-to-nearest-even of the fp32
  * value (tensor.to(torch.bfloat16)); a = the input activation (after VQ2_RELU_IN) and w the weight for the forward, a = dy
  * and w the flipped weight for the data gradient.  Every tensor in memory keeps its fp32 format and layout; the weight
- * gradient is not affected (it reads the unrounded x and dy).  No atomics and no split-K: bit-reproducible, and an image's
- * result does not depend on the batch it is in.
+ * gradient is not affected by the flag of these two launches (it has a permission of its own, below).  No atomics and no
+ * split-K: bit-reproducible, and an image's result does not depend on the batch it is in.
  * Eligibility, vq2_conv_bf16_eligible(d, dgrad): same_size == 1 and the depth-side channel count -- Ci for the forward
  * (dgrad = 0), Co for the data gradient (dgrad = 1) -- a multiple of 16.  An eligible launch with the flag reads `wp` as
  * the VQ2_PACK_FWD_BF16 / VQ2_PACK_DGRAD_BF16 panel; every other launch plans exactly as without the flag and reads the
@@ -145,6 +147,19 @@ typedef struct vq2_conv_desc {
 #define VQ2_PACK_FWD_BF16 2   /* operand of vq2_conv_fwd   with VQ2_ALLOW_BF16, eligible layers */
 #define VQ2_PACK_DGRAD_BF16 3 /* operand of vq2_conv_dgrad with VQ2_ALLOW_BF16, eligible layers */
 int vq2_conv_bf16_eligible(const vq2_conv_desc *d, int dgrad);
+/* The same bit in `flags` of vq2_conv_wgrad and vq2_conv_wgrad_partial is the permission of the WEIGHT GRADIENT, independent
+ * of the other two.  With it, a layer for which vq2_conv_wgrad_bf16_eligible() holds -- same_size == 1 and both Ci % 16 == 0
+ * and Co % 16 == 0 -- computes
+ *     dw[o][i][kh][kw] = sum over (n,h,w) of  bf16(dy[n,h,w,o]) * bf16(a[n, h-pad_top+kh, w-pad_left+kw, i])
+ * a = x, or relu(x) under VQ2_RELU_IN (the ReLU first, then the rounding); accumulated in fp32 by the matrix instruction;
+ * reads outside the image are 0; every tap enters.  db stays the fp32 sum of the UNROUNDED dy.  Every tensor in memory keeps
+ * its fp32 format and layout.  The split over the pixels stays deterministic: fp32 slabs [S][O][K] and bias partials [S][O]
+ * in the caller's workspace (vq2_wgrad_job.swapped = 0), summed in fixed order by the same reduction as the fp32 launch; no
+ * atomics, two runs give the same bits.  The launch has a plan of its own (plain roles, no Winograd mode, its own tile and
+ * split), so its workspace size and its reduction job differ from the fp32 launch's: ask vq2_conv_wgrad_workspace_bytes_ex
+ * and vq2_wgrad_job_init_ex with the SAME flags as the launch.  Every other layer, flag or not, plans and runs exactly as
+ * without it. */
+int vq2_conv_wgrad_bf16_eligible(const vq2_conv_desc *d);
 int vq2_pack_weight(const vq2_conv_desc *d, int which, const float *w, float *packed, vq2_stream_t stream);
 
 /* Re-packing every layer after an optimizer step in ONE launch: fill one job per (layer, which) on
@@ -207,8 +222,10 @@ int vq2_conv_dgrad(const vq2_conv_desc *d, int flags, const float *dy, const flo
 
 /* dw (reference layout, OIHW or IOHW) = wgrad([relu]x, dy) and, if db != NULL, db[Cor] = sum over
  * pixels of dy (bias gradient, fused).  Deterministic split-K: partial slabs in `ws`, then an
- * ordered reduction.  flags: VQ2_RELU_IN. */
+ * ordered reduction.  flags: VQ2_RELU_IN, VQ2_ALLOW_BF16 (see there).  vq2_conv_wgrad_workspace_bytes_ex(d, flags) is the
+ * workspace of a launch with these flags (only VQ2_ALLOW_BF16 matters); vq2_conv_wgrad_workspace_bytes(d) its flags = 0 case. */
 size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d);
+size_t vq2_conv_wgrad_workspace_bytes_ex(const vq2_conv_desc *d, int flags);
 int vq2_conv_wgrad(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *dw, float *db, void *ws,
                    size_t ws_bytes, vq2_stream_t stream);
 
@@ -234,6 +251,8 @@ typedef struct vq2_wgrad_job {
 int vq2_conv_wgrad_partial(const vq2_conv_desc *d, int flags, const float *x, const float *dy, float *db, void *ws,
                            size_t ws_bytes, vq2_stream_t stream);
 int vq2_wgrad_job_init(const vq2_conv_desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job);
+/* the job of a vq2_conv_wgrad_partial launch with `flags` (vq2_wgrad_job_init is its flags = 0 case) */
+int vq2_wgrad_job_init_ex(const vq2_conv_desc *d, int flags, const void *ws, float *dw, float *db, vq2_wgrad_job *job);
 int vq2_wgrad_reduce_batched(const vq2_wgrad_job *jobs_dev, int32_t njobs, int64_t total_units, vq2_stream_t stream);
 /* job of the 1x1 weight gradient that vq2_resblock_bwd_data left in `ws` (see there) */
 int vq2_resblock_w2_job_init(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Cm, const void *ws, float *dw, float *db,

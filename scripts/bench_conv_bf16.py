@@ -5,6 +5,12 @@ TFLOP/s from the minimum.  The weight panels are packed once (the weight does no
 in these numbers: scripts/bench_pixelsnail.py --amp O1 times the step that contains them.
 
     python scripts/bench_conv_bf16.py [--out FILE]      (default profiles/conv_bf16.json)
+
+--wgrad times the weight gradient of the same layers by the same method instead: the fp32 launch (its own plan: exchanged
+roles or a Winograd mode where the layer has one) against the bf16-operand launch (ConvSpec.bf16_wgrad), each with its
+reduction and the fused bias gradient, alternated inside every repeat.
+
+    python scripts/bench_conv_bf16.py --wgrad [--out FILE]      (default profiles/wgrad_bf16.json)
 """
 import argparse
 import dataclasses
@@ -47,7 +53,7 @@ def time_ms(fn, inner):
     return a.elapsed_time(b) / inner
 
 
-def measure(ops, shape):
+def measure(ops, shape, wgrad=False):
     name, ci, co, kh, kw, pt, pl, n, h, w = shape
     dev = torch.device("cuda:0")
     s32 = ops.ConvSpec.geom(ci, co, kh, kw, pt, pl)
@@ -58,7 +64,10 @@ def measure(ops, shape):
     b = torch.randn(co, device=dev)
     y = torch.empty(n, h, w, co, device=dev)
     dx = torch.empty(n, h, w, ci, device=dev)
-    fns = {"fwd32": lambda: ops.conv_forward(s32, x, wt, b, out=y),
+    w16 = dataclasses.replace(s32, bf16_wgrad=True)
+    fns = {"wg32": lambda: ops.conv_wgrad(s32, x, dy, False, wt, b),
+           "wg16": lambda: ops.conv_wgrad(w16, x, dy, False, wt, b)} if wgrad else \
+          {"fwd32": lambda: ops.conv_forward(s32, x, wt, b, out=y),
            "fwd16": lambda: ops.conv_forward(s16, x, wt, b, out=y),
            "dg32": lambda: ops.conv_dgrad(s32, x.shape, dy, wt, out=dx),
            "dg16": lambda: ops.conv_dgrad(s16, x.shape, dy, wt, out=dx)}
@@ -80,16 +89,21 @@ def measure(ops, shape):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_bf16.json"))
+    ap.add_argument("--wgrad", action="store_true", help="time the weight gradient (fp32 against bf16 operands) instead")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "wgrad_bf16.json" if args.wgrad else "conv_bf16.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_conv_bf16.py needs the MI355X")
     from vqvae2_amd import ops
     rows = []
     for shape in SHAPES:
-        rows.append(measure(ops, shape))
+        rows.append(measure(ops, shape, args.wgrad))
         print(json.dumps(rows[-1]), flush=True)
-    out = {"what": "conv forward / data gradient, fp32 kernel vs bf16-operand kernel (VQ2_ALLOW_BF16); the four launches of a "
+    what = "conv weight gradient with its reduction and bias gradient, fp32 launch (wg32) vs bf16-operand launch (wg16, " \
+           "VQ2_ALLOW_BF16); the two launches" if args.wgrad else \
+           "conv forward / data gradient, fp32 kernel vs bf16-operand kernel (VQ2_ALLOW_BF16); the four launches"
+    out = {"what": what + " of a "
                    f"layer alternated in one process, {WARMUP} warm-up launches, {REPEATS} windows of {INNER} launches between "
                    "two events, [min, max] ms per launch; TFLOP/s from the minimum; the shape name ends in the batch where "
                    "it is not 32 x 32x32 (top, unnamed) or 8 x 64x64 (bottom)",

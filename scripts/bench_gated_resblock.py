@@ -15,7 +15,12 @@ time of the WHOLE block call, so it is a lower bound for the conv kernels, again
 (vqvae2_amd.set_conv_precision), built from the same weights; "fused" is then the fp32 block and "eager" reads "bf16" in
 every key, the rate of the bf16 block is taken against the 2,500 TFLOP/s bf16 dense peak, and the agreement bound is 2e-2
 of the largest output (two operand roundings of 2^-9 each, through two convs).  Default output
-profiles/gated_resblock_bf16.json."""
+profiles/gated_resblock_bf16.json.
+
+--precision bf16_wgrad: the two paths are the block with bf16 conv operands ("fused" in every key) and the same block with
+bf16 weight gradients as well ("bf16_wgrad" in every key), built from the same weights.  Both rates are then taken against
+the bf16 dense peak ("peak_tflops" in the output says so), and the two forwards are the same launches.  Default output
+profiles/gated_resblock_bf16_wgrad.json."""
 import argparse
 import copy
 import json
@@ -50,24 +55,26 @@ def time_ms(fn, inner):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/gated_resblock.json, gated_resblock_bf16.json with --precision bf16")
-    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
-                    help="bf16: time the block with bf16 conv operands against the fp32 block instead of eager torch")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16_wgrad"],
+                    help="bf16: time the block with bf16 conv operands against the fp32 block instead of eager torch; "
+                         "bf16_wgrad: the block with bf16 weight gradients too against the bf16 block (then 'fused' in every key)")
     ap.add_argument("--repeats", type=int, default=5, help="timed repeats per path (one more is run first and discarded)")
     ap.add_argument("--inner", type=int, default=10)
     args = ap.parse_args()
-    low = args.precision == "bf16"
-    other = "bf16" if low else "eager"
+    low = args.precision != "fp32"
+    other = args.precision if low else "eager"
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "gated_resblock_bf16.json" if low else "gated_resblock.json")
+        args.out = os.path.join(ROOT, "profiles", "gated_resblock_%s.json" % args.precision if low else "gated_resblock.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_gated_resblock.py needs the MI355X")
     import vqvae2_amd
     import _pixelsnail_ref as R
     dev = torch.device("cuda:0")
+    fused_peak = PEAK_BF16_TFLOPS if args.precision == "bf16_wgrad" else PEAK_TFLOPS     # "fused" is the bf16 block there
     results = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "inner": args.inner,
-               "peak_tflops": PEAK_TFLOPS, "cases": []}
+               "peak_tflops": fused_peak, "cases": []}
     if low:
-        results.update(precision="bf16", peak_bf16_tflops=PEAK_BF16_TFLOPS)
+        results.update(precision=args.precision, peak_bf16_tflops=PEAK_BF16_TFLOPS)
     for c in CASES:
         b, hw, cin, ch = c["b"], c["hw"], c["cin"], c["ch"]
         torch.manual_seed(0)
@@ -77,7 +84,9 @@ def main():
         mod16 = None
         if low:
             mod16 = copy.deepcopy(mod)
-            vqvae2_amd.set_conv_precision(mod16, "bf16")
+            vqvae2_amd.set_conv_precision(mod16, args.precision)
+            if args.precision == "bf16_wgrad":      # bf16 against bf16_wgrad: the same forward and data gradient on both sides
+                vqvae2_amd.set_conv_precision(mod, "bf16")
 
         def act(channels):
             return torch.randn(b, channels, hw, hw, device=dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
@@ -140,7 +149,7 @@ def main():
                             "fused_spread": (max(tf) - min(tf)) / mf, other + "_spread": (max(te) - min(te)) / me,
                             other + "_over_fused": me / mf, "counted_conv_flop": flop,
                             "fused_conv_tflops": flop / (mf * 1e-3) / 1e12,
-                            "fused_fraction_of_peak": flop / (mf * 1e-3) / 1e12 / PEAK_TFLOPS}
+                            "fused_fraction_of_peak": flop / (mf * 1e-3) / 1e12 / fused_peak}
                 if low:
                     row[tag].update(bf16_conv_tflops=flop / (me * 1e-3) / 1e12,
                                     bf16_fraction_of_peak=flop / (me * 1e-3) / 1e12 / PEAK_BF16_TFLOPS)

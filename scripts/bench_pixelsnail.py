@@ -17,7 +17,8 @@ same number of pixels per step), dropout 0.1, random codes from a seed.  Per mod
 Writes one JSON document (default profiles/pixelsnail.json).  No GPU: fails.  Not measured here: kernel times (no
 profiler run), anything on more than one GPU.
 
---amp O1: instead, per model, the arena trainer with bf16 conv operands (Stage2Trainer.set_precision('bf16')) against the
+--amp O1: instead, per model, the arena trainers with bf16 conv operands (Stage2Trainer.set_precision('bf16'), and
+'bf16_wgrad' with bf16 weight gradients as well) against the
 arena trainer in fp32, from the same weights, alternating in the same way; the first losses must agree to 1e-2 relative
 (they cannot be bit-equal).  Default output profiles/pixelsnail_bf16.json."""
 import argparse
@@ -153,7 +154,8 @@ def bench_model(amd, spec, repeats, inner):
 
 
 def bench_amp(amd, spec, repeats, inner):
-    """One model: the fp32 arena trainer against the bf16 one, alternated."""
+    """One model: the fp32 arena trainer, the bf16 one and the bf16_wgrad one (bf16 weight gradients too), from the same
+    weights, alternated."""
     dev = torch.device("cuda:0")
     h, w = spec["shape"]
     gen = torch.Generator().manual_seed(1)
@@ -165,18 +167,18 @@ def bench_amp(amd, spec, repeats, inner):
     state = amd.PixelSNAIL(spec["shape"], *spec["args"], dropout=0.1, **spec["kw"]).state_dict()
     row = {"name": spec["name"], "shape": spec["shape"], "batch": spec["batch"], "args": spec["args"], "kw": spec["kw"]}
     trainers, first = {}, {}
-    for prec in ("fp32", "bf16"):
+    for prec in ("fp32", "bf16", "bf16_wgrad"):
         m = amd.PixelSNAIL(spec["shape"], *spec["args"], dropout=0.1, **spec["kw"])
         m.load_state_dict(state)
         tr = amd.Stage2Trainer(m.to(dev).train(), spec["hier"], lr=3e-4, sched="cycle", n_iter=1000)
-        if prec == "bf16":
-            row["eligible_layers"], row["conv_layers"] = tr.set_precision("bf16")
+        if prec != "fp32":
+            row["eligible_layers"], row["conv_layers"] = tr.set_precision(prec)
         torch.manual_seed(7)
         first[prec] = float(tr.step(*step_args)["loss"])
         tr.step(*step_args)
         trainers[prec] = tr
     row["first_loss"] = first
-    if not abs(first["bf16"] - first["fp32"]) <= 1e-2 * abs(first["fp32"]):
+    if not max(abs(first[p] - first["fp32"]) for p in first) <= 1e-2 * abs(first["fp32"]):
         raise SystemExit(f"{spec['name']}: first losses {first} are further apart than 1e-2 relative; not timed")
     fns = {p: (lambda t=t: t.step(*step_args)) for p, t in trainers.items()}
     torch.cuda.synchronize()
@@ -189,9 +191,11 @@ def bench_amp(amd, spec, repeats, inner):
         med = statistics.median(v)
         row[p + "_ms"], row[p + "_median_ms"], row[p + "_spread"] = v, med, (max(v) - min(v)) / med
     row["fp32_over_bf16"] = row["fp32_median_ms"] / row["bf16_median_ms"]
+    row["bf16_over_bf16_wgrad"] = row["bf16_median_ms"] / row["bf16_wgrad_median_ms"]
+    row["fp32_over_bf16_wgrad"] = row["fp32_median_ms"] / row["bf16_wgrad_median_ms"]
     print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()
                       if k in ("name", "batch", "fp32_median_ms", "bf16_median_ms", "fp32_spread", "bf16_spread", "fp32_over_bf16",
-                               "eligible_layers", "conv_layers", "first_loss")}), flush=True)
+                               "bf16_wgrad_median_ms", "bf16_wgrad_spread", "bf16_over_bf16_wgrad", "eligible_layers", "conv_layers", "first_loss")}), flush=True)
     return row
 
 

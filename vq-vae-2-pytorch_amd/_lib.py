@@ -67,10 +67,13 @@ def _load():
         "vq2_pack_weights_batched": (C.c_int, [P, I32, I64, P]),
         "vq2_conv_fwd": (C.c_int, [DP, C.c_int, P, P, P, P, I32, P, P]),
         "vq2_conv_dgrad": (C.c_int, [DP, C.c_int, P, P, P, I32, P, I32, P, I32, P]),
+        "vq2_conv_wgrad_bf16_eligible": (C.c_int, [DP]),
         "vq2_conv_wgrad_workspace_bytes": (SZ, [DP]),
+        "vq2_conv_wgrad_workspace_bytes_ex": (SZ, [DP, C.c_int]),
         "vq2_conv_wgrad": (C.c_int, [DP, C.c_int, P, P, P, P, P, SZ, P]),
         "vq2_conv_wgrad_partial": (C.c_int, [DP, C.c_int, P, P, P, P, SZ, P]),
         "vq2_wgrad_job_init": (C.c_int, [DP, P, P, P, C.POINTER(WgradJob)]),
+        "vq2_wgrad_job_init_ex": (C.c_int, [DP, C.c_int, P, P, P, C.POINTER(WgradJob)]),
         "vq2_wgrad_reduce_batched": (C.c_int, [P, I32, I64, P]),
         "vq2_colsum_workspace_bytes": (SZ, [I64, I32]),
         "vq2_colsum": (C.c_int, [P, I64, I32, I32, P, P, SZ, P]),

@@ -1,5 +1,5 @@
 // Launch parameters, kernel plan, host helpers and the device-side GEMM skeleton shared by the conv kernels of libvq2
-// (vq2_conv.hip, vq2_conv_bf16.hip, vq2_wino.hip, vq2_wgrad.hip); the epilogue contract is vq2_conv_epilogue.h, included below.
+// (vq2_conv.hip, vq2_conv_bf16.hip, vq2_wino.hip, vq2_wgrad.hip, vq2_wgrad_bf16.hip); the epilogue contract is vq2_conv_epilogue.h, included below.
 #pragma once
 #include "vq2_common.h"
 
@@ -163,6 +163,19 @@ ConvTiles bf16_tiles();                           // vq2_conv_bf16.hip
 // stays inside one tap.  vq2_conv_bf16_eligible() exports it; the host packs the bf16 panel exactly when it holds.
 static inline bool conv_bf16_shape(int same_size, int depth_channels) { return same_size == 1 && depth_channels % 16 == 0; }
 int pack_weight_bf16(const vq2_conv_desc *d, int flip, const float *w, float *packed, hipStream_t s);   // vq2_conv_bf16.hip
+
+// The eligibility rule of the bf16-operand WEIGHT GRADIENT (vq2_wgrad_bf16.hip), the one copy of it: a same_size layer with
+// both channel counts multiples of 16 (both operands are staged in 16-byte fp32 runs of whole channel groups, and a K tile
+// column run never straddles two taps).  vq2_conv_wgrad_bf16_eligible() exports it.
+static inline bool conv_wgrad_bf16_shape(const vq2_conv_desc *d) { return d->same_size == 1 && d->Ci % 16 == 0 && d->Co % 16 == 0; }
+
+// The plan of a bf16-operand weight gradient: the GEMM [O x M] * [M x K] in plain roles (O = Co, K = taps * Ci, M = pixels),
+// its own tile and split.  plan_wgrad_bf16 / launch_wgrad_bf16: vq2_wgrad_bf16.hip; vq2_wgrad.hip turns the plan into the
+// slab layout [S][O][K] + bias partials [S][O] that the unchanged reduction kernels read.
+struct WgradBf16Plan { int tile, bmo, bnk, O, I, K, M, S, rows_per_split; };
+WgradBf16Plan plan_wgrad_bf16(const vq2_conv_desc *d);
+int launch_wgrad_bf16(const WgradBf16Plan &p, const vq2_conv_desc *d, int relu_in, const float *x, const float *dy, float *ws,
+                      float *bias_ws, hipStream_t s);
 
 namespace wino {
 constexpr int BK = 8;   // input channels per staged block of the Winograd kernels (vq2_wino.hip)

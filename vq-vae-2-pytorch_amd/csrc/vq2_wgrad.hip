@@ -802,7 +802,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const vq2_wgr
 // forward side: plan_conv / conv_tiles / conv_label / launch_conv).
 // Roles (see the head of this file): plain conv, the same conv with x and dy exchanged (plan_wgrad says when), conv-transpose
 enum WgradRole { WGRAD_PLAIN, WGRAD_EXCHANGED, WGRAD_CONVT };
-enum WgradFamily { WGRAD_GEN, WGRAD_FAST, WGRAD_WINO };   // wgrad_kernel, wgrad_fast_kernel direct, wgrad_fast_kernel<..., WINO = wino>
+// wgrad_kernel, wgrad_fast_kernel direct, wgrad_fast_kernel<..., WINO = wino>, wgrad_bf16_kernel (vq2_wgrad_bf16.hip)
+enum WgradFamily { WGRAD_GEN, WGRAD_FAST, WGRAD_WINO, WGRAD_BF16 };
 
 struct WgradPlan {
     int role, family;   // WgradRole, WgradFamily
@@ -815,6 +816,7 @@ struct WgradPlan {
     size_t bias_floats; // bias partials behind the S slabs: [S][nslots][I] from the gathered operand, or [S][O]
     int mode;           // the reduction kernels' mode word (vq2_wgrad_job.swapped): bit 0 exchanged roles, bits 1-2 wino
     long ext_x, ext_g;  // element counts of the two operands as the kernels index them
+    WgradBf16Plan b16;  // WGRAD_BF16: the tile and split of the bf16-operand kernel (`tile` is then not a WGRAD_TILES position)
 };
 
 // The two operands as the kernels see them -- the exchange of x and dy, written once: X is gathered through the taps (an
@@ -980,6 +982,22 @@ static WgradPlan plan_wgrad(const vq2_conv_desc *d) {
     return p;
 }
 
+// The plan of a launch with its flags: VQ2_ALLOW_BF16 on an eligible layer (conv_wgrad_bf16_shape) takes the bf16-operand
+// kernel with a plan of its own -- plain roles, no Winograd mode, its own tile and split, whatever the fp32 plan of the layer
+// says; slabs [S][O][K] and bias partials [S][O] in the plain layout (mode word 0).  Every other launch, flag or not, is
+// plan_wgrad(d) unchanged.
+static WgradPlan plan_wgrad(const vq2_conv_desc *d, int flags) {
+    if (!((flags & VQ2_ALLOW_BF16) && conv_wgrad_bf16_shape(d))) return plan_wgrad(d);
+    WgradPlan p{};
+    p.b16 = plan_wgrad_bf16(d);
+    p.role = WGRAD_PLAIN; p.family = WGRAD_BF16;
+    p.O = p.b16.O; p.I = p.b16.I; p.K = p.b16.K; p.M = p.b16.M; p.S = p.b16.S; p.rows_per_split = p.b16.rows_per_split;
+    p.Or = real_co(d); p.Ir = real_ci(d);
+    p.bias_floats = (size_t)p.S * p.O;
+    p.ext_x = (long)p.M * d->ldx; p.ext_g = (long)p.M * d->ldy;
+    return p;
+}
+
 static size_t wgrad_ws_bytes(const WgradPlan &p) { return ((size_t)p.S * p.O * p.K + p.bias_floats) * sizeof(float); }
 
 // The kernels' arguments of a planned launch; the slabs [S][O][K] come first in ws, the bias partials behind them.
@@ -1000,10 +1018,10 @@ static int wgrad_params(const vq2_conv_desc *d, const WgradPlan &p, int flags, c
 
 // The profiler label of a planned launch, "wgrad<tile><form>|<shape>,fast|gen" (wgrad_fast_kernel or wgrad_kernel):
 // formatted here and nowhere else.
-static const char *wgrad_label(const WgradPlan &p, const WgradTile &t, const vq2_conv_desc *d) {
+static const char *wgrad_label(const WgradPlan &p, int bmo, int bnk, const vq2_conv_desc *d) {
     const char *form = p.wino == 3 ? "swwino" : p.role == WGRAD_EXCHANGED ? "sw" : p.wino == 1 ? "wino" : p.wino == 2 ? "wino4" : "";
-    return prof_label("wgrad<%dx%d>%s|O=%d,K=%d,M=%d,S=%d,k%d,%s", t.bmo, t.bnk, form, p.O, p.K, p.M, p.S, d->KH,
-                      p.family == WGRAD_GEN ? "gen" : "fast");
+    return prof_label("wgrad<%dx%d>%s|O=%d,K=%d,M=%d,S=%d,k%d,%s", bmo, bnk, form, p.O, p.K, p.M, p.S, d->KH,
+                      p.family == WGRAD_BF16 ? "bf16" : p.family == WGRAD_GEN ? "gen" : "fast");
 }
 
 // ------------------------------------------------------------------ column sums (bias gradient)
@@ -1082,11 +1100,14 @@ static int colsum_impl(const float *dy, int64_t rows, int C, int ld, float *db, 
 
 using namespace vq2;
 
-// 0 for anything check_conv_desc refuses
-extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) {
+extern "C" int vq2_conv_wgrad_bf16_eligible(const vq2_conv_desc *d) { return d != nullptr && conv_wgrad_bf16_shape(d); }
+
+// 0 for anything check_conv_desc refuses.  flags: those of the launch the workspace is for (VQ2_ALLOW_BF16 changes the plan)
+extern "C" size_t vq2_conv_wgrad_workspace_bytes_ex(const vq2_conv_desc *d, int flags) {
     if (!d || check_conv_desc(d, "conv_wgrad_workspace_bytes", DESC_PLAN_ONLY)) return 0;   // (null: no message)
-    return wgrad_ws_bytes(plan_wgrad(d));
+    return wgrad_ws_bytes(plan_wgrad(d, flags));
 }
+extern "C" size_t vq2_conv_wgrad_workspace_bytes(const vq2_conv_desc *d) { return vq2_conv_wgrad_workspace_bytes_ex(d, 0); }
 
 // The reduction job of a planned layer: what wgrad_reduce_batched_kernel reads, and the arguments of wgrad_reduce_kernel.
 static void wgrad_job_init_impl(const vq2_conv_desc *d, const WgradPlan &p, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
@@ -1109,15 +1130,22 @@ static int wgrad_impl(const vq2_conv_desc *d, int flags, const float *x, const f
     if (int e = check_conv_desc(d, "conv_wgrad")) return e;
     VQ2_REQUIRE(x && dy && ws && (dw || !reduce), "conv_wgrad: null pointer");
     VQ2_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(ws), "conv_wgrad: pointers must be 16-byte aligned");
-    const WgradPlan p = plan_wgrad(d);
+    const WgradPlan p = plan_wgrad(d, flags);
     VQ2_REQUIRE(ws_bytes >= wgrad_ws_bytes(p), "conv_wgrad: workspace too small");
-    WgradParams P;
-    if (int e = wgrad_params(d, p, flags, x, dy, db, ws, P)) return e;
     hipStream_t s = to_stream(stream);
-    const WgradTile &tile = WGRAD_TILES[p.tile];
     const ConvWork work = conv_work(d, 0, 0);
-    ProfScope prof(prof_enabled() ? wgrad_label(p, tile, d) : "wgrad", work.flops, work.bytes, s);
-    if (int e = tile.launch(p, P, s)) return e;
+    if (p.family == WGRAD_BF16) {
+        float *slabs = static_cast<float *>(ws);
+        ProfScope prof(prof_enabled() ? wgrad_label(p, p.b16.bmo, p.b16.bnk, d) : "wgrad", work.flops, work.bytes, s);
+        if (int e = launch_wgrad_bf16(p.b16, d, (flags & VQ2_RELU_IN) != 0, x, dy, slabs,
+                                      db ? slabs + (size_t)p.S * p.O * p.K : nullptr, s)) return e;
+    } else {
+        WgradParams P;
+        if (int e = wgrad_params(d, p, flags, x, dy, db, ws, P)) return e;
+        const WgradTile &tile = WGRAD_TILES[p.tile];
+        ProfScope prof(prof_enabled() ? wgrad_label(p, tile.bmo, tile.bnk, d) : "wgrad", work.flops, work.bytes, s);
+        if (int e = tile.launch(p, P, s)) return e;
+    }
     if (!reduce) return VQ2_OK;
     vq2_wgrad_job j;   // what the deferred path hands to wgrad_reduce_batched_kernel, reduced at once
     wgrad_job_init_impl(d, p, ws, dw, db, &j);
@@ -1137,11 +1165,14 @@ extern "C" int vq2_conv_wgrad_partial(const vq2_conv_desc *d, int flags, const f
     return wgrad_impl(d, flags, x, dy, nullptr, db, ws, ws_bytes, stream, false);
 }
 
-extern "C" int vq2_wgrad_job_init(const vq2_conv_desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
+extern "C" int vq2_wgrad_job_init_ex(const vq2_conv_desc *d, int flags, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
     if (int e = check_conv_desc(d, "wgrad_job_init", DESC_PLAN_ONLY)) return e;
     VQ2_REQUIRE(ws && dw && job, "wgrad_job_init: null pointer");
-    wgrad_job_init_impl(d, plan_wgrad(d), ws, dw, db, job);
+    wgrad_job_init_impl(d, plan_wgrad(d, flags), ws, dw, db, job);
     return VQ2_OK;
+}
+extern "C" int vq2_wgrad_job_init(const vq2_conv_desc *d, const void *ws, float *dw, float *db, vq2_wgrad_job *job) {
+    return vq2_wgrad_job_init_ex(d, 0, ws, dw, db, job);
 }
 
 extern "C" int vq2_wgrad_reduce_batched(const vq2_wgrad_job *jobs_dev, int32_t njobs, int64_t total_units,

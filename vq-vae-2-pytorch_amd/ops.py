@@ -5,7 +5,7 @@ contiguous and whose pixel stride `ld = t.stride(2)` may exceed C (a channel sli
 wider buffer).  PyTorch is used for device memory, streams and autograd bookkeeping only;
 every FLOP and every byte moved on this path is a libvq2 kernel.
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 import contextlib
 import ctypes as C
 import os
@@ -118,7 +118,12 @@ class ConvSpec:
     kw: int = 0               # kernel columns and left padding; without same_size always k and pad (__post_init__)
     pad_left: int = 0
     same_size: bool = False   # vq2_conv_desc.same_size
-    bf16: bool = False        # permission: forward and data gradient round their operands to bf16 where conv_bf16_eligible
+    # The two permissions are keyword-only: a positional argument can never land on the wrong one.  (`bf16` stays the last
+    # field, as tests/test_conv_bf16_cpu.py pins it.)
+    # the weight gradient rounds x and dy to bf16 where conv_wgrad_bf16_eligible
+    bf16_wgrad: bool = field(default=False, kw_only=True)
+    # forward and data gradient round their operands to bf16 where conv_bf16_eligible
+    bf16: bool = field(default=False, kw_only=True)
 
     def __post_init__(self):
         if not self.same_size:
@@ -159,6 +164,18 @@ def conv_bf16_eligible(spec, dgrad=False):
     padded input channels for the forward, output channels for the data gradient) is a multiple of 16.  A spec with
     `bf16` set takes the bf16-operand kernel, and packs the bf16 panel, exactly where this holds."""
     return bool(spec.same_size) and (spec.co if dgrad else spec.ci) % 16 == 0
+
+
+def conv_wgrad_bf16_eligible(spec):
+    """The host mirror of vq2_conv_wgrad_bf16_eligible (include/vq2.h): a same_size layer whose padded input AND output channel
+    counts are multiples of 16.  A spec with `bf16_wgrad` set takes the bf16-operand weight gradient exactly where this holds."""
+    return bool(spec.same_size) and spec.ci % 16 == 0 and spec.co % 16 == 0
+
+
+def _wgrad_flags(spec, relu_in):
+    """The flags of a weight-gradient launch of `spec`; workspace size and reduction job are asked with the same ones."""
+    bf16 = spec.bf16_wgrad and conv_wgrad_bf16_eligible(spec)
+    return (VQ2_RELU_IN if relu_in else 0) | (VQ2_ALLOW_BF16 if bf16 else 0)
 
 
 def _desc(spec, n, h, w, ldx, ldy):
@@ -355,18 +372,19 @@ class WgradBatch:
 
     def launch(self, spec, x, dy, relu_in, weight, bias, want_db, side):
         n, h, w, _ = x.shape
-        key = (id(weight), n, h, w, ld_of(x), ld_of(dy), relu_in)
+        flags = _wgrad_flags(spec, relu_in)
+        key = (id(weight), n, h, w, ld_of(x), ld_of(dy), relu_in, flags & VQ2_ALLOW_BF16)   # workspace and job differ with the bit
         d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
         ent = self._entry(key, x.device, lambda: (
-            lib.vq2_conv_wgrad_workspace_bytes(C.byref(d)), slot_of(weight), slot_of(bias) if want_db else None,
-            lambda *a: check(lib.vq2_wgrad_job_init(C.byref(d), *a), "wgrad_job_init")))
+            lib.vq2_conv_wgrad_workspace_bytes_ex(C.byref(d), flags), slot_of(weight), slot_of(bias) if want_db else None,
+            lambda *a: check(lib.vq2_wgrad_job_init_ex(C.byref(d), flags, *a), "wgrad_job_init")))
         # off the backward critical path: overlaps the next layers' data gradients.  A launch that fills the chip by
         # itself gains nothing from a second stream.
         on_side = n * h * w <= WGRAD_STREAM_MAX_PIXELS
         if on_side:
             side.wait_event(torch.cuda.current_stream().record_event())
         with (torch.cuda.stream(side) if on_side else _THIS_STREAM):
-            check(lib.vq2_conv_wgrad_partial(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(ent["db"]),
+            check(lib.vq2_conv_wgrad_partial(C.byref(d), flags, _p(x), _p(dy), _p(ent["db"]),
                                              _p(ent["ws"]), ent["nbytes"], _stream()), "conv_wgrad_partial")
         if on_side:
             x.record_stream(side)
@@ -438,7 +456,8 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
     """(dw, db) in the reference layouts; the bias gradient is fused into the same launches."""
     n, h, w, _ = x.shape
     d = _desc(spec, n, h, w, ld_of(x), ld_of(dy))
-    nbytes = lib.vq2_conv_wgrad_workspace_bytes(C.byref(d))
+    flags = _wgrad_flags(spec, relu_in)
+    nbytes = lib.vq2_conv_wgrad_workspace_bytes_ex(C.byref(d), flags)
     sc = _step_ctx(weight)
     in_slot = sc is not None and slot_of(weight) is not None
     # deferred: both slots writable (slot_of), and the bias exactly as long as the job's reduction writes
@@ -453,7 +472,7 @@ def conv_wgrad(spec, x, dy, relu_in, weight, bias=None, want_dw=True, want_db=Tr
         side.wait_event(torch.cuda.current_stream().record_event())
     with (torch.cuda.stream(side) if side is not None else _THIS_STREAM):
         ws = torch.empty(max(nbytes // 4, 4), device=x.device, dtype=torch.float32)
-        check(lib.vq2_conv_wgrad(C.byref(d), VQ2_RELU_IN if relu_in else 0, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes,
+        check(lib.vq2_conv_wgrad(C.byref(d), flags, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes,
                                  _stream()), "conv_wgrad")
     if side is not None:
         x.record_stream(side)   # keep the caching allocator from recycling these while the side stream reads

@@ -492,17 +492,21 @@ class PixelSNAIL(nn.Module):
 # ----------------------------------------------------------------------------- conv precision (--precision bf16)
 def set_conv_precision(module, precision):
     """Give every WNConv2d under `module` (those inside CausalConv2d, GatedResBlock, PixelBlock, CondResNet and PixelSNAIL
-    included) the conv precision 'bf16' or 'fp32' by replacing its `spec`; returns (eligible_layers, total_layers).
+    included) the conv precision 'bf16', 'bf16_wgrad' or 'fp32' by replacing its `spec`; returns (eligible_layers,
+    total_layers).
 
     'bf16' is a permission (ConvSpec.bf16): where ops.conv_bf16_eligible holds -- forward with input channels a multiple of
     16, data gradient with output channels a multiple of 16 -- the launch rounds both operands to bfloat16 (nearest even) and
     accumulates in fp32; every other launch, the weight gradient, and every tensor in memory stay fp32.  A layer counts as
-    eligible when its forward or its data gradient is.  Parameters, buffers and state_dict are untouched.  A PixelSNAIL's
+    eligible when its forward or its data gradient is.  'bf16_wgrad' sets that permission and ConvSpec.bf16_wgrad: where
+    ops.conv_wgrad_bf16_eligible holds -- input and output channels both multiples of 16 -- the weight gradient rounds x and
+    dy to bfloat16 as well (the bias gradient stays the fp32 sum of the unrounded dy); 'bf16' and 'fp32' clear it.
+    Parameters, buffers and state_dict are untouched.  A PixelSNAIL's
     two one-hot input convs never run a conv kernel and are left out; attention projections (_WNLinear), the cross-entropy
     head and stage 1 have no such layers."""
     import dataclasses
-    if precision not in ("bf16", "fp32"):
-        raise ValueError(f"set_conv_precision: precision must be 'bf16' or 'fp32', got {precision!r}")
+    if precision not in ("bf16", "bf16_wgrad", "fp32"):
+        raise ValueError(f"set_conv_precision: precision must be 'bf16', 'bf16_wgrad' or 'fp32', got {precision!r}")
     skip = set()
     for m in module.modules():
         if isinstance(m, PixelSNAIL):
@@ -510,12 +514,14 @@ def set_conv_precision(module, precision):
     eligible = total = 0
     for m in module.modules():
         if isinstance(m, WNConv2d) and id(m) not in skip:
-            m.spec = dataclasses.replace(m.spec, bf16=precision == "bf16")
+            m.spec = dataclasses.replace(m.spec, bf16=precision != "fp32", bf16_wgrad=precision == "bf16_wgrad")
             total += 1
             eligible += bool(ops.conv_bf16_eligible(m.spec) or ops.conv_bf16_eligible(m.spec, dgrad=True))
     return eligible, total
 
 
 def conv_precision(module):
-    """'bf16' if any WNConv2d under `module` carries the bf16 permission, else 'fp32'."""
-    return "bf16" if any(isinstance(m, WNConv2d) and m.spec.bf16 for m in module.modules()) else "fp32"
+    """'bf16_wgrad' if any WNConv2d under `module` carries the bf16 weight-gradient permission, else 'bf16' if any carries
+    the bf16 permission, else 'fp32'."""
+    specs = [m.spec for m in module.modules() if isinstance(m, WNConv2d)]
+    return "bf16_wgrad" if any(s.bf16_wgrad for s in specs) else "bf16" if any(s.bf16 for s in specs) else "fp32"

@@ -72,8 +72,8 @@ class _Conv:
             par, self.spec = mod, mod.spec
         else:
             raise NotImplementedError(f"vqvae2_amd.PriorSampler: cannot step through {type(mod).__name__}")
-        if self.spec.bf16:       # the row kernels are fp32: the sampler's copy of a spec drops the bf16 permission
-            self.spec = dataclasses.replace(self.spec, bf16=False)
+        if self.spec.bf16 or self.spec.bf16_wgrad:   # the row kernels are fp32: the sampler's copy of a spec drops the bf16 permissions
+            self.spec = dataclasses.replace(self.spec, bf16=False, bf16_wgrad=False)
         s = self.spec
         v = par.weight_v.detach().clone().contiguous()
         if causal_cols is not None:

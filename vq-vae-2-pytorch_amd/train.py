@@ -549,9 +549,9 @@ class Stage2Trainer(_ArenaTrainer):
         self._finish_construction()
 
     def set_precision(self, precision):
-        """The conv precision of the run, 'bf16' or 'fp32': pixelsnail.set_conv_precision on the model (bf16 operands in the
-        eligible conv forwards and data gradients; weight gradients, parameters and optimizer state stay fp32), remembered
-        for the checkpoint.  Returns (eligible_layers, total_layers).  A trainer that was never told keeps the model's convs
+        """The conv precision of the run, 'bf16', 'bf16_wgrad' or 'fp32': pixelsnail.set_conv_precision on the model (bf16
+        operands in the eligible conv forwards and data gradients, under 'bf16_wgrad' in the eligible weight gradients too;
+        parameters and optimizer state stay fp32), remembered for the checkpoint.  Returns (eligible_layers, total_layers).  A trainer that was never told keeps the model's convs
         as they are and saves no "precision"."""
         from .pixelsnail import set_conv_precision
         counts = set_conv_precision(self.model, precision)      # (refuses anything else)
