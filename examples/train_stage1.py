@@ -28,6 +28,10 @@ the first min(batch, 25) inputs over their reconstructions, nrow = len(sample)) 
 clipping; a step whose norm is not finite is skipped and counted, the count is printed at the end).  --ema_decay D keeps
 Polyak-averaged weights: every save also writes vqvae_<NNN>_ema.pt, the reference's file with the averaged weights (and the
 codebooks as they are), and the held-out line is printed for both sets of weights.
+
+--code_restart THRESHOLD restarts dead codes (Stage1Trainer.set_code_restart): from step --code_restart_start on, a code
+whose EMA cluster size is below THRESHOLD is replaced by an encoder output of the current batch, on the device; the
+periodic line and the held-out line then show the codes restarted so far at both levels.
 """
 import argparse
 import glob
@@ -103,11 +107,15 @@ def val_batches(args, plan, device):
         yield (t if a.dtype == np.uint8 else t.float()).to(device)
 
 
-def print_validation(epoch, i, r):
+def print_validation(epoch, i, r, restarted=None):
     print(f"epoch: {epoch + 1}; it {i}; val images: {r['images']}; val mse: {r['mse']:.5f}; val latent: {r['latent']:.3f}; "
           f"perplexity t/b: {r['perplexity_t']:.1f}/{r['perplexity_b']:.1f}; "
           f"used codes t/b: {r['used_t']}/{r['used_b']} of {r['n_embed']}"
-          + (f"; psnr: {r['psnr']:.2f} dB; ssim: {r['ssim']:.4f}" if "psnr" in r else ""), flush=True)
+          + (f"; psnr: {r['psnr']:.2f} dB; ssim: {r['ssim']:.4f}" if "psnr" in r else "") + restarted_text(restarted), flush=True)
+
+
+def restarted_text(totals):
+    return "" if totals is None else "; restarted codes: " + "/".join(str(v) for v in totals)
 
 
 def parse_args(argv=None):
@@ -132,6 +140,9 @@ def parse_args(argv=None):
                     help="with --val_path: also PSNR and SSIM of the 8-bit reconstructions of the held-out set")
     ap.add_argument("--clip_grad_norm", type=float, default=None, help="clip the global gradient norm to this value")
     ap.add_argument("--ema_decay", type=float, default=None, help="decay of the Polyak-averaged weights")
+    ap.add_argument("--code_restart", type=float, default=None, metavar="THRESHOLD",
+                    help="restart codes whose EMA cluster size falls below THRESHOLD from encoder outputs (default: off)")
+    ap.add_argument("--code_restart_start", type=int, default=0, metavar="STEPS", help="first step that may restart a code")
     args = ap.parse_args(argv)
     if args.eval_every and not args.val_path:
         raise SystemExit("--eval_every needs --val_path")
@@ -154,6 +165,9 @@ def main(argv=None):
     val_plan = plan_val_batches(args, rank, world) if args.eval_every else None
     trainer = vqvae2_amd.Stage1Trainer(model, lr=args.lr, sched=args.sched, n_iter=len(plan) * args.epoch,
                                        normalizer=normalizer, clip_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay)
+    if args.code_restart is not None:
+        trainer.set_code_restart(args.code_restart, start=args.code_restart_start)
+    restarted = (lambda: trainer.restarted_codes()) if args.code_restart is not None else (lambda: None)
     first_epoch = 0
     if args.resume:                                            # train_vqvae.py:173-182
         sd = torch.load(args.resume, map_location=device, weights_only=True)
@@ -175,13 +189,13 @@ def main(argv=None):
                 evaluate = trainer.evaluate_image_metrics if args.image_metrics else trainer.evaluate
                 r = evaluate(val_batches(args, val_plan, device))
                 if dist.is_primary():
-                    print_validation(epoch, i, r)
+                    print_validation(epoch, i, r, restarted())
                 if args.ema_decay is not None:
                     with trainer.averaged_weights():
                         r = evaluate(val_batches(args, val_plan, device))
                     if dist.is_primary():
                         print("averaged weights -- ", end="")
-                        print_validation(epoch, i, r)
+                        print_validation(epoch, i, r, restarted())
             if args.sample_every and i % args.sample_every == 0 and dist.is_primary():   # train_vqvae.py:120-139
                 grid = trainer.sample_grid(img[:min(img.shape[0], 25)].contiguous())
                 os.makedirs("sample", exist_ok=True)
@@ -193,7 +207,8 @@ def main(argv=None):
                     lr = trainer.optimizer.param_groups[0]["lr"]
                     print(f"epoch: {epoch + 1}; it {i}; mse: {float(out['recon']):.5f}; "
                           f"latent: {float(out['latent']):.3f}; avg mse: {float(agg[0] / agg[1]):.5f}; lr: {lr:.5f}"
-                          + (f"; gnorm: {float(out['grad_norm']):.5f}" if "grad_norm" in out else ""), flush=True)
+                          + (f"; gnorm: {float(out['grad_norm']):.5f}" if "grad_norm" in out else "")
+                          + restarted_text(restarted()), flush=True)
         if dist.is_primary() and (epoch % 10 == 0 or epoch == args.epoch - 1):   # train_vqvae.py:205-206
             os.makedirs(args.out, exist_ok=True)
             tag = str(epoch + 1).zfill(3)

@@ -62,11 +62,12 @@ typedef void *vq2_stream_t;
  * steps, averaged weights); revision 17: additions only -- the bf16-operand conv forward / data gradient: the flag
  * VQ2_ALLOW_BF16, the panels VQ2_PACK_FWD_BF16 / VQ2_PACK_DGRAD_BF16 and vq2_conv_bf16_eligible; revision 18: additions
  * only -- the bf16-operand weight gradient: VQ2_ALLOW_BF16 in the flags of vq2_conv_wgrad / vq2_conv_wgrad_partial (ignored
- * before), vq2_conv_wgrad_bf16_eligible, vq2_conv_wgrad_workspace_bytes_ex and vq2_wgrad_job_init_ex.
+ * before), vq2_conv_wgrad_bf16_eligible, vq2_conv_wgrad_workspace_bytes_ex and vq2_wgrad_job_init_ex;
+ * revision 19: additions only -- the dead-code restart of Quantize: vq2_vq_restart_candidates and vq2_vq_ema_update_restart.
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 18
+#define VQ2_API_VERSION 19
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -355,6 +356,28 @@ int vq2_vq_ema_update_prepare(float *embed, float *cluster_size, float *embed_av
                               float *embedT, float *enorm, vq2_stream_t stream);
 int vq2_vq_gather(const int64_t *idx, const float *embedT, int64_t M, int32_t D, int32_t K, float *out, int32_t ldo,
                   vq2_stream_t stream);
+/* Dead-code restart: a code whose EMA size falls below `threshold` is replaced by an encoder output
+ * of the current batch, on the device, with no host read, identically on every rank.
+ * Candidates: for every code k, w = word 0 of Philox4x32-7 at counter (k, lo32(step), hi32(step), slot) under the 64-bit
+ *   key `seed`; global row r = floor(w * world * M / 2^32); rank r / M copies its row r % M of x into cand[k, :], every
+ *   other rank writes zeros -- every element of cand[K, D] is written, and a SUM all-reduce of cand leaves the row on every
+ *   rank (v + 0 is exact; a -0.0 becomes +0.0).  picks (may be NULL): int64 [K], the global rows r.  x is what
+ *   vq2_vq_stats reads: ldx >= D, ldx % 4 == 0, 16-byte aligned, as cand.  Needs world >= 1, 0 <= rank < world and
+ *   M * world < 2^32.
+ * Update: the EMA update of vq2_vq_ema_update_prepare (embedT and enorm both NULL: of vq2_vq_ema_update) in which a code
+ *   with cs[k] = fma(1 - decay, counts[k], cluster_size[k] * decay) < threshold and a wholly finite cand[k, :] gets
+ *   cluster_size[k] = threshold and embed_avg[:, k] = threshold * cand[k, :] instead; n and embed follow by the usual
+ *   formula in the usual order, so threshold = 0 gives the bits of the plain update.  threshold finite and >= 0 (a start
+ *   step is the caller's: pass 0 before it).  scratch >= 4 + K floats, 16-byte aligned.  counter: int64 [2] on the device,
+ *   {codes restarted by this call (overwritten), running total (added to)}.  Two launches, no float atomics.
+ * Both: D % 4 == 0 in 4..256, 1 <= K <= 16384; every refusal precedes the first launch. */
+int vq2_vq_restart_candidates(const float *x, int32_t ldx, int64_t M, int32_t D, int32_t K, uint64_t seed, uint64_t step,
+                              uint32_t slot, int32_t rank, int32_t world, float *cand /* [K,D] */,
+                              int64_t *picks /* [K] or NULL */, vq2_stream_t stream);
+int vq2_vq_ema_update_restart(float *embed, float *cluster_size, float *embed_avg, const float *counts,
+                              const float *sumsT, const float *cand, int32_t D, int32_t K, double decay, double eps,
+                              double threshold, float *scratch, float *embedT, float *enorm, int64_t *counter,
+                              vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ AdaIN (VQVAE_Deep decoder, vqvae_deep.py:99-134)
  * vq2_instnorm_stats: mean / rstd [N,C] of nn.InstanceNorm2d(C, affine=False) over the HW pixels of each image

@@ -108,6 +108,8 @@ def _load():
         "vq2_vq_ema_update": (C.c_int, [P, P, P, P, P, I32, I32, D, D, P, P]),
         "vq2_vq_ema_update_prepare": (C.c_int, [P, P, P, P, P, I32, I32, D, D, P, P, P, P]),
         "vq2_vq_gather": (C.c_int, [P, P, I64, I32, I32, P, I32, P]),
+        "vq2_vq_restart_candidates": (C.c_int, [P, I32, I64, I32, I32, U64, U64, C.c_uint32, I32, I32, P, P, P]),
+        "vq2_vq_ema_update_restart": (C.c_int, [P, P, P, P, P, P, I32, I32, D, D, D, P, P, P, P, P]),
         "vq2_instnorm_stats": (C.c_int, [P, I32, I32, I64, I32, D, P, P, P]),
         "vq2_adain_fwd": (C.c_int, [P, I32, P, P, P, I32, I64, I32, C.c_int, P, I32, P]),
         "vq2_adain_bwd": (C.c_int, [P, I32, P, I32, P, I32, P, P, P, I32, I64, I32, P, P, I32, P]),

@@ -13,6 +13,7 @@
 // dist is evaluated exactly as the reference writes it (vqvae.py:44-48):
 //     (||x||^2 - 2*(x.e)) + ||e||^2      in fp32, in that order.
 #include "vq2_common.h"
+#include "vq2_philox.h"
 
 namespace vq2 {
 
@@ -529,6 +530,101 @@ __global__ __launch_bounds__(1024) void vq_ema_counts_kernel(float *__restrict__
     if (threadIdx.x == 0) n_out[0] = red[0];
 }
 
+// ----------------------------------------------------------------------------- dead-code restart
+// Candidate row of every code: word 0 of Philox at counter (k, lo32(step), hi32(step), slot) under the 64-bit seed,
+// scaled to a global row r = umulhi(w, world * M).  The rank that owns row r copies it, every other rank writes zeros, so
+// a SUM all-reduce of cand leaves the row on every rank.  Q = D / 4 lanes move one code with 16-byte loads and stores.
+__global__ __launch_bounds__(256) void vq_restart_candidates_kernel(const float *__restrict__ x, int ldx, uint32_t M,
+                                                                    int D, int K, uint32_t seed_lo, uint32_t seed_hi,
+                                                                    uint32_t step_lo, uint32_t step_hi, uint32_t slot,
+                                                                    uint32_t rank, uint32_t m_total,
+                                                                    float *__restrict__ cand, int64_t *__restrict__ picks) {
+    const int Q = D >> 2;
+    const int total = K * Q;
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < total; t += gridDim.x * 256) {
+        const int k = t / Q, q = t - k * Q;
+        const uint32_t w = philox4x32_7((uint32_t)k, step_lo, step_hi, slot, seed_lo, seed_hi).x;
+        const uint32_t r = __umulhi(w, m_total);          // < m_total = world * M
+        const uint32_t owner = r / M, row = r - owner * M;   // row < M: inside this rank's x
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (owner == rank) v = *reinterpret_cast<const float4 *>(x + (size_t)row * ldx + 4 * q);
+        *reinterpret_cast<float4 *>(cand + (size_t)k * D + 4 * q) = v;
+        if (picks && q == 0) picks[k] = (int64_t)r;
+    }
+}
+
+// vq_ema_counts_kernel with the restart decision (one workgroup).  Three passes between barriers:
+//   1. thread t forms cs[k] for k = t, t + 1024, ... exactly as vq_ema_counts_kernel does, stores it, and marks
+//      mask[k] = cs[k] < threshold;
+//   2. groups of Q = D / 4 threads read the candidate rows of the MARKED codes only and clear the mark of a row that
+//      holds an Inf or a NaN (plain stores of the same value 0: no atomics);
+//   3. thread t walks its codes again in the same order: a code still marked gets cs = threshold; the sizes are summed in
+//      vq_ema_counts_kernel's order (per-thread chain, then the halving tree), the restarts are counted as integers.
+// mask (K int32 after the first 4 floats of scratch) and n go to the embed kernel; counter = {this step, total} (int64).
+__global__ __launch_bounds__(1024) void vq_ema_counts_restart_kernel(float *__restrict__ cluster_size,
+                                                                     const float *__restrict__ counts,
+                                                                     const float *__restrict__ cand, int D, int K,
+                                                                     float decay, float alpha, float threshold,
+                                                                     float *n_out, int *mask, int64_t *__restrict__ counter) {
+    __shared__ float red[1024];
+    __shared__ int nred[1024];
+    for (int k = threadIdx.x; k < K; k += 1024) {
+        const float cs = fmaf(alpha, counts[k], cluster_size[k] * decay);
+        cluster_size[k] = cs;
+        mask[k] = cs < threshold ? 1 : 0;
+    }
+    __syncthreads();
+    const int Q = D >> 2, G = 1024 / Q;                    // G whole groups; threads past G * Q (Q = 12: 4 of them) idle
+    const int g = threadIdx.x / Q, q = threadIdx.x - g * Q;
+    constexpr int U = 4;                                   // candidate rows in flight per group
+    for (int k0 = g < G ? g : K; k0 < K; k0 += G * U) {
+        float4 v[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int k = k0 + j * G;
+            v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (k < K && mask[k]) v[j] = *reinterpret_cast<const float4 *>(cand + (size_t)k * D + 4 * q);
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int k = k0 + j * G;
+            // an Inf or a NaN has all eight exponent bits set
+            const uint32_t a = __float_as_uint(v[j].x), b = __float_as_uint(v[j].y);
+            const uint32_t c = __float_as_uint(v[j].z), d = __float_as_uint(v[j].w);
+            const uint32_t E = 0x7F800000u;
+            const bool bad = (a & E) == E || (b & E) == E || (c & E) == E || (d & E) == E;
+            if (k < K && bad) mask[k] = 0;
+        }
+    }
+    __syncthreads();
+    float local = 0.f;
+    int dead = 0;
+    for (int k = threadIdx.x; k < K; k += 1024) {
+        float cs = cluster_size[k];
+        if (mask[k]) {
+            cs = threshold;
+            cluster_size[k] = cs;
+            ++dead;
+        }
+        local += cs;
+    }
+    red[threadIdx.x] = local;
+    nred[threadIdx.x] = dead;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[threadIdx.x] += red[threadIdx.x + o];
+            nred[threadIdx.x] += nred[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        n_out[0] = red[0];
+        counter[0] = nred[0];
+        counter[1] += nred[0];
+    }
+}
+
 // vqvae.py:64, 67-70: embed_avg EMA and the normalised codebook; thread index runs over [k][d] so the
 // transposed statistics are read coalesced
 // PREP (embedT / enorm outputs, D <= 256): the launch also leaves what the NEXT forward's vq2_vq_prepare would
@@ -536,12 +632,16 @@ __global__ __launch_bounds__(1024) void vq_ema_counts_kernel(float *__restrict__
 // d = g, g+4, ..., then (p0+p1)+(p2+p3)), so distances and indices are bit-identical to preparing separately.  A block's
 // first `per` = floor(256/D) * D threads own floor(256/D) complete codes (`per` and the grid stride are multiples of D; the
 // other 256 - per threads, none when D divides 256, only meet the barriers).
-template <bool PREP>
+// RESTART: a code marked in `mask` by vq_ema_counts_restart_kernel takes embed_avg = threshold * cand instead of its EMA
+// (cand is [K][D] like sumsT); cluster_size already holds the threshold for it.  Without RESTART the three arguments are
+// not looked at and the kernel is the one it was.
+template <bool PREP, bool RESTART>
 __global__ __launch_bounds__(256) void vq_ema_embed_kernel(float *__restrict__ embed, const float *__restrict__ cluster_size,
                                                            float *__restrict__ embed_avg, const float *__restrict__ sumsT,
                                                            int D, int K, float decay, float alpha, float eps, float keps,
                                                            const float *__restrict__ n_in, float *__restrict__ embedT,
-                                                           float *__restrict__ enorm) {
+                                                           float *__restrict__ enorm, const float *__restrict__ cand,
+                                                           const int *__restrict__ mask, float threshold) {
     __shared__ float e2[256];
     __shared__ float part[256];
     const float n = n_in[0];
@@ -556,7 +656,9 @@ __global__ __launch_bounds__(256) void vq_ema_embed_kernel(float *__restrict__ e
         float e = 0.f;
         if (tv) {
             const size_t o = (size_t)d * K + k;
-            const float ea = fmaf(alpha, sumsT[t], embed_avg[o] * decay);
+            float ea;
+            if (RESTART && mask[k]) ea = threshold * cand[t];
+            else ea = fmaf(alpha, sumsT[t], embed_avg[o] * decay);
             embed_avg[o] = ea;
             const float cs = (cluster_size[k] + eps) / denom * n;
             e = ea / cs;
@@ -785,23 +887,32 @@ extern "C" int vq2_vq_bwd(const float *g_out, int32_t ldg, const float *g_diff, 
     return check_launch("vq_bwd_kernel");
 }
 
+// cand != NULL: the restart form (vq_ema_counts_restart_kernel decides, the embed kernel applies), else the plain update
 static int ema_update_impl(float *embed, float *cluster_size, float *embed_avg, const float *counts, const float *sumsT,
                            int32_t D, int32_t K, double decay, double eps, float *scratch, float *embedT, float *enorm,
-                           hipStream_t s) {
+                           hipStream_t s, const float *cand = nullptr, float threshold = 0.f, int64_t *counter = nullptr) {
     // Python forms (1 - decay) and n_embed * eps in double before the fp32 ops (vqvae.py:62,67)
     const float alpha = (float)(1.0 - decay);
-    hipLaunchKernelGGL(vq_ema_counts_kernel, dim3(1), dim3(1024), 0, s, cluster_size, counts, K, (float)decay, alpha,
-                       scratch);
-    if (int e = check_launch("vq_ema_counts_kernel")) return e;
+    const int *mask = reinterpret_cast<const int *>(scratch + 4);   // restart form only: K int32 behind n
+    if (cand) {
+        hipLaunchKernelGGL(vq_ema_counts_restart_kernel, dim3(1), dim3(1024), 0, s, cluster_size, counts, cand, D, K,
+                           (float)decay, alpha, threshold, scratch, reinterpret_cast<int *>(scratch + 4), counter);
+        if (int e = check_launch("vq_ema_counts_restart_kernel")) return e;
+    } else {
+        hipLaunchKernelGGL(vq_ema_counts_kernel, dim3(1), dim3(1024), 0, s, cluster_size, counts, K, (float)decay, alpha,
+                           scratch);
+        if (int e = check_launch("vq_ema_counts_kernel")) return e;
+    }
     const int per = embedT ? (256 / D) * D : 256;   // see vq_ema_embed_kernel
     const int blocks = (D * K + per - 1) / per;
     const dim3 grid(blocks > 1024 ? 1024 : blocks);
-    if (embedT)
-        hipLaunchKernelGGL(vq_ema_embed_kernel<true>, grid, dim3(256), 0, s, embed, cluster_size, embed_avg, sumsT, D, K,
-                           (float)decay, alpha, (float)eps, (float)((double)K * eps), scratch, embedT, enorm);
-    else
-        hipLaunchKernelGGL(vq_ema_embed_kernel<false>, grid, dim3(256), 0, s, embed, cluster_size, embed_avg, sumsT, D, K,
-                           (float)decay, alpha, (float)eps, (float)((double)K * eps), scratch, embedT, enorm);
+#define VQ2_LAUNCH_EMBED(PREP, RESTART)                                                                              \
+    hipLaunchKernelGGL((vq_ema_embed_kernel<PREP, RESTART>), grid, dim3(256), 0, s, embed, cluster_size, embed_avg,  \
+                       sumsT, D, K, (float)decay, alpha, (float)eps, (float)((double)K * eps), scratch, embedT, enorm, \
+                       cand, mask, threshold)
+    if (embedT) { if (cand) VQ2_LAUNCH_EMBED(true, true); else VQ2_LAUNCH_EMBED(true, false); }
+    else { if (cand) VQ2_LAUNCH_EMBED(false, true); else VQ2_LAUNCH_EMBED(false, false); }
+#undef VQ2_LAUNCH_EMBED
     return check_launch("vq_ema_embed_kernel");
 }
 
@@ -823,6 +934,44 @@ extern "C" int vq2_vq_ema_update_prepare(float *embed, float *cluster_size, floa
     return ema_update_impl(embed, cluster_size, embed_avg, counts, sumsT, D, K, decay, eps, scratch, embedT, enorm,
                            to_stream(stream));
 }
+
+// what both restart entry points refuse about the codebook (the limits of vq2_vq_ema_update_prepare and vq2_vq_stats)
+#define VQ2_REQUIRE_RESTART_DIMS(who)                                                                              \
+    VQ2_REQUIRE(D >= 4 && D <= 256 && D % 4 == 0 && K > 0 && K <= 16384,                                           \
+                who ": need D %% 4 == 0 in 4..256 and 1 <= K <= 16384 (D=%d K=%d)", D, K)
+
+extern "C" int vq2_vq_restart_candidates(const float *x, int32_t ldx, int64_t M, int32_t D, int32_t K, uint64_t seed,
+                                         uint64_t step, uint32_t slot, int32_t rank, int32_t world, float *cand,
+                                         int64_t *picks, vq2_stream_t stream) {
+    VQ2_REQUIRE(x && cand, "vq_restart_candidates: null pointer");
+    VQ2_REQUIRE_RESTART_DIMS("vq_restart_candidates");
+    VQ2_REQUIRE(world >= 1, "vq_restart_candidates: world must be at least 1 (world=%d)", world);
+    VQ2_REQUIRE(rank >= 0 && rank < world, "vq_restart_candidates: rank %d outside [0, %d)", rank, world);
+    VQ2_REQUIRE(M > 0 && M < (1ll << 32) && M * world < (1ll << 32),
+                "vq_restart_candidates: need 0 < M * world < 2^32 (M=%lld world=%d)", (long long)M, world);
+    VQ2_REQUIRE(ldx >= D && ldx % 4 == 0, "vq_restart_candidates: bad pixel stride (ldx=%d D=%d)", ldx, D);
+    VQ2_REQUIRE(aligned16(x) && aligned16(cand), "vq_restart_candidates: pointers must be 16-byte aligned");
+    hipLaunchKernelGGL(vq_restart_candidates_kernel, dim3(grid_for((int64_t)K * (D / 4))), dim3(256), 0, to_stream(stream),
+                       x, ldx, (uint32_t)M, D, K, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step,
+                       (uint32_t)(step >> 32), slot, (uint32_t)rank, (uint32_t)(M * world), cand, picks);
+    return check_launch("vq_restart_candidates_kernel");
+}
+
+extern "C" int vq2_vq_ema_update_restart(float *embed, float *cluster_size, float *embed_avg, const float *counts,
+                                         const float *sumsT, const float *cand, int32_t D, int32_t K, double decay,
+                                         double eps, double threshold, float *scratch, float *embedT, float *enorm,
+                                         int64_t *counter, vq2_stream_t stream) {
+    VQ2_REQUIRE(embed && cluster_size && embed_avg && counts && sumsT && cand && scratch && counter,
+                "vq_ema_update_restart: null pointer");
+    VQ2_REQUIRE((embedT == nullptr) == (enorm == nullptr), "vq_ema_update_restart: embedT and enorm go together");
+    VQ2_REQUIRE_RESTART_DIMS("vq_ema_update_restart");
+    VQ2_REQUIRE(threshold >= 0.0 && threshold <= 3.4028234663852886e38, "vq_ema_update_restart: threshold must be finite and >= 0 (%g)",
+                threshold);
+    VQ2_REQUIRE(aligned16(cand) && aligned16(scratch), "vq_ema_update_restart: cand and scratch must be 16-byte aligned");
+    return ema_update_impl(embed, cluster_size, embed_avg, counts, sumsT, D, K, decay, eps, scratch, embedT, enorm,
+                           to_stream(stream), cand, (float)threshold, counter);
+}
+#undef VQ2_REQUIRE_RESTART_DIMS
 
 extern "C" int vq2_vq_gather(const int64_t *idx, const float *embedT, int64_t M, int32_t D, int32_t K, float *out,
                              int32_t ldo, vq2_stream_t stream) {

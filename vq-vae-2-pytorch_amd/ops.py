@@ -1607,12 +1607,14 @@ class QuantizeFn(Function):
     fp32 statistics buffer of vqvae.py:55-56 in the layout of vq_stats_views (None in eval mode)."""
 
     @staticmethod
-    def forward(ctx, x, embed, want_stats, stats_buf, out_buf, prep=None, stats_stream=None):
+    def forward(ctx, x, embed, want_stats, stats_buf, out_buf, prep=None, stats_stream=None, restart=None):
         """prep: (embedT, enorm) of `embed` if the caller already holds them (Quantize caches what
         vq2_vq_ema_update_prepare leaves), else they are computed here.
         stats_stream: side stream for the EMA statistics when their consumer is far away (Stage1Trainer applies the
         EMA update after backward): five small latency-bound launches that then run beside the matrix-bound
-        forward / backward kernels instead of between them.  The caller joins the stream before it reads stats_buf."""
+        forward / backward kernels instead of between them.  The caller joins the stream before it reads stats_buf.
+        restart: None, or (cand [K*D], seed, step, slot, rank, world) of the dead-code restart: with want_stats the
+        candidate rows are gathered from the same x right after the statistics, on their stream (vq_restart_candidates)."""
         x = as_nhwc(x)
         n, h, w, d = x.shape
         k = embed.shape[1]
@@ -1643,11 +1645,15 @@ class QuantizeFn(Function):
                 with torch.cuda.stream(stats_stream):
                     check(lib.vq2_vq_stats(_p(x), ld_of(x), _p(idx), m, d, k, _p(counts), _p(sums_t), _p(ws), nbytes,
                                            _stream()), "vq_stats")
+                    if restart is not None:
+                        vq_restart_candidates(x, k, *restart)
                 for tns in (x, idx, ws):
                     tns.record_stream(stats_stream)
             else:
                 check(lib.vq2_vq_stats(_p(x), ld_of(x), _p(idx), m, d, k, _p(counts), _p(sums_t), _p(ws), nbytes,
                                        _stream()), "vq_stats")
+                if restart is not None:
+                    vq_restart_candidates(x, k, *restart)
         diff = torch.empty((), device=x.device, dtype=torch.float32)
         check(lib.vq2_vq_loss(_p(part), m, d, _p(diff), _stream()), "vq_loss")
         ctx.save_for_backward(x, idx, embed_t)
@@ -1663,7 +1669,7 @@ class QuantizeFn(Function):
         x, idx, embed_t = ctx.saved_tensors
         n, h, w, d = x.shape
         if g_out is None and g_diff is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         if g_out is not None:
             g_out = as_nhwc(g_out)
         if g_diff is not None and not g_diff.is_contiguous():
@@ -1671,7 +1677,7 @@ class QuantizeFn(Function):
         dx = torch.empty((n, h, w, d), device=x.device, dtype=torch.float32)
         check(lib.vq2_vq_bwd(_p(g_out), ld_of(g_out) if g_out is not None else d, _p(g_diff), _p(x), ld_of(x),
                              _p(idx), _p(embed_t), n * h * w, d, ctx.k, _p(dx), d, _stream()), "vq_bwd")
-        return dx, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None
 
 
 def vq_ema_update(embed, cluster_size, embed_avg, stats, decay, eps, prep_out=None):
@@ -1687,6 +1693,35 @@ def vq_ema_update(embed, cluster_size, embed_avg, stats, decay, eps, prep_out=No
     check(lib.vq2_vq_ema_update(_p(embed), _p(cluster_size), _p(embed_avg), _p(counts), _p(sums_t), d, k,
                                 float(decay), float(eps), _p(scratch), _stream()), "vq_ema_update")
     return False
+
+
+def vq_restart_candidates(x, k, cand, seed, step, slot, rank=0, world=1, picks=None):
+    """cand [K*D] <- the candidate row of every code from this rank's x [..., D] (NHWC latents, as vq2_vq_stats reads them),
+    zeros for rows another rank owns; picks (int64 [K], optional) <- the global rows drawn.  On the current stream."""
+    n, h, w, d = x.shape
+    m = n * h * w
+    if cand.numel() != k * d or not cand.is_contiguous() or cand.dtype != torch.float32:
+        raise RuntimeError(f"vq_restart_candidates: cand must be {k * d} contiguous floats (K={k}, D={d})")
+    if picks is not None and (picks.numel() != k or picks.dtype != torch.int64 or not picks.is_contiguous()):
+        raise RuntimeError(f"vq_restart_candidates: picks must be {k} contiguous int64")
+    check(lib.vq2_vq_restart_candidates(_p(x), ld_of(x), m, d, k, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                                        int(slot), int(rank), int(world), _p(cand), _p(picks), _stream()),
+          "vq_restart_candidates")
+
+
+def vq_ema_update_restart(embed, cluster_size, embed_avg, stats, cand, decay, eps, threshold, counter, prep_out=None):
+    """vq_ema_update with dead-code restarts: a code whose new size is below `threshold` and whose candidate row in
+    cand [K*D] is finite restarts from it.  counter: int64 [2] on the device, {restarted by this call, running total}."""
+    d, k = embed.shape
+    counts, sums_t = vq_stats_views(stats, k, d)
+    if counter.dtype != torch.int64 or counter.numel() != 2 or not counter.is_contiguous() or counter.device != embed.device:
+        raise RuntimeError("vq_ema_update_restart: counter must be 2 contiguous int64 on the codebook's device")
+    scratch = torch.empty(4 + k, device=embed.device, dtype=torch.float32)    # n, then the dead mask
+    et, en = prep_out if prep_out is not None else (None, None)
+    check(lib.vq2_vq_ema_update_restart(_p(embed), _p(cluster_size), _p(embed_avg), _p(counts), _p(sums_t), _p(cand), d, k,
+                                        float(decay), float(eps), float(threshold), _p(scratch), _p(et), _p(en),
+                                        _p(counter), _stream()), "vq_ema_update_restart")
+    return prep_out is not None
 
 
 def vq_gather(idx, embed, prep=None):

@@ -354,11 +354,52 @@ class Stage1Trainer(_ArenaTrainer):
             if self.dp:
                 first = enc_t.blocks[0]
                 self._send_when_reported(middle, (first.weight, first.bias), self._flush_slabs)
+        self.code_restart = self._restart_cand = self._restart_counters = None      # set_code_restart()
         self._finish_construction()
 
     def _params_overwritten(self):
         for q in self.quantizers:       # anything a Quantize derived from its OLD codebook is stale now
             q.invalidate_prepared()
+
+    # ------------------------------------------------------------------ dead-code restart
+    def set_code_restart(self, threshold=1.0, start=0, seed=0):
+        """Random restart of dead codes in every quantizer (Quantize.enable_code_restart with slot = its index in
+        self.quantizers); threshold None turns it off.  The Philox step is this trainer's step count (the optimizer's, which
+        the checkpoint holds), so a resumed run draws the rows an uninterrupted one draws.  The candidate rows of all
+        quantizers live in ONE flat buffer outside the arena; data parallel it is summed by one collective on the
+        communication stream, which the deferred updates wait for.  step() then also returns "restarted"."""
+        if threshold is None:
+            for q in self.quantizers:
+                q.disable_code_restart()
+                q.restart_cand = q.restart_counter = None
+            self.code_restart = self._restart_cand = self._restart_counters = None
+            return
+        for slot, q in enumerate(self.quantizers):
+            q.enable_code_restart(threshold, start, seed, slot)      # (refuses a bad threshold before anything changes)
+        dev = self.arena.flat_p.device
+        sizes = [q.n_embed * q.dim for q in self.quantizers]         # multiples of 4: every slice stays 16-byte aligned
+        self._restart_cand = torch.zeros(sum(sizes), device=dev, dtype=torch.float32)
+        self._restart_counters = torch.zeros((len(sizes), 2), device=dev, dtype=torch.int64)
+        off = 0
+        for i, (q, n) in enumerate(zip(self.quantizers, sizes)):
+            q.restart_cand, q.restart_counter = self._restart_cand[off:off + n], self._restart_counters[i]
+            off += n
+        self.code_restart = {"threshold": float(threshold), "start": int(start), "seed": int(seed)}
+
+    def restarted_codes(self):
+        """Codes restarted so far, one total per quantizer: the one host read of the device counters."""
+        if self.code_restart is None:
+            return [0] * len(self.quantizers)
+        return [int(v) for v in self._restart_counters[:, 1].tolist()]
+
+    def _reduce_candidates(self):
+        """Data parallel: the owner of each drawn row wrote it, every other rank zeros; one SUM leaves it everywhere."""
+        if self.code_restart is None or not self.dp:
+            return
+        ev = torch.cuda.current_stream().record_event()
+        with torch.cuda.stream(self.comm_stream):
+            self.comm_stream.wait_event(ev)
+            self.comm.all_reduce(self._restart_cand)
 
     def _weights_replaced(self):
         super()._weights_replaced()
@@ -381,6 +422,9 @@ class Stage1Trainer(_ArenaTrainer):
         if u8 and self.normalizer is None:
             raise TypeError("Stage1Trainer.step: a uint8 batch needs Stage1Trainer(..., normalizer=ImageNormalizer(...))")
         model.train()
+        if self.code_restart is not None:
+            for q in self.quantizers:       # the draw of this step: a function of the step count the checkpoint holds
+                q.restart_step = self.optimizer._t
         # the EMA statistics slots are fully rewritten by vq2_vq_stats, and their pad floats (ops.vq_stats_views) were
         # zeroed with the arena and are never written: nothing to zero
         self.arena.zero_grad()
@@ -416,6 +460,7 @@ class Stage1Trainer(_ArenaTrainer):
         self.ctx.batch.flush()   # one launch reduces the split-K slabs of every layer into the arena
         # gradients (SUM; Adam divides by world) and EMA sums (SUM, vqvae.py:58-59) travel together; normally only
         # enc_b's slice is left
+        self._reduce_candidates()
         self._reduce_unsent()
         for q in self.quantizers:
             q.apply_deferred_update()
@@ -424,6 +469,8 @@ class Stage1Trainer(_ArenaTrainer):
         self.optimizer.step()
         self.pack_plan.run()
         out = self._clip_result({"loss": loss.detach(), "recon": recon, "latent": latent})
+        if self.code_restart is not None:
+            out["restarted"] = self._restart_counters[:, 0]     # per quantizer, this step (a view: the next step rewrites it)
         if return_dec:
             d = dec.detach()
             out["dec"] = ops.from_nhwc(d, channels) if hasattr(model, "forward_nhwc") else d
@@ -470,8 +517,34 @@ class Stage1Trainer(_ArenaTrainer):
                 dec, _ = model.forward_nhwc(x)
             return self.normalizer.inverse().grid([x, dec], nrow=x.shape[0], nhwc=True)
 
+    def state_dict(self):
+        """_ArenaTrainer.state_dict(), with "code_restart" = {threshold, start, seed, totals} when set_code_restart() is on."""
+        sd = super().state_dict()
+        if self.code_restart is not None:
+            sd["code_restart"] = dict(self.code_restart, totals=self.restarted_codes())
+        return sd
+
     def load_state_dict(self, sd):
+        """_ArenaTrainer.load_state_dict(); a full checkpoint and a trainer that disagree about the code restart (one has
+        it and the other not, or its threshold / start / seed differ) are refused before anything changes: the steps that
+        follow would not be the run's."""
+        if split_checkpoint(sd)[1]:
+            mine, theirs = self.code_restart, sd.get("code_restart")
+            who = "Stage1Trainer.load_state_dict"
+            if (mine is None) != (theirs is None):
+                raise RuntimeError(f"{who}: the checkpoint was trained {'with' if theirs else 'without'} code restart and the "
+                                   f"trainer runs {'with' if mine else 'without'} it (set_code_restart)")
+            if mine is not None:
+                if any(theirs.get(k) != mine[k] for k in mine):
+                    raise RuntimeError(f"{who}: code restart settings differ: checkpoint "
+                                       f"{ {k: theirs.get(k) for k in mine} }, trainer {mine} (set_code_restart)")
+                if len(theirs.get("totals", ())) != len(self.quantizers):
+                    raise RuntimeError(f"{who}: code restart totals belong to a different model")
         super().load_state_dict(sd)
+        if self.code_restart is not None and split_checkpoint(sd)[1]:
+            totals = torch.tensor(sd["code_restart"]["totals"], dtype=torch.int64)
+            self._restart_counters[:, 0].zero_()
+            self._restart_counters[:, 1].copy_(totals)
         self.pack_plan.run()
 
 

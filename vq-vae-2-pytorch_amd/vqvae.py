@@ -120,6 +120,44 @@ class Quantize(nn.Module):
         self._prep = None
         self._prep_key = None
         self._raw_updates = 0
+        # dead-code restart (enable_code_restart): plain attributes, nothing registered -- the state_dict is the reference's
+        self._restart = None         # {"threshold", "start", "seed", "slot"} when on
+        self.restart_step = 0        # Philox step of the NEXT training forward; advances once per training forward
+        self.restart_cand = None     # set by Stage1Trainer: this quantizer's slice of its flat candidate buffer
+        self.restart_counter = None  # int64 [2] on the device: {restarted by the last update, running total}
+        self._restart_pending = None
+
+    def enable_code_restart(self, threshold=1.0, start=0, seed=0, slot=0):
+        """Random restart of dead codes: at a training step t >= start, a code whose EMA cluster size has fallen below
+        `threshold` is replaced by an encoder output of the current batch (drawn by Philox from seed, t, slot and the code's
+        number: the same row on every rank), on the device and without a host read.  threshold = 0 restarts nothing and
+        leaves the bits of the plain update.  slot tells the quantizers of one model apart."""
+        threshold = float(threshold)
+        if not (0.0 <= threshold < float("inf")):
+            raise ValueError(f"Quantize.enable_code_restart: threshold must be finite and >= 0, got {threshold}")
+        if int(start) < 0 or int(slot) < 0:
+            raise ValueError("Quantize.enable_code_restart: start and slot must be >= 0")
+        self._restart = {"threshold": threshold, "start": int(start), "seed": int(seed), "slot": int(slot)}
+
+    def disable_code_restart(self):
+        self._restart = None
+        self._restart_pending = None
+
+    def _restart_args(self, flat):
+        """What QuantizeFn needs to gather this step's candidates; remembers them for the update.  flat: the drop-in path's
+        [statistics | candidates] buffer, or None when a trainer owns the candidate buffer."""
+        r = self._restart
+        n = self.n_embed * self.dim
+        cand = self.restart_cand if flat is None else flat[-n:]
+        if cand is None or cand.numel() != n or cand.device != self.embed.device:
+            raise RuntimeError("Quantize: deferred statistics with code restart need the trainer's candidate buffer "
+                               "(Stage1Trainer.set_code_restart)")
+        if self.restart_counter is None or self.restart_counter.device != self.embed.device:
+            self.restart_counter = torch.zeros(2, device=self.embed.device, dtype=torch.int64)
+        step = self.restart_step
+        self.restart_step = step + 1
+        self._restart_pending = (cand, r["threshold"] if step >= r["start"] else 0.0)
+        return cand, r["seed"], step, r["slot"], dist_fn.get_rank(), dist_fn.get_world_size()
 
     def _embed_key(self):
         return (self.embed.data_ptr(), self.embed._version, self._raw_updates, self.embed.device)
@@ -141,8 +179,13 @@ class Quantize(nn.Module):
         # searched the pre-update codebook (the drop-in path updates inside forward, before backward reads embedT)
         self._prep = (torch.empty((self.n_embed, self.dim), device=self.embed.device, dtype=torch.float32),
                       torch.empty(self.n_embed, device=self.embed.device, dtype=torch.float32))
-        fused = ops.vq_ema_update(self.embed, self.cluster_size, self.embed_avg, stats, self.decay, self.eps, self._prep)
-        self._raw_updates += 1       # the kernels write through raw pointers: tensor._version does not move
+        if self._restart_pending is not None:      # code restart: the candidates of the forward these statistics came from
+            (cand, threshold), self._restart_pending = self._restart_pending, None
+            fused = ops.vq_ema_update_restart(self.embed, self.cluster_size, self.embed_avg, stats, cand, self.decay,
+                                              self.eps, threshold, self.restart_counter, self._prep)
+        else:
+            fused = ops.vq_ema_update(self.embed, self.cluster_size, self.embed_avg, stats, self.decay, self.eps, self._prep)
+        self._raw_updates += 1      # the kernels write through raw pointers: tensor._version does not move
         self._prep_key = self._embed_key() if fused else None
 
     def forward(self, input, _out=None):
@@ -151,10 +194,23 @@ class Quantize(nn.Module):
             raise RuntimeError(f"Quantize: last dim {input.shape[-1]} != {self.dim}")
         x = input if input.dim() == 4 else input.reshape(-1, 1, 1, self.dim)
         want = self.training
-        out, diff, ind, stats = ops.QuantizeFn.apply(x, self.embed, want, self.deferred_stats, _out, self._prepared(),
-                                                      self.stats_stream if self.deferred_stats is not None else None)
+        stats_buf, flat, restart = self.deferred_stats, None, None
+        if want and self._restart is not None:      # (eval mode draws nothing, launches nothing new, writes nothing)
+            if stats_buf is None:
+                # drop-in path: statistics and candidates share one buffer [statistics | candidates], so that they
+                # still travel in ONE collective
+                ns = ops.vq_stats_numel(self.n_embed, self.dim)
+                flat = torch.empty(ns + self.n_embed * self.dim, device=self.embed.device, dtype=torch.float32)
+                if self.n_embed % 4:
+                    flat[self.n_embed:ns - self.n_embed * self.dim].zero_()     # the pad of ops.vq_stats_views
+                stats_buf = flat[:ns]
+            restart = self._restart_args(flat)
+        out, diff, ind, stats = ops.QuantizeFn.apply(x, self.embed, want, stats_buf, _out, self._prepared(),
+                                                      self.stats_stream if self.deferred_stats is not None else None,
+                                                      restart)
         if want and self.deferred_stats is None:
-            dist_fn.all_reduce(stats)  # counts and sums in ONE collective (vqvae.py:58-59 issues two)
+            # counts and sums in ONE collective (vqvae.py:58-59 issues two); the restart candidates ride along
+            dist_fn.all_reduce(stats if flat is None else flat)
             self._ema_update(stats)
         if input.dim() != 4:
             out = out.reshape(input.shape)
