@@ -15,6 +15,9 @@ examples/train_stage1.py saves a bare state_dict.  A PNG needs PIL; without it t
 Truncated sampling, for both priors: --top_k INT draws from the INT most likely codes only, --top_p FLOAT from the smallest set
 of most likely codes that holds FLOAT of the probability (0 and 1.0: off).
 
+--stepping row (the default) recomputes a whole row per drawn code; --stepping pixel computes the drawn column only
+(PriorSampler's `stepping`).
+
 Completing images: --from_images FILE.npy --keep_rows R.  FILE.npy holds uint8 [B, H, W, 3]; the images are normalised to
 [-1, 1], encoded with the VQ-VAE, and the first R rows of their top codes and 2 R rows of their bottom codes are kept; the priors
 draw the rest.  The batch size is that of the file."""
@@ -41,6 +44,7 @@ def parse_args(argv=None):
     parser.add_argument('--vqvae_arg', action='append', default=[], metavar='NAME=INT')
     parser.add_argument('--top_k', type=int, default=0)
     parser.add_argument('--top_p', type=float, default=1.0)
+    parser.add_argument('--stepping', choices=['row', 'pixel'], default='row')
     parser.add_argument('--from_images', type=str, metavar='FILE.npy')
     parser.add_argument('--keep_rows', type=int, default=0)
     return parser.parse_args(argv)
@@ -74,7 +78,7 @@ def draw_codes(args, model_vqvae, model_top, model_bottom, device):
             raise SystemExit(f"--keep_rows must be in 0..{top_size[0]}")
         batch = id_t.shape[0]
         top_prefix, bottom_prefix = id_t[:, :args.keep_rows].contiguous(), id_b[:, :2 * args.keep_rows].contiguous()
-    kw = dict(top_k=args.top_k, top_p=args.top_p)
+    kw = dict(top_k=args.top_k, top_p=args.top_p, stepping=args.stepping)
     top_sample = vqvae2_amd.sample_model(model_top, device, batch, top_size, args.temp, prefix=top_prefix, **kw)
     bottom_sample = vqvae2_amd.sample_model(model_bottom, device, batch, bottom_size, args.temp, condition=top_sample,
                                             prefix=bottom_prefix, **kw)

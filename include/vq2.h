@@ -63,11 +63,12 @@ typedef void *vq2_stream_t;
  * VQ2_ALLOW_BF16, the panels VQ2_PACK_FWD_BF16 / VQ2_PACK_DGRAD_BF16 and vq2_conv_bf16_eligible; revision 18: additions
  * only -- the bf16-operand weight gradient: VQ2_ALLOW_BF16 in the flags of vq2_conv_wgrad / vq2_conv_wgrad_partial (ignored
  * before), vq2_conv_wgrad_bf16_eligible, vq2_conv_wgrad_workspace_bytes_ex and vq2_wgrad_job_init_ex;
- * revision 19: additions only -- the dead-code restart of Quantize: vq2_vq_restart_candidates and vq2_vq_ema_update_restart.
+ * revision 19: additions only -- the dead-code restart of Quantize: vq2_vq_restart_candidates and vq2_vq_ema_update_restart;
+ * revision 20: additions only -- pixel-incremental sampling: vq2_conv_fwd_col with its workspace query.
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 19
+#define VQ2_API_VERSION 20
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -654,7 +655,8 @@ int vq2_upsample2_bwd(const float *dy, int32_t lddy, float *dx, int32_t lddx, in
 /* ------------------------------------------------------------------ sampling from the prior, one image row at a time
  * The reference's sample_model (sample.py:17-29) runs the whole model on rows 0..i for every pixel (i, j).  Every layer is
  * causal in raster order, so a sampler keeps what earlier rows produced and computes row i only; the two layer kinds that
- * look at earlier rows get entry points that read a history in place, and the draw is one launch.
+ * look at earlier rows get entry points that read a history in place, and the draw is one launch.  A sampler may also
+ * compute one column of the row per step: the convs over several rows then go through vq2_conv_fwd_col.
  *
  * vq2_conv_fwd_row: output row `row` of what vq2_conv_fwd computes for the same descriptor (d->H is the number of rows
  *              the image has; 0 <= row < H; same_size == 1 and pad_top == KH - 1 are required, else VQ2_ERR_INVALID;
@@ -667,6 +669,19 @@ int vq2_upsample2_bwd(const float *dy, int32_t lddy, float *dx, int32_t lddx, in
  *              [N * W, Co] slab per split in `ws` (>= vq2_conv_fwd_row_workspace_bytes(d, flags), 16-byte aligned), then the
  *              slabs are added in ascending order with the epilogue.  fp32-input MFMA, fp32 accumulation, no atomics:
  *              bit-reproducible.  The sums run in another order than vq2_conv_fwd's, so the two agree to rounding only.
+ * vq2_conv_fwd_col: output pixel (row, col) of what vq2_conv_fwd computes for the same descriptor, for all d->N images
+ *              (0 <= row < H, 0 <= col < W; whatever vq2_conv_fwd_row refuses is refused here too: VQ2_ERR_INVALID).  The
+ *              input is addressed as for vq2_conv_fwd_row; y is dense [N, ldy] and residual [N, ldres].  wp is the same
+ *              VQ2_PACK_FWD panel; bias, VQ2_RELU_IN / VQ2_RELU_OUT, the residual, the Cir / Cor padding and the zeroed pad
+ *              lanes are those of vq2_conv_fwd.  Never read: rows > row, and taps outside the image (they count as 0).  With
+ *              VQ2_ROW_CAUSAL_TAPS the last kernel row's columns KW / 2 .. KW - 1 are skipped, so that of row `row` no
+ *              column >= col is read: those cells may hold anything.  Without the flag every tap inside the image is read.
+ *              The work is the weight panel: it is cut over output channels and over (tap, 64 input channels) steps, every
+ *              element read once per 64 images; one [N, Co] slab per split in `ws` (>=
+ *              vq2_conv_fwd_col_workspace_bytes(d, flags), 16-byte aligned; a smaller one is VQ2_ERR_INVALID before any
+ *              launch; the size depends on the descriptor and the flags, not on row or col), then the slabs are added in
+ *              ascending order with the epilogue.  fp32-input MFMA, fp32 accumulation, no atomics: bit-reproducible; agrees
+ *              with vq2_conv_fwd and vq2_conv_fwd_row to rounding.
  * vq2_causal_attn_fwd_rows: vq2_causal_attn_fwd for the queries at raster positions q0 .. q0 + nq - 1 (q0 + nq <= d->L).
  *              q and o are dense [B, nq, ldq / ldo]; the key or value at position p of image b is at
  *              base + b * kv_image_stride + (p / W) * kv_row_stride + (p % W) * ldk (ldv); positions < q0 + nq - 1 are read, the last
@@ -711,6 +726,10 @@ size_t vq2_conv_fwd_row_workspace_bytes(const vq2_conv_desc *d, int flags);
 int vq2_conv_fwd_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
                       const float *x, const float *wp, const float *bias, const float *residual, int32_t ldres, float *y,
                       void *ws, size_t ws_bytes, vq2_stream_t stream);
+size_t vq2_conv_fwd_col_workspace_bytes(const vq2_conv_desc *d, int flags);
+int vq2_conv_fwd_col(const vq2_conv_desc *d, int32_t row, int32_t col, int64_t x_image_stride, int64_t x_row_stride,
+                     int flags, const float *x, const float *wp, const float *bias, const float *residual, int32_t ldres,
+                     float *y, void *ws, size_t ws_bytes, vq2_stream_t stream);
 int vq2_causal_attn_fwd_rows(const vq2_attn_desc *d, int32_t q0, int32_t nq, int32_t W, int64_t kv_image_stride,
                              int64_t kv_row_stride, const float *q, const float *k, const float *v, float *o,
                              vq2_stream_t stream);

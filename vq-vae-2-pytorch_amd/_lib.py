@@ -146,6 +146,8 @@ def _load():
         "vq2_upsample2_bwd": (C.c_int, [P, I32, P, I32, I32, I32, I32, I32, P]),
         "vq2_conv_fwd_row_workspace_bytes": (SZ, [DP, C.c_int]),
         "vq2_conv_fwd_row": (C.c_int, [DP, I32, I64, I64, C.c_int, P, P, P, P, I32, P, P, SZ, P]),
+        "vq2_conv_fwd_col_workspace_bytes": (SZ, [DP, C.c_int]),
+        "vq2_conv_fwd_col": (C.c_int, [DP, I32, I32, I64, I64, C.c_int, P, P, P, P, I32, P, P, SZ, P]),
         "vq2_causal_attn_fwd_rows": (C.c_int, [C.POINTER(AttnDesc), I32, I32, I32, I64, I64, P, P, P, P, P]),
         "vq2_sample_categorical": (C.c_int, [P, I64, I32, I32, F, U64, U64, P, I64, P]),
         "vq2_sample_filtered": (C.c_int, [P, I64, I32, I32, F, I32, F, U64, U64, P, I64, P, P, P]),

@@ -11,6 +11,14 @@
 //                      reads of 4 consecutive input channels (k step s of an MFMA quadruple takes channel 4 * g + s from
 //                      both sides, as in vq2_attn.hip); the four waves of a workgroup share the panel rows through the
 //                      vector cache and differ in their 32 pixels.  It reads the VQ2_PACK_FWD panel [Co][tap][Ci].
+//   column convolution  output pixel (row, col) of the same conv for all N images: M = N, so the weight panel is the traffic.
+//                      Work is cut into steps of (one computed tap, 64 input channels); a workgroup owns 32 output channels
+//                      and one contiguous range of steps, its four waves take 16 channels of a step each (a float4 per lane
+//                      from either side, every panel element read once per 64 images) and add their accumulators through
+//                      LDS in wave order.  convg_col_partial_kernel writes one [N][Co] slab per range,
+//                      convg_row_reduce_kernel (M = N) adds the slabs in ascending order with the epilogue.  The same
+//                      v_mfma_f32_16x16x4_f32 with the images on the 16-wide B side; taps outside the image are skipped for
+//                      the whole grid (row and col are launch constants).  No atomics.
 //   categorical draw   one wave per row of logits: maximum, sum of exponentials over lane-contiguous chunks, a fixed-order
 //                      scan over the lanes, then every lane walks its chunk for the first class whose running sum passes
 //                      u * sum; the lowest such lane wins.  u comes from Philox4x32-7 keyed by (seed, position, row).
@@ -163,6 +171,125 @@ __global__ __launch_bounds__(256) void convg_row_reduce_kernel(const float *__re
         if (relu_out) o[k] = fmaxf(o[k], 0.f);
     }
     *reinterpret_cast<float4 *>(y + (size_t)p * ldy + c) = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// ----------------------------------------------------------------------------- column convolution
+constexpr int CC_BN = 32;    // output channels per workgroup: 2 MFMA tiles, every wave computes both
+constexpr int CC_BK = 64;    // input channels per step: 16 per wave
+
+struct ColConv {
+    const float *x, *w;
+    float *ws;
+    long long x_image_stride, x_row_stride;
+    int N, W, Ci, Co, KH, KW, pad_left, ldx, row, col, K;
+    int relu_in;
+    int cb;              // channel blocks per tap: ceil(Ci / CC_BK)
+    int steps, sps;      // steps = computed taps * cb; steps per split
+    unsigned char taps[32];   // the computed taps (kh * KW + kw), ascending
+};
+
+// which taps are computed and how the steps are cut into splits: a function of the shape and the flags alone
+struct ColPlan { unsigned char taps[32]; int ntaps, cb, steps, sps, splits, mt; };
+static ColPlan col_plan(const vq2_conv_desc *d, int flags) {
+    ColPlan p{};
+    for (int kh = 0; kh < d->KH; ++kh)
+        for (int kw = 0; kw < d->KW; ++kw) {
+            if ((flags & VQ2_ROW_CAUSAL_TAPS) && kh == d->KH - 1 && kw >= d->KW / 2) continue;
+            p.taps[p.ntaps++] = (unsigned char)(kh * d->KW + kw);
+        }
+    p.cb = (d->Ci + CC_BK - 1) / CC_BK;
+    p.steps = p.ntaps * p.cb;
+    p.mt = d->N <= 16 ? 1 : 4;                       // image tiles of 16 per workgroup
+    p.sps = 1;
+    p.splits = 1;
+    if (p.steps == 0) return p;                      // a 1 x 1 'causal' kernel: nothing but the bias
+    const long tiles = (long)((d->Co + CC_BN - 1) / CC_BN) * ((d->N + 16 * p.mt - 1) / (16 * p.mt));
+    long want = (512 + tiles - 1) / tiles;           // about two workgroups per compute unit
+    // a slab is written and read once: keep that at or below half the panel's bytes (splits * N <= K / 4)
+    const long cap = (long)p.ntaps * d->Ci / (4l * d->N);
+    if (want > cap) want = cap;
+    if (want > p.steps) want = p.steps;
+    if (want < 1) want = 1;
+    p.sps = (int)((p.steps + want - 1) / want);
+    p.splits = (p.steps + p.sps - 1) / p.sps;
+    return p;
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void convg_col_partial_kernel(const ColConv P) {
+    __shared__ float4 red[4][2 * MT][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
+    const int co0 = blockIdx.x * CC_BN, split = blockIdx.y, n0 = blockIdx.z * (16 * MT);
+    const float *wrow[2];
+    bool wv[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        const int co = co0 + 16 * nt + col;
+        wv[nt] = co < P.Co;
+        wrow[nt] = P.w + (size_t)(wv[nt] ? co : 0) * P.K;
+    }
+    const float *ximg[MT];
+    bool pv[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int n = n0 + 16 * mt + col;
+        pv[mt] = n < P.N;
+        ximg[mt] = P.x + (pv[mt] ? (long long)n * P.x_image_stride : 0ll);
+    }
+    f32x4 acc[2][MT];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int s0 = split * P.sps, s1 = min(s0 + P.sps, P.steps);
+    for (int step = s0; step < s1; ++step) {
+        const int ai = step / P.cb, c = (step - ai * P.cb) * CC_BK + wave * 16 + 4 * g;
+        const int tap = P.taps[ai];
+        const int kh = tap / P.KW, kw = tap - kh * P.KW;
+        const int r = P.row - (P.KH - 1) + kh, wi = P.col - P.pad_left + kw;
+        if (r < 0 || wi < 0 || wi >= P.W) continue;            // outside the image: zeros (the same for the whole grid)
+        const bool cv = c < P.Ci;
+        const long long xoff = (long long)r * P.x_row_stride + (long long)wi * P.ldx + c;
+        const int koff = tap * P.Ci + c;
+        float4 a[2], b[MT];
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+            a[nt] = (wv[nt] && cv) ? *reinterpret_cast<const float4 *>(wrow[nt] + koff) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            b[mt] = (pv[mt] && cv) ? *reinterpret_cast<const float4 *>(ximg[mt] + xoff) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (P.relu_in) b[mt] = vq2::relu4(b[mt]);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                acc[nt][mt] = mfma4(a[nt].x, b[mt].x, acc[nt][mt]);
+                acc[nt][mt] = mfma4(a[nt].y, b[mt].y, acc[nt][mt]);
+                acc[nt][mt] = mfma4(a[nt].z, b[mt].z, acc[nt][mt]);
+                acc[nt][mt] = mfma4(a[nt].w, b[mt].w, acc[nt][mt]);
+            }
+    }
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+            red[wave][nt * MT + mt][lane] = make_float4(acc[nt][mt][0], acc[nt][mt][1], acc[nt][mt][2], acc[nt][mt][3]);
+    __syncthreads();
+    // the four waves' sums in wave order; accumulator register r of lane (col, g) is output channel 16 * nt + 4 * g + r of
+    // image col of its tile
+    for (int e = threadIdx.x; e < 2 * MT * 64; e += 256) {
+        const int t = e >> 6, l = e & 63, nt = t / MT, mt = t - nt * MT;
+        const int n = n0 + 16 * mt + (l & 15), co = co0 + 16 * nt + 4 * (l >> 4);
+        if (n >= P.N || co >= P.Co) continue;
+        float4 s = red[0][t][l];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            const float4 v = red[w][t][l];
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        *reinterpret_cast<float4 *>(P.ws + ((size_t)split * P.N + n) * P.Co + co) = s;
+    }
 }
 
 // ----------------------------------------------------------------------------- categorical draw
@@ -374,16 +501,17 @@ __global__ __launch_bounds__(256) void sample_uniforms_kernel(float *__restrict_
     if (row < M) u[row] = uniform_of(seed_lo, seed_hi, pos_lo, pos_hi, (uint32_t)row);
 }
 
-// what the row form asks beyond vq2::check_conv_desc
-int check_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags) {
-    if (int e = vq2::check_conv_desc(d, "conv_fwd_row")) return e;
+// what the row and column forms ask beyond vq2::check_conv_desc
+int check_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
+              const char *who = "conv_fwd_row") {
+    if (int e = vq2::check_conv_desc(d, who)) return e;
     VQ2_REQUIRE(d->same_size == 1 && d->pad_top == d->KH - 1,
-                "conv_fwd_row: same_size and pad_top == KH - 1 required (the kernel must end at the output row)");
-    VQ2_REQUIRE(row >= 0 && row < d->H, "conv_fwd_row: row %d outside the %d rows", row, d->H);
+                "%s: same_size and pad_top == KH - 1 required (the kernel must end at the output row)", who);
+    VQ2_REQUIRE(row >= 0 && row < d->H, "%s: row %d outside the %d rows", who, row, d->H);
     VQ2_REQUIRE(x_image_stride >= 0 && x_row_stride >= 0 && x_image_stride % 4 == 0 && x_row_stride % 4 == 0,
-                "conv_fwd_row: input strides must be non-negative multiples of 4");
-    VQ2_REQUIRE((flags & ~(VQ2_RELU_IN | VQ2_RELU_OUT | VQ2_ROW_CAUSAL_TAPS)) == 0, "conv_fwd_row: unknown flag");
-    VQ2_REQUIRE((int64_t)d->Co * d->KH * d->KW * d->Ci < ((int64_t)1 << 31), "conv_fwd_row: tensor exceeds 2^31 elements");
+                "%s: input strides must be non-negative multiples of 4", who);
+    VQ2_REQUIRE((flags & ~(VQ2_RELU_IN | VQ2_RELU_OUT | VQ2_ROW_CAUSAL_TAPS)) == 0, "%s: unknown flag", who);
+    VQ2_REQUIRE((int64_t)d->Co * d->KH * d->KW * d->Ci < ((int64_t)1 << 31), "%s: tensor exceeds 2^31 elements", who);
     return VQ2_OK;
 }
 
@@ -421,6 +549,48 @@ extern "C" int vq2_conv_fwd_row(const vq2_conv_desc *d, int32_t row, int64_t x_i
     if (int e = vq2::check_launch("convg_row_partial_kernel")) return e;
     const long total = (long)P.M * (P.Co / 4);
     hipLaunchKernelGGL(convg_row_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P.ws, pl.splits, P.M, P.Co,
+                       d->Cor ? d->Cor : d->Co, bias, residual, ldres, y, d->ldy, (flags & VQ2_RELU_OUT) != 0);
+    return vq2::check_launch("convg_row_reduce_kernel");
+}
+
+extern "C" size_t vq2_conv_fwd_col_workspace_bytes(const vq2_conv_desc *d, int flags) {
+    if (!d || d->N <= 0 || d->Ci <= 0 || d->Co <= 0 || d->KH < 1 || d->KW < 1 || d->KH * d->KW > 32) return 0;
+    const ColPlan p = col_plan(d, flags);
+    return (size_t)p.splits * d->N * d->Co * sizeof(float);
+}
+
+extern "C" int vq2_conv_fwd_col(const vq2_conv_desc *d, int32_t row, int32_t col, int64_t x_image_stride, int64_t x_row_stride,
+                                int flags, const float *x, const float *wp, const float *bias, const float *residual,
+                                int32_t ldres, float *y, void *ws, size_t ws_bytes, vq2_stream_t stream) {
+    if (int e = check_row(d, row, x_image_stride, x_row_stride, flags, "conv_fwd_col")) return e;
+    VQ2_REQUIRE(col >= 0 && col < d->W, "conv_fwd_col: col %d outside the %d columns", col, d->W);
+    VQ2_REQUIRE(x && wp && y && ws, "conv_fwd_col: null pointer");
+    VQ2_REQUIRE(vq2::aligned16(x) && vq2::aligned16(wp) && vq2::aligned16(y) && vq2::aligned16(ws) &&
+                    (!residual || vq2::aligned16(residual)),
+                "conv_fwd_col: pointers must be 16-byte aligned");
+    VQ2_REQUIRE(!residual || (ldres >= d->Co && ldres % 4 == 0), "conv_fwd_col: ldres must be >= Co and a multiple of 4");
+    const ColPlan pl = col_plan(d, flags);
+    const size_t need = vq2_conv_fwd_col_workspace_bytes(d, flags);
+    VQ2_REQUIRE(ws_bytes >= need, "conv_fwd_col: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    const int chunks = (d->N + 16 * pl.mt - 1) / (16 * pl.mt);
+    VQ2_REQUIRE(chunks <= 65535, "conv_fwd_col: %d images exceed the grid", d->N);
+    hipStream_t s = vq2::to_stream(stream);
+    ColConv P{};
+    P.x = x; P.w = wp; P.ws = static_cast<float *>(ws);
+    P.x_image_stride = x_image_stride; P.x_row_stride = x_row_stride;
+    P.N = d->N; P.W = d->W; P.Ci = d->Ci; P.Co = d->Co; P.KH = d->KH; P.KW = d->KW; P.pad_left = d->pad_left; P.ldx = d->ldx;
+    P.row = row; P.col = col; P.K = d->KH * d->KW * d->Ci;
+    P.relu_in = (flags & VQ2_RELU_IN) != 0;
+    P.cb = pl.cb; P.steps = pl.steps; P.sps = pl.sps;
+    for (int t = 0; t < 32; ++t) P.taps[t] = pl.taps[t];
+    const dim3 grid((P.Co + CC_BN - 1) / CC_BN, pl.splits, chunks);
+    if (pl.mt == 1)
+        hipLaunchKernelGGL(convg_col_partial_kernel<1>, grid, dim3(256), 0, s, P);
+    else
+        hipLaunchKernelGGL(convg_col_partial_kernel<4>, grid, dim3(256), 0, s, P);
+    if (int e = vq2::check_launch("convg_col_partial_kernel")) return e;
+    const long total = (long)P.N * (P.Co / 4);
+    hipLaunchKernelGGL(convg_row_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P.ws, pl.splits, P.N, P.Co,
                        d->Cor ? d->Cor : d->Co, bias, residual, ldres, y, d->ldy, (flags & VQ2_RELU_OUT) != 0);
     return vq2::check_launch("convg_row_reduce_kernel");
 }

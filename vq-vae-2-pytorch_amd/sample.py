@@ -17,7 +17,12 @@ Histories are row-outer so that every row slice is dense.  Effective weights (g 
 their packed panels are formed once, when the sampler is built; the launches of a row are recorded once per (batch, rows) as a
 list of library calls with their arguments and replayed W times, without autograd, dropout or a host synchronisation.  Step
 (i, j) recomputes the whole row: columns <= j are exact, later ones are placeholders nothing reads.  The integer code map
-is moved by torch copies once per row (band of row i + 1 from band of row i); everything else is a libvq2 kernel."""
+is moved by torch copies once per row (band of row i + 1 from band of row i); everything else is a libvq2 kernel.
+
+PriorSampler(model, stepping='pixel') computes column j only at step (i, j): the same histories, dense [B, C] column
+buffers, every row-local kernel with pixels = B (into a history through the pixel stride W * C), every 'causal' conv through
+vq2_conv_fwd_col, the attention with one query.  Its launches are recorded once per row; the arguments that move with the
+column carry their stride and get j at replay."""
 import ctypes as C
 import dataclasses
 import os
@@ -50,6 +55,34 @@ class _Program:
 
     def run(self):
         for fn, args, what in self.calls:
+            rc = fn(*args)
+            if rc:
+                check(rc, what)
+
+
+class _Moving:
+    """An argument of a recorded call that moves with the column: base + j * step, a device address or an integer."""
+    __slots__ = ("base", "step", "pointer")
+
+    def __init__(self, base, step, pointer=True):
+        self.base, self.step, self.pointer = base, step, pointer
+
+    def at(self, j):
+        v = self.base + j * self.step
+        return C.c_void_p(v) if self.pointer else v
+
+
+class _PixelProgram(_Program):
+    """The calls of one step of a row, recorded once: run(j) replays them for column j."""
+
+    def add(self, what, fn, *args):
+        moving = tuple((k, a) for k, a in enumerate(args) if isinstance(a, _Moving))
+        self.calls.append((fn, list(args), what, moving))
+
+    def run(self, j):
+        for fn, args, what, moving in self.calls:
+            for k, a in moving:
+                args[k] = a.at(j)
             rc = fn(*args)
             if rc:
                 check(rc, what)
@@ -93,10 +126,11 @@ class _Conv:
     def row_desc(self, batch, rows, width):
         return ops._desc(self.spec, batch, rows, width, self.spec.ci, self.spec.co)
 
-    def workspace_bytes(self, batch, rows, width):
+    def workspace_bytes(self, batch, rows, width, query=None):
         if self.kh == 1:
             return 0
-        return lib.vq2_conv_fwd_row_workspace_bytes(C.byref(self.row_desc(batch, rows, width)), self.row_flags)
+        query = query or lib.vq2_conv_fwd_row_workspace_bytes
+        return query(C.byref(self.row_desc(batch, rows, width)), self.row_flags)
 
 
 class _Plan:
@@ -109,7 +143,7 @@ class _Plan:
         self.stream_id = torch.cuda.current_stream().cuda_stream
         self.bufs = {}
         m = sampler.model
-        ws_bytes = max([c.workspace_bytes(batch, rows, self.W) for c in sampler.convs] + [16])
+        ws_bytes = self.workspace_bytes()
         self.ws = torch.empty((ws_bytes + 3) // 4, device=self.dev, dtype=torch.float32)
         self.ws_bytes = ws_bytes
         self.R = sampler.band_rows
@@ -122,7 +156,11 @@ class _Plan:
         self.bg_rows = torch.empty((rows, batch, self.W, 4), device=self.dev, dtype=torch.float32)
         self.to_row_outer(bg, self.bg_rows)
         self.logits = None
+        self.pixels = batch * self.W          # what one call of a row-local kernel covers
         self.programs = [self.record(i) for i in range(rows)]
+
+    def workspace_bytes(self):
+        return max([c.workspace_bytes(self.B, self.H, self.W) for c in self.s.convs] + [16])
 
     # -- buffers
     def buf(self, name, c):
@@ -160,10 +198,15 @@ class _Plan:
     def record(self, i):
         self.prog = _Program()
         self.row = i
-        s, m = self.s, self.s.model
         x = self.input_stage()
         bg = self.bg_rows[i].view(self.B, 1, self.W, 4)
         cond = None if self.cond_rows is None else self.cond_rows[i].view(self.B, 1, self.W, -1)
+        self.logits = self.body(x, bg, cond)
+        return self.prog
+
+    def body(self, x, bg, cond):
+        """Everything after the input stage; returns the logits buffer."""
+        s, m = self.s, self.s.model
         for bi, block in enumerate(m.blocks):
             x = self.pixel_block(f"b{bi}", block, x, bg, cond)
         n_out = len(m.out) - 2
@@ -171,33 +214,45 @@ class _Plan:
             x = self.gated(f"o{k}", m.out[k], x)
         e = self.buf("head.elu", m.channel)
         self.elu(x, m.channel, e)
-        self.logits = self.buf("head.logits", ops.ceil4(m.n_class))
-        self.conv(s.conv_of[m.out[n_out + 1]], e, None, self.logits)
-        return self.prog
+        logits = self.buf("head.logits", ops.ceil4(m.n_class))
+        self.conv(s.conv_of[m.out[n_out + 1]], e, None, logits)
+        return logits
+
+    @staticmethod
+    def ld(t):
+        """Pixel stride of a buffer."""
+        return t.shape[3]
+
+    p = staticmethod(_ptr)
 
     def add(self, what, fn, *args):
         self.prog.add(what, fn, *(args + (self.stream,)))
 
     def elu(self, x, c, out):
-        self.add("elu_fwd", lib.vq2_elu_fwd, _ptr(x), x.shape[3], _ptr(out), out.shape[3], self.B * self.W, c)
+        self.add("elu_fwd", lib.vq2_elu_fwd, self.p(x), self.ld(x), self.p(out), self.ld(out), self.pixels, c)
 
     def copy(self, src, dst, dst_off):
-        self.add("slice_copy", lib.vq2_slice_copy, _ptr(src), src.shape[3], _ptr(dst, dst_off), dst.shape[3], self.B * self.W,
+        self.add("slice_copy", lib.vq2_slice_copy, self.p(src), self.ld(src), self.p(dst, dst_off), self.ld(dst), self.pixels,
                  src.shape[3], 0)
 
     def conv_input(self, name, conv):
         """Where the input row of `conv` is to be written: its history's row, or a plain row buffer."""
         if conv.kh > 1:
-            return self.hist(name + ".hist", conv.spec.ci)[self.row].view(self.B, 1, self.W, conv.spec.ci)
+            return self.hist_row(self.hist(name + ".hist", conv.spec.ci))
         return self.buf(name + ".in", conv.spec.ci)
 
     def conv(self, conv, x, residual, out, name=None):
         sp = conv.spec
-        ldres = residual.shape[3] if residual is not None else 0
+        ldres = self.ld(residual) if residual is not None else 0
         if conv.kh == 1:
-            d = ops._desc(sp, self.B, 1, self.W, x.shape[3], out.shape[3])
-            self.add("conv_fwd", lib.vq2_conv_fwd, d, 0, _ptr(x), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres, _ptr(out))
+            d = ops._desc(sp, self.B, 1, self.pixels // self.B, self.ld(x), self.ld(out))
+            self.add("conv_fwd", lib.vq2_conv_fwd, d, 0, self.p(x), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres,
+                     self.p(out))
             return
+        self.conv_rows(conv, x, residual, ldres, out, name)
+
+    def conv_rows(self, conv, x, residual, ldres, out, name):
+        sp = conv.spec
         hist = self.hist(name + ".hist", sp.ci)
         assert x.data_ptr() == hist[self.row].data_ptr() and out.shape[3] == sp.co
         d = conv.row_desc(self.B, self.H, self.W)
@@ -205,6 +260,16 @@ class _Plan:
                  _ptr(hist), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres, _ptr(out), _ptr(self.ws), self.ws_bytes)
 
     def input_stage(self):
+        cp = ops.ceil4(self.s.model.channel)
+        y = self.input_band()
+        x = self.buf("in.x", cp)
+        # the band's last row of every image: B runs of W * cp floats
+        self.add("slice_copy", lib.vq2_slice_copy, _ptr(y, (self.R - 1) * self.W * cp), self.R * self.W * cp, _ptr(x), self.W * cp,
+                 self.B, self.W * cp, 0)
+        return x
+
+    def input_band(self):
+        """The two one-hot convs over the band of code rows that ends at this row: [B, R, W, cp], the last row is the row's."""
         s, m, i = self.s, self.s.model, self.row
         cp = ops.ceil4(m.channel)
         band = self.bands[i]
@@ -220,11 +285,7 @@ class _Plan:
         d = ops._onehot_desc(self.B, self.R, self.W, sp.cout, sp.cin, (sp.k, sp.kw, sp.pad_top, sp.pad_left), (0, 1), cp)
         self.add("onehot_conv_fwd", lib.vq2_onehot_conv_fwd, d, _ptr(band), _ptr(s.vertical_wp), ops._p(s.vertical.bias),
                  ops._p(acc), cp if acc is not None else 0, _ptr(y))
-        x = self.buf("in.x", cp)
-        # the band's last row of every image: B runs of W * cp floats
-        self.add("slice_copy", lib.vq2_slice_copy, _ptr(y, (self.R - 1) * self.W * cp), self.R * self.W * cp, _ptr(x), self.W * cp,
-                 self.B, self.W * cp, 0)
-        return x
+        return y
 
     def gated(self, name, block, x, aux=None, cond=None):
         s = self.s
@@ -248,8 +309,8 @@ class _Plan:
         t = self.buf(name + ".t", conv2.spec.co)
         self.conv(conv2, e2, r, t, name + ".c2")
         out = self.buf(name + ".out", ops.ceil4(block.in_channel))
-        self.add("glu_res_fwd", lib.vq2_glu_res_fwd, _ptr(t), t.shape[3], _ptr(x), x.shape[3], _ptr(out), out.shape[3],
-                 self.B * self.W, block.in_channel)
+        self.add("glu_res_fwd", lib.vq2_glu_res_fwd, self.p(t), self.ld(t), self.p(x), self.ld(x), self.p(out), self.ld(out),
+                 self.pixels, block.in_channel)
         return out
 
     def cat(self, name, parts):
@@ -276,19 +337,105 @@ class _Plan:
         q = self.buf(name + ".q", ch)
         kh, vh = self.hist(name + ".khist", ch), self.hist(name + ".vhist", ch)
         self.conv(s.conv_of[att.query], query, None, q)
-        self.conv(s.conv_of[att.key], key, None, kh[self.row].view(self.B, 1, self.W, ch))
-        self.conv(s.conv_of[att.value], key, None, vh[self.row].view(self.B, 1, self.W, ch))
+        self.conv(s.conv_of[att.key], key, None, self.hist_row(kh))
+        self.conv(s.conv_of[att.value], key, None, self.hist_row(vh))
         o = self.buf(name + ".att", ch)
         d = AttnDesc()
         d.B, d.L, d.n_head, d.dim_head = self.B, self.H * self.W, att.n_head, att.dim_head
         d.ldq = d.ldk = d.ldv = d.ldo = ch
+        self.attend(d, q, kh, vh, o)
+        return self.gated(name + ".outb", block.out_resblock, out, aux=o)
+
+    def hist_row(self, hist):
+        """Where this program writes its part of a history [H, B, W, C]: the whole row."""
+        return hist[self.row].view(self.B, 1, self.W, hist.shape[3])
+
+    def attend(self, d, q, kh, vh, o):
+        ch = kh.shape[3]
         self.add("causal_attn_fwd_rows", lib.vq2_causal_attn_fwd_rows, d, self.row * self.W, self.W, self.W, self.W * ch,
                  self.B * self.W * ch, _ptr(q), _ptr(kh), _ptr(vh), _ptr(o))
-        return self.gated(name + ".outb", block.out_resblock, out, aux=o)
+
+
+class _PixelPlan(_Plan):
+    """A plan that also steps one column at a time.  It keeps the row programs (a row given by `prefix` costs one run of its
+    row program, which fills the same histories) and, per row, one pixel program over dense column buffers [B, 1, 1, C].
+    A buffer that moves with the column is a view of column 0 that carries `_step`, its elements per column."""
+
+    def __init__(self, sampler, batch, rows, with_condition):
+        self.px = False
+        super().__init__(sampler, batch, rows, with_condition)
+        self.px, self.pixels = True, batch
+        self.pixel_programs = [self.record_pixel(i) for i in range(rows)]
+
+    def workspace_bytes(self):
+        col = [c.workspace_bytes(self.B, self.H, self.W, lib.vq2_conv_fwd_col_workspace_bytes) for c in self.s.convs]
+        return max(col + [super().workspace_bytes()])
+
+    def record_pixel(self, i):
+        self.prog = _PixelProgram()
+        self.row = i
+        cp = ops.ceil4(self.s.model.channel)
+        y = self.input_band()
+        x = self.buf("in.x", cp)
+        # column j of the band's last row of every image
+        self.add("slice_copy", lib.vq2_slice_copy, _Moving(y.data_ptr() + (self.R - 1) * self.W * cp * 4, cp * 4),
+                 self.R * self.W * cp, _ptr(x), cp, self.B, cp, 0)
+        cond = None if self.cond_rows is None else self.column(self.cond_rows[i])
+        self.pixel_logits = self.body(x, self.column(self.bg_rows[i]), cond)
+        return self.prog
+
+    def column(self, row):
+        """Column 0 of a row [B, W, C] as [B, 1, 1, C] with the pixel stride W * C; it moves by C per column."""
+        v = row.view(self.B, 1, self.W, row.shape[2])[:, :, :1]
+        v._step = row.shape[2]
+        return v
+
+    def buf(self, name, c):
+        if not self.px:
+            return super().buf(name, c)
+        t = self.bufs.get("px." + name)
+        if t is None:
+            t = self.bufs["px." + name] = torch.empty((self.B, 1, 1, c), device=self.dev, dtype=torch.float32)
+        return t
+
+    def ld(self, t):
+        return t.stride(0) if self.px else t.shape[3]
+
+    def p(self, t, offset=0):
+        step = getattr(t, "_step", 0) if self.px else 0
+        if step:
+            return _Moving(t.data_ptr() + offset * t.element_size(), step * t.element_size())
+        return _ptr(t, offset)
+
+    def hist_row(self, hist):
+        return self.column(hist[self.row]) if self.px else super().hist_row(hist)
+
+    def conv_rows(self, conv, x, residual, ldres, out, name):
+        if not self.px:
+            return super().conv_rows(conv, x, residual, ldres, out, name)
+        sp = conv.spec
+        hist = self.hist(name + ".hist", sp.ci)
+        assert x.data_ptr() == hist[self.row].data_ptr() and self.ld(out) == sp.co and conv.row_flags == VQ2_ROW_CAUSAL_TAPS
+        d = conv.row_desc(self.B, self.H, self.W)
+        self.add("conv_fwd_col", lib.vq2_conv_fwd_col, d, self.row, _Moving(0, 1, pointer=False), self.W * sp.ci,
+                 self.B * self.W * sp.ci, conv.row_flags, _ptr(hist), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres,
+                 _ptr(out), _ptr(self.ws), self.ws_bytes)
+
+    def attend(self, d, q, kh, vh, o):
+        if not self.px:
+            return super().attend(d, q, kh, vh, o)
+        ch = kh.shape[3]
+        self.add("causal_attn_fwd_rows", lib.vq2_causal_attn_fwd_rows, d, _Moving(self.row * self.W, 1, pointer=False), 1, self.W,
+                 self.W * ch, self.B * self.W * ch, _ptr(q), _ptr(kh), _ptr(vh), _ptr(o))
 
 
 class PriorSampler:
-    """PriorSampler(model): a row-incremental sampler over a vqvae2_amd.PixelSNAIL on the GPU.
+    """PriorSampler(model, stepping='row'): an incremental sampler over a vqvae2_amd.PixelSNAIL on the GPU.
+
+    stepping   'row' (the default): step (i, j) recomputes row i, M = B * W pixels per launch.  'pixel': step (i, j) computes
+               column j only, M = B; every conv over several rows must then be a 'causal' one.  Both give what the model
+               gives, to rounding; the draws of one seed may differ between them where a logit's last bits decide.  Anything
+               else is a ValueError.
 
     sample(batch, temperature=1.0, condition=None, seed=None, rows=None, *, top_k=0, top_p=1.0, prefix=None,
         return_logp=False) -> int64 [B, rows, W] on the device.  condition: the
@@ -312,9 +459,12 @@ class PriorSampler:
     every time).  The sampler holds device pointers: it cannot be pickled or deep-copied, and nothing of it is stored on the
     model."""
 
-    def __init__(self, model, _weak=False):
+    def __init__(self, model, stepping='row', _weak=False):
         if not isinstance(model, PixelSNAIL):
             raise TypeError("vqvae2_amd.PriorSampler: a vqvae2_amd.PixelSNAIL expected")
+        if stepping not in ('row', 'pixel'):
+            raise ValueError(f"vqvae2_amd.PriorSampler: stepping must be 'row' or 'pixel', got {stepping!r}")
+        self.stepping = stepping
         # _weak: sample_model's cache is keyed weakly by the model; its samplers must not keep the model alive themselves
         self._model_ref = weakref.ref(model)
         self._model = None if _weak else model
@@ -348,6 +498,10 @@ class PriorSampler:
                     self.conv_of[block.out] = _Conv(block.out)
             self.conv_of[m.out[-1]] = _Conv(m.out[-1])
             self.convs = list(self.conv_of.values())
+            if self.stepping == 'pixel':
+                for c in self.convs:
+                    if (c.kh > 1 and not c.row_flags) or (c.kh == 1 and c.kw > 1):
+                        raise NotImplementedError("vqvae2_amd.PriorSampler: pixel stepping takes 1 x 1 and 'causal' convs only")
             self.horizontal, self.vertical = _Conv(m.horizontal, pack=False), _Conv(m.vertical, pack=False)
             self.horizontal_wp, self.vertical_wp = self._onehot_panel(self.horizontal), self._onehot_panel(self.vertical)
         self.band_rows = max(self.horizontal.kh + 1, self.vertical.kh)
@@ -380,7 +534,7 @@ class PriorSampler:
         key = (batch, rows, condition is not None, torch.cuda.current_stream().cuda_stream)
         if self._plan is None or self._plan[0] != key:
             self._plan = None       # free the old histories before the new ones are allocated
-            self._plan = (key, _Plan(self, batch, rows, condition is not None))
+            self._plan = (key, (_PixelPlan if self.stepping == 'pixel' else _Plan)(self, batch, rows, condition is not None))
         plan = self._plan[1]
         if condition is not None:
             if not hasattr(m, "cond_resnet"):
@@ -424,6 +578,9 @@ class PriorSampler:
         filtered = top_k > 0 or top_p < 1.0 or return_logp
         # step-outer [rows, W, B]: the draw of step (i, j) writes its B values densely
         logp = torch.zeros((rows, w, b), device=self.device, dtype=torch.float32) if return_logp else None
+        pixel = self.stepping == 'pixel'
+        # where the logits of step (i, j) stand: column j of the row buffer, or the column buffer
+        logits, lrow, lcol = (plan.pixel_logits, ld, 0) if pixel else (plan.logits, w * ld, ld)
         for i in range(rows):
             prog = plan.programs[i]
             band = plan.bands[i]
@@ -434,14 +591,17 @@ class PriorSampler:
                 plan.end_row(i)
                 continue
             for j in range(w):
-                prog.run()
+                if pixel:
+                    plan.pixel_programs[i].run(j)
+                else:
+                    prog.run()
                 if filtered:
-                    check(lib.vq2_sample_filtered(_ptr(plan.logits, j * ld), w * ld, b, n_class, t, top_k, top_p, seed, i * w + j,
+                    check(lib.vq2_sample_filtered(_ptr(logits, j * lcol), lrow, b, n_class, t, top_k, top_p, seed, i * w + j,
                                                   _ptr(band, (r - 1) * w + j), r * w,
                                                   _ptr(logp, (i * w + j) * b) if return_logp else None, None, plan.stream),
                           "sample_filtered")
                 else:
-                    check(lib.vq2_sample_categorical(_ptr(plan.logits, j * ld), w * ld, b, n_class, t, seed, i * w + j,
+                    check(lib.vq2_sample_categorical(_ptr(logits, j * lcol), lrow, b, n_class, t, seed, i * w + j,
                                                      _ptr(band, (r - 1) * w + j), r * w, plan.stream), "sample_categorical")
             plan.end_row(i)
         if return_logp:
@@ -457,11 +617,16 @@ class PriorSampler:
         plan = self._plan_for(batch, rows, condition)
         ld = ops.ceil4(self.model.n_class)
         out = torch.zeros((batch, rows, w, ld), device=self.device, dtype=torch.float32)
+        pixel = self.stepping == 'pixel'
+        logits, lrow, lcol = (plan.pixel_logits, ld, 0) if pixel else (plan.logits, w * ld, ld)
         for i in range(rows):
             prog = plan.programs[i]
             for j in range(w):
-                prog.run()
-                check(lib.vq2_slice_copy(_ptr(plan.logits, j * ld), w * ld, _ptr(out, (i * w + j) * ld), rows * w * ld, batch, ld, 0,
+                if pixel:
+                    plan.pixel_programs[i].run(j)
+                else:
+                    prog.run()
+                check(lib.vq2_slice_copy(_ptr(logits, j * lcol), lrow, _ptr(out, (i * w + j) * ld), rows * w * ld, batch, ld, 0,
                                          plan.stream), "slice_copy")
                 plan.bands[i, :, plan.R - 1, j] = codes[:, i, j]
             plan.end_row(i)
@@ -469,19 +634,24 @@ class PriorSampler:
 
 
 _SAMPLERS = weakref.WeakKeyDictionary()      # model -> its PriorSampler (which refers to the model weakly)
+_PIXEL_SAMPLERS = weakref.WeakKeyDictionary()    # the same for stepping='pixel'
 
 
-def sample_model(model, device, batch, size, temperature, condition=None, *, top_k=0, top_p=1.0, prefix=None):
+def sample_model(model, device, batch, size, temperature, condition=None, *, top_k=0, top_p=1.0, prefix=None, stepping='row'):
     """The reference's sample_model (sample.py:12-24): int64 codes [batch, size[0], size[1]] on `device`, drawn from `model`
     pixel by pixel in raster order.  One PriorSampler per model is kept in this module, keyed weakly by the model (it goes
     when the model goes, and the model itself carries nothing: it still pickles and deep-copies), and is rebuilt when the
-    model's parameters change.  top_k, top_p and prefix (keyword only, not in the reference) are PriorSampler.sample's."""
+    model's parameters change.  top_k, top_p and prefix (keyword only, not in the reference) are PriorSampler.sample's;
+    stepping ('row' or 'pixel') is PriorSampler's."""
+    if stepping not in ('row', 'pixel'):
+        raise ValueError(f"sample_model: stepping must be 'row' or 'pixel', got {stepping!r}")
     if tuple(size)[1] != model.background.shape[3]:
         raise RuntimeError(f"sample_model: width {size[1]} does not fit the model's {model.background.shape[3]}")
     model = model.to(device)
-    sampler = _SAMPLERS.get(model)
+    cache = _PIXEL_SAMPLERS if stepping == 'pixel' else _SAMPLERS
+    sampler = cache.get(model)
     if sampler is None or sampler._snapshot() != sampler._versions:
-        sampler = _SAMPLERS[model] = PriorSampler(model, _weak=True)
+        sampler = cache[model] = PriorSampler(model, stepping, _weak=True)
     return sampler.sample(batch, temperature, condition, rows=int(size[0]), top_k=top_k, top_p=top_p, prefix=prefix)
 
 
