@@ -100,7 +100,7 @@ def bench(name, model, batch, rows, condition, repeats, baseline_steps, top_k=0,
     res = {"batch": batch, "rows": rows, "width": width, "steps": rows * width, "top_k": top_k, "top_p": top_p}
     for s in steppings:
         plan = samplers[s]._plan[1]
-        calls = (plan.pixel_programs if s == "pixel" else plan.programs)[rows // 2].calls
+        calls = plan.step_programs[rows // 2].calls
         two_kernels = sum(1 for call in calls if call[2] in ("conv_fwd_row", "conv_fwd_col"))
         med = statistics.median(times[s])
         entry = {

@@ -310,10 +310,10 @@ def test_free_run(amd, g, ci):
     torch.save(m, io.BytesIO())
     torch.manual_seed(5)
     assert torch.equal(codes, amd.sample_model(clone, "cuda", b, [h, w], temperature, condition=cond))
-    held = weakref.ref(amd.sample._SAMPLERS[clone])
+    held = weakref.ref(amd.sample._SAMPLERS[clone]["row"])
     del clone
     gc.collect()
-    assert held() is None and m in amd.sample._SAMPLERS
+    assert held() is None and "row" in amd.sample._SAMPLERS[m]
     sampler = amd.PriorSampler(m)
     first = sampler.sample(b, temperature, cond, seed=seed)
     assert torch.equal(first, codes)

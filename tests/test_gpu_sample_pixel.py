@@ -247,7 +247,7 @@ def test_free_run(amd, g, ci):
     torch.manual_seed(5)
     via = amd.sample_model(m, "cuda", b, [h, w], temperature, condition=cond, stepping="pixel")
     assert torch.equal(via, sampler.sample(b, temperature, cond, seed=drawn))
-    assert amd.sample._PIXEL_SAMPLERS[m].stepping == "pixel" and m not in amd.sample._SAMPLERS
+    assert amd.sample._SAMPLERS[m]["pixel"].stepping == "pixel" and "row" not in amd.sample._SAMPLERS[m]
     # every drawn code against the float64 softmax of the logits its step saw
     logits = sampler.logits_given(codes, cond)
     with torch.no_grad():
@@ -306,16 +306,65 @@ def test_programs(amd, g, ci):
     assert row.stepping == "row"
     row.logits_given(ins["input"], cond)
     plan = row._plan[1]
-    assert type(plan).__name__ == "_Plan" and not hasattr(plan, "pixel_programs")
+    # a row-mode plan has no pixel programs: a step runs the row's program, and no column buffer exists
+    assert type(plan).__name__ == "_Plan" and plan.step_programs is plan.row_programs and len(plan.row_programs) == h
+    assert not any(name.startswith("px.") for name in plan.bufs)
     for i in range(h):
-        assert [what for _, _, what in plan.programs[i].calls] == _expected_calls(m, i, cond is not None, "conv_fwd_row"), i
+        calls = plan.row_programs[i].calls
+        assert [call[2] for call in calls] == _expected_calls(m, i, cond is not None, "conv_fwd_row"), i
+        _check_row_program(amd, calls, i, w)
     pix = amd.PriorSampler(m, stepping="pixel")
     pix.logits_given(ins["input"], cond)
     plan = pix._plan[1]
+    assert type(plan).__name__ == "_Plan" and plan.step_programs is not plan.row_programs
     for i in range(h):
-        names = [call[2] for call in plan.pixel_programs[i].calls]
+        names = [call[2] for call in plan.step_programs[i].calls]
         assert "conv_fwd_col" in names and "conv_fwd_row" not in names
         assert names == _expected_calls(m, i, cond is not None, "conv_fwd_col"), i
-        assert [what for _, _, what in plan.programs[i].calls] == _expected_calls(m, i, cond is not None, "conv_fwd_row"), i
+        calls = plan.row_programs[i].calls
+        assert [call[2] for call in calls] == _expected_calls(m, i, cond is not None, "conv_fwd_row"), i
+        _check_row_program(amd, calls, i, w)
+        _check_pixel_program(amd, plan, plan.step_programs[i].calls, i, w)
     # recorded per row, not per pixel: h programs, each with as many calls as a step makes
-    assert len(plan.pixel_programs) == h
+    assert len(plan.step_programs) == h and len(plan.row_programs) == h
+
+
+def _check_row_program(amd, calls, i, w):
+    """No argument of a row program moves; the attention takes the row's W queries."""
+    for fn, args, what, moving in calls:
+        assert not moving and not any(isinstance(a, amd.sample._Moving) for a in args), what
+        if what == "causal_attn_fwd_rows":                   # (desc, q0, nq, ...)
+            assert (args[1], args[2]) == (i * w, w)
+
+
+def _check_pixel_program(amd, plan, calls, i, w):
+    """The arguments of step (i, j), resolved as run(j) resolves them but without a launch: the column conv is at (i, j), the
+    attention takes the one query i * W + j, and every pointer that moves does so by the channels of the buffer it addresses."""
+    Moving = amd.sample._Moving
+    held = list(plan.bufs.values()) + [plan.bg_rows] + ([plan.cond_rows] if plan.cond_rows is not None else [])
+
+    def channels_at(address):
+        owners = [t for t in held if t.data_ptr() <= address < t.data_ptr() + t.numel() * t.element_size()]
+        assert len(owners) == 1, address
+        return owners[0].shape[3]
+
+    # the integers that move, where the C signatures have them: (desc, row, col, ...) and (desc, q0, nq, ...)
+    moving_ints = {"conv_fwd_col": [2], "causal_attn_fwd_rows": [1]}
+    n_pointers = 0
+    for j in sorted({0, w - 1}):
+        for fn, args, what, moving in calls:
+            assert all(k in dict(moving) for k, a in enumerate(args) if isinstance(a, Moving)), what      # none left unpatched
+            at = list(args)
+            for k, a in moving:
+                assert isinstance(a, Moving)
+                at[k] = a.at(j)
+            assert [k for k, a in moving if not a.pointer] == moving_ints.get(what, []), what
+            if what == "conv_fwd_col":
+                assert (at[1], at[2]) == (i, j)
+            if what == "causal_attn_fwd_rows":
+                assert (at[1], at[2]) == (i * w + j, 1)
+            for k, a in moving:
+                if a.pointer:
+                    n_pointers += 1
+                    assert at[k].value == a.at(0).value + j * 4 * channels_at(a.at(0).value), (what, k)
+    assert n_pointers > 0

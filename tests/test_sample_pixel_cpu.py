@@ -1,6 +1,7 @@
 """CPU checks of pixel stepping: the column-incremental evaluation (tests/_sample_pixel_ref.py: column buffers, conv
-histories that start as NaN, single-query attention) gives the logits of the full model on the goldens, and the library and
-the package declare the new entry point and keyword."""
+histories that start as NaN, single-query attention) gives the logits of the full model on the goldens, the library and
+the package declare the new entry point and keyword, and the sampler's recorder keeps its replay contract (a program's
+moving arguments, the views the two step geometries give of a history row)."""
 import ctypes
 
 import numpy as np
@@ -66,6 +67,61 @@ def test_library_declares_the_column_conv():
     assert call(0, 0, need - 1) == 1 and b"workspace" in L.lib.vq2_last_error()
     d.pad_top = 1
     assert call(0, 0, need) == 1 and b"pad_top" in L.lib.vq2_last_error()
+
+
+def test_program_replay_contract():
+    """_Program.run(j): the moving arguments are taken at column j, a call without one gets the objects it was recorded with."""
+    from vqvae2_amd import sample as S
+    got = {"still": [], "moving": []}
+
+    def still(*args):
+        got["still"].append(args)
+        return 0
+
+    def moving(*args):
+        got["moving"].append(args)
+        return 0
+
+    prog = S._Program()
+    fixed = (ctypes.c_void_p(64), 7, None)
+    prog.add("still", still, *fixed)
+    prog.add("moving", moving, 3, S._Moving(1000, 24), S._Moving(5, 1, pointer=False), None)
+    assert [len(call) for call in prog.calls] == [4, 4]                   # one shape of entry
+    assert [(call[2], len(call[3])) for call in prog.calls] == [("still", 0), ("moving", 2)]
+    prog.run()
+    prog.run(0)
+    prog.run(3)
+    assert len(got["still"]) == 3
+    for args in got["still"]:
+        assert len(args) == 3 and all(a is f for a, f in zip(args, fixed))
+    seen = []
+    for three, p, n, none in got["moving"]:
+        assert three == 3 and none is None and type(p) is ctypes.c_void_p and type(n) is int
+        seen.append((p.value, n))
+    assert seen == [(1000, 5), (1000, 5), (1072, 8)]
+    failing = S._Program()
+    failing.add("elu_fwd", lambda *args: 1, 0)
+    with pytest.raises(RuntimeError, match="elu_fwd"):
+        failing.run()
+
+
+def test_step_geometries_view_a_history_row():
+    from vqvae2_amd import sample as S
+    row = torch.zeros(2, 5, 8)                                            # [B, W, C]
+    v = S._ColumnStep(2, 5).row(row)
+    assert isinstance(v, S._View) and v.t is row and (v.c, v.ld, v.step) == (8, 40, 8)
+    p = v.ptr()
+    assert isinstance(p, S._Moving) and p.pointer
+    for j in (0, 4):
+        at = p.at(j)
+        assert type(at) is ctypes.c_void_p and at.value == row.data_ptr() + 32 * j
+    assert v.ptr(3).at(4).value == row.data_ptr() + 4 * 3 + 32 * 4
+    v = S._RowStep(2, 5).row(row)
+    assert isinstance(v, S._View) and v.t is row and (v.c, v.ld, v.step) == (8, 8, 0)
+    p = v.ptr()
+    assert type(p) is ctypes.c_void_p and p.value == row.data_ptr()
+    assert v.ptr(3).value == row.data_ptr() + 12
+    assert (S._ColumnStep(2, 5).pixels, S._RowStep(2, 5).pixels) == (2, 10)
 
 
 def test_stepping_keyword():

@@ -48,16 +48,24 @@ struct RowConv {
     int tps;             // active taps per split
 };
 
+// the computed taps kh * KW + kw, ascending, and their number (VQ2_ROW_CAUSAL_TAPS: the last kernel row ends before its centre)
+static int computed_taps(const vq2_conv_desc *d, int flags, unsigned char *taps) {
+    int n = 0;
+    for (int kh = 0; kh < d->KH; ++kh)
+        for (int kw = 0; kw < d->KW; ++kw) {
+            if ((flags & VQ2_ROW_CAUSAL_TAPS) && kh == d->KH - 1 && kw >= d->KW / 2) continue;
+            taps[n++] = (unsigned char)(kh * d->KW + kw);
+        }
+    return n;
+}
+
 // which taps are computed and how they are cut into splits: a function of the shape and the flags alone
 struct RowPlan { unsigned mask; int ntaps, tps, splits; };
 static RowPlan row_plan(const vq2_conv_desc *d, int flags) {
     RowPlan p{0u, 0, 1, 1};
-    for (int kh = 0; kh < d->KH; ++kh)
-        for (int kw = 0; kw < d->KW; ++kw) {
-            if ((flags & VQ2_ROW_CAUSAL_TAPS) && kh == d->KH - 1 && kw >= d->KW / 2) continue;
-            p.mask |= 1u << (kh * d->KW + kw);
-            ++p.ntaps;
-        }
+    unsigned char taps[32];
+    p.ntaps = computed_taps(d, flags, taps);
+    for (int t = 0; t < p.ntaps; ++t) p.mask |= 1u << taps[t];
     if (p.ntaps == 0) return p;   // a 1 x 1 'causal' kernel: nothing but the bias
     const long tiles = (((long)d->N * d->W + RC_BM - 1) / RC_BM) * ((d->Co + RC_BN - 1) / RC_BN);
     long want = (512 + tiles - 1) / tiles;          // about two workgroups per compute unit
@@ -192,11 +200,7 @@ struct ColConv {
 struct ColPlan { unsigned char taps[32]; int ntaps, cb, steps, sps, splits, mt; };
 static ColPlan col_plan(const vq2_conv_desc *d, int flags) {
     ColPlan p{};
-    for (int kh = 0; kh < d->KH; ++kh)
-        for (int kw = 0; kw < d->KW; ++kw) {
-            if ((flags & VQ2_ROW_CAUSAL_TAPS) && kh == d->KH - 1 && kw >= d->KW / 2) continue;
-            p.taps[p.ntaps++] = (unsigned char)(kh * d->KW + kw);
-        }
+    p.ntaps = computed_taps(d, flags, p.taps);
     p.cb = (d->Ci + CC_BK - 1) / CC_BK;
     p.steps = p.ntaps * p.cb;
     p.mt = d->N <= 16 ? 1 : 4;                       // image tiles of 16 per workgroup
@@ -501,9 +505,10 @@ __global__ __launch_bounds__(256) void sample_uniforms_kernel(float *__restrict_
     if (row < M) u[row] = uniform_of(seed_lo, seed_hi, pos_lo, pos_hi, (uint32_t)row);
 }
 
-// what the row and column forms ask beyond vq2::check_conv_desc
-int check_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
-              const char *who = "conv_fwd_row") {
+// what both forms ask beyond vq2::check_conv_desc; a workspace below the form's own `need` is answered with its `short_ws`
+int check_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags, const float *x,
+              const float *wp, const float *residual, int32_t ldres, const float *y, const void *ws, size_t ws_bytes, size_t need,
+              int short_ws, const char *who) {
     if (int e = vq2::check_conv_desc(d, who)) return e;
     VQ2_REQUIRE(d->same_size == 1 && d->pad_top == d->KH - 1,
                 "%s: same_size and pad_top == KH - 1 required (the kernel must end at the output row)", who);
@@ -512,7 +517,21 @@ int check_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64
                 "%s: input strides must be non-negative multiples of 4", who);
     VQ2_REQUIRE((flags & ~(VQ2_RELU_IN | VQ2_RELU_OUT | VQ2_ROW_CAUSAL_TAPS)) == 0, "%s: unknown flag", who);
     VQ2_REQUIRE((int64_t)d->Co * d->KH * d->KW * d->Ci < ((int64_t)1 << 31), "%s: tensor exceeds 2^31 elements", who);
+    VQ2_REQUIRE(x && wp && y && ws, "%s: null pointer", who);
+    VQ2_REQUIRE(vq2::aligned16(x) && vq2::aligned16(wp) && vq2::aligned16(y) && vq2::aligned16(ws) &&
+                    (!residual || vq2::aligned16(residual)), "%s: pointers must be 16-byte aligned", who);
+    VQ2_REQUIRE(!residual || (ldres >= d->Co && ldres % 4 == 0), "%s: ldres must be >= Co and a multiple of 4", who);
+    if (ws_bytes < need) return vq2::set_error(short_ws, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
     return VQ2_OK;
+}
+
+// the second kernel of both forms: the slabs [splits][M][Co] of ws summed in ascending order, then the epilogue
+int launch_reduce(const vq2_conv_desc *d, int flags, const float *ws, int splits, int M, const float *bias, const float *residual,
+                  int32_t ldres, float *y, hipStream_t s) {
+    const dim3 grid((unsigned)(((long)M * (d->Co / 4) + 255) / 256));      // a thread per 4 output channels of a pixel
+    hipLaunchKernelGGL(convg_row_reduce_kernel, grid, dim3(256), 0, s, ws, splits, M, d->Co, d->Cor ? d->Cor : d->Co, bias,
+                       residual, ldres, y, d->ldy, (flags & VQ2_RELU_OUT) != 0);
+    return vq2::check_launch("convg_row_reduce_kernel");
 }
 
 }  // namespace
@@ -526,16 +545,9 @@ extern "C" size_t vq2_conv_fwd_row_workspace_bytes(const vq2_conv_desc *d, int f
 extern "C" int vq2_conv_fwd_row(const vq2_conv_desc *d, int32_t row, int64_t x_image_stride, int64_t x_row_stride, int flags,
                                 const float *x, const float *wp, const float *bias, const float *residual, int32_t ldres,
                                 float *y, void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    if (int e = check_row(d, row, x_image_stride, x_row_stride, flags)) return e;
-    VQ2_REQUIRE(x && wp && y && ws, "conv_fwd_row: null pointer");
-    VQ2_REQUIRE(vq2::aligned16(x) && vq2::aligned16(wp) && vq2::aligned16(y) && vq2::aligned16(ws) &&
-                    (!residual || vq2::aligned16(residual)),
-                "conv_fwd_row: pointers must be 16-byte aligned");
-    VQ2_REQUIRE(!residual || (ldres >= d->Co && ldres % 4 == 0), "conv_fwd_row: ldres must be >= Co and a multiple of 4");
+    if (int e = check_row(d, row, x_image_stride, x_row_stride, flags, x, wp, residual, ldres, y, ws, ws_bytes,
+                          vq2_conv_fwd_row_workspace_bytes(d, flags), VQ2_ERR_WORKSPACE, "conv_fwd_row")) return e;
     const RowPlan pl = row_plan(d, flags);
-    if (ws_bytes < vq2_conv_fwd_row_workspace_bytes(d, flags))
-        return vq2::set_error(VQ2_ERR_WORKSPACE, "conv_fwd_row: workspace of %zu bytes, %zu needed", ws_bytes,
-                              vq2_conv_fwd_row_workspace_bytes(d, flags));
     hipStream_t s = vq2::to_stream(stream);
     RowConv P{};
     P.x = x; P.w = wp; P.ws = static_cast<float *>(ws);
@@ -547,10 +559,7 @@ extern "C" int vq2_conv_fwd_row(const vq2_conv_desc *d, int32_t row, int64_t x_i
     const dim3 grid((P.M + RC_BM - 1) / RC_BM, (P.Co + RC_BN - 1) / RC_BN, pl.splits);
     hipLaunchKernelGGL(convg_row_partial_kernel, grid, dim3(256), 0, s, P);
     if (int e = vq2::check_launch("convg_row_partial_kernel")) return e;
-    const long total = (long)P.M * (P.Co / 4);
-    hipLaunchKernelGGL(convg_row_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P.ws, pl.splits, P.M, P.Co,
-                       d->Cor ? d->Cor : d->Co, bias, residual, ldres, y, d->ldy, (flags & VQ2_RELU_OUT) != 0);
-    return vq2::check_launch("convg_row_reduce_kernel");
+    return launch_reduce(d, flags, P.ws, pl.splits, P.M, bias, residual, ldres, y, s);
 }
 
 extern "C" size_t vq2_conv_fwd_col_workspace_bytes(const vq2_conv_desc *d, int flags) {
@@ -562,16 +571,10 @@ extern "C" size_t vq2_conv_fwd_col_workspace_bytes(const vq2_conv_desc *d, int f
 extern "C" int vq2_conv_fwd_col(const vq2_conv_desc *d, int32_t row, int32_t col, int64_t x_image_stride, int64_t x_row_stride,
                                 int flags, const float *x, const float *wp, const float *bias, const float *residual,
                                 int32_t ldres, float *y, void *ws, size_t ws_bytes, vq2_stream_t stream) {
-    if (int e = check_row(d, row, x_image_stride, x_row_stride, flags, "conv_fwd_col")) return e;
+    if (int e = check_row(d, row, x_image_stride, x_row_stride, flags, x, wp, residual, ldres, y, ws, ws_bytes,
+                          vq2_conv_fwd_col_workspace_bytes(d, flags), VQ2_ERR_INVALID, "conv_fwd_col")) return e;
     VQ2_REQUIRE(col >= 0 && col < d->W, "conv_fwd_col: col %d outside the %d columns", col, d->W);
-    VQ2_REQUIRE(x && wp && y && ws, "conv_fwd_col: null pointer");
-    VQ2_REQUIRE(vq2::aligned16(x) && vq2::aligned16(wp) && vq2::aligned16(y) && vq2::aligned16(ws) &&
-                    (!residual || vq2::aligned16(residual)),
-                "conv_fwd_col: pointers must be 16-byte aligned");
-    VQ2_REQUIRE(!residual || (ldres >= d->Co && ldres % 4 == 0), "conv_fwd_col: ldres must be >= Co and a multiple of 4");
     const ColPlan pl = col_plan(d, flags);
-    const size_t need = vq2_conv_fwd_col_workspace_bytes(d, flags);
-    VQ2_REQUIRE(ws_bytes >= need, "conv_fwd_col: workspace of %zu bytes, %zu needed", ws_bytes, need);
     const int chunks = (d->N + 16 * pl.mt - 1) / (16 * pl.mt);
     VQ2_REQUIRE(chunks <= 65535, "conv_fwd_col: %d images exceed the grid", d->N);
     hipStream_t s = vq2::to_stream(stream);
@@ -589,10 +592,7 @@ extern "C" int vq2_conv_fwd_col(const vq2_conv_desc *d, int32_t row, int32_t col
     else
         hipLaunchKernelGGL(convg_col_partial_kernel<4>, grid, dim3(256), 0, s, P);
     if (int e = vq2::check_launch("convg_col_partial_kernel")) return e;
-    const long total = (long)P.N * (P.Co / 4);
-    hipLaunchKernelGGL(convg_row_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P.ws, pl.splits, P.N, P.Co,
-                       d->Cor ? d->Cor : d->Co, bias, residual, ldres, y, d->ldy, (flags & VQ2_RELU_OUT) != 0);
-    return vq2::check_launch("convg_row_reduce_kernel");
+    return launch_reduce(d, flags, P.ws, pl.splits, P.N, bias, residual, ldres, y, s);
 }
 
 extern "C" int vq2_sample_categorical(const float *logits, int64_t row_stride, int32_t M, int32_t n_class, float temperature,

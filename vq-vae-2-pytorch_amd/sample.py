@@ -21,8 +21,14 @@ is moved by torch copies once per row (band of row i + 1 from band of row i); ev
 
 PriorSampler(model, stepping='pixel') computes column j only at step (i, j): the same histories, dense [B, C] column
 buffers, every row-local kernel with pixels = B (into a history through the pixel stride W * C), every 'causal' conv through
-vq2_conv_fwd_col, the attention with one query.  Its launches are recorded once per row; the arguments that move with the
-column carry their stride and get j at replay."""
+vq2_conv_fwd_col, the attention with one query.
+
+The recording is written once.  A _Recorder writes the calls of one step of row i into a _Program against a step geometry,
+which states all that the two modes differ in: _RowStep (the whole row, B * W pixels per call) or _ColumnStep (column j, B
+pixels).  An activation is a _View (tensor, channels, pixel stride, elements per column): a scratch buffer stays; a history,
+background or condition row seen through _ColumnStep moves, and its pointer is recorded as a _Moving argument that gets j at
+replay, as do the integers `col` and `q0`.  A _Plan holds the buffers and, per row, the program of a step and the program
+that fills a given row from all its codes; under _RowStep the two are one program."""
 import ctypes as C
 import dataclasses
 import os
@@ -44,22 +50,6 @@ def _ptr(t, offset=0):
     return C.c_void_p(t.data_ptr() + offset * t.element_size())
 
 
-class _Program:
-    """Library calls recorded with their arguments; run() replays them in order."""
-
-    def __init__(self):
-        self.calls = []
-
-    def add(self, what, fn, *args):
-        self.calls.append((fn, args, what))
-
-    def run(self):
-        for fn, args, what in self.calls:
-            rc = fn(*args)
-            if rc:
-                check(rc, what)
-
-
 class _Moving:
     """An argument of a recorded call that moves with the column: base + j * step, a device address or an integer."""
     __slots__ = ("base", "step", "pointer")
@@ -72,20 +62,100 @@ class _Moving:
         return C.c_void_p(v) if self.pointer else v
 
 
-class _PixelProgram(_Program):
-    """The calls of one step of a row, recorded once: run(j) replays them for column j."""
+class _Program:
+    """Library calls recorded with their arguments; run(j) replays them in order with the _Moving arguments taken at column j.
+    calls holds (fn, args, what, ((index, _Moving), ...)); a call without a moving argument is replayed as it was recorded."""
+
+    def __init__(self):
+        self.calls = []
 
     def add(self, what, fn, *args):
-        moving = tuple((k, a) for k, a in enumerate(args) if isinstance(a, _Moving))
-        self.calls.append((fn, list(args), what, moving))
+        for a in args:
+            if type(a) is _Moving:
+                args = list(args)       # run() patches these places
+                moving = tuple((k, a) for k, a in enumerate(args) if type(a) is _Moving)
+                break
+        else:
+            moving = ()
+        self.calls.append((fn, args, what, moving))
 
-    def run(self, j):
+    def run(self, j=0):
         for fn, args, what, moving in self.calls:
             for k, a in moving:
                 args[k] = a.at(j)
             rc = fn(*args)
             if rc:
                 check(rc, what)
+
+
+class _View:
+    """An activation as the recording passes it around: float32 tensor `t` (which keeps the memory and gives the base address),
+    `c` stored channels per pixel, pixels `ld` elements apart; it moves by `step` elements per column (0: it stays)."""
+    __slots__ = ("t", "c", "ld", "step")
+
+    def __init__(self, t, c, ld, step=0):
+        self.t, self.c, self.ld, self.step = t, c, ld, step
+
+    def ptr(self, offset=0):
+        a = self.t.data_ptr() + 4 * offset
+        return _Moving(a, 4 * self.step) if self.step else C.c_void_p(a)
+
+
+class _RowStep:
+    """Step (i, j) computes the whole of row i: a row-local call covers B * W pixels."""
+    prefix = ""                          # name space of the scratch buffers [B, 1, w, c]
+
+    def __init__(self, batch, width):
+        self.W, self.w, self.pixels = width, width, batch * width          # w: the pixels of one image in a step
+        self.workspace_query = lib.vq2_conv_fwd_row_workspace_bytes
+
+    def row(self, t):
+        """A row [B, W, C] of a history, the background or the condition: all of it."""
+        return _View(t, t.shape[2], t.shape[2])
+
+    def band_row(self, t):
+        """A row [B, W, c] out of the band [B, R, W, c], image by image (ld is the image stride): runs of W * c."""
+        return _View(t, self.W * t.shape[2], t.stride(0))
+
+    def column(self, j):
+        """The pixel of a scratch buffer at which column j stands."""
+        return j
+
+    def conv_rows(self, conv, row):
+        """The call of a conv over several rows and the arguments that say where."""
+        return "conv_fwd_row", lib.vq2_conv_fwd_row, (row,)
+
+    def queries(self, row):
+        return row * self.W, self.W      # q0, nq
+
+
+class _ColumnStep:
+    """Step (i, j) computes column j of row i: a row-local call covers B pixels, and what is read from or written into a row
+    is its column 0, moving by the row's channels per column."""
+    prefix = "px."
+
+    def __init__(self, batch, width):
+        self.W, self.w, self.pixels = width, 1, batch
+        self.workspace_query = lib.vq2_conv_fwd_col_workspace_bytes
+
+    def row(self, t):
+        return _View(t, t.shape[2], self.W * t.shape[2], t.shape[2])
+
+    def band_row(self, t):
+        return _View(t, t.shape[2], t.stride(0), t.shape[2])
+
+    def column(self, j):
+        return 0
+
+    def conv_rows(self, conv, row):
+        assert conv.row_flags == VQ2_ROW_CAUSAL_TAPS        # row `row` holds columns <= j only
+        return "conv_fwd_col", lib.vq2_conv_fwd_col, (row, _Moving(0, 1, pointer=False))
+
+    def queries(self, row):
+        return _Moving(row * self.W, 1, pointer=False), 1
+
+
+_STEPS = {'row': _RowStep, 'pixel': _ColumnStep}
 
 
 class _Conv:
@@ -126,83 +196,35 @@ class _Conv:
     def row_desc(self, batch, rows, width):
         return ops._desc(self.spec, batch, rows, width, self.spec.ci, self.spec.co)
 
-    def workspace_bytes(self, batch, rows, width, query=None):
+    def workspace_bytes(self, batch, rows, width, query):
         if self.kh == 1:
             return 0
-        query = query or lib.vq2_conv_fwd_row_workspace_bytes
         return query(C.byref(self.row_desc(batch, rows, width)), self.row_flags)
 
 
-class _Plan:
-    """Buffers, histories and the recorded launches of every row for one (batch, rows, condition?) on one stream."""
+class _Recorder:
+    """Records the library calls of one step of row `row` under the step geometry `geo`: prog is the program, logits the view
+    in which a step leaves its logits."""
 
-    def __init__(self, sampler, batch, rows, with_condition):
-        self.s, self.B, self.H, self.W = sampler, batch, rows, sampler.width
-        self.dev = sampler.device
-        self.stream = ops._stream()
-        self.stream_id = torch.cuda.current_stream().cuda_stream
-        self.bufs = {}
-        m = sampler.model
-        ws_bytes = self.workspace_bytes()
-        self.ws = torch.empty((ws_bytes + 3) // 4, device=self.dev, dtype=torch.float32)
-        self.ws_bytes = ws_bytes
-        self.R = sampler.band_rows
-        # band i: code rows i - R + 1 .. i as the input convs see them at row i; -1 above the image
-        self.bands = torch.empty((rows, batch, self.R, self.W), device=self.dev, dtype=torch.int64)
-        self.cond_rows = None
-        if with_condition:
-            self.cond_rows = torch.empty((rows, batch, self.W, ops.ceil4(m.cond_res_channel)), device=self.dev, dtype=torch.float32)
-        bg = m._background(batch, rows)                                   # [B, rows, W, 4]
-        self.bg_rows = torch.empty((rows, batch, self.W, 4), device=self.dev, dtype=torch.float32)
-        self.to_row_outer(bg, self.bg_rows)
-        self.logits = None
-        self.pixels = batch * self.W          # what one call of a row-local kernel covers
-        self.programs = [self.record(i) for i in range(rows)]
+    def __init__(self, plan, geo, row):
+        self.plan, self.geo, self.row, self.prog = plan, geo, row, _Program()
+        self.s, self.B, self.H, self.W, self.R, self.stream = plan.s, plan.B, plan.H, plan.W, plan.R, plan.stream
+        cond = None if plan.cond_rows is None else geo.row(plan.cond_rows[row])
+        self.logits = self.body(self.input_stage(), geo.row(plan.bg_rows[row]), cond)
 
-    def workspace_bytes(self):
-        return max([c.workspace_bytes(self.B, self.H, self.W) for c in self.s.convs] + [16])
-
-    # -- buffers
     def buf(self, name, c):
-        t = self.bufs.get(name)
-        if t is None:
-            t = self.bufs[name] = torch.empty((self.B, 1, self.W, c), device=self.dev, dtype=torch.float32)
-        return t
+        """A scratch buffer of this geometry: dense, and it stays."""
+        return _View(self.plan.tensor(self.geo.prefix + name, (self.B, 1, self.geo.w, c)), c, c)
 
     def hist(self, name, c):
-        t = self.bufs.get(name)
-        if t is None:
-            t = self.bufs[name] = torch.empty((self.H, self.B, self.W, c), device=self.dev, dtype=torch.float32)
-        return t
+        return self.plan.tensor(name, (self.H, self.B, self.W, c))
 
-    def to_row_outer(self, src, dst):
-        """NHWC [B, >= rows, W, C] -> [rows, B, W, C]: one slice copy per row (an image's row is one run of W * C floats)."""
-        b, h, w, c = src.shape
-        for i in range(self.H):
-            check(lib.vq2_slice_copy(_ptr(src, i * w * c), h * w * c, _ptr(dst, i * b * w * c), w * c, b, w * c, 0, self.stream),
-                  "slice_copy")
+    def hist_row(self, hist):
+        """Where this step writes its part of a history [H, B, W, C]."""
+        return self.geo.row(hist[self.row])
 
-    def reset_codes(self):
-        self.bands.zero_()
-        for r in range(self.R - 1):
-            self.bands[:self.R - 1 - r, :, r].fill_(-1)
-
-    def end_row(self, i):
-        if i + 1 < self.H:
-            self.bands[i + 1, :, :self.R - 1].copy_(self.bands[i, :, 1:])
-
-    def codes(self):
-        return self.bands[:, :, self.R - 1].permute(1, 0, 2).contiguous()
-
-    # -- recording
-    def record(self, i):
-        self.prog = _Program()
-        self.row = i
-        x = self.input_stage()
-        bg = self.bg_rows[i].view(self.B, 1, self.W, 4)
-        cond = None if self.cond_rows is None else self.cond_rows[i].view(self.B, 1, self.W, -1)
-        self.logits = self.body(x, bg, cond)
-        return self.prog
+    def add(self, what, fn, *args):
+        self.prog.add(what, fn, *args, self.stream)
 
     def body(self, x, bg, cond):
         """Everything after the input stage; returns the logits buffer."""
@@ -218,69 +240,52 @@ class _Plan:
         self.conv(s.conv_of[m.out[n_out + 1]], e, None, logits)
         return logits
 
-    @staticmethod
-    def ld(t):
-        """Pixel stride of a buffer."""
-        return t.shape[3]
-
-    p = staticmethod(_ptr)
-
-    def add(self, what, fn, *args):
-        self.prog.add(what, fn, *(args + (self.stream,)))
-
     def elu(self, x, c, out):
-        self.add("elu_fwd", lib.vq2_elu_fwd, self.p(x), self.ld(x), self.p(out), self.ld(out), self.pixels, c)
+        self.add("elu_fwd", lib.vq2_elu_fwd, x.ptr(), x.ld, out.ptr(), out.ld, self.geo.pixels, c)
 
     def copy(self, src, dst, dst_off):
-        self.add("slice_copy", lib.vq2_slice_copy, self.p(src), self.ld(src), self.p(dst, dst_off), self.ld(dst), self.pixels,
-                 src.shape[3], 0)
+        self.add("slice_copy", lib.vq2_slice_copy, src.ptr(), src.ld, dst.ptr(dst_off), dst.ld, self.geo.pixels, src.c, 0)
 
     def conv_input(self, name, conv):
-        """Where the input row of `conv` is to be written: its history's row, or a plain row buffer."""
+        """Where the input of `conv` is to be written: its history's row, or a plain scratch buffer."""
         if conv.kh > 1:
             return self.hist_row(self.hist(name + ".hist", conv.spec.ci))
         return self.buf(name + ".in", conv.spec.ci)
 
     def conv(self, conv, x, residual, out, name=None):
         sp = conv.spec
-        ldres = self.ld(residual) if residual is not None else 0
+        res, ldres = (residual.ptr(), residual.ld) if residual is not None else (None, 0)
         if conv.kh == 1:
-            d = ops._desc(sp, self.B, 1, self.pixels // self.B, self.ld(x), self.ld(out))
-            self.add("conv_fwd", lib.vq2_conv_fwd, d, 0, self.p(x), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres,
-                     self.p(out))
+            d = ops._desc(sp, self.B, 1, self.geo.w, x.ld, out.ld)
+            self.add("conv_fwd", lib.vq2_conv_fwd, d, 0, x.ptr(), _ptr(conv.wp), ops._p(conv.bias), res, ldres, out.ptr())
             return
-        self.conv_rows(conv, x, residual, ldres, out, name)
-
-    def conv_rows(self, conv, x, residual, ldres, out, name):
-        sp = conv.spec
         hist = self.hist(name + ".hist", sp.ci)
-        assert x.data_ptr() == hist[self.row].data_ptr() and out.shape[3] == sp.co
-        d = conv.row_desc(self.B, self.H, self.W)
-        self.add("conv_fwd_row", lib.vq2_conv_fwd_row, d, self.row, self.W * sp.ci, self.B * self.W * sp.ci, conv.row_flags,
-                 _ptr(hist), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres, _ptr(out), _ptr(self.ws), self.ws_bytes)
+        want = self.hist_row(hist)          # the conv reads its history: x must be this step's part of row `row` of it
+        assert (x.t.data_ptr(), x.ld, x.step) == (want.t.data_ptr(), want.ld, want.step) and (out.ld, out.step) == (sp.co, 0)
+        what, fn, where = self.geo.conv_rows(conv, self.row)
+        self.add(what, fn, conv.row_desc(self.B, self.H, self.W), *where, self.W * sp.ci, self.B * self.W * sp.ci, conv.row_flags,
+                 _ptr(hist), _ptr(conv.wp), ops._p(conv.bias), res, ldres, out.ptr(), _ptr(self.plan.ws), self.plan.ws_bytes)
 
     def input_stage(self):
         cp = ops.ceil4(self.s.model.channel)
-        y = self.input_band()
+        src = self.geo.band_row(self.input_band()[:, self.R - 1])      # the band's last row of every image, B runs
         x = self.buf("in.x", cp)
-        # the band's last row of every image: B runs of W * cp floats
-        self.add("slice_copy", lib.vq2_slice_copy, _ptr(y, (self.R - 1) * self.W * cp), self.R * self.W * cp, _ptr(x), self.W * cp,
-                 self.B, self.W * cp, 0)
+        self.add("slice_copy", lib.vq2_slice_copy, src.ptr(), src.ld, x.ptr(), src.c, self.B, src.c, 0)
         return x
 
     def input_band(self):
         """The two one-hot convs over the band of code rows that ends at this row: [B, R, W, cp], the last row is the row's."""
         s, m, i = self.s, self.s.model, self.row
         cp = ops.ceil4(m.channel)
-        band = self.bands[i]
+        band = self.plan.bands[i]
         acc = None
         if i > 0:       # at row 0 the shift brings in a row of zeros (no bias); the band would give the bias
-            acc = self.bufs.setdefault("in.h", torch.empty((self.B, self.R, self.W, cp), device=self.dev, dtype=torch.float32))
+            acc = self.plan.tensor("in.h", (self.B, self.R, self.W, cp))
             sp = s.horizontal.spec
             d = ops._onehot_desc(self.B, self.R, self.W, sp.cout, sp.cin, (sp.k, sp.kw, sp.pad_top, sp.pad_left), (1, 0), cp)
             self.add("onehot_conv_fwd", lib.vq2_onehot_conv_fwd, d, _ptr(band), _ptr(s.horizontal_wp), ops._p(s.horizontal.bias),
                      None, 0, _ptr(acc))
-        y = self.bufs.setdefault("in.v", torch.empty((self.B, self.R, self.W, cp), device=self.dev, dtype=torch.float32))
+        y = self.plan.tensor("in.v", (self.B, self.R, self.W, cp))
         sp = s.vertical.spec
         d = ops._onehot_desc(self.B, self.R, self.W, sp.cout, sp.cin, (sp.k, sp.kw, sp.pad_top, sp.pad_left), (0, 1), cp)
         self.add("onehot_conv_fwd", lib.vq2_onehot_conv_fwd, d, _ptr(band), _ptr(s.vertical_wp), ops._p(s.vertical.bias),
@@ -292,7 +297,7 @@ class _Plan:
         conv1, conv2 = s.conv_of[block.conv1], s.conv_of[block.conv2]
         r = None
         if aux is not None:
-            ea = self.buf(name + ".ea", aux.shape[3])
+            ea = self.buf(name + ".ea", aux.c)
             self.elu(aux, block.auxiliary_channel, ea)
             r = self.buf(name + ".aux", conv1.spec.co)
             self.conv(s.conv_of[block.aux_conv], ea, None, r)
@@ -309,16 +314,16 @@ class _Plan:
         t = self.buf(name + ".t", conv2.spec.co)
         self.conv(conv2, e2, r, t, name + ".c2")
         out = self.buf(name + ".out", ops.ceil4(block.in_channel))
-        self.add("glu_res_fwd", lib.vq2_glu_res_fwd, self.p(t), self.ld(t), self.p(x), self.ld(x), self.p(out), self.ld(out),
-                 self.pixels, block.in_channel)
+        self.add("glu_res_fwd", lib.vq2_glu_res_fwd, t.ptr(), t.ld, x.ptr(), x.ld, out.ptr(), out.ld, self.geo.pixels,
+                 block.in_channel)
         return out
 
     def cat(self, name, parts):
-        out = self.buf(name, sum(p.shape[3] for p in parts))
+        out = self.buf(name, sum(p.c for p in parts))
         off = 0
         for p in parts:
             self.copy(p, out, off)
-            off += p.shape[3]
+            off += p.c
         return out
 
     def pixel_block(self, name, block, x, bg, cond):
@@ -343,90 +348,75 @@ class _Plan:
         d = AttnDesc()
         d.B, d.L, d.n_head, d.dim_head = self.B, self.H * self.W, att.n_head, att.dim_head
         d.ldq = d.ldk = d.ldv = d.ldo = ch
-        self.attend(d, q, kh, vh, o)
+        q0, nq = self.geo.queries(self.row)
+        self.add("causal_attn_fwd_rows", lib.vq2_causal_attn_fwd_rows, d, q0, nq, self.W, self.W * ch, self.B * self.W * ch,
+                 q.ptr(), _ptr(kh), _ptr(vh), o.ptr())
         return self.gated(name + ".outb", block.out_resblock, out, aux=o)
 
-    def hist_row(self, hist):
-        """Where this program writes its part of a history [H, B, W, C]: the whole row."""
-        return hist[self.row].view(self.B, 1, self.W, hist.shape[3])
 
-    def attend(self, d, q, kh, vh, o):
-        ch = kh.shape[3]
-        self.add("causal_attn_fwd_rows", lib.vq2_causal_attn_fwd_rows, d, self.row * self.W, self.W, self.W, self.W * ch,
-                 self.B * self.W * ch, _ptr(q), _ptr(kh), _ptr(vh), _ptr(o))
+class _Plan:
+    """Buffers, histories and the recorded programs of every row for one (batch, rows, condition?) on one stream, under the
+    step geometry `step`.  step_programs[i].run(j) is step (i, j); row_programs[i].run() fills row i when all its codes are
+    given (a `prefix` row costs one run, not W).  Under _RowStep they are the same programs, and nothing of a column is
+    recorded or allocated; under _ColumnStep both kinds fill the same histories."""
 
+    def __init__(self, sampler, step, batch, rows, with_condition):
+        self.s, self.B, self.H, self.W = sampler, batch, rows, sampler.width
+        self.dev = sampler.device
+        self.stream = ops._stream()
+        self.stream_id = torch.cuda.current_stream().cuda_stream
+        self.bufs = {}
+        m = sampler.model
+        self.step = step(batch, self.W)
+        fill = self.step if step is _RowStep else _RowStep(batch, self.W)
+        self.ws_bytes = max([c.workspace_bytes(batch, rows, self.W, g.workspace_query) for g in {self.step, fill} for c in sampler.convs]
+                            + [16])
+        self.ws = torch.empty((self.ws_bytes + 3) // 4, device=self.dev, dtype=torch.float32)
+        self.R = sampler.band_rows
+        # band i: code rows i - R + 1 .. i as the input convs see them at row i; -1 above the image
+        self.bands = torch.empty((rows, batch, self.R, self.W), device=self.dev, dtype=torch.int64)
+        self.cond_rows = None
+        if with_condition:
+            self.cond_rows = torch.empty((rows, batch, self.W, ops.ceil4(m.cond_res_channel)), device=self.dev, dtype=torch.float32)
+        bg = m._background(batch, rows)                                   # [B, rows, W, 4]
+        self.bg_rows = torch.empty((rows, batch, self.W, 4), device=self.dev, dtype=torch.float32)
+        self.to_row_outer(bg, self.bg_rows)
+        recorded = [_Recorder(self, fill, i) for i in range(rows)]
+        self.row_programs = self.step_programs = [r.prog for r in recorded]
+        if self.step is not fill:
+            recorded = [_Recorder(self, self.step, i) for i in range(rows)]
+            self.step_programs = [r.prog for r in recorded]
+        self.logits = recorded[-1].logits
 
-class _PixelPlan(_Plan):
-    """A plan that also steps one column at a time.  It keeps the row programs (a row given by `prefix` costs one run of its
-    row program, which fills the same histories) and, per row, one pixel program over dense column buffers [B, 1, 1, C].
-    A buffer that moves with the column is a view of column 0 that carries `_step`, its elements per column."""
+    def logits_at(self, j):
+        """Where the logits of step (i, j) stand once it has run: (pointer to image 0's, elements between images)."""
+        v = self.logits
+        return v.ptr(self.step.column(j) * v.c), self.step.w * v.c
 
-    def __init__(self, sampler, batch, rows, with_condition):
-        self.px = False
-        super().__init__(sampler, batch, rows, with_condition)
-        self.px, self.pixels = True, batch
-        self.pixel_programs = [self.record_pixel(i) for i in range(rows)]
-
-    def workspace_bytes(self):
-        col = [c.workspace_bytes(self.B, self.H, self.W, lib.vq2_conv_fwd_col_workspace_bytes) for c in self.s.convs]
-        return max(col + [super().workspace_bytes()])
-
-    def record_pixel(self, i):
-        self.prog = _PixelProgram()
-        self.row = i
-        cp = ops.ceil4(self.s.model.channel)
-        y = self.input_band()
-        x = self.buf("in.x", cp)
-        # column j of the band's last row of every image
-        self.add("slice_copy", lib.vq2_slice_copy, _Moving(y.data_ptr() + (self.R - 1) * self.W * cp * 4, cp * 4),
-                 self.R * self.W * cp, _ptr(x), cp, self.B, cp, 0)
-        cond = None if self.cond_rows is None else self.column(self.cond_rows[i])
-        self.pixel_logits = self.body(x, self.column(self.bg_rows[i]), cond)
-        return self.prog
-
-    def column(self, row):
-        """Column 0 of a row [B, W, C] as [B, 1, 1, C] with the pixel stride W * C; it moves by C per column."""
-        v = row.view(self.B, 1, self.W, row.shape[2])[:, :, :1]
-        v._step = row.shape[2]
-        return v
-
-    def buf(self, name, c):
-        if not self.px:
-            return super().buf(name, c)
-        t = self.bufs.get("px." + name)
+    def tensor(self, name, shape):
+        t = self.bufs.get(name)
         if t is None:
-            t = self.bufs["px." + name] = torch.empty((self.B, 1, 1, c), device=self.dev, dtype=torch.float32)
+            t = self.bufs[name] = torch.empty(shape, device=self.dev, dtype=torch.float32)
         return t
 
-    def ld(self, t):
-        return t.stride(0) if self.px else t.shape[3]
+    def to_row_outer(self, src, dst):
+        """NHWC [B, >= rows, W, C] -> [rows, B, W, C]: one slice copy per row (an image's row is one run of W * C floats)."""
+        b, h, w, c = src.shape
+        for i in range(self.H):
+            check(lib.vq2_slice_copy(_ptr(src, i * w * c), h * w * c, _ptr(dst, i * b * w * c), w * c, b, w * c, 0, self.stream),
+                  "slice_copy")
 
-    def p(self, t, offset=0):
-        step = getattr(t, "_step", 0) if self.px else 0
-        if step:
-            return _Moving(t.data_ptr() + offset * t.element_size(), step * t.element_size())
-        return _ptr(t, offset)
+    def reset_codes(self):
+        self.bands.zero_()
+        for r in range(self.R - 1):
+            self.bands[:self.R - 1 - r, :, r].fill_(-1)
 
-    def hist_row(self, hist):
-        return self.column(hist[self.row]) if self.px else super().hist_row(hist)
+    def end_row(self, i):
+        if i + 1 < self.H:
+            self.bands[i + 1, :, :self.R - 1].copy_(self.bands[i, :, 1:])
 
-    def conv_rows(self, conv, x, residual, ldres, out, name):
-        if not self.px:
-            return super().conv_rows(conv, x, residual, ldres, out, name)
-        sp = conv.spec
-        hist = self.hist(name + ".hist", sp.ci)
-        assert x.data_ptr() == hist[self.row].data_ptr() and self.ld(out) == sp.co and conv.row_flags == VQ2_ROW_CAUSAL_TAPS
-        d = conv.row_desc(self.B, self.H, self.W)
-        self.add("conv_fwd_col", lib.vq2_conv_fwd_col, d, self.row, _Moving(0, 1, pointer=False), self.W * sp.ci,
-                 self.B * self.W * sp.ci, conv.row_flags, _ptr(hist), _ptr(conv.wp), ops._p(conv.bias), ops._p(residual), ldres,
-                 _ptr(out), _ptr(self.ws), self.ws_bytes)
-
-    def attend(self, d, q, kh, vh, o):
-        if not self.px:
-            return super().attend(d, q, kh, vh, o)
-        ch = kh.shape[3]
-        self.add("causal_attn_fwd_rows", lib.vq2_causal_attn_fwd_rows, d, _Moving(self.row * self.W, 1, pointer=False), 1, self.W,
-                 self.W * ch, self.B * self.W * ch, _ptr(q), _ptr(kh), _ptr(vh), _ptr(o))
+    def codes(self):
+        return self.bands[:, :, self.R - 1].permute(1, 0, 2).contiguous()
 
 
 class PriorSampler:
@@ -462,9 +452,9 @@ class PriorSampler:
     def __init__(self, model, stepping='row', _weak=False):
         if not isinstance(model, PixelSNAIL):
             raise TypeError("vqvae2_amd.PriorSampler: a vqvae2_amd.PixelSNAIL expected")
-        if stepping not in ('row', 'pixel'):
+        if stepping not in _STEPS:
             raise ValueError(f"vqvae2_amd.PriorSampler: stepping must be 'row' or 'pixel', got {stepping!r}")
-        self.stepping = stepping
+        self.stepping, self.step = stepping, _STEPS[stepping]
         # _weak: sample_model's cache is keyed weakly by the model; its samplers must not keep the model alive themselves
         self._model_ref = weakref.ref(model)
         self._model = None if _weak else model
@@ -534,7 +524,7 @@ class PriorSampler:
         key = (batch, rows, condition is not None, torch.cuda.current_stream().cuda_stream)
         if self._plan is None or self._plan[0] != key:
             self._plan = None       # free the old histories before the new ones are allocated
-            self._plan = (key, (_PixelPlan if self.stepping == 'pixel' else _Plan)(self, batch, rows, condition is not None))
+            self._plan = (key, _Plan(self, self.step, batch, rows, condition is not None))
         plan = self._plan[1]
         if condition is not None:
             if not hasattr(m, "cond_resnet"):
@@ -554,7 +544,7 @@ class PriorSampler:
         rows = self.model.background.shape[2] if rows is None else int(rows)
         if not temperature > 0:
             raise ValueError(f"PriorSampler: temperature must be positive, got {temperature}")
-        n_class, ld = self.model.n_class, ops.ceil4(self.model.n_class)
+        n_class = self.model.n_class
         if int(top_k) != top_k or top_k < 0:
             raise ValueError(f"PriorSampler: top_k must be 0 (off) or a positive integer, got {top_k}")
         if not 0 < top_p <= 1:
@@ -578,30 +568,25 @@ class PriorSampler:
         filtered = top_k > 0 or top_p < 1.0 or return_logp
         # step-outer [rows, W, B]: the draw of step (i, j) writes its B values densely
         logp = torch.zeros((rows, w, b), device=self.device, dtype=torch.float32) if return_logp else None
-        pixel = self.stepping == 'pixel'
-        # where the logits of step (i, j) stand: column j of the row buffer, or the column buffer
-        logits, lrow, lcol = (plan.pixel_logits, ld, 0) if pixel else (plan.logits, w * ld, ld)
         for i in range(rows):
-            prog = plan.programs[i]
             band = plan.bands[i]
             if i < r0:
                 # a given row: with all its codes in place one run of the row's program is exact in every column
                 band[:, r - 1].copy_(prefix[:, i])
-                prog.run()
+                plan.row_programs[i].run()
                 plan.end_row(i)
                 continue
+            prog = plan.step_programs[i]
             for j in range(w):
-                if pixel:
-                    plan.pixel_programs[i].run(j)
-                else:
-                    prog.run()
+                prog.run(j)
+                logits, lrow = plan.logits_at(j)
                 if filtered:
-                    check(lib.vq2_sample_filtered(_ptr(logits, j * lcol), lrow, b, n_class, t, top_k, top_p, seed, i * w + j,
+                    check(lib.vq2_sample_filtered(logits, lrow, b, n_class, t, top_k, top_p, seed, i * w + j,
                                                   _ptr(band, (r - 1) * w + j), r * w,
                                                   _ptr(logp, (i * w + j) * b) if return_logp else None, None, plan.stream),
                           "sample_filtered")
                 else:
-                    check(lib.vq2_sample_categorical(_ptr(logits, j * lcol), lrow, b, n_class, t, seed, i * w + j,
+                    check(lib.vq2_sample_categorical(logits, lrow, b, n_class, t, seed, i * w + j,
                                                      _ptr(band, (r - 1) * w + j), r * w, plan.stream), "sample_categorical")
             plan.end_row(i)
         if return_logp:
@@ -617,41 +602,36 @@ class PriorSampler:
         plan = self._plan_for(batch, rows, condition)
         ld = ops.ceil4(self.model.n_class)
         out = torch.zeros((batch, rows, w, ld), device=self.device, dtype=torch.float32)
-        pixel = self.stepping == 'pixel'
-        logits, lrow, lcol = (plan.pixel_logits, ld, 0) if pixel else (plan.logits, w * ld, ld)
         for i in range(rows):
-            prog = plan.programs[i]
+            prog = plan.step_programs[i]
             for j in range(w):
-                if pixel:
-                    plan.pixel_programs[i].run(j)
-                else:
-                    prog.run()
-                check(lib.vq2_slice_copy(_ptr(logits, j * lcol), lrow, _ptr(out, (i * w + j) * ld), rows * w * ld, batch, ld, 0,
-                                         plan.stream), "slice_copy")
+                prog.run(j)
+                logits, lrow = plan.logits_at(j)
+                check(lib.vq2_slice_copy(logits, lrow, _ptr(out, (i * w + j) * ld), rows * w * ld, batch, ld, 0, plan.stream),
+                      "slice_copy")
                 plan.bands[i, :, plan.R - 1, j] = codes[:, i, j]
             plan.end_row(i)
         return ops.from_nhwc(out, self.model.n_class)
 
 
-_SAMPLERS = weakref.WeakKeyDictionary()      # model -> its PriorSampler (which refers to the model weakly)
-_PIXEL_SAMPLERS = weakref.WeakKeyDictionary()    # the same for stepping='pixel'
+_SAMPLERS = weakref.WeakKeyDictionary()      # model -> {stepping: its PriorSampler, which refers to the model weakly}
 
 
 def sample_model(model, device, batch, size, temperature, condition=None, *, top_k=0, top_p=1.0, prefix=None, stepping='row'):
     """The reference's sample_model (sample.py:12-24): int64 codes [batch, size[0], size[1]] on `device`, drawn from `model`
-    pixel by pixel in raster order.  One PriorSampler per model is kept in this module, keyed weakly by the model (it goes
-    when the model goes, and the model itself carries nothing: it still pickles and deep-copies), and is rebuilt when the
-    model's parameters change.  top_k, top_p and prefix (keyword only, not in the reference) are PriorSampler.sample's;
+    pixel by pixel in raster order.  One PriorSampler per model and stepping is kept in this module, keyed weakly by the model
+    (it goes when the model goes, and the model itself carries nothing: it still pickles and deep-copies), and is rebuilt when
+    the model's parameters change.  top_k, top_p and prefix (keyword only, not in the reference) are PriorSampler.sample's;
     stepping ('row' or 'pixel') is PriorSampler's."""
-    if stepping not in ('row', 'pixel'):
+    if stepping not in _STEPS:
         raise ValueError(f"sample_model: stepping must be 'row' or 'pixel', got {stepping!r}")
     if tuple(size)[1] != model.background.shape[3]:
         raise RuntimeError(f"sample_model: width {size[1]} does not fit the model's {model.background.shape[3]}")
     model = model.to(device)
-    cache = _PIXEL_SAMPLERS if stepping == 'pixel' else _SAMPLERS
-    sampler = cache.get(model)
+    cache = _SAMPLERS.setdefault(model, {})
+    sampler = cache.get(stepping)
     if sampler is None or sampler._snapshot() != sampler._versions:
-        sampler = cache[model] = PriorSampler(model, stepping, _weak=True)
+        sampler = cache[stepping] = PriorSampler(model, stepping, _weak=True)
     return sampler.sample(batch, temperature, condition, rows=int(size[0]), top_k=top_k, top_p=top_p, prefix=prefix)
 
 
