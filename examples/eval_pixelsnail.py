@@ -27,8 +27,8 @@ def parse_args(argv=None):
     parser.add_argument('--batch', type=int, default=32)
     parser.add_argument('--top_k', type=int, default=5)
     parser.add_argument('--dump_map', type=str, default=None, metavar='FILE.npy')
-    parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16', 'bf16_wgrad'],
-                        help='fp32 (default), or bf16: the eligible conv forwards and data gradients multiply bf16-rounded operands and accumulate in fp32; weight gradients, weights, optimizer state and every stored tensor stay fp32 (no loss scaling); the counterpart of --amp O1 of the reference; bf16_wgrad is accepted as an alias of bf16 (evaluation has no weight gradient)')
+    parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16', 'bf16_wgrad', 'bf16_attn'],
+                        help='fp32 (default), or bf16: the eligible conv forwards and data gradients multiply bf16-rounded operands and accumulate in fp32; weight gradients, weights, optimizer state and every stored tensor stay fp32 (no loss scaling); the counterpart of --amp O1 of the reference; bf16_wgrad is accepted as an alias of bf16 (evaluation has no weight gradient); bf16_attn: bf16 convs, and the eligible attention cores (heads of 16, 32, 48 or 64 channels) on bf16-rounded operands as well')
     parser.add_argument('path', type=str)
     return parser.parse_args(argv)
 
@@ -41,8 +41,10 @@ def main(argv=None):
     device = 'cuda'
     ckpt_dir, name = os.path.split(os.path.abspath(args.ckpt))
     model = vqvae2_amd.load_model('pixelsnail_' + args.hier, name, device, ckpt_dir=ckpt_dir)
-    if args.precision in ('bf16', 'bf16_wgrad'):
+    if args.precision != 'fp32':
         vqvae2_amd.set_conv_precision(model, 'bf16')
+    if args.precision == 'bf16_attn':
+        vqvae2_amd.set_attention_precision(model, 'bf16')
     dataset = vqvae2_amd.codes.CodeDataset(args.path)
     share = Subset(dataset, range(rank, len(dataset), max(world, 1)))
     evaluator = vqvae2_amd.PriorEvaluator(model, args.hier, top_k=args.top_k)

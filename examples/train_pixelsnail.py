@@ -5,7 +5,7 @@
     python -m torch.distributed.run --nproc-per-node N examples/train_pixelsnail.py [...] CODES
 
 CODES is what examples/extract_code.py wrote (vqvae2_amd.codes.CodeDataset reads it).  The command line is the
-reference's; `--amp` is accepted only as O0; `--precision bf16` is this path's reduced precision (bf16 conv operands, see --help).  The reference wraps the model in nn.DataParallel; here
+reference's; `--amp` is accepted only as O0; `--precision bf16` (and bf16_wgrad, bf16_attn) is this path's reduced precision (bf16 conv and attention operands, see --help).  The reference wraps the model in nn.DataParallel; here
 data parallelism is one process per GPU under torch.distributed.run: every rank takes its shard of each epoch (--batch is
 per rank), Stage2Trainer all-reduces the gradients, and only the primary rank prints and saves.  Every epoch whose number
 is 1 modulo 10, and the last, saves {'model': state_dict, 'args': args} as <ckpt_dir>/pixelsnail_<hier>_<NNN>.pt, the
@@ -61,8 +61,8 @@ def parse_args(argv=None):
     parser.add_argument('--eval_every', type=int, default=0)
     parser.add_argument('--clip_grad_norm', type=float, default=None)
     parser.add_argument('--ema_decay', type=float, default=None)
-    parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16', 'bf16_wgrad'],
-                        help='fp32 (default), or bf16: the eligible conv forwards and data gradients multiply bf16-rounded operands and accumulate in fp32; weight gradients, weights, optimizer state and every stored tensor stay fp32 (no loss scaling); the counterpart of --amp O1 of the reference; bf16_wgrad: as bf16, and the eligible weight gradients (input and output channels both multiples of 16) multiply bf16-rounded x and dy as well, bias gradients stay fp32 sums')
+    parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16', 'bf16_wgrad', 'bf16_attn'],
+                        help='fp32 (default), or bf16: the eligible conv forwards and data gradients multiply bf16-rounded operands and accumulate in fp32; weight gradients, weights, optimizer state and every stored tensor stay fp32 (no loss scaling); the counterpart of --amp O1 of the reference; bf16_wgrad: as bf16, and the eligible weight gradients (input and output channels both multiples of 16) multiply bf16-rounded x and dy as well, bias gradients stay fp32 sums; bf16_attn: as bf16_wgrad, and the attention cores with heads of 16, 32, 48 or 64 channels multiply bf16-rounded q, k, v, probabilities and gradients as well (softmax and the three projections stay fp32)')
     return parser.parse_args(argv)
 
 
@@ -114,7 +114,7 @@ def main(argv=None):
     model = model.to(device).train()
     trainer = vqvae2_amd.Stage2Trainer(model, args.hier, lr=args.lr, sched=args.sched, n_iter=len(loader) * args.epoch,
                                        clip_grad_norm=clip_grad_norm, ema_decay=ema_decay)
-    if precision in ('bf16', 'bf16_wgrad'):
+    if precision != 'fp32':
         trainer.set_precision(precision)
     first_epoch = 0
     if resume is not None:

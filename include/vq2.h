@@ -64,11 +64,13 @@ typedef void *vq2_stream_t;
  * only -- the bf16-operand weight gradient: VQ2_ALLOW_BF16 in the flags of vq2_conv_wgrad / vq2_conv_wgrad_partial (ignored
  * before), vq2_conv_wgrad_bf16_eligible, vq2_conv_wgrad_workspace_bytes_ex and vq2_wgrad_job_init_ex;
  * revision 19: additions only -- the dead-code restart of Quantize: vq2_vq_restart_candidates and vq2_vq_ema_update_restart;
- * revision 20: additions only -- pixel-incremental sampling: vq2_conv_fwd_col with its workspace query.
+ * revision 20: additions only -- pixel-incremental sampling: vq2_conv_fwd_col with its workspace query;
+ * revision 21: additions only -- bf16-operand causal attention: vq2_causal_attn_fwd_ex / vq2_causal_attn_bwd_ex (the flags
+ * argument, VQ2_ALLOW_BF16) and vq2_causal_attn_bf16_eligible.
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 20
+#define VQ2_API_VERSION 21
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -546,6 +548,25 @@ int vq2_causal_attn_bwd(const vq2_attn_desc *d, const float *q, const float *k, 
                         const float *lse, const float *dO, int32_t lddo, float *dq, int32_t lddq, float *dk, int32_t lddk,
                         float *dv, int32_t lddv, float *delta_ws, vq2_stream_t stream);
 int vq2_causal_attn_keep_mask(const vq2_attn_desc *d, uint8_t *mask, vq2_stream_t stream);
+
+/* The same two calls with a flags argument.  flags = 0 is vq2_causal_attn_fwd / vq2_causal_attn_bwd; the only flag is
+ * VQ2_ALLOW_BF16 (any other bit: VQ2_ERR_INVALID).  It is a permission, as on the convs: where
+ * vq2_causal_attn_bf16_eligible(d) is 1 (dim_head % 16 == 0, that is 16, 32, 48, 64) the four matrix products take
+ * operands rounded to bf16 (round to nearest even, r() below) and accumulate in fp32 (v_mfma_f32_16x16x16_bf16); elsewhere
+ * the call is the fp32 one, bit for bit.  Everything in memory stays fp32, with the shapes and strides above.
+ *     forward:   S = sum_d r(q) r(k), ONE rounded multiply by scale * log2(e); mask, running max / sum, exp2 and lse in
+ *                fp32 (the row sum adds the unrounded p); O = sum_j r(p~) r(v) / sum_j p, p~ = p after dropout scaling.
+ *     backward:  S recomputed by the same operations (the forward's bits); dP = sum_d r(dO) r(v); D = sum_j P dP and
+ *                dS = P (dP - D) in fp32; dV = sum_i r(p~) r(dO); dQ = scale sum_j r(dS) r(k); dK = scale sum_i r(dS) r(q).
+ * Mask, exact-zero row 0, the dropout decision (vq2_causal_attn_keep_mask describes this path too), accumulation orders
+ * and bit-reproducibility are those of the fp32 calls.  The forward and the backward of one pass take the same flags.
+ * vq2_causal_attn_fwd_rows (the sampler) has no such form. */
+int vq2_causal_attn_bf16_eligible(const vq2_attn_desc *d);
+int vq2_causal_attn_fwd_ex(const vq2_attn_desc *d, int flags, const float *q, const float *k, const float *v, float *o,
+                           float *lse, vq2_stream_t stream);
+int vq2_causal_attn_bwd_ex(const vq2_attn_desc *d, int flags, const float *q, const float *k, const float *v,
+                           const float *lse, const float *dO, int32_t lddo, float *dq, int32_t lddq, float *dk, int32_t lddk,
+                           float *dv, int32_t lddv, float *delta_ws, vq2_stream_t stream);
 
 /* weight_norm(nn.Linear) (pixelsnail.py:17-18): w[r][c] = g[r] * v[r][c] / ||v[r]||_2 over `rows` output rows of `cols`
  * floats, and its backward: dg[r] = (dw[r] . v[r]) / ||v[r]||, dv[r] = (g[r] / ||v[r]||) * (dw[r] - v[r] * (dw[r] . v[r]) /

@@ -8,7 +8,12 @@ training mode (p = 0.1).  The two paths alternate inside every repeat, the first
 Counted from the shapes (not measured): exponentials = B * n_head * L * (L - 1) / 2 per forward evaluation of P (the
 backward pass evaluates P three times more: row terms, dK/dV, dQ); bytes = what the fused attention core must move (q, k, v in, o and the
 log-sum-exp out; backward: q, k, v, dO and the log-sum-exp in, dq, dk, dv out) -- reported over the time of the WHOLE module call
-(projections included), so both rates are lower bounds for the core kernels."""
+(projections included), so both rates are lower bounds for the core kernels.
+
+--precision both: the second path is not eager torch but the SAME module with bf16-operand attention
+(vqvae2_amd.set_attention_precision), built from the same weights; "fused" is then the fp32 module and "eager" reads "bf16" in
+every key, so "bf16_over_fused" below 1 means the bf16 core is faster.  eval_max_abs_diff is then the difference between the two
+precisions.  Default output profiles/attention_bf16.json."""
 import argparse
 import json
 import math
@@ -61,31 +66,47 @@ def time_ms(fn, repeats, inner):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attention.json"))
+    ap.add_argument("--out", default=None, help="default profiles/attention.json, attention_bf16.json with --precision both")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "both"],
+                    help="both: time the fp32 fused module against the same module with bf16-operand attention")
     ap.add_argument("--repeats", type=int, default=7, help="timed repeats per path (one more is run first and discarded)")
     ap.add_argument("--inner", type=int, default=50)
     args = ap.parse_args()
+    low = args.precision != "fp32"
+    other = "bf16" if low else "eager"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "attention_bf16.json" if low else "attention.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_attention.py needs the MI355X")
     import vqvae2_amd
     dev = torch.device("cuda:0")
     results = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "inner": args.inner, "cases": []}
+    if low:
+        results["precision"] = args.precision
     for b, hw in ((32, 32), (2, 64)):
         l, nh, dh, cq, ck = hw * hw, 8, 16, 258, 514
         torch.manual_seed(0)
         mod = vqvae2_amd.CausalAttention(cq, ck, nh * dh, n_head=nh, dropout=0.1).to(dev)
         sd = {k: v.detach().clone().requires_grad_(True) for k, v in mod.state_dict().items()}
+        mod16 = None
+        if low:
+            mod16 = vqvae2_amd.CausalAttention(cq, ck, nh * dh, n_head=nh, dropout=0.1).to(dev)
+            mod16.load_state_dict(mod.state_dict())
+            assert vqvae2_amd.set_attention_precision(mod16, "bf16") == (1, 1)
         query = torch.randn(b, cq, hw, hw, device=dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
         key = torch.randn(b, ck, hw, hw, device=dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
         gout = torch.randn(b, nh * dh, hw, hw, device=dev).contiguous(memory_format=torch.channels_last)
         # faster and different is not faster: the two paths must agree in eval mode at the timed size
         mod.eval()
         with torch.no_grad():
-            diff = float((mod(query, key) - eager_forward(query, key, sd, nh, 0.0, False)).abs().max())
+            ref = mod16.eval()(query, key) if low else eager_forward(query, key, sd, nh, 0.0, False)
+            diff = float((mod(query, key) - ref).abs().max())
         unit = b * l * nh * dh * 4
         exps = b * nh * l * (l - 1) // 2
         for training in (False, True):
             mod.train(training)
+            if low:
+                mod16.train(training)
 
             def fused_f():
                 with torch.no_grad():
@@ -93,13 +114,13 @@ def main():
 
             def eager_f():
                 with torch.no_grad():
-                    eager_forward(query, key, sd, nh, 0.1, training)
+                    mod16(query, key) if low else eager_forward(query, key, sd, nh, 0.1, training)
 
             def fused_fb():
                 mod(query, key).backward(gout)
 
             def eager_fb():
-                eager_forward(query, key, sd, nh, 0.1, training).backward(gout)
+                (mod16(query, key) if low else eager_forward(query, key, sd, nh, 0.1, training)).backward(gout)
 
             row = {"B": b, "L": l, "n_head": nh, "dim_head": dh, "training": training, "eval_max_abs_diff": diff}
             for tag, ff, ef, n_exp, byts in (("fwd", fused_f, eager_f, exps, 4 * unit + unit // dh),
@@ -114,16 +135,16 @@ def main():
                     te += time_ms(ef, 1, args.inner)
                 tf, te = tf[1:], te[1:]              # the first window of a series still carries warm-up
                 mf, me = statistics.median(tf), statistics.median(te)
-                row[tag] = {"fused_ms": tf, "eager_ms": te, "fused_median_ms": mf, "eager_median_ms": me,
-                            "fused_spread": (max(tf) - min(tf)) / mf, "eager_spread": (max(te) - min(te)) / me,
-                            "eager_over_fused": me / mf, "counted_exponentials": n_exp,
+                row[tag] = {"fused_ms": tf, other + "_ms": te, "fused_median_ms": mf, other + "_median_ms": me,
+                            "fused_spread": (max(tf) - min(tf)) / mf, other + "_spread": (max(te) - min(te)) / me,
+                            other + "_over_fused": me / mf, "counted_exponentials": n_exp,
                             "fused_exponentials_per_s": n_exp / (mf * 1e-3), "counted_core_bytes": byts,
                             "fused_core_bytes_per_s": byts / (mf * 1e-3)}
                 print(json.dumps({"B": b, "L": l, "training": training, "pass": tag, "fused_ms": round(mf, 4),
-                                  "eager_ms": round(me, 4), "spread": [round(row[tag]["fused_spread"], 3),
-                                                                       round(row[tag]["eager_spread"], 3)]}), flush=True)
+                                  other + "_ms": round(me, 4), "spread": [round(row[tag]["fused_spread"], 3),
+                                                                          round(row[tag][other + "_spread"], 3)]}), flush=True)
             results["cases"].append(row)
-            for t in (query, key, *sd.values(), *mod.parameters()):
+            for t in (query, key, *sd.values(), *mod.parameters(), *(mod16.parameters() if low else ())):
                 t.grad = None
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

@@ -17,8 +17,8 @@ same number of pixels per step), dropout 0.1, random codes from a seed.  Per mod
 Writes one JSON document (default profiles/pixelsnail.json).  No GPU: fails.  Not measured here: kernel times (no
 profiler run), anything on more than one GPU.
 
---amp O1: instead, per model, the arena trainers with bf16 conv operands (Stage2Trainer.set_precision('bf16'), and
-'bf16_wgrad' with bf16 weight gradients as well) against the
+--amp O1: instead, per model, the arena trainers with bf16 conv operands (Stage2Trainer.set_precision('bf16'),
+'bf16_wgrad' with bf16 weight gradients as well, and 'bf16_attn' with bf16-operand attention cores on top) against the
 arena trainer in fp32, from the same weights, alternating in the same way; the first losses must agree to 1e-2 relative
 (they cannot be bit-equal).  Default output profiles/pixelsnail_bf16.json."""
 import argparse
@@ -154,7 +154,8 @@ def bench_model(amd, spec, repeats, inner):
 
 
 def bench_amp(amd, spec, repeats, inner):
-    """One model: the fp32 arena trainer, the bf16 one and the bf16_wgrad one (bf16 weight gradients too), from the same
+    """One model: the fp32 arena trainer, the bf16 one, the bf16_wgrad one (bf16 weight gradients too) and the bf16_attn
+    one (bf16 attention cores too; the bottom prior has no attention, so there it repeats bf16_wgrad), from the same
     weights, alternated."""
     dev = torch.device("cuda:0")
     h, w = spec["shape"]
@@ -167,12 +168,14 @@ def bench_amp(amd, spec, repeats, inner):
     state = amd.PixelSNAIL(spec["shape"], *spec["args"], dropout=0.1, **spec["kw"]).state_dict()
     row = {"name": spec["name"], "shape": spec["shape"], "batch": spec["batch"], "args": spec["args"], "kw": spec["kw"]}
     trainers, first = {}, {}
-    for prec in ("fp32", "bf16", "bf16_wgrad"):
+    for prec in ("fp32", "bf16", "bf16_wgrad", "bf16_attn"):
         m = amd.PixelSNAIL(spec["shape"], *spec["args"], dropout=0.1, **spec["kw"])
         m.load_state_dict(state)
         tr = amd.Stage2Trainer(m.to(dev).train(), spec["hier"], lr=3e-4, sched="cycle", n_iter=1000)
         if prec != "fp32":
             row["eligible_layers"], row["conv_layers"] = tr.set_precision(prec)
+        if prec == "bf16_attn":
+            row["eligible_attention_layers"], row["attention_layers"] = amd.set_attention_precision(tr.model, "bf16")
         torch.manual_seed(7)
         first[prec] = float(tr.step(*step_args)["loss"])
         tr.step(*step_args)
@@ -193,9 +196,12 @@ def bench_amp(amd, spec, repeats, inner):
     row["fp32_over_bf16"] = row["fp32_median_ms"] / row["bf16_median_ms"]
     row["bf16_over_bf16_wgrad"] = row["bf16_median_ms"] / row["bf16_wgrad_median_ms"]
     row["fp32_over_bf16_wgrad"] = row["fp32_median_ms"] / row["bf16_wgrad_median_ms"]
+    row["bf16_wgrad_over_bf16_attn"] = row["bf16_wgrad_median_ms"] / row["bf16_attn_median_ms"]
+    row["fp32_over_bf16_attn"] = row["fp32_median_ms"] / row["bf16_attn_median_ms"]
     print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()
                       if k in ("name", "batch", "fp32_median_ms", "bf16_median_ms", "fp32_spread", "bf16_spread", "fp32_over_bf16",
-                               "bf16_wgrad_median_ms", "bf16_wgrad_spread", "bf16_over_bf16_wgrad", "eligible_layers", "conv_layers", "first_loss")}), flush=True)
+                               "bf16_wgrad_median_ms", "bf16_wgrad_spread", "bf16_over_bf16_wgrad", "bf16_attn_median_ms", "bf16_attn_spread", "bf16_wgrad_over_bf16_attn",
+                               "eligible_layers", "conv_layers", "eligible_attention_layers", "attention_layers", "first_loss")}), flush=True)
     return row
 
 

@@ -10,8 +10,11 @@ in one session; every figure is reported as the mean of the repeats with their m
 
     python scripts/bench_prior_eval.py            (REPEATS=3 STEPS=20 WARMUP=5 by default; writes profiles/prior_eval.json)
     python scripts/bench_prior_eval.py --amp O1   (also `update` of the same model with bf16 conv operands
-                                                   (set_conv_precision), alternated with the fp32 one inside every repeat;
+                                                   (set_conv_precision), and with bf16 attention cores on top
+                                                   (set_attention_precision, the evaluator's --precision bf16_attn),
+                                                   alternated with the fp32 one inside every repeat;
                                                    writes profiles/prior_eval_bf16.json)
+    --out PATH                                    write there instead
 """
 import argparse
 import copy
@@ -66,11 +69,14 @@ def measure(hier, batch):
     bottom = torch.randint(0, N_CLASS, (batch, 64, 64), generator=g).to(dev)
     target = top if hier == "top" else bottom
     ev = vqvae2_amd.PriorEvaluator(model, hier)
-    ev16 = None
+    ev16 = ev16a = None
     if AMP == "O1":
         model16 = copy.deepcopy(model)
         layers = vqvae2_amd.set_conv_precision(model16, "bf16")
         ev16 = vqvae2_amd.PriorEvaluator(model16, hier)
+        model16a = copy.deepcopy(model16)
+        attn_layers = vqvae2_amd.set_attention_precision(model16a, "bf16")
+        ev16a = vqvae2_amd.PriorEvaluator(model16a, hier)
 
     def forward():
         with eval_mode(model), torch.no_grad():
@@ -86,11 +92,12 @@ def measure(hier, batch):
         ops.prior_eval_accumulate(nll, entropy, rank, batch, ev.top_k, pos_nll, pos_entropy, hit1, hitk, counters)
         ops.index_hist(target, counts, flag)
 
-    t = {"update": [], "update_bf16": [], "forward": [], "added": [], "rows": []}
+    t = {"update": [], "update_bf16": [], "update_bf16_attn": [], "forward": [], "added": [], "rows": []}
     for _ in range(REPEATS):
         t["update"].append(by_events(lambda: ev.update(top, bottom if hier == "bottom" else None), STEPS, WARMUP))
         if ev16 is not None:
             t["update_bf16"].append(by_events(lambda: ev16.update(top, bottom if hier == "bottom" else None), STEPS, WARMUP))
+            t["update_bf16_attn"].append(by_events(lambda: ev16a.update(top, bottom if hier == "bottom" else None), STEPS, WARMUP))
         t["forward"].append(by_events(forward, STEPS, WARMUP))
         t["added"].append(by_events(added, 10 * STEPS, 10 * WARMUP))
         t["rows"].append(by_events(lambda: ops.prior_eval_rows(x, target, N_CLASS), 10 * STEPS, 10 * WARMUP))
@@ -102,9 +109,15 @@ def measure(hier, batch):
     if ev16 is not None:
         ev16.reset()
         ev16.update(top, bottom if hier == "bottom" else None)
+        ev16a.reset()
+        ev16a.update(top, bottom if hier == "bottom" else None)
         extra = {"update_bf16_ms": spread(t["update_bf16"], 1e3), "eligible_layers": layers[0], "conv_layers": layers[1],
                  "update_fp32_over_bf16": round(sum(t["update"]) / sum(t["update_bf16"]), 3),
-                 "nll_of_the_untrained_model_bf16": round(ev16.result()["nll"], 4)}
+                 "nll_of_the_untrained_model_bf16": round(ev16.result()["nll"], 4),
+                 "update_bf16_attn_ms": spread(t["update_bf16_attn"], 1e3),
+                 "eligible_attention_layers": attn_layers[0], "attention_layers": attn_layers[1],
+                 "update_bf16_over_bf16_attn": round(sum(t["update_bf16"]) / sum(t["update_bf16_attn"]), 3),
+                 "nll_of_the_untrained_model_bf16_attn": round(ev16a.result()["nll"], 4)}
     return {**extra, "hier": hier, "batch": batch, "codes_per_batch": rows, "n_class": N_CLASS, "row_stride": ld,
             "update_ms": spread(t["update"], 1e3), "update_codes_per_s": spread([rows / v for v in t["update"]], 1.0, 0),
             "forward_ms": spread(t["forward"], 1e3), "added_launches_us": spread(t["added"], 1e6, 2),
@@ -116,15 +129,19 @@ def measure(hier, batch):
 def main():
     global AMP
     ap = argparse.ArgumentParser()
-    ap.add_argument("--amp", default="O0", choices=["O0", "O1"], help="O1: also time update() with bf16 conv operands")
-    AMP = ap.parse_args().amp
+    ap.add_argument("--amp", default="O0", choices=["O0", "O1"],
+                    help="O1: also time update() with bf16 conv operands, and with bf16 attention cores on top")
+    ap.add_argument("--out", default=None, help="default profiles/prior_eval.json, prior_eval_bf16.json with --amp O1")
+    args = ap.parse_args()
+    AMP = args.amp
     out = {"method": f"HIP events around {STEPS} calls after {WARMUP} warm-up calls (10x both for the launches alone), "
                      f"{REPEATS} repeats in one session; mean with min and max of the repeats",
            "device": torch.cuda.get_device_name(0), "results": [measure("top", 32), measure("bottom", 8)]}
     for r in out["results"]:
         print(json.dumps(r), flush=True)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "prior_eval_bf16.json" if AMP == "O1" else "prior_eval.json"), "w") as f:
+    path = args.out or os.path.join(ROOT, "profiles", "prior_eval_bf16.json" if AMP == "O1" else "prior_eval.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
 

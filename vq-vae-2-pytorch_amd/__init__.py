@@ -8,7 +8,7 @@ from . import vqvae_deep  # noqa: F401
 from .vqvae_deep import VQVAE_Deep  # noqa: F401
 from . import pixelsnail  # noqa: F401
 from .pixelsnail import (CausalAttention, WNConv2d, CausalConv2d, GatedResBlock, PixelBlock, CondResNet,  # noqa: F401
-                         PixelSNAIL, set_conv_precision, conv_precision)
+                         PixelSNAIL, set_conv_precision, conv_precision, set_attention_precision, attention_precision)
 from .ops import prior_loss, vq_restart_candidates, vq_ema_update_restart  # noqa: F401
 from . import distributed  # noqa: F401
 from . import ops  # noqa: F401

@@ -125,6 +125,9 @@ def _load():
         "vq2_causal_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P, P]),
         "vq2_causal_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P, I32, P, I32, P, I32, P, I32, P, P]),
         "vq2_causal_attn_keep_mask": (C.c_int, [C.POINTER(AttnDesc), P, P]),
+        "vq2_causal_attn_bf16_eligible": (C.c_int, [C.POINTER(AttnDesc)]),
+        "vq2_causal_attn_fwd_ex": (C.c_int, [C.POINTER(AttnDesc), C.c_int, P, P, P, P, P, P]),
+        "vq2_causal_attn_bwd_ex": (C.c_int, [C.POINTER(AttnDesc), C.c_int, P, P, P, P, P, I32, P, I32, P, I32, P, I32, P, P]),
         "vq2_weight_norm_fwd": (C.c_int, [P, P, P, I32, I32, P]),
         "vq2_weight_norm_bwd": (C.c_int, [P, P, P, P, P, I32, I32, P]),
         "vq2_wn_table_fwd": (C.c_int, [P, I32, P, P, P]),

@@ -1035,6 +1035,14 @@ def attn_check_geometry(channel, n_head):
     return dh
 
 
+def attn_bf16_eligible(channel, n_head):
+    """Whether CausalAttnFn(..., bf16=True) takes the bf16-operand kernels at this geometry (vq2_causal_attn_bf16_eligible):
+    dim_head = channel / n_head is 16, 32, 48 or 64.  Elsewhere the permission changes nothing."""
+    d = AttnDesc()
+    d.B, d.L, d.n_head, d.dim_head = 1, 1, n_head, attn_check_geometry(channel, n_head)
+    return bool(lib.vq2_causal_attn_bf16_eligible(C.byref(d)))
+
+
 def _attn_desc(b, l, n_head, dh, q, k, v, o, p, seed):
     d = AttnDesc()
     d.B, d.L, d.n_head, d.dim_head = b, l, n_head, dh
@@ -1052,10 +1060,12 @@ def _attn_operand(t, what):
 class CausalAttnFn(Function):
     """pixelsnail.py:220-228 for projected q, k, v ([B,H,W,n_head * dim_head] NHWC): strictly causal softmax(QK^T /
     sqrt(dim_head)) V over the H * W positions, dropout p on the probabilities keyed by `seed`.  Saves q, k, v and
-    one log-sum-exp per (b, h, i); nothing of size L^2 exists in either pass."""
+    one log-sum-exp per (b, h, i); nothing of size L^2 exists in either pass.  bf16=True is the permission VQ2_ALLOW_BF16
+    (include/vq2.h, vq2_causal_attn_fwd_ex): where attn_bf16_eligible holds the four matrix products take operands rounded
+    to bfloat16 and accumulate in fp32, every tensor stays fp32; the backward runs the precision of its forward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, n_head, p, seed):
+    def forward(ctx, q, k, v, n_head, p, seed, bf16=False):
         q, k, v = _attn_operand(q, "q"), _attn_operand(k, "k"), _attn_operand(v, "v")
         b, hh, w, c = q.shape
         if k.shape != q.shape or v.shape != q.shape:
@@ -1067,9 +1077,10 @@ class CausalAttnFn(Function):
         o = torch.empty((b, hh, w, c), device=q.device, dtype=torch.float32)
         lse = torch.empty((b, n_head, l), device=q.device, dtype=torch.float32)
         d = _attn_desc(b, l, n_head, dh, q, k, v, o, p, seed)
-        check(lib.vq2_causal_attn_fwd(C.byref(d), _p(q), _p(k), _p(v), _p(o), _p(lse), _stream()), "causal_attn_fwd")
+        flags = VQ2_ALLOW_BF16 if bf16 else 0
+        check(lib.vq2_causal_attn_fwd_ex(C.byref(d), flags, _p(q), _p(k), _p(v), _p(o), _p(lse), _stream()), "causal_attn_fwd")
         ctx.save_for_backward(q, k, v, lse)   # the backward kernels recompute P and need neither o nor anything of size L^2
-        ctx.n_head, ctx.p, ctx.seed = n_head, p, seed
+        ctx.n_head, ctx.p, ctx.seed, ctx.flags = n_head, p, seed, flags
         return o
 
     @staticmethod
@@ -1081,9 +1092,9 @@ class CausalAttnFn(Function):
         dq, dk, dv = (torch.empty((b, hh, w, c), device=q.device, dtype=torch.float32) for _ in range(3))
         delta = torch.empty_like(lse)
         d = _attn_desc(b, l, ctx.n_head, c // ctx.n_head, q, k, v, dq, ctx.p, ctx.seed)
-        check(lib.vq2_causal_attn_bwd(C.byref(d), _p(q), _p(k), _p(v), _p(lse), _p(do), ld_of(do), _p(dq), c, _p(dk), c,
-                                      _p(dv), c, _p(delta), _stream()), "causal_attn_bwd")
-        return dq, dk, dv, None, None, None
+        check(lib.vq2_causal_attn_bwd_ex(C.byref(d), ctx.flags, _p(q), _p(k), _p(v), _p(lse), _p(do), ld_of(do), _p(dq), c,
+                                         _p(dk), c, _p(dv), c, _p(delta), _stream()), "causal_attn_bwd")
+        return dq, dk, dv, None, None, None, None
 
 
 def causal_attn_keep_mask(b, n_head, l, p, seed, device):

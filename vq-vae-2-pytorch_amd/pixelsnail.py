@@ -43,7 +43,10 @@ class CausalAttention(nn.Module):
     """CausalAttention(query_channel, key_channel, channel, n_head=8, dropout=0.1) of the reference: position i of the
     H * W raster attends to positions j < i.  forward(query [B,Cq,H,W], key [B,Ck,H,W]) -> [B,channel,H,W] (a
     channels-last view, as the reference returns).  Masked scores are excluded where the reference fills in -1e4: equal
-    to the last bit of every exponential while all unmasked scores of a row are above about -9,896."""
+    to the last bit of every exponential while all unmasked scores of a row are above about -9,896.
+    `bf16` (a plain attribute, default False, no parameter or buffer; set_attention_precision sets it) is the permission
+    of ops.CausalAttnFn: bf16 operands in the attention core where dim_head is a multiple of 16.  The three projections
+    stay fp32, and so does PriorSampler's attention (vq2_causal_attn_fwd_rows), whatever this says."""
 
     def __init__(self, query_channel, key_channel, channel, n_head=8, dropout=0.1):
         super().__init__()
@@ -53,12 +56,13 @@ class CausalAttention(nn.Module):
         self.n_head = n_head
         self.channel = channel
         self.p = float(dropout)
+        self.bf16 = False
         self.query = _WNLinear(query_channel, channel)
         self.key = _WNLinear(key_channel, channel)
         self.value = _WNLinear(key_channel, channel)
 
     def extra_repr(self):
-        return f"channel={self.channel}, n_head={self.n_head}, dropout={self.p}"
+        return f"channel={self.channel}, n_head={self.n_head}, dropout={self.p}" + (", bf16" if self.bf16 else "")
 
     def forward(self, query, key):
         ops._require_cuda(query, "query")
@@ -70,7 +74,7 @@ class CausalAttention(nn.Module):
         p = self.p if self.training else 0.0
         # one integer per call from torch's default CPU generator: torch.manual_seed makes a run repeatable
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
-        o = ops.CausalAttnFn.apply(q, k, v, self.n_head, p, seed)
+        o = ops.CausalAttnFn.apply(q, k, v, self.n_head, p, seed, self.bf16)
         return ops.from_nhwc(o, self.channel)
 
     def nhwc(self, qx, kx):
@@ -80,7 +84,7 @@ class CausalAttention(nn.Module):
         q, k, v = self.query.nhwc(qx), self.key.nhwc(kx1), self.value.nhwc(kx2)
         p = self.p if self.training else 0.0
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
-        return ops.CausalAttnFn.apply(q, k, v, self.n_head, p, seed)
+        return ops.CausalAttnFn.apply(q, k, v, self.n_head, p, seed, self.bf16)
 
 
 # ----------------------------------------------------------------------------- weight-normed convs and the gated block
@@ -525,3 +529,26 @@ def conv_precision(module):
     the bf16 permission, else 'fp32'."""
     specs = [m.spec for m in module.modules() if isinstance(m, WNConv2d)]
     return "bf16_wgrad" if any(s.bf16_wgrad for s in specs) else "bf16" if any(s.bf16 for s in specs) else "fp32"
+
+
+# ----------------------------------------------------------------------------- attention precision (--precision bf16_attn)
+def set_attention_precision(module, precision):
+    """Give every CausalAttention under `module` the attention precision 'bf16' or 'fp32' (its `bf16` attribute); returns
+    (eligible_layers, total_layers).  'bf16' is a permission: where ops.attn_bf16_eligible holds (dim_head 16, 32, 48 or 64)
+    the core's four matrix products round their operands to bfloat16 (nearest even) and accumulate in fp32; softmax, the
+    three projections, every tensor in memory and every other geometry stay fp32.  Parameters, buffers and state_dict are
+    untouched.  PriorSampler's attention is fp32 whatever this says."""
+    if precision not in ("bf16", "fp32"):
+        raise ValueError(f"set_attention_precision: precision must be 'bf16' or 'fp32', got {precision!r}")
+    eligible = total = 0
+    for m in module.modules():
+        if isinstance(m, CausalAttention):
+            m.bf16 = precision == "bf16"
+            total += 1
+            eligible += ops.attn_bf16_eligible(m.channel, m.n_head)
+    return eligible, total
+
+
+def attention_precision(module):
+    """'bf16' if any CausalAttention under `module` carries the bf16 permission, else 'fp32'."""
+    return "bf16" if any(m.bf16 for m in module.modules() if isinstance(m, CausalAttention)) else "fp32"

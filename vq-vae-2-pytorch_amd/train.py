@@ -622,12 +622,16 @@ class Stage2Trainer(_ArenaTrainer):
         self._finish_construction()
 
     def set_precision(self, precision):
-        """The conv precision of the run, 'bf16', 'bf16_wgrad' or 'fp32': pixelsnail.set_conv_precision on the model (bf16
-        operands in the eligible conv forwards and data gradients, under 'bf16_wgrad' in the eligible weight gradients too;
-        parameters and optimizer state stay fp32), remembered for the checkpoint.  Returns (eligible_layers, total_layers).  A trainer that was never told keeps the model's convs
-        as they are and saves no "precision"."""
-        from .pixelsnail import set_conv_precision
-        counts = set_conv_precision(self.model, precision)      # (refuses anything else)
+        """The precision of the run, 'bf16', 'bf16_wgrad', 'bf16_attn' or 'fp32': pixelsnail.set_conv_precision on the model
+        (bf16 operands in the eligible conv forwards and data gradients, under 'bf16_wgrad' in the eligible weight gradients
+        too; parameters and optimizer state stay fp32), remembered for the checkpoint.  'bf16_attn' is 'bf16_wgrad' plus
+        pixelsnail.set_attention_precision(model, 'bf16'): bf16 operands in the eligible attention cores as well; the other
+        three levels set the attention back to fp32.  Returns the convs' (eligible_layers, total_layers).  A trainer that was
+        never told keeps the model's convs and attention as they are and saves no "precision"."""
+        from .pixelsnail import set_conv_precision, set_attention_precision
+        attn = precision == "bf16_attn"
+        counts = set_conv_precision(self.model, "bf16_wgrad" if attn else precision)      # (refuses anything else)
+        set_attention_precision(self.model, "bf16" if attn else "fp32")
         self.precision = precision
         return counts
 
@@ -639,7 +643,7 @@ class Stage2Trainer(_ArenaTrainer):
         return sd
 
     def load_state_dict(self, sd):
-        """_ArenaTrainer.load_state_dict(); a full checkpoint whose conv precision (absent = 'fp32') differs from this
+        """_ArenaTrainer.load_state_dict(); a full checkpoint whose precision (absent = 'fp32') differs from this
         trainer's (None = 'fp32') is refused before anything changes: the steps that follow would not be the run's."""
         if split_checkpoint(sd)[1]:
             mine, theirs = self.precision or "fp32", sd.get("precision") or "fp32"
