@@ -8,7 +8,8 @@ the mean predictive entropy, and the entropy of the codes' own histogram (what t
 --ckpt is a pixelsnail_<hier>_<NNN>.pt as examples/train_pixelsnail.py (or the reference) saves it; the model is rebuilt
 from the checkpoint's 'args'.  CODES is what examples/extract_code.py wrote.  With one process per GPU every rank scores
 the rows rank, rank + world, ... and PriorEvaluator.result() sums over the group; the primary rank prints one line.
---dump_map FILE.npy saves the mean nll per position as a float64 [H,W] array."""
+--dump_map FILE.npy saves the mean nll per position as a float64 [H,W] array.  A class-conditional checkpoint (trained with
+--n_label) is recognised by its args: every row is scored under the label of its directory in the checkpoint's class_names."""
 import argparse
 import os
 import sys
@@ -48,8 +49,13 @@ def main(argv=None):
     dataset = vqvae2_amd.codes.CodeDataset(args.path)
     share = Subset(dataset, range(rank, len(dataset), max(world, 1)))
     evaluator = vqvae2_amd.PriorEvaluator(model, args.hier, top_k=args.top_k)
-    for top, bottom, _ in DataLoader(share, batch_size=args.batch, shuffle=False, num_workers=0):
-        evaluator.update(top.to(device), bottom.to(device) if args.hier == 'bottom' else None)
+    class_names = None
+    if model.n_label > 0:
+        saved = torch.load(args.ckpt, map_location='cpu', weights_only=False)['args']
+        class_names = saved['class_names'] if isinstance(saved, dict) else saved.class_names
+    for top, bottom, names in DataLoader(share, batch_size=args.batch, shuffle=False, num_workers=0):
+        label = vqvae2_amd.codes.labels_of(names, class_names).to(device) if class_names is not None else None
+        evaluator.update_labelled(label, top.to(device), bottom.to(device) if args.hier == 'bottom' else None)
     r = evaluator.result()
     if dist_fn.is_primary():
         print(vqvae2_amd.PriorEvaluator.summary(r))

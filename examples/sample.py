@@ -18,6 +18,10 @@ of most likely codes that holds FLOAT of the probability (0 and 1.0: off).
 --stepping row (the default) recomputes a whole row per drawn code; --stepping pixel computes the drawn column only
 (PriorSampler's `stepping`).
 
+--label K draws class K from class-conditional priors (checkpoints of examples/train_pixelsnail.py --n_label N, which carry
+n_label and the sorted class names in their args): both priors get the same label for every image.  Such priors need it;
+priors trained without labels refuse it.
+
 Completing images: --from_images FILE.npy --keep_rows R.  FILE.npy holds uint8 [B, H, W, 3]; the images are normalised to
 [-1, 1], encoded with the VQ-VAE, and the first R rows of their top codes and 2 R rows of their bottom codes are kept; the priors
 draw the rest.  The batch size is that of the file."""
@@ -47,6 +51,7 @@ def parse_args(argv=None):
     parser.add_argument('--stepping', choices=['row', 'pixel'], default='row')
     parser.add_argument('--from_images', type=str, metavar='FILE.npy')
     parser.add_argument('--keep_rows', type=int, default=0)
+    parser.add_argument('--label', type=int, default=None, metavar='K')
     return parser.parse_args(argv)
 
 
@@ -79,6 +84,8 @@ def draw_codes(args, model_vqvae, model_top, model_bottom, device):
         batch = id_t.shape[0]
         top_prefix, bottom_prefix = id_t[:, :args.keep_rows].contiguous(), id_b[:, :2 * args.keep_rows].contiguous()
     kw = dict(top_k=args.top_k, top_p=args.top_p, stepping=args.stepping)
+    if args.label is not None:
+        kw['label'] = args.label
     top_sample = vqvae2_amd.sample_model(model_top, device, batch, top_size, args.temp, prefix=top_prefix, **kw)
     bottom_sample = vqvae2_amd.sample_model(model_bottom, device, batch, bottom_size, args.temp, condition=top_sample,
                                             prefix=bottom_prefix, **kw)

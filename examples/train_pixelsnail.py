@@ -20,7 +20,10 @@ dropout seed drawn, the training run itself unchanged) and the primary rank prin
 --clip_grad_norm X clips the global gradient norm to X on the device (the printed line gains gnorm:, the norm before
 clipping; a step whose norm is not finite is skipped and counted, the count is printed at the end).  --ema_decay D keeps
 Polyak-averaged weights: every save also writes pixelsnail_<hier>_<NNN>_ema.pt, the same file with the averaged weights
-(sample.py and eval_pixelsnail.py load it like any checkpoint), and the held-out line is printed for both sets of weights."""
+(sample.py and eval_pixelsnail.py load it like any checkpoint), and the held-out line is printed for both sets of weights.
+--n_label N (0, the default: off) trains a class-conditional prior: the label of a row is the directory part of its stored
+file name (class_dir/name.png), the class names are sorted as ImageFolder numbers them (at most N of them) and written into
+the checkpoint's args as class_names; the held-out codes use the same list, a class it does not hold gets label -1."""
 import argparse
 import os
 import sys
@@ -61,6 +64,7 @@ def parse_args(argv=None):
     parser.add_argument('--eval_every', type=int, default=0)
     parser.add_argument('--clip_grad_norm', type=float, default=None)
     parser.add_argument('--ema_decay', type=float, default=None)
+    parser.add_argument('--n_label', type=int, default=0)
     parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16', 'bf16_wgrad', 'bf16_attn'],
                         help='fp32 (default), or bf16: the eligible conv forwards and data gradients multiply bf16-rounded operands and accumulate in fp32; weight gradients, weights, optimizer state and every stored tensor stay fp32 (no loss scaling); the counterpart of --amp O1 of the reference; bf16_wgrad: as bf16, and the eligible weight gradients (input and output channels both multiples of 16) multiply bf16-rounded x and dy as well, bias gradients stay fp32 sums; bf16_attn: as bf16_wgrad, and the attention cores with heads of 16, 32, 48 or 64 channels multiply bf16-rounded q, k, v, probabilities and gradients as well (softmax and the three projections stay fp32)')
     return parser.parse_args(argv)
@@ -71,10 +75,12 @@ def build_model(args):
     h, w = args.size
     if args.hier == 'top':
         return vqvae2_amd.PixelSNAIL([h, w], args.n_class, args.channel, args.kernel_size, args.n_block, args.n_res_block,
-                                     args.n_res_channel, dropout=args.dropout, n_out_res_block=args.n_out_res_block)
+                                     args.n_res_channel, dropout=args.dropout, n_out_res_block=args.n_out_res_block,
+                                     n_label=getattr(args, 'n_label', 0))
     return vqvae2_amd.PixelSNAIL([2 * h, 2 * w], args.n_class, args.channel, args.kernel_size, args.n_block, args.n_res_block,
                                  args.n_res_channel, attention=False, dropout=args.dropout,
-                                 n_cond_res_block=args.n_cond_res_block, cond_res_channel=args.n_res_channel)
+                                 n_cond_res_block=args.n_cond_res_block, cond_res_channel=args.n_res_channel,
+                                 n_label=getattr(args, 'n_label', 0))
 
 
 def main(argv=None):
@@ -108,6 +114,20 @@ def main(argv=None):
     if args.ckpt is not None:
         ckpt = torch.load(args.ckpt, weights_only=False)
         args = ckpt['args']
+    n_label = getattr(args, 'n_label', 0)
+    if n_label > 0:
+        from vqvae2_amd.codes import class_names, labels_of
+        if not getattr(args, 'class_names', None):
+            args.class_names = class_names(dataset)
+        if len(args.class_names) > n_label:
+            raise SystemExit(f"--n_label {n_label}: the codes hold {len(args.class_names)} classes")
+
+    def labels(filenames):
+        return labels_of(filenames, args.class_names).to(device) if n_label > 0 else None
+
+    def labelled(batches):      # (top, bottom, filename) -> (top, bottom, label) for Stage2Trainer.evaluate
+        return ((top, bottom, labels_of(names, args.class_names)) for top, bottom, names in batches) if n_label > 0 else batches
+
     model = build_model(args)
     if 'model' in ckpt:
         model.load_state_dict(ckpt['model'])
@@ -126,19 +146,19 @@ def main(argv=None):
     for i in range(first_epoch, args.epoch):
         if distributed:
             sampler.set_epoch(i)
-        for top, bottom, _ in loader:
-            r = trainer.step(top.to(device), bottom.to(device) if args.hier == 'bottom' else None)
+        for top, bottom, names in loader:
+            r = trainer.step(top.to(device), bottom.to(device) if args.hier == 'bottom' else None, labels(names))
             steps += 1
             if primary:
                 gnorm = f"; gnorm: {r['grad_norm'].item():.5f}" if 'grad_norm' in r else ''
                 print(f"epoch: {i + 1}; loss: {r['loss'].item():.5f}; acc: {r['accuracy'].item():.5f}; lr: {r['lr']:.5f}{gnorm}")
             if val_loader is not None and steps % eval_every == 0:
-                held = trainer.evaluate(val_loader)
+                held = trainer.evaluate(labelled(val_loader))
                 if primary:
                     print(f"step: {steps}; held-out {vqvae2_amd.PriorEvaluator.summary(held)}")
                 if ema_decay is not None:
                     with trainer.averaged_weights():
-                        held = trainer.evaluate(val_loader)
+                        held = trainer.evaluate(labelled(val_loader))
                     if primary:
                         print(f"step: {steps}; held-out (averaged weights) {vqvae2_amd.PriorEvaluator.summary(held)}")
             if args.max_steps and steps >= args.max_steps:

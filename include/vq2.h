@@ -66,11 +66,13 @@ typedef void *vq2_stream_t;
  * revision 19: additions only -- the dead-code restart of Quantize: vq2_vq_restart_candidates and vq2_vq_ema_update_restart;
  * revision 20: additions only -- pixel-incremental sampling: vq2_conv_fwd_col with its workspace query;
  * revision 21: additions only -- bf16-operand causal attention: vq2_causal_attn_fwd_ex / vq2_causal_attn_bwd_ex (the flags
- * argument, VQ2_ALLOW_BF16) and vq2_causal_attn_bf16_eligible.
+ * argument, VQ2_ALLOW_BF16) and vq2_causal_attn_bf16_eligible;
+ * revision 22: additions only -- the class label in the gated blocks: vq2_glu_res_label_fwd, vq2_glu_res_label_bwd and
+ * vq2_label_embed_grad with its workspace query.
  * vq2_version()
  * returns the revision the LIBRARY was built from: a host must refuse to run when the two differ (a mismatched
  * workspace size would let a kernel write past the caller's buffer). */
-#define VQ2_API_VERSION 21
+#define VQ2_API_VERSION 22
 
 int vq2_version(void);
 const char *vq2_last_error(void);
@@ -627,6 +629,32 @@ int vq2_glu_res_fwd(const float *t, int32_t ldt, const float *res, int32_t ldres
                     int32_t Ch, vq2_stream_t stream);
 int vq2_glu_res_bwd(const float *dout, int32_t lddo, const float *t, int32_t ldt, float *dt, int32_t lddt, int64_t pixels,
                     int32_t Ch, vq2_stream_t stream);
+
+/* ------------------------------------------------------------------ the class label in the gate (revision 22)
+ * A class-conditional GatedResBlock adds one row of a table E [n_label, 2 * Ch] (fp32, rows lde >= 2 * Ch floats apart) to
+ * the gate's operand: [a | b] = t + E[label[image]], out = a * sigmoid(b) + res.  label is int64 [images]; pixel p belongs to
+ * image p / pixels_per_image, and pixels must be images * pixels_per_image (else VQ2_ERR_INVALID).  A label outside
+ * [0, n_label) adds nothing and receives no gradient: the range is checked before an address is formed from it.  With
+ * Ch % 4 == 0 the table is read 16 bytes at a time (lde % 4 == 0, 16-byte aligned), else dword by dword.
+ * vq2_glu_res_label_fwd: vq2_glu_res_fwd with the row added to t in registers; t in memory stays the conv output.  The same
+ *               layout contract: any Ch >= 1, the unaligned second half when Ch % 4 != 0, pad lanes of out written 0.
+ * vq2_glu_res_label_bwd: vq2_glu_res_bwd's formulas with the row added to a and b before the sigmoid; dt as there (it is the
+ *               gradient of t and, summed over an image's pixels, of that image's row).
+ * vq2_label_embed_grad: dE[l] = sum over the images b with label[b] == l, b ascending, of (sum over the pixels of image b of
+ *               dt), dt [images * pixels_per_image, C2 real channels] with pixel stride lddt, dE dense [n_label, C2]; the rows
+ *               of labels no image has are written 0.  Two launches: per-image column sums of runs of pixels into ws (fixed
+ *               split by shape alone, as vq2_colsum), then one pass per label row.  Fixed order, no atomics: two calls give
+ *               the same bits.  images <= 65,536, C2 <= 8,192, n_label <= 2^24; ws 16-byte aligned, at least
+ *               vq2_label_embed_grad_workspace_bytes (0 for a shape that is refused). */
+int vq2_glu_res_label_fwd(const float *t, int32_t ldt, const float *res, int32_t ldres, const float *embed, int32_t lde,
+                          const int64_t *label, int64_t images, int64_t pixels_per_image, float *out, int32_t ldo,
+                          int64_t pixels, int32_t Ch, int32_t n_label, vq2_stream_t stream);
+int vq2_glu_res_label_bwd(const float *dout, int32_t lddo, const float *t, int32_t ldt, const float *embed, int32_t lde,
+                          const int64_t *label, int64_t images, int64_t pixels_per_image, float *dt, int32_t lddt,
+                          int64_t pixels, int32_t Ch, int32_t n_label, vq2_stream_t stream);
+size_t vq2_label_embed_grad_workspace_bytes(int64_t images, int64_t pixels_per_image, int32_t C2);
+int vq2_label_embed_grad(const float *dt, int32_t lddt, const int64_t *label, int64_t images, int64_t pixels_per_image,
+                         int32_t C2, int32_t n_label, float *dE, void *ws, size_t ws_bytes, vq2_stream_t stream);
 
 /* ------------------------------------------------------------------ the two ends of PixelSNAIL (pixelsnail.py:397-431)
  * One-hot convolution (pixelsnail.py:401-406, :416-421): y = shift(conv(one_hot(idx), w) + bias) [+ acc] without a one-hot

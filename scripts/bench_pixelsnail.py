@@ -20,7 +20,12 @@ profiler run), anything on more than one GPU.
 --amp O1: instead, per model, the arena trainers with bf16 conv operands (Stage2Trainer.set_precision('bf16'),
 'bf16_wgrad' with bf16 weight gradients as well, and 'bf16_attn' with bf16-operand attention cores on top) against the
 arena trainer in fp32, from the same weights, alternating in the same way; the first losses must agree to 1e-2 relative
-(they cannot be bit-equal).  Default output profiles/pixelsnail_bf16.json."""
+(they cannot be bit-equal).  Default output profiles/pixelsnail_bf16.json.
+
+--n_label N: instead, per model, the arena trainer of the class-conditional prior (PixelSNAIL(..., n_label=N), random labels
+from the seed, the other weights shared) against the arena trainer of the unlabelled one, alternating in the same way; min,
+max and median of the repeats.  Both first losses are recorded (the tables start at normal(0, 0.05): a small change of the
+model, not none).  Default output profiles/label_cond.json."""
 import argparse
 import collections
 import gc
@@ -205,6 +210,54 @@ def bench_amp(amd, spec, repeats, inner):
     return row
 
 
+def bench_label(amd, spec, n_label, repeats, inner):
+    """One model: the unlabelled arena trainer and the class-conditional one with n_label classes, alternated."""
+    dev = torch.device("cuda:0")
+    h, w = spec["shape"]
+    gen = torch.Generator().manual_seed(1)
+    n_class = spec["args"][0]
+    codes = torch.randint(0, n_class, (spec["batch"], h, w), generator=gen).to(dev)
+    top = torch.randint(0, n_class, (spec["batch"], h // 2, w // 2), generator=gen).to(dev)
+    label = torch.randint(0, n_label, (spec["batch"],), generator=gen).to(dev)
+    step_args = (codes,) if spec["hier"] == "top" else (top, codes)
+    torch.manual_seed(0)
+    state = amd.PixelSNAIL(spec["shape"], *spec["args"], dropout=0.1, **spec["kw"]).state_dict()
+    row = {"name": spec["name"], "shape": spec["shape"], "batch": spec["batch"], "args": spec["args"], "kw": spec["kw"],
+           "n_label": n_label}
+    fns, first = {}, {}
+    for tag, n in (("unlabelled", 0), ("labelled", n_label)):
+        torch.manual_seed(3)
+        m = amd.PixelSNAIL(spec["shape"], *spec["args"], dropout=0.1, n_label=n, **spec["kw"])
+        missing = m.load_state_dict(state, strict=False)
+        assert not missing.unexpected_keys and all(k.endswith("label_embed") for k in missing.missing_keys)
+        row[tag + "_parameters"] = sum(p.numel() for p in m.parameters())
+        tr = amd.Stage2Trainer(m.to(dev).train(), spec["hier"], lr=3e-4, sched="cycle", n_iter=1000)
+        kw = {"label": label} if n else {}
+        torch.manual_seed(7)
+        first[tag] = float(tr.step(*step_args, **kw)["loss"])
+        tr.step(*step_args, **kw)
+        torch.cuda.synchronize()
+        with CallCounter(amd) as cc:
+            tr.step(*step_args, **kw)
+        torch.cuda.synchronize()
+        row[tag + "_library_calls_per_step"] = sum(cc.counts.values())
+        row[tag + "_label_calls"] = {k: v for k, v in sorted(cc.counts.items()) if "label" in k or "glu_res" in k}
+        fns[tag] = (lambda t=tr, kw=kw: t.step(*step_args, **kw))
+    row["first_loss"] = first
+    ms = {p: [] for p in fns}
+    for _ in range(repeats + 1):
+        for p, fn in fns.items():
+            ms[p].append(time_ms(fn, inner))
+    for p in ms:
+        v = ms[p][1:]
+        row[p + "_ms"], row[p + "_min_ms"], row[p + "_max_ms"], row[p + "_median_ms"] = v, min(v), max(v), statistics.median(v)
+    row["labelled_over_unlabelled"] = row["labelled_median_ms"] / row["unlabelled_median_ms"]
+    print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()
+                      if k in ("name", "batch", "n_label", "unlabelled_min_ms", "unlabelled_max_ms", "labelled_min_ms",
+                               "labelled_max_ms", "labelled_over_unlabelled", "labelled_label_calls", "first_loss")}), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/pixelsnail.json, pixelsnail_bf16.json with --amp O1")
@@ -212,19 +265,31 @@ def main():
                     help="O1: time the arena trainer with bf16 conv operands against the fp32 one (not arena against per-layer)")
     ap.add_argument("--repeats", type=int, default=4, help="timed repeats per path (one more is run first and discarded)")
     ap.add_argument("--inner", type=int, default=3, help="steps per timed window")
+    ap.add_argument("--n_label", type=int, default=0,
+                    help="N > 0: time the class-conditional arena trainer (n_label=N) against the unlabelled one")
     ap.add_argument("--tiny", action="store_true", help="toy models: a rehearsal of the script, not a measurement")
     args = ap.parse_args()
+    if args.n_label > 0 and args.amp == "O1":
+        raise SystemExit("--n_label and --amp O1 are separate measurements")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "pixelsnail_bf16.json" if args.amp == "O1" else "pixelsnail.json")
+        args.out = os.path.join(ROOT, "profiles", "label_cond.json" if args.n_label > 0 else
+                                "pixelsnail_bf16.json" if args.amp == "O1" else "pixelsnail.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_pixelsnail.py needs the MI355X")
     import vqvae2_amd
+
+    def bench(amd, spec, repeats, inner):
+        if args.n_label > 0:
+            return bench_label(amd, spec, args.n_label, repeats, inner)
+        return (bench_amp if args.amp == "O1" else bench_model)(amd, spec, repeats, inner)
+
     results = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "inner": args.inner, "tiny": args.tiny,
                "not_measured": ["kernel times (no profiler run)", "more than one GPU"],
-               "models": [(bench_amp if args.amp == "O1" else bench_model)(vqvae2_amd, spec, args.repeats, args.inner)
-                          for spec in (TINY if args.tiny else MODELS)]}
+               "models": [bench(vqvae2_amd, spec, args.repeats, args.inner) for spec in (TINY if args.tiny else MODELS)]}
     if args.amp == "O1":
         results["amp"] = "O1"
+    if args.n_label > 0:
+        results["n_label"] = args.n_label
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(results, f, indent=1)

@@ -16,6 +16,6 @@ from . import codes  # noqa: F401
 from .optim import FusedAdam, CycleScheduler  # noqa: F401
 from .train import Stage1Trainer, Stage2Trainer, stage1_loss  # noqa: F401
 from .data import ImageNormalizer, ImageDenormalizer, HostBatchPrefetcher, grid_layout, save_u8_image  # noqa: F401
-from .evaluate import Evaluator, PriorEvaluator, score_codes, perplexity_from_counts, psnr_from_mse_u8  # noqa: F401
+from .evaluate import Evaluator, PriorEvaluator, score_codes, score_codes_labelled, perplexity_from_counts, psnr_from_mse_u8  # noqa: F401
 from . import sample  # noqa: F401
 from .sample import PriorSampler, sample_model, load_model  # noqa: F401

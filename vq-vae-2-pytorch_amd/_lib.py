@@ -139,6 +139,10 @@ def _load():
         "vq2_dropout_keep_mask": (C.c_int, [P, I64, I32, F, U64, P]),
         "vq2_glu_res_fwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
         "vq2_glu_res_bwd": (C.c_int, [P, I32, P, I32, P, I32, I64, I32, P]),
+        "vq2_glu_res_label_fwd": (C.c_int, [P, I32, P, I32, P, I32, P, I64, I64, P, I32, I64, I32, I32, P]),
+        "vq2_glu_res_label_bwd": (C.c_int, [P, I32, P, I32, P, I32, P, I64, I64, P, I32, I64, I32, I32, P]),
+        "vq2_label_embed_grad_workspace_bytes": (SZ, [I64, I64, I32]),
+        "vq2_label_embed_grad": (C.c_int, [P, I32, P, I64, I64, I32, I32, P, P, SZ, P]),
         "vq2_onehot_pack_weight": (C.c_int, [P, P, I32, I32, I32, I32, P]),
         "vq2_onehot_conv_fwd": (C.c_int, [C.POINTER(OneHotDesc), P, P, P, P, I32, P, P]),
         "vq2_onehot_conv_wgrad_workspace_bytes": (SZ, [C.POINTER(OneHotDesc)]),

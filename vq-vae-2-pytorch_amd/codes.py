@@ -175,3 +175,21 @@ class CodeDataset(torch.utils.data.Dataset):
     def __getitem__(self, index):
         top, bottom, filename = load_code_row(self.store.get(str(index).encode("utf-8")))
         return torch.from_numpy(top), torch.from_numpy(bottom), filename
+
+
+# ----------------------------------------------------------------------------- class labels from the stored file names
+def class_name(filename):
+    """The directory part of a row's relative file name ('class_dir/name.png' -> 'class_dir'; '' without one)."""
+    name = str(filename).replace("\\", "/")
+    return name.rsplit("/", 1)[0] if "/" in name else ""
+
+
+def class_names(dataset):
+    """The sorted class names of a CodeDataset (one pass over its rows): index = label, as ImageFolder numbers them."""
+    return sorted({class_name(dataset[i][2]) for i in range(len(dataset))})
+
+
+def labels_of(filenames, names):
+    """int64 [len(filenames)] (CPU): each file's index in `names`, -1 (a label that adds nothing) for a class not in it."""
+    index = {n: i for i, n in enumerate(names)}
+    return torch.tensor([index.get(class_name(f), -1) for f in filenames], dtype=torch.int64)

@@ -164,13 +164,16 @@ class Evaluator:
         return out
 
 
-def _prior_forward(model, codes, condition):
+def _prior_forward(model, codes, condition, label=None):
     """The logits of an eval-mode forward as the NHWC tensor the row kernels read in place, and the targets' device copy.
     Eval mode draws no dropout seed (p == 0 at every site of pixelsnail.py) and no_grad keeps every gradient slot as it
     is; outside a trainer's step each layer forms its effective weight from the parameters as they are now."""
     ops._require_codes(codes, "codes")
     with eval_mode(model), torch.no_grad():
-        out, _ = model(codes) if condition is None else model(codes, condition=condition)
+        kw = {} if condition is None else {"condition": condition}
+        if label is not None:       # (a model built with n_label > 0 raises without it, one built without raises with it)
+            kw["label"] = label
+        out, _ = model(codes, **kw)
         return ops.to_nhwc(out)
 
 
@@ -186,6 +189,8 @@ class PriorEvaluator:
                   target), vq2_prior_eval_accumulate (per-position running totals, no atomics) and one vq2_index_hist of
                   the targets.  Nothing is read back.  return_image_nll=True returns the float32 [B] device tensor of each
                   image's summed negative log-likelihood in nats.  Every module's train / eval flag is restored.
+    update_labelled(label, top, bottom=None, return_image_nll=False)
+                  update() for a class-conditional model (PixelSNAIL(..., n_label > 0)): label is int64 [B] on the GPU.
     result()      ONE device-to-host copy -> {"nll" (nats per code), "bits_per_code", "perplexity", "accuracy",
                   "top_k_accuracy", "top_k", "entropy" (mean predictive entropy, nats), "unigram_nll" (the entropy of the
                   target histogram: what the best context-free model reaches, the baseline a prior has to beat), "images",
@@ -227,6 +232,9 @@ class PriorEvaluator:
             self._state.zero_()
 
     def update(self, top, bottom=None, return_image_nll=False):
+        return self.update_labelled(None, top, bottom, return_image_nll)
+
+    def update_labelled(self, label, top, bottom=None, return_image_nll=False):
         if self.hier == "top":
             target, condition = top, None
         else:
@@ -237,7 +245,7 @@ class PriorEvaluator:
             raise RuntimeError("PriorEvaluator.update: codes [B,H,W] expected")
         if self._state is not None and tuple(target.shape[1:]) != self.shape:
             raise ValueError(f"PriorEvaluator: a batch of {tuple(target.shape[1:])} code maps after batches of {self.shape}")
-        x = _prior_forward(self.model, target, condition)
+        x = _prior_forward(self.model, target, condition, label)
         pos_nll, pos_entropy, hit1, hitk, counters, counts, flag = self._buffers(x.device, target.shape[1:])
         nll, entropy, rank = ops.prior_eval_rows(x, target, self.n_class)
         image_nll = ops.prior_eval_accumulate(nll, entropy, rank, target.shape[0], self.top_k, pos_nll, pos_entropy, hit1, hitk,
@@ -307,9 +315,14 @@ def score_codes(model, codes, condition=None):
     of the cross-entropy terms (PriorEvaluator's image nll), from an eval-mode forward under no_grad.  codes int64 [B,H,W];
     condition: the top codes [B,H/2,W/2] for a bottom prior.  A code outside [0, n_class) adds nothing to its image's
     score, as in prior_loss.  Nothing is read back."""
+    return score_codes_labelled(model, codes, None, condition)
+
+
+def score_codes_labelled(model, codes, label, condition=None):
+    """score_codes for a class-conditional model: label is int64 [B] on the GPU (None: score_codes itself)."""
     if codes.dim() != 3:
         raise RuntimeError("score_codes: codes [B,H,W] expected")
-    x = _prior_forward(model, codes, condition)
+    x = _prior_forward(model, codes, condition, label)
     b, length = codes.shape[0], codes.shape[1] * codes.shape[2]
     nll, entropy, rank = ops.prior_eval_rows(x, codes, int(model.n_class))
     state = torch.zeros(4 * length + 2, device=x.device, dtype=torch.int64)

@@ -1379,6 +1379,59 @@ class GluResFn(Function):
         return dt, (dout if ctx.needs_input_grad[1] else None), None
 
 
+def require_labels(label, batch, device):
+    """`label` as the label kernels read it: int64 [batch], contiguous, on `device`."""
+    if not (isinstance(label, torch.Tensor) and label.dtype == torch.int64 and label.device == device and label.dim() == 1
+            and label.shape[0] == batch):
+        raise RuntimeError(f"vqvae2_amd: label must be an int64 tensor [{batch}] on {device} (got "
+                           f"{getattr(label, 'dtype', type(label))} {tuple(getattr(label, 'shape', ()))} on "
+                           f"{getattr(label, 'device', '?')})")
+    return label if label.is_contiguous() else label.contiguous()
+
+
+class GluResLabelFn(Function):
+    """GluResFn with the class label: [a | b] = t + embed[label[image]], out = a * sigmoid(b) + res.  embed is the fp32 table
+    [n_label, 2 * ch], label int64 [N] on the device; a label outside [0, n_label) adds nothing and receives no gradient.
+    Saves t (the conv output, as GluResFn) and label; the backward recomputes the sum and the sigmoid, writes dt
+    (vq2_glu_res_label_bwd) and sums it per image and label row into the table's gradient slot (vq2_label_embed_grad, fixed
+    order)."""
+
+    @staticmethod
+    def forward(ctx, t, res, ch, embed, label):
+        t, res = _rows(t, 2 * ch), _rows(res, ch)
+        n, h, w, _ = t.shape
+        if tuple(res.shape[:3]) != (n, h, w):
+            raise RuntimeError("GluResLabelFn: t and res must cover the same pixels")
+        if embed.dim() != 2 or embed.shape[1] != 2 * ch or embed.dtype != torch.float32 or not embed.is_contiguous():
+            raise RuntimeError(f"GluResLabelFn: a contiguous float32 table [n_label, {2 * ch}] expected")
+        label = require_labels(label, n, t.device)
+        out = torch.empty((n, h, w, ceil4(ch)), device=t.device, dtype=torch.float32)
+        check(lib.vq2_glu_res_label_fwd(_p(t), ld_of(t), _p(res), ld_of(res), _p(embed), 2 * ch, _p(label), n, h * w, _p(out),
+                                        ceil4(ch), n * h * w, ch, embed.shape[0], _stream()), "glu_res_label_fwd")
+        ctx.save_for_backward(t, label)
+        ctx.ch, ctx.embed = ch, embed
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        t, label = ctx.saved_tensors
+        embed, ch = ctx.embed, ctx.ch
+        dout = _rows(dout, ch)
+        n, h, w, cp = t.shape
+        dt = dE = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[3]:
+            dt = torch.empty((n, h, w, cp), device=t.device, dtype=torch.float32)
+            check(lib.vq2_glu_res_label_bwd(_p(dout), ld_of(dout), _p(t), ld_of(t), _p(embed), 2 * ch, _p(label), n, h * w,
+                                            _p(dt), cp, n * h * w, ch, embed.shape[0], _stream()), "glu_res_label_bwd")
+        if ctx.needs_input_grad[3]:
+            dE = _grad_slot(embed)
+            nbytes = lib.vq2_label_embed_grad_workspace_bytes(n, h * w, 2 * ch)
+            ws = torch.empty(max(nbytes // 4, 4), device=t.device, dtype=torch.float32)
+            check(lib.vq2_label_embed_grad(_p(dt), cp, _p(label), n, h * w, 2 * ch, embed.shape[0], _p(dE), _p(ws), nbytes,
+                                           _stream()), "label_embed_grad")
+        return (dt if ctx.needs_input_grad[0] else None), (dout if ctx.needs_input_grad[1] else None), None, dE, None
+
+
 # ----------------------------------------------------------------------------- the two ends of PixelSNAIL (stage-2 prior)
 ONEHOT_MAX_CLASSES = 16384
 

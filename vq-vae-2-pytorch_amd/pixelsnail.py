@@ -227,12 +227,18 @@ class CausalConv2d(nn.Module):
 
 class GatedResBlock(nn.Module):
     """GatedResBlock(in_channel, channel, kernel_size, conv='wnconv2d', activation=nn.ELU, dropout=0.1,
-    auxiliary_channel=0, condition_dim=0) of the reference (pixelsnail.py:122-179):
+    auxiliary_channel=0, condition_dim=0) of the reference (pixelsnail.py:122-179), and n_label=0 as a last argument:
 
         h = conv1(ELU(input)) [+ aux_conv(ELU(aux_input))]       the add is conv1's residual epilogue
         h = dropout(ELU(h))                                       one kernel
         t = conv2(h) [+ condition(condition)]                     again the residual epilogue
         out = t[:, :in_channel] * sigmoid(t[:, in_channel:]) + input       one kernel
+
+    n_label > 0 makes the block class-conditional, the way PixelCNN++ puts a class vector into a gate: the fp32 parameter
+    label_embed [n_label, 2 * in_channel] (normal(0, 0.05)) exists, nhwc() / forward() need `label` (int64 [N] on the device)
+    and the last line reads [a | b] = t + label_embed[label[image]], out = a * sigmoid(b) + input: still one kernel, t in
+    memory stays the conv output.  A label outside [0, n_label) adds nothing and receives no gradient.  n_label == 0: no
+    such parameter, `label` is refused, and every launch is what it is without this argument.
 
     forward takes and returns NCHW-shaped tensors; nhwc() the internal [N,H,W,ceil4(C)] ones, so that blocks chain
     without layout changes.  Kept for the backward: ELU(input) (and ELU(aux_input)), conv1's output, the dropped-out
@@ -240,8 +246,10 @@ class GatedResBlock(nn.Module):
     input."""
 
     def __init__(self, in_channel, channel, kernel_size, conv='wnconv2d', activation=nn.ELU, dropout=0.1,
-                 auxiliary_channel=0, condition_dim=0):
+                 auxiliary_channel=0, condition_dim=0, n_label=0):
         super().__init__()
+        if n_label < 0:
+            raise ValueError(f"vqvae2_amd.GatedResBlock: n_label must be >= 0, got {n_label}")
         if activation is not nn.ELU:
             raise NotImplementedError(f"vqvae2_amd.GatedResBlock: activation must be nn.ELU, got {activation!r}")
         if not 0.0 <= dropout < 1.0:
@@ -270,11 +278,17 @@ class GatedResBlock(nn.Module):
         self.conv2 = conv_module(channel, in_channel * 2, kernel_size)
         if condition_dim > 0:
             self.condition = WNConv2d(condition_dim, in_channel * 2, 1, bias=False)
+        self.n_label = int(n_label)
+        if self.n_label > 0:
+            self.label_embed = nn.Parameter(torch.empty(self.n_label, in_channel * 2).normal_(0.0, 0.05))
 
     def extra_repr(self):
         return f"dropout={self.p}"
 
-    def nhwc(self, x, aux=None, condition=None):
+    def nhwc(self, x, aux=None, condition=None, label=None):
+        if (label is not None) != (self.n_label > 0):
+            raise RuntimeError("GatedResBlock: a block built with n_label > 0 needs `label`" if label is None else
+                               "GatedResBlock: label given to a block built with n_label=0")
         r = None
         if aux is not None:
             if self.auxiliary_channel <= 0:
@@ -293,13 +307,15 @@ class GatedResBlock(nn.Module):
                 raise RuntimeError("GatedResBlock: condition given to a block built with condition_dim=0")
             r = self.condition.nhwc(condition)
         t = self.conv2.nhwc(h, residual=r)
+        if label is not None:
+            return ops.GluResLabelFn.apply(t, skip, self.in_channel, self.label_embed, label)
         return ops.GluResFn.apply(t, skip, self.in_channel)
 
-    def forward(self, input, aux_input=None, condition=None):
+    def forward(self, input, aux_input=None, condition=None, label=None):
         x = ops.to_nhwc(input)
         aux = ops.to_nhwc(aux_input) if aux_input is not None else None
         cond = ops.to_nhwc(condition) if condition is not None else None
-        return ops.from_nhwc(self.nhwc(x, aux, cond), self.in_channel)
+        return ops.from_nhwc(self.nhwc(x, aux, cond, label), self.in_channel)
 
 
 # ----------------------------------------------------------------------------- PixelBlock, CondResNet, PixelSNAIL
@@ -324,12 +340,14 @@ def _repeat_batch(x1, batch):
 
 class PixelBlock(nn.Module):
     """PixelBlock(in_channel, channel, kernel_size, n_res_block, attention=True, dropout=0.1, condition_dim=0) of the
-    reference (pixelsnail.py:237-308): n_res_block 'causal' GatedResBlocks, then either the attention branch (key and query
+    reference (pixelsnail.py:237-308), and n_label=0 as a last argument (the 'causal' blocks take the class label, the
+    attention branch does not): n_res_block 'causal' GatedResBlocks, then either the attention branch (key and query
     blocks over the concatenations with the two coordinate planes, CausalAttention, and a block that takes the attention
     output as its auxiliary input) or a 1x1 WNConv2d over [out, background].  in_channel must be a multiple of 4 (the
     concatenations are slice copies of whole 16-byte groups) and kernel_size odd."""
 
-    def __init__(self, in_channel, channel, kernel_size, n_res_block, attention=True, dropout=0.1, condition_dim=0):
+    def __init__(self, in_channel, channel, kernel_size, n_res_block, attention=True, dropout=0.1, condition_dim=0,
+                 n_label=0):
         super().__init__()
         if in_channel % 4 != 0:
             raise NotImplementedError(f"vqvae2_amd.PixelBlock: in_channel must be a multiple of 4, got {in_channel}")
@@ -340,8 +358,10 @@ class PixelBlock(nn.Module):
             ops.attn_check_geometry(in_channel // 2, 8)
         self.in_channel = in_channel
         self.resblocks = nn.ModuleList([
-            GatedResBlock(in_channel, channel, kernel_size, conv='causal', dropout=dropout, condition_dim=condition_dim)
+            GatedResBlock(in_channel, channel, kernel_size, conv='causal', dropout=dropout, condition_dim=condition_dim,
+                          n_label=n_label)
             for _ in range(n_res_block)])
+        self.n_label = int(n_label)
         self.attention = attention
         if attention:
             self.key_resblock = GatedResBlock(in_channel * 2 + 2, in_channel, 1, dropout=dropout)
@@ -351,14 +371,17 @@ class PixelBlock(nn.Module):
         else:
             self.out = WNConv2d(in_channel + 2, in_channel, 1)
 
-    def nhwc(self, x, background, conditions=None):
+    def nhwc(self, x, background, conditions=None, label=None):
         """x [N,H,W,in_channel], background [N,H,W,4] (two real channels); conditions: None or one NHWC alias of the
-        condition per res block."""
+        condition per res block; label: int64 [N] on the device for a block built with n_label > 0, else None."""
+        if (label is not None) != (self.n_label > 0):
+            raise RuntimeError("PixelBlock: a block built with n_label > 0 needs `label`" if label is None else
+                               "PixelBlock: label given to a block built with n_label=0")
         if self.attention:
             x, x_key = ops.FanOutFn.apply(x)
         out = x
         for i, resblock in enumerate(self.resblocks):
-            out = resblock.nhwc(out, condition=None if conditions is None else conditions[i])
+            out = resblock.nhwc(out, condition=None if conditions is None else conditions[i], label=label)
         if self.attention:
             out_key, out_query, out = _fan(out, 3)
             key = self.key_resblock.nhwc(ops.CatNFn.apply(x_key, out_key, background))
@@ -367,11 +390,11 @@ class PixelBlock(nn.Module):
             return self.out_resblock.nhwc(out, aux=attn_out)
         return self.out.nhwc(ops.CatNFn.apply(out, background))
 
-    def forward(self, input, background, condition=None):
+    def forward(self, input, background, condition=None, label=None):
         cond = None
         if condition is not None:
             cond = _fan(ops.to_nhwc(condition), len(self.resblocks)) if len(self.resblocks) else None
-        return ops.from_nhwc(self.nhwc(ops.to_nhwc(input), ops.to_nhwc(background), cond), self.in_channel)
+        return ops.from_nhwc(self.nhwc(ops.to_nhwc(input), ops.to_nhwc(background), cond, label), self.in_channel)
 
 
 class CondResNet(nn.Module):
@@ -403,9 +426,12 @@ class CondResNet(nn.Module):
 class PixelSNAIL(nn.Module):
     """PixelSNAIL(shape, n_class, channel, kernel_size, n_block, n_res_block, res_channel, attention=True, dropout=0.1,
     n_cond_res_block=0, cond_res_channel=0, cond_res_kernel=3, n_out_res_block=0) of the reference (pixelsnail.py:326-431),
-    with its parameter and buffer names.
+    with its parameter and buffer names, and n_label=0 as a last argument: with n_label > 0 the prior is class-conditional,
+    every 'causal' GatedResBlock of every PixelBlock holds a table blocks.<i>.resblocks.<k>.label_embed [n_label, 2 * channel]
+    and forward needs label, int64 [B] on the device (see GatedResBlock; a label outside [0, n_label) adds nothing).  With
+    n_label == 0 the state_dict keys and every launch are those of the reference's model, and a label is refused.
 
-    forward(input [B,H,W] int64, condition=None [B,H/2,W/2] int64, cache=None) -> (out, cache): out is a channels-last view
+    forward(input [B,H,W] int64, condition=None [B,H/2,W/2] int64, cache=None, label=None) -> (out, cache): out is a channels-last view
     of shape [B,n_class,H,W] (a copy when n_class is no multiple of 4); cache['condition'] is a detached clone of the
     upsampled condition features and is used instead of running cond_resnet when present; an input of fewer rows than
     shape[0] uses the first rows of the coordinate planes and of the condition.  A code outside [0, n_class) contributes
@@ -413,9 +439,14 @@ class PixelSNAIL(nn.Module):
     and with attention a channel whose half the 8-head attention kernels do not take."""
 
     def __init__(self, shape, n_class, channel, kernel_size, n_block, n_res_block, res_channel, attention=True,
-                 dropout=0.1, n_cond_res_block=0, cond_res_channel=0, cond_res_kernel=3, n_out_res_block=0):
+                 dropout=0.1, n_cond_res_block=0, cond_res_channel=0, cond_res_kernel=3, n_out_res_block=0, n_label=0):
         super().__init__()
         height, width = shape
+        if n_label < 0:
+            raise ValueError(f"vqvae2_amd.PixelSNAIL: n_label must be >= 0, got {n_label}")
+        if n_label > 0 and n_res_block < 1:
+            raise ValueError("vqvae2_amd.PixelSNAIL: n_label > 0 needs n_res_block >= 1 (the label enters the 'causal' blocks)")
+        self.n_label = int(n_label)
         if channel % 4 != 0:
             raise NotImplementedError(f"vqvae2_amd.PixelSNAIL: channel must be a multiple of 4, got {channel}")
         if not isinstance(kernel_size, int) or kernel_size % 2 == 0:
@@ -439,7 +470,7 @@ class PixelSNAIL(nn.Module):
         self.register_buffer('background', torch.cat([coord_x, coord_y], 1))
         self.blocks = nn.ModuleList([
             PixelBlock(channel, res_channel, kernel_size, n_res_block, attention=attention, dropout=dropout,
-                       condition_dim=cond_res_channel) for _ in range(n_block)])
+                       condition_dim=cond_res_channel, n_label=n_label) for _ in range(n_block)])
         if n_cond_res_block > 0:
             self.cond_resnet = CondResNet(n_class, cond_res_channel, cond_res_kernel, n_cond_res_block)
         out = [GatedResBlock(channel, res_channel, 1) for _ in range(n_out_res_block)]
@@ -455,12 +486,18 @@ class PixelSNAIL(nn.Module):
             self._bg = (key, _repeat_batch(planes, batch))
         return self._bg[1]
 
-    def forward(self, input, condition=None, cache=None):
+    def forward(self, input, condition=None, cache=None, label=None):
         if cache is None:
             cache = {}
         if input.dim() != 3:
             raise RuntimeError("PixelSNAIL: input [B,H,W] of int64 codes expected")
         batch, height, width = input.shape
+        if label is None and self.n_label > 0:
+            raise RuntimeError(f"PixelSNAIL: a model built with n_label={self.n_label} needs `label` (int64 [B])")
+        if label is not None:
+            if self.n_label <= 0:
+                raise RuntimeError("PixelSNAIL: label given to a model built with n_label=0")
+            label = ops.require_labels(label, batch, input.device)
         if height > self.background.shape[2] or width != self.background.shape[3]:
             raise RuntimeError(f"PixelSNAIL: input of {height} x {width} does not fit shape "
                                f"{tuple(self.background.shape[2:])} (fewer rows are allowed, other widths are not)")
@@ -484,7 +521,7 @@ class PixelSNAIL(nn.Module):
             mine = None
             if conditions is not None:
                 mine, conditions = conditions[:n], conditions[n:]
-            out = block.nhwc(out, background, mine)
+            out = block.nhwc(out, background, mine, label)
         for layer in self.out:
             if isinstance(layer, nn.ELU):
                 out = ops.EluFn.apply(out, self.channel)       # nn.ELU(inplace=True) of the reference

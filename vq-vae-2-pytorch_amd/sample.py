@@ -314,6 +314,11 @@ class _Recorder:
         t = self.buf(name + ".t", conv2.spec.co)
         self.conv(conv2, e2, r, t, name + ".c2")
         out = self.buf(name + ".out", ops.ceil4(block.in_channel))
+        if block.n_label > 0:       # image b's pixels of a step are geo.w consecutive ones: the row's W, or the column's one
+            e = s.label_embed[block]
+            self.add("glu_res_label_fwd", lib.vq2_glu_res_label_fwd, t.ptr(), t.ld, x.ptr(), x.ld, _ptr(e), e.shape[1],
+                     _ptr(self.plan.labels), self.B, self.geo.w, out.ptr(), out.ld, self.geo.pixels, block.in_channel, e.shape[0])
+            return out
         self.add("glu_res_fwd", lib.vq2_glu_res_fwd, t.ptr(), t.ld, x.ptr(), x.ld, out.ptr(), out.ld, self.geo.pixels,
                  block.in_channel)
         return out
@@ -375,6 +380,8 @@ class _Plan:
         self.R = sampler.band_rows
         # band i: code rows i - R + 1 .. i as the input convs see them at row i; -1 above the image
         self.bands = torch.empty((rows, batch, self.R, self.W), device=self.dev, dtype=torch.int64)
+        # the class labels the recorded gates read (a class-conditional model): filled once per call, -1 adds nothing
+        self.labels = torch.full((batch,), -1, device=self.dev, dtype=torch.int64) if m.n_label > 0 else None
         self.cond_rows = None
         if with_condition:
             self.cond_rows = torch.empty((rows, batch, self.W, ops.ceil4(m.cond_res_channel)), device=self.dev, dtype=torch.float32)
@@ -440,8 +447,12 @@ class PriorSampler:
                        position i * W + j, so a prefix taken from sample(seed=s) is completed to that very map.
         return_logp    returns (codes, logp): logp float32 [B, rows, W], the log-probability of each drawn code under the
                        tempered, truncated distribution it was drawn from; 0 at prefix positions.
+        label          for a class-conditional model (PixelSNAIL(..., n_label > 0)), which needs it: an int (every image) or
+                       an int64 [B] tensor on the device.  It is written once per call into the buffer the recorded gates
+                       (vq2_glu_res_label_fwd, pixels_per_image = W in row stepping, 1 in pixel stepping) read; a label
+                       outside [0, n_label) adds nothing.  A model built with n_label=0 refuses it.
         With these at their defaults the calls and their arguments are what they were without them.
-    logits_given(codes, condition=None) -> [B, n_class, H, W]: the same stepping with `codes` written where sample() draws;
+    logits_given(codes, condition=None, label=None) -> [B, n_class, H, W]: the same stepping with `codes` written where sample() draws;
         entry (i, j) is what step (i, j) saw, which by causality is the model's own output for those codes.
     The weights are those of the moment of construction: a model whose parameters changed since is refused until refresh().
     One set of histories and recorded launches is kept, for the last (batch, rows, condition or not, stream): a call with
@@ -475,6 +486,8 @@ class PriorSampler:
         self.width = m.background.shape[3]
         with torch.no_grad():
             self.conv_of = {}
+            self.label_embed = {mod: mod.label_embed.detach().clone().contiguous() for mod in self._gated_blocks()
+                                if mod.n_label > 0}
             for mod in self._gated_blocks():
                 names = ["conv1", "conv2"] + (["aux_conv"] if mod.auxiliary_channel > 0 else []) + \
                         (["condition"] if mod.condition_dim > 0 else [])
@@ -515,7 +528,7 @@ class PriorSampler:
     def _snapshot(self):
         return [(p.data_ptr(), p._version, ops.weight_epoch(p)) for p in self.model.parameters()]
 
-    def _plan_for(self, batch, rows, condition):
+    def _plan_for(self, batch, rows, condition, label=None):
         if self._snapshot() != self._versions:
             raise RuntimeError("vqvae2_amd.PriorSampler: the model's parameters changed since the sampler was built; call refresh()")
         m = self.model
@@ -535,12 +548,20 @@ class PriorSampler:
             with eval_mode(m.cond_resnet):
                 cond = ops.Upsample2Fn.apply(m.cond_resnet.nhwc(condition), m.cond_res_channel)
             plan.to_row_outer(cond, plan.cond_rows)
+        if (label is not None) != (m.n_label > 0):
+            raise RuntimeError(f"PriorSampler: a model built with n_label={m.n_label} needs `label`" if label is None else
+                               "PriorSampler: label given to a model built with n_label=0")
+        if label is not None:
+            if isinstance(label, int):
+                plan.labels.fill_(label)
+            else:
+                plan.labels.copy_(ops.require_labels(label, batch, self.device))
         plan.reset_codes()
         return plan
 
     @torch.no_grad()
     def sample(self, batch, temperature=1.0, condition=None, seed=None, rows=None, *, top_k=0, top_p=1.0, prefix=None,
-               return_logp=False):
+               return_logp=False, label=None):
         rows = self.model.background.shape[2] if rows is None else int(rows)
         if not temperature > 0:
             raise ValueError(f"PriorSampler: temperature must be positive, got {temperature}")
@@ -562,7 +583,7 @@ class PriorSampler:
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         seed = int(seed) & _MASK64
-        plan = self._plan_for(batch, rows, condition)
+        plan = self._plan_for(batch, rows, condition, label)
         b, w, r = plan.B, plan.W, plan.R
         t = float(temperature)
         filtered = top_k > 0 or top_p < 1.0 or return_logp
@@ -594,12 +615,12 @@ class PriorSampler:
         return plan.codes()
 
     @torch.no_grad()
-    def logits_given(self, codes, condition=None):
+    def logits_given(self, codes, condition=None, label=None):
         codes = ops._require_codes(codes, "codes")
         if codes.dim() != 3 or codes.shape[2] != self.width:
             raise RuntimeError("PriorSampler: codes [B, H, W] of int64 expected")
         batch, rows, w = codes.shape
-        plan = self._plan_for(batch, rows, condition)
+        plan = self._plan_for(batch, rows, condition, label)
         ld = ops.ceil4(self.model.n_class)
         out = torch.zeros((batch, rows, w, ld), device=self.device, dtype=torch.float32)
         for i in range(rows):
@@ -617,12 +638,13 @@ class PriorSampler:
 _SAMPLERS = weakref.WeakKeyDictionary()      # model -> {stepping: its PriorSampler, which refers to the model weakly}
 
 
-def sample_model(model, device, batch, size, temperature, condition=None, *, top_k=0, top_p=1.0, prefix=None, stepping='row'):
+def sample_model(model, device, batch, size, temperature, condition=None, *, top_k=0, top_p=1.0, prefix=None, stepping='row',
+                 label=None):
     """The reference's sample_model (sample.py:12-24): int64 codes [batch, size[0], size[1]] on `device`, drawn from `model`
     pixel by pixel in raster order.  One PriorSampler per model and stepping is kept in this module, keyed weakly by the model
     (it goes when the model goes, and the model itself carries nothing: it still pickles and deep-copies), and is rebuilt when
     the model's parameters change.  top_k, top_p and prefix (keyword only, not in the reference) are PriorSampler.sample's;
-    stepping ('row' or 'pixel') is PriorSampler's."""
+    stepping ('row' or 'pixel') is PriorSampler's, and so is label (a class-conditional model's class: an int or int64 [B])."""
     if stepping not in _STEPS:
         raise ValueError(f"sample_model: stepping must be 'row' or 'pixel', got {stepping!r}")
     if tuple(size)[1] != model.background.shape[3]:
@@ -632,7 +654,7 @@ def sample_model(model, device, batch, size, temperature, condition=None, *, top
     sampler = cache.get(stepping)
     if sampler is None or sampler._snapshot() != sampler._versions:
         sampler = cache[stepping] = PriorSampler(model, stepping, _weak=True)
-    return sampler.sample(batch, temperature, condition, rows=int(size[0]), top_k=top_k, top_p=top_p, prefix=prefix)
+    return sampler.sample(batch, temperature, condition, rows=int(size[0]), top_k=top_k, top_p=top_p, prefix=prefix, label=label)
 
 
 def _arg(args, name, default):
@@ -644,7 +666,7 @@ def _arg(args, name, default):
 def load_model(model, checkpoint, device, ckpt_dir='checkpoint', **overrides):
     """The reference's load_model (sample.py:27-68): model is 'vqvae', 'pixelsnail_top' or 'pixelsnail_bottom', `checkpoint`
     a file under `ckpt_dir`.  Constructor arguments come from ckpt['args'] where the checkpoint has them (what
-    examples/train_pixelsnail.py saves, including its extras size / n_class / n_block / kernel_size), then from `overrides`.
+    examples/train_pixelsnail.py saves, including its extras size / n_class / n_block / kernel_size / n_label), then from `overrides`.
     Returns the model on `device` in eval mode."""
     from .vqvae import VQVAE
     ckpt = torch.load(os.path.join(ckpt_dir, checkpoint), map_location='cpu', weights_only=False)
@@ -659,13 +681,15 @@ def load_model(model, checkpoint, device, ckpt_dir='checkpoint', **overrides):
     elif model in ('pixelsnail_top', 'pixelsnail_bottom'):
         h, w = get('size', [32, 32])
         n_class, kernel, n_block = get('n_class', 512), get('kernel_size', 5), get('n_block', 4)
+        n_label = get('n_label', 0) or 0
         if model == 'pixelsnail_top':
             net = PixelSNAIL([h, w], n_class, get('channel', 256), kernel, n_block, get('n_res_block', 4), get('n_res_channel', 256),
-                             dropout=get('dropout', 0.1), n_out_res_block=get('n_out_res_block', 0))
+                             dropout=get('dropout', 0.1), n_out_res_block=get('n_out_res_block', 0), n_label=n_label)
         else:
             net = PixelSNAIL([2 * h, 2 * w], n_class, get('channel', 256), kernel, n_block, get('n_res_block', 4),
                              get('n_res_channel', 256), attention=False, dropout=get('dropout', 0.1),
-                             n_cond_res_block=get('n_cond_res_block', 3), cond_res_channel=get('n_res_channel', 256))
+                             n_cond_res_block=get('n_cond_res_block', 3), cond_res_channel=get('n_res_channel', 256),
+                             n_label=n_label)
     else:
         raise ValueError(f"load_model: model must be 'vqvae', 'pixelsnail_top' or 'pixelsnail_bottom', got {model!r}")
     if isinstance(ckpt, dict) and 'model' in ckpt:

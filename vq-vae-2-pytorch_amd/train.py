@@ -552,7 +552,8 @@ class Stage2Trainer(_ArenaTrainer):
     """The train step of the reference's train_pixelsnail.py:20-57 for one PixelSNAIL: zero_grad, forward, cross-entropy with
     accuracy (ops.prior_loss), backward, scheduler step, Adam step.  `hier` is 'top' (the model sees the top codes) or
     'bottom' (the bottom codes, conditioned on the top ones).  step() returns {'loss', 'accuracy'} as 0-dim device tensors
-    and 'lr'; nothing is copied to the host.
+    and 'lr'; nothing is copied to the host.  step(top, bottom=None, label=None): label is int64 [B] on the device for a
+    class-conditional model (PixelSNAIL(..., n_label > 0)); its label_embed tables are ordinary parameters of the arena.
 
     arena=True (the default): the parameters live in a ParamArena and an ops.WeightNormPlan forms every effective weight
     with one launch per step and differentiates them with one more, straight into the gradient arena; Adam is one launch.
@@ -667,20 +668,21 @@ class Stage2Trainer(_ArenaTrainer):
         return torch.cuda.current_stream().record_event()
 
     # ------------------------------------------------------------------ the step
-    def _forward_loss(self, top, bottom):
+    def _forward_loss(self, top, bottom, label=None):
+        kw = {} if label is None else {"label": label}      # (the model refuses a label it has no tables for, and a missing one)
         if self.hier == "top":
             target = top
-            out, _ = self.model(top)
+            out, _ = self.model(top, **kw)
         else:
             target = bottom
-            out, _ = self.model(bottom, condition=top)
+            out, _ = self.model(bottom, condition=top, **kw)
         return ops.prior_loss(out, target)
 
-    def step(self, top, bottom=None):
+    def step(self, top, bottom=None, label=None):
         plan = self.plan
         if plan is None:                # arena=False: one weight-norm launch per layer and pass, one Adam launch per tensor
             self.model.zero_grad(set_to_none=True)
-            loss, accuracy = self._forward_loss(top, bottom)
+            loss, accuracy = self._forward_loss(top, bottom, label)
             loss.backward()
         else:
             self.arena.zero_grad()
@@ -688,7 +690,7 @@ class Stage2Trainer(_ArenaTrainer):
             plan.prepare()
             plan.active = True
             try:
-                loss, accuracy = self._forward_loss(top, bottom)
+                loss, accuracy = self._forward_loss(top, bottom, label)
                 loss.backward()
             finally:
                 plan.active = False
@@ -703,7 +705,8 @@ class Stage2Trainer(_ArenaTrainer):
 
     # ------------------------------------------------------------------ held-out evaluation
     def evaluate(self, batches, top_k=5):
-        """PriorEvaluator.result() over an iterable of (top, bottom) or (top, bottom, filename) code batches, between two
+        """PriorEvaluator.result() over an iterable of (top, bottom) or (top, bottom, filename) code batches -- for a
+        class-conditional model (top, bottom, label) with label an int64 tensor [B] -- between two
         steps: eval-mode forwards under no_grad that draw no dropout seed and write no arena slot; the plan is not active,
         so every layer forms its weight from the parameters as they are, and the steps that follow are bit for bit those of
         a run that never evaluated.  Every module's train / eval flag is restored.  Data parallel: every rank calls it
@@ -713,5 +716,6 @@ class Stage2Trainer(_ArenaTrainer):
         device = next(self.model.parameters()).device
         for batch in batches:
             top, bottom = batch[0], batch[1]
-            ev.update(top.to(device), bottom.to(device) if self.hier == "bottom" else None)
+            label = batch[2].to(device) if len(batch) > 2 and isinstance(batch[2], torch.Tensor) else None
+            ev.update_labelled(label, top.to(device), bottom.to(device) if self.hier == "bottom" else None)
         return ev.result()
